@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput bench of the MISO1 -> MVDR -> MISO3 hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: either launched by the driver as ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or started plainly -- then this script re-executes itself under
@@ -11,16 +11,25 @@ A "step" = one pass of the complete reference semantics (6 x MISO_1 forward over
 shift alignment + clean alignment + 2 x MVDR + 2 x MISO_3 forward; reference tester.py:865-939) over one batch of
 synthetic 6-mic / 16 kHz / 4 s utterances (T = 1001 frames, F = 129) already resident in HBM.  Workload at N = 1 =
 BASELINE.json configs[3] (batch 16, full pipeline); at N = 8 = configs[4] (batch 128 = 8 x 16): utterances are sharded
-over ranks with no data-path collective (weak scaling; ``config.workload`` names what ran).  Every N > 1 line verifies itself
-(after the timed loop: each rank repeats its pass bit for bit, the results are all_gathered over RCCL -- the path's one
-collective -- checksummed per shard, and rank 0 checks an utterance of the LAST rank against the CPU oracle: ``parity``,
-``shard_checksums_match``, ``second_pass_bit_identical``; ``--no-verify-gather`` skips it).  Prints ONE JSON line on rank 0.
+over ranks with no data-path collective (weak scaling; ``config.workload`` names what ran).  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: set-up, the headline-mode calibration (below), ``--warmup`` passes,
+``--steps`` timed passes, the NaN check of the timed path, ``--dump-outputs`` if given, the line.  ``ms_per_step`` = wall time of
+the timed passes / ``--steps``.  ``--dump-outputs DIR`` writes what the last timed pass handed its caller -- the enhanced
+spectrograms, complex64 [B, 2, T, 129] -- as DIR/enhanced.npy, float32 [B, 2, T, 129, 2] (real, imaginary; at N > 1 one
+DIR/enhanced_rank<r>.npy per rank); inputs and weights are seeded, so two runs with the same arguments see the same inputs.
+
+``--full`` adds everything else the script measures or checks (the legs below; each keeps its ``--no-*`` switch).  Under
+``--full`` every N > 1 line verifies itself (after the timed loop: each rank repeats its pass bit for bit, the results are
+all_gathered over RCCL -- the path's one collective -- checksummed per shard, and rank 0 checks an utterance of the LAST rank
+against the CPU oracle: ``parity``, ``shard_checksums_match``, ``second_pass_bit_identical``; ``--no-verify-gather`` skips it).
+``--verify-gather``, ``--pmc`` and ``--wav`` run their own leg with or without ``--full``.
 
 The timed loop is un-instrumented.  The headline arithmetic is ``HEADLINE_PRECISION`` -- "auto": a short un-timed calibration
-picks between the two fp32-faithful fast modes on this box (``headline_selection``) -- ; the other two product modes are timed
-beside it with the same steps / warm-up and reported under ``alt_precision``.
+picks between the two fp32-faithful fast modes on this box (``headline_selection``) -- ; under ``--full`` the other two product
+modes are timed beside it with the same steps / warm-up and reported under ``alt_precision``.
 
-Extra objects on the line:
+Extra objects on the line (``--full``):
   roofline     -- dominant kernel (the 3x3 conv launches, MFMA bound): algorithmic FLOPs / summed launch time, from a
                   SEPARATE pass of the same workload with HIP events around every launch on the launch stream
                   (misonet_profile_*); ``instrumented_ms_per_step`` shows what the events cost.
@@ -435,6 +444,21 @@ def wav_leg(enh, W, rank, B, n, steps, warmup, dev, headline_value):
                     "the headline starts and ends at spectrograms"}, pcm_d
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, name, out, budget=DUMP_BUDGET_BYTES):
+    """``out`` (complex64 [B, S, T, F]: the enhanced spectrograms of the timed path) -> dirpath/<name>.npy, float32
+    [B', S, T, F, 2] (real, imaginary).  B' = B when that fits in ``budget`` bytes, else the first utterances that do."""
+    per_utt = out[0].numel() * 2 * 4
+    k = max(1, min(out.shape[0], budget // per_utt))
+    a = torch.view_as_real(out[:k]).to(torch.float32).cpu().numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    path = os.path.join(dirpath, name + ".npy")
+    np.save(path, np.ascontiguousarray(a))
+    return path
+
+
 def workload_name(world, B):
     """BASELINE.json's name of what this launch runs: configs[3] = batch 16 on one GPU, configs[4] = batch 128 sharded over
     8 GPUs (8 x 16); other rank counts / batch sizes run configs[4]'s sharding at their own global batch."""
@@ -482,18 +506,26 @@ def main():
     ap.add_argument("--frames", type=int, default=1001)
     ap.add_argument("--precision", choices=sorted(MODES) + ["auto"], default=HEADLINE_PRECISION,
                     help="arithmetic of the 3x3 convs (default: the fp32-faithful headline mode)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the runs of the other precision modes (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass computed (the enhanced spectrograms) to "
+                         "DIR/enhanced.npy as float32 [B, 2, T, 129, 2] (real, imaginary), at most 64 MB (the first utterances)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the roofline pass (with live rocprofv3 --pmc counters), the "
+                         "other precision modes, B = 1 latency, the wav leg, the CPU baseline and, at N > 1, the verification leg; "
+                         "the --no-* switches below pick from it")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the runs of the other precision modes (N = 1 only)")
     ap.add_argument("--alt", default="f32,f32w,bf16x6",
-                    help="comma-separated precision modes timed beside the headline (alt_precision on the line); the default is "
-                         "the product library's other two modes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="comma-separated precision modes timed beside the headline under --full (alt_precision on the line); the "
+                         "default is the product library's other two modes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle leg")
     ap.add_argument("--wav", action="store_true",
                     help="time the reference's real unit of work, wav in -> int16 wav out (HIP STFT front-end, pipeline, batched "
-                         "iSTFT, x 32767 -> int16), device-resident and host-resident with overlapped copies; runs by default "
+                         "iSTFT, x 32767 -> int16), device-resident and host-resident with overlapped copies; runs under --full "
                          "at N = 1 unless --no-alt, this flag forces it")
-    ap.add_argument("--no-profile", action="store_true", help="skip the event-instrumented pass (no roofline object)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the event-instrumented pass (no roofline object)")
     ap.add_argument("--pmc", action="store_true",
-                    help="force the live rocprofv3 --pmc passes (they run by default at N = 1 unless --no-alt / --no-pmc)")
+                    help="force the event-instrumented pass and its live rocprofv3 --pmc passes (they run under --full at N = 1 "
+                         "unless --no-alt / --no-pmc)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not re-execute under rocprofv3 --pmc for the live counters of the roofline object (traffic, matrix-"
                          "pipe busy fraction, observed clock): ~2 min; the fields then come from profiles/*_traffic.json")
@@ -502,10 +534,10 @@ def main():
                          "spectrograms over the process group (RCCL on GPUs; 33 MB per rank at batch 16, SURVEY.md 8(e)), shard "
                          "checksums, and rank 0 checks one utterance that came from the LAST rank against the CPU oracle "
                          "(~3 s at 16 threads): parity / gather_parity / shard_checksums_match / second_pass_bit_identical on "
-                         "the line.  ON BY DEFAULT when N > 1 (a multi-GPU line without correctness evidence is not a result)")
-    ap.add_argument("--no-verify-gather", action="store_true", help="N > 1: skip the verification leg")
+                         "the line.  ON under --full when N > 1 (a multi-GPU line without correctness evidence is not a result)")
+    ap.add_argument("--no-verify-gather", action="store_true", help="--full, N > 1: skip the verification leg")
     args = ap.parse_args()
-    if args.gpus > 1 and not args.no_verify_gather:
+    if args.gpus > 1 and args.full and not args.no_verify_gather:
         args.verify_gather = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -588,6 +620,9 @@ def main():
     dt, _, _ = run_steps(enh, mix, clean, out, args.steps, args.warmup, dist, L, _lib, False)
     if not os.environ.get("MISONET_BENCH_NOCHECK"):      # (timing experiments with deliberately wrong results)
         _lib.check(L.misonet_pipeline_check(enh._pipe, enh.workspace(B, T).data_ptr(), _lib.stream_ptr(dev)))
+    if args.dump_outputs:                                # `out` = the last timed pass's result (nothing has run since)
+        dump_outputs(args.dump_outputs, "enhanced" if world == 1 else f"enhanced_rank{rank}", out,
+                     budget=DUMP_BUDGET_BYTES // world)
     dt_rank = dt
     per_rank = [B * args.steps / dt]
     rccl_ranks = 1
@@ -657,7 +692,7 @@ def main():
                                         "ok": bool(np.isfinite(err) and err < 1e-3)}}
     # ---- roofline leg: the same steps once more with HIP events around every launch ----
     prof = None
-    if not args.no_profile:
+    if (args.full or args.pmc) and not args.no_profile:
         kp = max(1, min(args.steps, 5))
         dtp, ms, cnt = run_steps(enh, mix, clean, out, kp, 1, dist, L, _lib, True)
         prof = (kp, dtp, ms, cnt)
@@ -669,7 +704,7 @@ def main():
         if prof and prof[3][0] > 0:
             kp, dtp, ms, cnt = prof
             live = None
-            if world == 1 and not args.no_pmc and (args.pmc or not args.no_alt):   # (--no-alt = the quick A/B form of this script)
+            if world == 1 and not args.no_pmc and (args.pmc or (args.full and not args.no_alt)):   # (--no-alt = the quick A/B form)
                 live = pmc_live(args.precision, B, T)
             roof, roof2 = roofline_objects(args.precision, B, T, kp, ms[0], cnt[0], live)
             roof["time_share"] = {"conv_ms_per_step": round(ms[0] / kp, 2), "tcn_ms_per_step": round(ms[1] / kp, 2),
@@ -678,7 +713,7 @@ def main():
             roof["instrumented_ms_per_step"] = round(dtp / kp * 1e3, 2)
             roof["hbm_frac_pipeline"] = round(ALGO_BYTES_PER_UTT * (value / world) / (PEAK_HBM_TBS * 1e12), 4)
         alts = []
-        if world == 1 and not args.no_alt:
+        if world == 1 and args.full and not args.no_alt:
             for other in [m for m in args.alt.split(",") if m]:
                 if other == args.precision or other not in MODES:
                     continue
@@ -725,7 +760,7 @@ def main():
                                         if r2.get(kk) is not None}}
         # latency of ONE utterance (B = 1: the reference harness' own batch size, tester.py:846-975) in the headline mode
         b1 = None
-        if world == 1 and not args.no_alt:
+        if world == 1 and args.full and not args.no_alt:
             o1 = torch.empty((1, N_SPK, T, 129), dtype=torch.complex64, device=dev)
             for _ in range(3):
                 enh.enhance(mix[:1], clean[:1], check_nan=False, out=o1)
@@ -777,7 +812,7 @@ def main():
             enh.enhance(mix, clean, check_nan=False, out=out)            # restore the batch workspace / result
             torch.cuda.synchronize()
         wavp, wav_pcm = None, None
-        if world == 1 and (args.wav or not args.no_alt) and T == 1001:
+        if world == 1 and (args.wav or (args.full and not args.no_alt)) and T == 1001:
             try:
                 wavp, wav_pcm = wav_leg(enh, W, rank, B, n, args.steps, args.warmup, dev, value)
             except Exception as e:                                       # the extra leg never costs the headline its line
@@ -785,7 +820,7 @@ def main():
             enh.enhance(mix, clean, check_nan=False, out=out)
             torch.cuda.synchronize()
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             enh.enhance(mix, clean, check_nan=False, out=out)            # the headline mode's result for the checker
             torch.cuda.synchronize()
             cpu = cpu_baseline(sd1, sd3, T, out[:4].cpu().numpy(),

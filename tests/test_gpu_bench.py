@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _last_json(out: str):
 
 
 def test_bench_single_process_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -62,12 +63,34 @@ def test_bench_line_records_environment():
     assert d["value"] > 100.0            # ... and the product library ignored the kernel switch (it would run 64 of 256 CUs)
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline and nothing else, and --dump-outputs writes what the last timed step
+    handed its caller: the enhanced spectrograms of the batch, utterance 0 of which the real reference computed (G12)."""
+    from test_gpu_parity import _assert_parity
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "utt/s" and d["higher_is_better"] is True
+    assert d["dtype"] in ("bf16x6", "f32w") and d["headline_selection"]["picked"] == d["dtype"]
+    assert abs(d["ms_per_step"] - 16 / d["value"] * 1e3) <= 0.01 + 1e-3 * d["ms_per_step"]     # one step = the batch of 16
+    for k in ("roofline", "roofline_other", "single_utterance", "wav_path", "cpu_baseline", "parity"):
+        assert d[k] is None, k
+    assert d["alt_precision"] == []
+    assert sorted(os.listdir(tmp_path)) == ["enhanced.npy"]
+    y = np.load(tmp_path / "enhanced.npy")
+    assert y.dtype == np.float32 and y.shape == (16, 2, 1001, 129, 2) and np.isfinite(y).all()
+    g = np.load(os.path.join(ROOT, "tests", "golden", "g12_fullsize_T1001.npz"))
+    st = int(g["frame_step"])
+    _assert_parity(y[0, :, ::st, :, 0] + 1j * y[0, :, ::st, :, 1], g["out_frames"], "bench --dump-outputs utt 0 vs G12")
+
+
 def test_bench_mode_floors():
     """Per-mode floor on the measured roofline fraction of the conv kernels (the bench's own instrumented pass): round 3
     shipped an f32 mode that had silently lost 36 % (88 -> 56 utt/s, frac 0.68 -> 0.43) to register spills.  Boxes differ
     by a few per cent in sustained clocks (round 4: bf16x6 0.429 ... 0.450 on seven boxes, f32 0.675 ... 0.684); the floors sit
     5 % under the slowest box seen (a false alarm on a slow box costs more than a missed 5 %) -- a spilled kernel loses 30 %."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-pmc"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-pmc"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -94,7 +117,7 @@ def test_bench_live_pmc_fields():
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("rocprofv3 not installed")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--alt", ""],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--alt", ""],
                        cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -115,7 +138,7 @@ def test_bench_two_ranks_on_one_device():
     env = dict(os.environ, MISONET_BENCH_ONE_DEVICE="1", MISONET_BENCH_BACKEND="gloo")
     # plain ``python bench.py --gpus 2``: the script starts its own ranks (torch.distributed.run on 127.0.0.1)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt",
            "--batch", "4"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -125,7 +148,7 @@ def test_bench_two_ranks_on_one_device():
     assert d["rccl_ranks"] == 2 and len(d["per_rank_utt_per_s"]) == 2
     assert d["per_rank_utterances"] == [[0, 4], [4, 8]] and d["backend"] == "gloo"
     assert "configs[4]" in d["config"]["workload"] and d["config"]["global_batch"] == 8
-    # every N > 1 line verifies itself WITHOUT a flag: the all_gather of the results (the path's only
+    # every --full N > 1 line verifies itself without --verify-gather: the all_gather of the results (the path's only
     # collective), one utterance of the LAST rank's shard checked by the oracle on rank 0 -> `parity` on the line
     assert d["parity"] is not None and d["parity"]["worst"] < 1e-3 and d["parity"]["checked_rank"] == 1, d["parity"]
     assert d["gathered_shape"] == [8, 2, 1001, 129] and d["gather_ms"] > 0
@@ -143,7 +166,7 @@ def test_bench_eight_ranks_on_one_device():
     env = dict(os.environ, MISONET_BENCH_ONE_DEVICE="1", MISONET_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt",
            "--batch", "2"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -153,7 +176,7 @@ def test_bench_eight_ranks_on_one_device():
     assert "configs[4]" in d["config"]["workload"] and d["config"]["global_batch"] == 16
     assert len(d["per_rank_utt_per_s"]) == 8 and min(d["per_rank_utt_per_s"]) > 0
     gp = d["gather_parity"]
-    assert d["parity"] is not None and d["parity"]["worst"] < 1e-3 and d["parity"]["checked_rank"] == 7, d["parity"]   # no --verify-gather on the command line
+    assert d["parity"] is not None and d["parity"]["worst"] < 1e-3 and d["parity"]["checked_rank"] == 7, d["parity"]   # --full, no --verify-gather
     assert d["roofline"] is None or "NOT this run's counters" in (d["roofline"].get("traffic_source") or "")
     assert d["gathered_shape"] == [16, 2, 1001, 129]
     assert gp["from_rank"] == 7 and gp["utterance"] == 14 and gp["ok"] and gp["rel_l2_magnitudes_vs_oracle"] < 1e-3
@@ -175,7 +198,7 @@ def test_bench_two_ranks_rccl():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MISONET_BENCH_ONE_DEVICE", "MISONET_BENCH_BACKEND"):
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-alt"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-alt"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)

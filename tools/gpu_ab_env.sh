@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 A="$1"; B="$2"; N=${3:-3}; shift 3
 for i in $(seq $N); do
   for ARM in "$A" "$B"; do
-    V=$(env $ARM timeout 300 python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt "$@" 2>/dev/null | python -c "
+    V=$(env $ARM timeout 300 python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-alt "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}
 print(d['value'], 'utt/s  conv', r.get('achieved'), 'TF/s', (r.get('time_share') or {}))")
