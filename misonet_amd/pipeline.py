@@ -101,6 +101,95 @@ class CapturedPass:
         yield self.out
 
 
+class _Overlapped:
+    """The stream and event discipline of :meth:`Enhancer.stream_wav`, for any pass: the H2D copies of a batch's inputs on a
+    copy-in stream, the pass on the CURRENT stream, the D2H copy of its result and of the pipeline's NaN flag word on a
+    copy-out stream, ``depth`` slots of device input / pinned output buffers (batch i uses slot i % depth).  The caller
+    keeps at most ``depth`` batches in flight: :meth:`finish` of batch i - depth comes before :meth:`submit` of batch i."""
+
+    def __init__(self, dev, depth: int):
+        self.dev, self.depth = dev, max(1, int(depth))
+        self.s_in, self.s_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+        self.slots = [dict() for _ in range(self.depth)]
+
+    @staticmethod
+    def _staged(sl, name, host, dtype):
+        """pinned source for the H2D copy of `host` (itself if already pinned, or already on a device)"""
+        host = host.to(dtype).contiguous() if host.dtype != dtype or not host.is_contiguous() else host
+        if host.is_cuda or host.is_pinned():
+            return host
+        pin = sl.get("pin_" + name)
+        if pin is None or pin.shape != host.shape:
+            pin = sl["pin_" + name] = torch.empty(host.shape, dtype=dtype, pin_memory=True)
+        elif "ev_in" in sl:
+            sl["ev_in"].synchronize()                 # the previous H2D out of this staging buffer is done
+        pin.copy_(host)
+        return pin
+
+    def submit(self, i: int, inputs, compute, dtype=torch.float32, to_host: bool = True):
+        """Queue batch ``i``: ``inputs`` is a sequence of tensors (host, pinned or device) or None; ``compute(*device
+        inputs)`` enqueues the pass on the current stream and returns ``(result, flag)`` (flag: the int32 NaN flag word,
+        a device copy).  ``to_host``: the result (a device tensor) goes back through a pinned slot buffer; otherwise it
+        stays on the device (any object).  Returns the record :meth:`finish` takes."""
+        dev = self.dev
+        s_in, s_out = self.s_in, self.s_out
+        sl = self.slots[i % self.depth]
+        cur = torch.cuda.current_stream(dev)          # the consumer may have changed streams between two next() calls
+        srcs = [self._staged(sl, str(j), x, dtype) if x is not None else None for j, x in enumerate(inputs)]
+        fresh = False
+        for j, src in enumerate(srcs):
+            if src is not None and (sl.get(f"d{j}") is None or sl[f"d{j}"].shape != src.shape):
+                sl[f"d{j}"] = torch.empty(src.shape, dtype=dtype, device=dev)
+                fresh = True
+        if any(src is not None and src.is_cuda for src in srcs):
+            s_in.wait_stream(cur)                     # a device-resident input: after its producer on the current stream
+        if fresh:
+            # a new slot buffer comes out of the CURRENT stream's allocator pool: its block may be one that work
+            # already queued on the current stream still writes (e.g. the previous batch's spectrogram, freed on the
+            # host the moment its iSTFT was enqueued).  The copy-in stream must not touch it before that work is
+            # done.  (Found when the iSTFT became a HIP kernel: torch.istft synchronises the host, which had hidden it.)
+            s_in.wait_stream(cur)
+        with torch.cuda.stream(s_in):
+            if "ev_free" in sl:
+                s_in.wait_event(sl["ev_free"])        # the pass that read this slot's device buffers is done
+            for j, src in enumerate(srcs):
+                if src is not None:
+                    sl[f"d{j}"].copy_(src, non_blocking=True)
+            # device-resident inputs are read by the copy-in stream: the caching allocator must not hand their blocks out
+            # on the current stream before that copy is done, whatever the caller does with them after next() returns
+            for src in srcs:
+                if src is not None and src.is_cuda:
+                    src.record_stream(s_in)
+            sl["ev_in"] = torch.cuda.Event()
+            sl["ev_in"].record(s_in)
+        cur.wait_event(sl["ev_in"])
+        res, flag = compute(*[sl[f"d{j}"] if src is not None else None for j, src in enumerate(srcs)])
+        sl["ev_free"] = torch.cuda.Event()
+        sl["ev_free"].record(cur)
+        rec = {"pcm_h": sl.get("pcm_h") if to_host else None, "flag_h": sl.get("flag_h"), "res": None if to_host else res}
+        if to_host and (rec["pcm_h"] is None or rec["pcm_h"].shape != res.shape or rec["pcm_h"].dtype != res.dtype):
+            rec["pcm_h"] = sl["pcm_h"] = torch.empty(res.shape, dtype=res.dtype, pin_memory=True)
+        if rec["flag_h"] is None:
+            rec["flag_h"] = sl["flag_h"] = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        with torch.cuda.stream(s_out):
+            s_out.wait_event(sl["ev_free"])
+            if to_host:
+                rec["pcm_h"].copy_(res, non_blocking=True)
+                res.record_stream(s_out)
+            rec["flag_h"].copy_(flag, non_blocking=True)
+            flag.record_stream(s_out)
+            rec["ev_out"] = torch.cuda.Event()
+            rec["ev_out"].record(s_out)
+        return rec
+
+    @staticmethod
+    def finish(rec):
+        """Wait for a batch's D2H; returns (result: an ndarray copy of the pinned buffer, or the device object; NaN flag)"""
+        rec["ev_out"].synchronize()
+        res = rec["pcm_h"].numpy().copy() if rec["pcm_h"] is not None else rec["res"]
+        return res, int(rec["flag_h"][0]) != 0
+
+
 class Enhancer:
     """Fused on-device MISO1 -> (alignment) -> MVDR -> MISO3 for batches of 4 s chunks."""
 
@@ -342,88 +431,78 @@ class Enhancer:
         dev = self.device
         depth = max(1, int(depth))
         with torch.cuda.device(dev):
-            s_in, s_out = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
-            slots = [dict() for _ in range(depth)]
+            ov = _Overlapped(dev, depth)
             pending = collections.deque()
 
             def finish(rec):
-                rec["ev_out"].synchronize()
-                if check_nan and int(rec["flag_h"][0]) != 0:
+                pcm, nan = ov.finish(rec)
+                if check_nan and nan:
                     raise FloatingPointError("libmisonet_hip: NaN in pipeline output")
-                return rec["pcm_h"].numpy().copy()
-
-            def staged(sl, name, host):
-                """pinned source for the H2D copy of `host` (itself if already pinned, or already on a device)"""
-                host = host.to(torch.float32).contiguous() if host.dtype != torch.float32 or not host.is_contiguous() else host
-                if host.is_cuda or host.is_pinned():
-                    return host
-                pin = sl.get("pin_" + name)
-                if pin is None or pin.shape != host.shape:
-                    pin = sl["pin_" + name] = torch.empty(host.shape, dtype=torch.float32, pin_memory=True)
-                elif "ev_in" in sl:
-                    sl["ev_in"].synchronize()                 # the previous H2D out of this staging buffer is done
-                pin.copy_(host)
-                return pin
+                return pcm
 
             for i, item in enumerate(batches):
                 wav_h, clean_h = item if isinstance(item, (tuple, list)) else (item, None)
                 while len(pending) >= depth:                  # slot i % depth still belongs to batch i - depth
                     yield finish(pending.popleft())
-                sl = slots[i % depth]
-                cur = torch.cuda.current_stream(dev)          # the consumer may have changed streams between two next() calls
-                src_w = staged(sl, "wav", wav_h)
-                src_c = staged(sl, "clean", clean_h) if clean_h is not None else None
-                fresh = False
-                if sl.get("wav_d") is None or sl["wav_d"].shape != src_w.shape:
-                    sl["wav_d"] = torch.empty(src_w.shape, dtype=torch.float32, device=dev)
-                    fresh = True
-                if src_c is not None and (sl.get("clean_d") is None or sl["clean_d"].shape != src_c.shape):
-                    sl["clean_d"] = torch.empty(src_c.shape, dtype=torch.float32, device=dev)
-                    fresh = True
-                if src_w.is_cuda or (src_c is not None and src_c.is_cuda):
-                    s_in.wait_stream(cur)                     # a device-resident input: after its producer on the current stream
-                if fresh:
-                    # a new slot buffer comes out of the CURRENT stream's allocator pool: its block may be one that work
-                    # already queued on the current stream still writes (e.g. the previous batch's spectrogram, freed on the
-                    # host the moment its iSTFT was enqueued).  The copy-in stream must not touch it before that work is
-                    # done.  (Found when the iSTFT became a HIP kernel: torch.istft synchronises the host, which had hidden it.)
-                    s_in.wait_stream(cur)
-                with torch.cuda.stream(s_in):
-                    if "ev_free" in sl:
-                        s_in.wait_event(sl["ev_free"])        # the pass that read this slot's device buffers is done
-                    sl["wav_d"].copy_(src_w, non_blocking=True)
-                    if src_c is not None:
-                        sl["clean_d"].copy_(src_c, non_blocking=True)
-                    # device-resident inputs are read by the copy-in stream: the caching allocator must not hand their blocks out
-                    # on the current stream before that copy is done, whatever the caller does with them after next() returns
-                    if src_w.is_cuda:
-                        src_w.record_stream(s_in)
-                    if src_c is not None and src_c.is_cuda:
-                        src_c.record_stream(s_in)
-                    sl["ev_in"] = torch.cuda.Event()
-                    sl["ev_in"].record(s_in)
-                cur.wait_event(sl["ev_in"])
-                B, Ls, _ = sl["wav_d"].shape
-                pcm = self.enhance_wav_int16(sl["wav_d"], sl["clean_d"] if src_c is not None else None, check_nan=False)
-                T = _lib.lib().misonet_stft_frames(Ls)
-                flag = self.workspace(B, T)[:4].view(torch.int32).clone()      # the pass's NaN flag word (ws[0])
-                sl["ev_free"] = torch.cuda.Event()
-                sl["ev_free"].record(cur)
-                rec = {"pcm_h": sl.get("pcm_h"), "flag_h": sl.get("flag_h")}
-                if rec["pcm_h"] is None or rec["pcm_h"].shape != pcm.shape:
-                    rec["pcm_h"] = sl["pcm_h"] = torch.empty(pcm.shape, dtype=torch.int16, pin_memory=True)
-                    rec["flag_h"] = sl["flag_h"] = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                with torch.cuda.stream(s_out):
-                    s_out.wait_event(sl["ev_free"])
-                    rec["pcm_h"].copy_(pcm, non_blocking=True)
-                    rec["flag_h"].copy_(flag, non_blocking=True)
-                    pcm.record_stream(s_out)
-                    flag.record_stream(s_out)
-                    rec["ev_out"] = torch.cuda.Event()
-                    rec["ev_out"].record(s_out)
-                pending.append(rec)
+                pending.append(ov.submit(i, (wav_h, clean_h), self._wav_pass))
             while pending:
                 yield finish(pending.popleft())
+
+    def _wav_pass(self, wav, clean_wav):
+        """one stream_wav batch on the current stream: int16 waves and a copy of the pass's NaN flag word (ws[0])"""
+        pcm = self.enhance_wav_int16(wav, clean_wav, check_nan=False)
+        B, Ls, _ = wav.shape
+        T = _lib.lib().misonet_stft_frames(Ls)
+        return pcm, self.workspace(B, T)[:4].view(torch.int32).clone()
+
+    def _spec_pass(self, mix, clean):
+        """one coalesced Tester_Enhance batch on the current stream: the pass, ONE iSTFT + int16 over its N * S
+        spectrograms, and a copy of the pass's NaN flag word (ws[0])"""
+        N, _, T, _ = mix.shape
+        pcm = S.istft_int16(self.enhance(mix, clean, check_nan=False))                      # [N, S, (T - 1) * 64]
+        return pcm, self.workspace(N, T)[:4].view(torch.int32).clone()
+
+    def _coalesced(self, items, fill, compute, dtype, max_batch: int, depth: int, label, to_host: bool = True):
+        """The engine of the coalesced drop-ins: :func:`coalesce.coalesce` over :class:`_Overlapped`.
+
+        ``items``: :class:`coalesce.Item` whose ``key`` is the tuple of the per-chunk input shapes (None: input absent);
+        ``fill(chunk, rows)`` copies one chunk's inputs into its rows of the pinned staging buffers ([max_batch, *shape]
+        per input, ``dtype``, one set per slot: batch i - depth, their last user, has been collected when batch i is
+        staged); ``compute(*device inputs [N, ...])`` -> (result [N, ...], flag) on the current stream.  No per-batch host
+        synchronisation: the host waits for the oldest batch in flight only.  Yields completed items in loader order with
+        ``item.outputs[split][b]`` = the chunk's result row (ndarray; the device row(s) with ``to_host=False``).  A NaN in a
+        batch raises FloatingPointError naming ``label(chunk)`` of its chunks."""
+        from .coalesce import coalesce
+        depth = max(1, int(depth))
+        ov = _Overlapped(self.device, depth)
+        staging = [dict() for _ in range(depth)]
+
+        def submit(i, chunks):
+            st, n = staging[i % depth], len(chunks)
+            bufs = []
+            for j, shape in enumerate(chunks[0].item.key):
+                if shape is None:
+                    bufs.append(None)
+                    continue
+                pin = st.get(j)
+                if pin is None or tuple(pin.shape[1:]) != tuple(shape) or pin.shape[0] < n:
+                    pin = st[j] = torch.empty((max(n, int(max_batch)),) + tuple(shape), dtype=dtype, pin_memory=True)
+                bufs.append(pin)
+            for r, c in enumerate(chunks):
+                fill(c, [b[r] if b is not None else None for b in bufs])
+            rec = ov.submit(i, [b[:n] if b is not None else None for b in bufs], compute, dtype=dtype, to_host=to_host)
+            return rec, chunks
+
+        def collect(handle):
+            rec, chunks = handle
+            res, nan = ov.finish(rec)
+            if nan:
+                names = list(dict.fromkeys(label(c) for c in chunks))
+                raise FloatingPointError(f"libmisonet_hip: NaN in pipeline output of the batch holding {', '.join(names)}")
+            return list(zip(*res)) if isinstance(res, tuple) else list(res)
+
+        with torch.cuda.device(self.device):
+            yield from coalesce(items, submit, collect, max_batch, depth)
 
     def separate(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, check_nan=True) -> torch.Tensor:
         """Separation stage only: MISO1_Inference over the circular shifts + alignments (tester.py:1014-1068, 889-915).
@@ -461,7 +540,6 @@ class Enhancer:
         speaker is solved over all its frames (spatial covariances accumulated over the full utterance instead of per 4 s
         chunk).  obs_splits: list of complex [M,T,F]; clean_splits: list of complex [S,T,F].  Returns int16 [S, n] (an ndarray;
         ``to_host=False``: the device tensor, nothing synchronises)."""
-        from .beamform import Apply_Beamforming
         K = len(obs_splits)
         if K < 1 or len(clean_splits) != K:
             raise ValueError("obs_splits / clean_splits must be non-empty lists of equal length")
@@ -469,6 +547,15 @@ class Enhancer:
         cl = torch.stack([torch.as_tensor(c) for c in clean_splits]).to(self.device, non_blocking=True)  # [K,S,T,F]
         est = torch.cat([self.separate(obs[lo:lo + max_batch], cl[lo:lo + max_batch])          # [K,S,M,T,F], in groups of
                          for lo in range(0, K, max_batch)])                                   # <= max_batch splits (workspace)
+        pcm = self._utterance_tail(est, obs, gap, epsi)
+        return pcm.cpu().numpy() if to_host else pcm
+
+    def _utterance_tail(self, est: torch.Tensor, obs: torch.Tensor, gap: int, epsi: float = 1e-6) -> torch.Tensor:
+        """The per-recording tail of :meth:`beamform_utterance` (and of the coalesced utterance-wise Tester_Beamforming):
+        est complex [K,S,M,T,F] = the separated splits, obs complex [K,M,T,F] (device) -> int16 [S, n] (device): one
+        batched iSTFT, the splits stitched (last one trimmed by ``gap``), one long STFT, one MVDR per speaker, int16."""
+        from .beamform import Apply_Beamforming
+        K = est.shape[0]
         e = S.istft(est)                                                                      # [K,S,M,chunk]
         o = S.istft(obs)                                                                      # [K,M,chunk]
         n = e.shape[-1]
@@ -483,16 +570,16 @@ class Enhancer:
         mix_bf = spec[0].permute(2, 0, 1)[None]                               # [1,F,M,Tt]
         bf = torch.stack([Apply_Beamforming(spec[1 + s].permute(2, 0, 1)[None], mix_bf, epsi)[0]
                           for s in range(self.num_spks)])                     # [S,Tt,F]
-        pcm = S.istft_int16(bf)
-        return pcm.cpu().numpy() if to_host else pcm
+        return S.istft_int16(bf)
 
-    def beamform_chunks(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, epsi: float = 1e-6) -> torch.Tensor:
+    def beamform_chunks(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, epsi: float = 1e-6,
+                        check_nan: bool = True) -> torch.Tensor:
         """Chunk-wise MVDR (BASELINE configs[2]: MISO1 -> MVDR; the ``utterance_flag = False`` branch of the reference's
         Tester_Beamforming, tester.py:452-535): separation of a batch of 4 s chunks, then one MVDR per (chunk, speaker) over
         the chunk's own frames.  mix complex [B,M,T,F], clean complex [B,S,T,F] or None -> beamformer outputs complex64
         [B,S,T,F].  (With MISO_3 attached, ``enhance(..., want_bf=True)`` returns the same tensor from the fused pass.)"""
         from .beamform import Apply_Beamforming
-        est = self.separate(mix, clean)                                                       # [B,S,M,T,F]
+        est = self.separate(mix, clean, check_nan=check_nan)                                  # [B,S,M,T,F]
         mix_bf = self._check_c64(mix, "mix").permute(0, 3, 1, 2)                              # [B,F,M,T]
         return torch.stack([Apply_Beamforming(est[:, s].permute(0, 3, 1, 2), mix_bf, epsi)
                             for s in range(self.num_spks)], dim=1)                            # [B,S,T,F]
@@ -516,6 +603,20 @@ class Enhancer:
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
+        pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
+        K = len(pieces)
+
+        def batches():
+            for lo in range(0, K, max_batch):
+                w = torch.from_numpy(np.stack(pieces[lo:lo + max_batch]))
+                yield (w, torch.from_numpy(np.stack(cpieces[lo:lo + max_batch]))) if cpieces is not None else w
+
+        pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
+        return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
+
+    def _recording_chunks(self, wav_observe, wav_clean, num_ch_utilize, chunk_size):
+        """enhance_recording's loader side: microphone sub-sampling, the clean sources at ref_ch, 4 s chunks ->
+        (list of float32 [chunk, M], list of float32 [chunk, S] or None, gap)"""
         obs = np.asarray(wav_observe, dtype=np.float32)
         if obs.ndim != 2 or obs.shape[0] <= obs.shape[1]:
             raise ValueError("wav_observe must be [n_samples, n_mics] with n_samples > n_mics (data.py:510)")
@@ -542,15 +643,11 @@ class Enhancer:
             cl = np.stack(srcs, axis=1)                                    # [L, S]
         pieces, gap = S.split_chunks(obs, int(chunk_size))
         cpieces = S.split_chunks(cl, int(chunk_size))[0] if cl is not None else None
-        K = len(pieces)
+        return pieces, cpieces, gap
 
-        def batches():
-            for lo in range(0, K, max_batch):
-                w = torch.from_numpy(np.stack(pieces[lo:lo + max_batch]))
-                yield (w, torch.from_numpy(np.stack(cpieces[lo:lo + max_batch]))) if cpieces is not None else w
-
-        pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
-        out = np.stack([S.stitch_int16([pcm[k, s] for k in range(K)], gap) for s in range(self.num_spks)])
+    def _finish_recording(self, pcm_chunks, gap, save_path, fs):
+        """the K int16 chunks [S, chunk] of one recording -> stitched int16 [S, L]; ``save_path``: the PCM-24 files"""
+        out = np.stack([S.stitch_int16([p[s] for p in pcm_chunks], gap) for s in range(self.num_spks)])
         if save_path is not None:
             import os
             os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
@@ -558,14 +655,61 @@ class Enhancer:
                 S.write_wav_pcm24(f"{save_path}_{s}.wav", out[s], fs)
         return out
 
-    def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32):
+    def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
+                           max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
+                           depth: int = 2) -> Dict[str, np.ndarray]:
+        """:meth:`enhance_recording` over many recordings, with every launch filled across them.
+
+        ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
+        it (``num_ch_utilize`` and ``chunk_size`` apply to every one).  Every recording is cut into its 4 s chunks; the
+        chunks go through the pipeline in batches of ``max_batch`` taken across recordings (:mod:`coalesce`; the HIP STFT
+        front-end, the fused pass, one iSTFT + int16 per batch, copies overlapped as in :meth:`stream_wav`, at most
+        ``depth`` batches in flight); the int16 chunks are scattered back and every recording stitched.  ``save_path``: a
+        directory; recording ``name`` is written as ``<save_path>/<name>_{s}.wav``.  Returns {name: int16 [S, L]} in input
+        order; each recording bit for bit what :meth:`enhance_recording` returns for it alone (results do not depend on the
+        batch)."""
+        import os
+        from .coalesce import Item
+        self._ready()
+        if self.model is None:
+            raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
+
+        def items():
+            for i, (wav_observe, wav_clean, name) in enumerate(recordings):
+                pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
+                key = (pieces[0].shape, cpieces[0].shape if cpieces is not None else None)
+                yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name))
+
+        def fill(c, rows):
+            pieces, cpieces, _, _ = c.item.payload
+            rows[0].copy_(torch.from_numpy(pieces[c.split]))
+            if rows[1] is not None:
+                rows[1].copy_(torch.from_numpy(cpieces[c.split]))
+
+        results = {}
+        for it in self._coalesced(items(), fill, self._wav_pass, torch.float32, max_batch, depth,
+                                  lambda c: str(c.item.payload[3])):
+            _, _, gap, name = it.payload
+            path = os.path.join(save_path, str(name)) if save_path is not None else None
+            results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
+        return results
+
+    def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2):
         """Drop-in for ``Tester_Enhance.inference(data_loader, saveDir)`` (tester.py:846-975): the loader yields
         ``(split_observe_dict, split_clean_s0_dict, split_clean_s1_dict, gap, wav_name)`` with dict values complex
         ``[B, Ch, T, F]`` keyed '0', '1', ... (dataloader/data.py:524-597).  Every split runs through
         :meth:`enhance`; the int16 waves of the splits are stitched (last split trimmed by ``gap``) and written as
-        ``<saveDir>/<wav_name>_{0,1}.wav`` (PCM-24).  Returns {wav_name: int16 [2, n_samples]}."""
+        ``<saveDir>/<wav_name>_{0,1}.wav`` (PCM-24).  Returns {wav_name: int16 [2, n_samples]}.
+
+        ``coalesce=True``: every launch holds ``max_batch`` chunks taken across loader items (:mod:`coalesce`; a change of
+        T and the end of the loader flush a shorter one), staged in pinned slots, with no host synchronisation per batch
+        (at most ``depth`` batches in flight, the NaN flag word travels with each batch's D2H).  ``coalesce=False``: one
+        item at a time, its splits in groups of at most ``max_batch``.  Both return and write the same bits (results do not
+        depend on the batch)."""
         import os
         os.makedirs(saveDir, exist_ok=True)
+        if coalesce:
+            return self._inference_coalesced(data_loader, saveDir, fs, write, max_batch, depth)
         results = {}
         dev = self.device
 
@@ -628,6 +772,44 @@ class Enhancer:
                 prev = rec
             if prev is not None:
                 finalize(prev)
+        return results
+
+    def _loader_items(self, data_loader):
+        """Loader tuples ``(split_observe_dict, split_clean_s0_dict, split_clean_s1_dict, gap, wav_name)`` ->
+        :class:`coalesce.Item` (B utterances x n_split chunks, keyed by the chunk shapes [M,T,F] / [S,T,F]); the payload
+        holds the splits, the clean sources, the per-utterance gaps and names"""
+        from .coalesce import Item
+        for i, (obs_d, s0_d, s1_d, gap, wav_name) in enumerate(data_loader):
+            K = len(obs_d)
+            obs = [torch.as_tensor(obs_d[str(k)]) for k in range(K)]
+            s0 = [torch.as_tensor(s0_d[str(k)]) for k in range(K)]
+            s1 = [torch.as_tensor(s1_d[str(k)]) for k in range(K)]
+            B, M, T, F = obs[0].shape
+            gaps = [int(gap[b]) if hasattr(gap, "__len__") else int(gap) for b in range(B)]
+            names = [wav_name] * B if isinstance(wav_name, str) else list(wav_name)
+            yield Item(i, B, K, ((M, T, F), (self.num_spks, T, F)), dict(obs=obs, s0=s0, s1=s1, gaps=gaps, names=names))
+
+    def _fill_spec(self, c, rows):
+        """stage one loader chunk: the observation [M,T,F] and the clean sources at ref_ch [S,T,F] (tester.py:889-890)"""
+        p = c.item.payload
+        rows[0].copy_(p["obs"][c.split][c.b])
+        rows[1][0].copy_(p["s0"][c.split][c.b, self.ref_ch])
+        rows[1][1].copy_(p["s1"][c.split][c.b, self.ref_ch])
+
+    def _inference_coalesced(self, data_loader, saveDir, fs, write, max_batch, depth):
+        import os
+        results = {}
+        for it in self._coalesced(self._loader_items(data_loader), self._fill_spec, self._spec_pass, torch.complex64,
+                                  max_batch, depth, lambda c: str(c.item.payload["names"][c.b])):
+            p = it.payload
+            for b in range(it.n_b):
+                wav = np.stack([S.stitch_int16([it.outputs[k][b][s] for k in range(it.n_split)], p["gaps"][b])
+                                for s in range(self.num_spks)])                               # [S, n_total]
+                name = p["names"][b]
+                results[name] = wav
+                if write:
+                    for s in range(self.num_spks):
+                        S.write_wav_pcm24(os.path.join(saveDir, f"{name}_{s}.wav"), wav[s], fs)
         return results
 
     def to_wav_int16(self, enhanced_chunks: List[torch.Tensor], gap: int) -> np.ndarray:

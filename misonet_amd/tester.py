@@ -110,10 +110,16 @@ class Tester_Beamforming(object):
             out[sub] = self.inference(loader, save_dir)
         return out
 
-    def inference(self, data_loader, saveDir, write=True):
+    def inference(self, data_loader, saveDir, write=True, coalesce=True, max_batch=16, depth=2):
         """tester.py:327-535.  The loader yields ``(split_observe_dict, split_clean_s0_dict, split_clean_s1_dict, gap,
         wav_name)`` with dict values complex ``[B, Ch, T, F]`` keyed '0', '1', ... (dataloader/data.py:524-597).  Returns
-        {wav_name: int16 [num_spks, n_samples]} besides writing the files."""
+        {wav_name: int16 [num_spks, n_samples]} besides writing the files.
+
+        ``coalesce=True``: the separations run in batches of ``max_batch`` chunks taken across loader items
+        (:mod:`misonet_amd.coalesce`, at most ``depth`` batches in flight, no host synchronisation per batch).  Chunk-wise
+        (``utterance_flag = False``): separation, MVDR, one iSTFT + int16 and one D2H per batch.  Utterance-wise: once all
+        of a recording's chunks are separated, the tail of :meth:`Enhancer.beamform_utterance` runs on its slice.
+        ``coalesce=False``: one item at a time.  Both return and write the same bits."""
         import numpy as np
         import torch
         os.makedirs(saveDir, exist_ok=True)
@@ -144,6 +150,50 @@ class Tester_Beamforming(object):
                     for s in range(self.num_spks):
                         S.write_wav_pcm24(os.path.join(saveDir, f"{name}_{s}.wav"), wav[s], self.fs)
 
+        if coalesce and not self.utterance_flag:
+            return self._inference_chunks_coalesced(data_loader, saveDir, write, max_batch, depth)
+
+        def enqueue_d2h(rec, dev_out):
+            """one D2H per item on the copy-out stream, after the work queued so far on the current stream"""
+            ev_done = torch.cuda.Event()
+            ev_done.record(torch.cuda.current_stream(dev))
+            rec["host"] = [torch.empty(t.shape, dtype=torch.int16, pin_memory=True) for t in dev_out]
+            with torch.cuda.stream(s_out):                   # the item's D2H beside the next item's compute
+                s_out.wait_event(ev_done)
+                for h, t in zip(rec["host"], dev_out):
+                    h.copy_(t, non_blocking=True)
+                    t.record_stream(s_out)
+                rec["ev"] = torch.cuda.Event()
+                rec["ev"].record(s_out)
+            return rec
+
+        if coalesce:
+            enh = self._enh
+
+            def sep_pass(mix, clean):
+                N, _, T, _ = mix.shape
+                est = enh.separate(mix, clean, check_nan=False)                                     # [N,S,M,T,F]
+                # the observation rows outlive the slot buffer they were copied into: the tail reads them later
+                return (est, mix.clone()), enh.workspace(N, T)[:4].view(torch.int32).clone()
+
+            with torch.cuda.device(dev):
+                s_out = torch.cuda.Stream(dev)
+                prev = None
+                for it in enh._coalesced(enh._loader_items(data_loader), enh._fill_spec, sep_pass, torch.complex64,
+                                         max_batch, depth, lambda c: str(c.item.payload["names"][c.b]), to_host=False):
+                    p = it.payload
+                    dev_out = [enh._utterance_tail(torch.stack([it.outputs[k][b][0] for k in range(it.n_split)]),
+                                                   torch.stack([it.outputs[k][b][1] for k in range(it.n_split)]),
+                                                   p["gaps"][b]) for b in range(it.n_b)]                 # B x int16 [S, n_b]
+                    it.outputs = None                                    # the batches' device rows can go
+                    rec = enqueue_d2h({"names": p["names"], "gaps": p["gaps"], "utterance": True}, dev_out)
+                    if prev is not None:
+                        finalize(prev)
+                    prev = rec
+                if prev is not None:
+                    finalize(prev)
+            return results
+
         with torch.cuda.device(dev):
             s_out = torch.cuda.Stream(dev)
             prev = None
@@ -160,20 +210,35 @@ class Tester_Beamforming(object):
                                for b in range(B)]                                                    # B x int16 [S, n_b] (device)
                 else:
                     dev_out = [torch.stack([S.istft_int16(self._enh.beamform_chunks(obs[k], clean[k])) for k in range(K)])]
-                ev_done = torch.cuda.Event()
-                ev_done.record(torch.cuda.current_stream(dev))
-                rec = {"names": names, "gaps": gaps, "utterance": self.utterance_flag,
-                       "host": [torch.empty(t.shape, dtype=torch.int16, pin_memory=True) for t in dev_out]}
-                with torch.cuda.stream(s_out):                   # the item's D2H beside the next item's compute
-                    s_out.wait_event(ev_done)
-                    for h, t in zip(rec["host"], dev_out):
-                        h.copy_(t, non_blocking=True)
-                        t.record_stream(s_out)
-                    rec["ev"] = torch.cuda.Event()
-                    rec["ev"].record(s_out)
+                rec = enqueue_d2h({"names": names, "gaps": gaps, "utterance": self.utterance_flag}, dev_out)
                 if prev is not None:
                     finalize(prev)
                 prev = rec
             if prev is not None:
                 finalize(prev)
+        return results
+
+    def _inference_chunks_coalesced(self, data_loader, saveDir, write, max_batch, depth):
+        """chunk-wise branch on the coalescer: per batch the separation, one MVDR per (chunk, speaker), one iSTFT + int16
+        and one D2H; every recording's int16 chunks stitched as the per-item path does"""
+        import numpy as np
+        import torch
+        enh = self._enh
+
+        def chunk_pass(mix, clean):
+            N, _, T, _ = mix.shape
+            pcm = S.istft_int16(enh.beamform_chunks(mix, clean, check_nan=False))                  # [N, S, n]
+            return pcm, enh.workspace(N, T)[:4].view(torch.int32).clone()
+
+        results = {}
+        for it in enh._coalesced(enh._loader_items(data_loader), enh._fill_spec, chunk_pass, torch.complex64, max_batch,
+                                 depth, lambda c: str(c.item.payload["names"][c.b])):
+            p = it.payload
+            for b, name in enumerate(p["names"]):
+                wav = np.stack([S.stitch_int16([it.outputs[k][b][s] for k in range(it.n_split)], p["gaps"][b])
+                                for s in range(self.num_spks)])
+                results[name] = wav
+                if write:
+                    for s in range(self.num_spks):
+                        S.write_wav_pcm24(os.path.join(saveDir, f"{name}_{s}.wav"), wav[s], self.fs)
         return results
