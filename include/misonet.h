@@ -139,6 +139,35 @@ long long misonet_pit_scratch_bytes(int B, int S, int F);
 int misonet_pit_select(const void* anchor_dev, const void* cand_dev, int B, int S, int T, int F,
                        int* sel_dev, double* dist_dev, long long dist_bytes, misonet_stream stream);
 
+/* ---- continuous separation: a long recording in overlapping windows without clean references (ABI 460) -------------
+ * Window k of the recording covers samples [kH, kH + W) (64 | W, 64 | H, W/2 <= H <= W - 256); each window goes through
+ * misonet_pipeline_run_wav with clean_dev == NULL.  The speaker order of window k is linked to window k-1 through their
+ * T - H/64 shared frames, and the windows' waveforms are joined by a raised-cosine cross-fade over the overlap ov = W - H.
+ *
+ * misonet_css_align: est_dev complex64 [K, S, T, F] = K consecutive windows hop_frames = H/64 frames apart.
+ *   D_k[i][j] = sum_{t < T - hop_frames} sum_f | |est[k-1, i, t + hop_frames, f]| - |est[k, j, t, f]| | (k = 1..K-1;
+ *   magnitudes float32 sqrtf(re^2 + im^2), float64 sums in a fixed order: bit-reproducible, as misonet_pit_select);
+ *   L_k = the cheapest of the S! permutations (itertools.permutations order, first minimum: an all-silent overlap keeps
+ *   the identity); P_0 = perm0_dev int32 [S] (NULL: identity), P_k[s] = L_k[P_{k-1}[s]].  perm_dev int32 [K, S] receives P
+ *   (output speaker s of window k = est[k, P_k[s]]); perm0_dev may point at perm_dev's first row.  dist_dev: the first
+ *   (K-1)*S*S doubles receive D_1..D_{K-1}, the rest is scratch; dist_bytes < misonet_css_scratch_bytes(K, S, F) returns
+ *   MISONET_ENOMEM (dist_dev may be NULL when K == 1).  MISONET_EINVAL: S outside 1..4, F != 129, K < 1, hop_frames <= 0
+ *   or fewer than 5 shared frames.
+ *   A recording processed in batches carries the last window of a batch over as est[0] of the next, with its P as perm0.
+ * misonet_css_stitch: y_dev float32 [K, S, W] = the iSTFT of the K windows (misonet_istft out_f32), perm_dev [K, S] = P.
+ *   Sample m of the batch (k = min(K-1, m / H), j = m - kH) is y[k, P_k[s], j], for k >= 1 and j < ov cross-faded:
+ *   c(j) y[k-1, P_{k-1}[s], H + j] + r(j) y[k, P_k[s], j], r(j) = sin^2, c(j) = cos^2 of pi (j + 1/2) / (2 ov), each
+ *   evaluated in float64 and rounded to float32; int16 = the truncating cast of y * 32767 (as misonet_istft).
+ *   first != 0: y[0] is window 0 of the recording and samples m = 0 .. n_out-1 are written; first == 0: y[0] is the window
+ *   carried over from the previous call and samples m = H .. H + n_out - 1 (windows 1..K-1) are written.  out_i16_dev /
+ *   out_f32_dev [S, n_out] (either may be NULL); n_out trims the padded tail on the last call.  MISONET_EINVAL: S outside
+ *   1..4, K < 1, H outside [W/2, W - 256], n_out beyond the last window. */
+long long misonet_css_scratch_bytes(int K, int S, int F);
+int misonet_css_align(const void* est_dev, int K, int S, int T, int F, int hop_frames, const int* perm0_dev,
+                      int* perm_dev, double* dist_dev, long long dist_bytes, misonet_stream stream);
+int misonet_css_stitch(const float* y_dev, const int* perm_dev, int K, int S, int W, int hop, int first,
+                       long long n_out, short* out_i16_dev, float* out_f32_dev, misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

@@ -56,6 +56,11 @@ SIGNATURES = {
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),
+    "misonet_css_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "misonet_css_align": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_css_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_pipeline_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.POINTER(C.c_void_p)]),
     "misonet_pipeline_destroy": (C.c_int, [C.c_void_p]),

@@ -31,6 +31,9 @@ void istft_build_twiddles(float* tw);
 int istft_twiddle_count();
 void stft_build_twiddles(float* tw);
 int stft_twiddle_count();
+hipError_t launch_css_chain(const int* perm0, int* perm, int K, int S, hipStream_t s);
+hipError_t launch_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, long long base, long long n_out,
+                             short* out_i16, float* out_f32, hipStream_t s);
 }  // namespace mn
 
 using namespace mn;
@@ -675,7 +678,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 450; }   // 450: product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 460; }   // 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1319,6 +1322,60 @@ int misonet_pit_select(const void* anchor, const void* cand, int B, int S, int T
   double* part = dist + (long long)B * S * S;          // per-bin partials [B][F][S][S] behind the result
   HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
   HIPCHK(launch_pit_pick(part, F, S, B, dist, sel, s));
+  return MISONET_OK;
+}
+
+// ---- continuous separation: speaker tracking across overlapping windows + cross-fade stitch (css.hip) -------------
+long long misonet_css_scratch_bytes(int K, int S, int F) {
+  if (K <= 0 || S <= 0 || F <= 0) return -1;
+  return (long long)(K - 1) * S * S * (F + 1) * (long long)sizeof(double);
+}
+
+int misonet_css_align(const void* est, int K, int S, int T, int F, int hop_frames, const int* perm0, int* perm,
+                      double* dist, long long dist_bytes, misonet_stream stream) {
+  if (!est || !perm) return fail(MISONET_EINVAL, "null argument");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "the alignment enumerates S! permutations: 1 <= S <= 4 (got %d)", S);
+  if (F != 129) return fail(MISONET_EINVAL, "F must be 129 (got %d)", F);
+  if (K < 1 || K - 1 > 65535) return fail(MISONET_EINVAL, "K must be in [1, 65536] (got %d)", K);
+  if (hop_frames <= 0 || T - hop_frames < 5)
+    return fail(MISONET_EINVAL, "hop_frames must be positive and leave an overlap of at least 5 frames (T %d, hop %d)", T,
+                hop_frames);
+  if (K > 1 && !dist) return fail(MISONET_EINVAL, "null argument (dist is required for K > 1: (K-1)*S*S*(F+1) doubles)");
+  if (dist_bytes < misonet_css_scratch_bytes(K, S, F))
+    return fail(MISONET_ENOMEM, "dist scratch %lld < %lld bytes ((K-1)*S*S*(F+1) doubles)", dist_bytes,
+                misonet_css_scratch_bytes(K, S, F));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (K > 1) {
+    // est complex64 [K,S,T,F]: element (k, f, spk, t) at ((k*S + spk)*T + t)*F + f.  Item b = k - 1 of the distance launch:
+    // anchor = window k - 1 from frame hop_frames on, candidate = window k from frame 0, over the T - hop_frames shared frames
+    const float* e = reinterpret_cast<const float*>(est);
+    const long long win = 2LL * S * T * F;
+    const float* a = e + 2LL * hop_frames * F;
+    const float* c = e + win;
+    PitArgs p;
+    p.a = {a, a + 1, win, 2, 2LL * T * F, 2 * F};
+    p.b = {c, c + 1, win, 2, 2LL * T * F, 2 * F};
+    p.B = K - 1; p.F = F; p.T = T - hop_frames;
+    double* part = dist + (long long)(K - 1) * S * S;                // per-bin partials [K-1][F][S][S] behind D
+    HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
+    HIPCHK(launch_pit_pick(part, F, S, K - 1, dist, perm + S, s));   // L_k -> row k of perm, composed in place below
+  }
+  HIPCHK(launch_css_chain(perm0, perm, K, S, s));
+  return MISONET_OK;
+}
+
+int misonet_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, int first, long long n_out,
+                       short* out_i16, float* out_f32, misonet_stream stream) {
+  if (!y || !perm || (!out_i16 && !out_f32)) return fail(MISONET_EINVAL, "null argument");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "S must be in [1, 4] (got %d)", S);
+  if (K < 1) return fail(MISONET_EINVAL, "K must be positive (got %d)", K);
+  if (W <= 0 || hop <= 0 || 2LL * hop < W || hop > W - 256)
+    return fail(MISONET_EINVAL, "hop %d outside [W/2, W-256] for W = %d", hop, W);
+  const long long base = first ? 0 : hop;
+  const long long cap = (long long)(K - 1) * hop + W - base;
+  if (n_out < 0 || n_out > cap) return fail(MISONET_EINVAL, "n_out %lld outside [0, %lld]", n_out, cap);
+  if (n_out == 0) return MISONET_OK;
+  HIPCHK(launch_css_stitch(y, perm, K, S, W, hop, base, n_out, out_i16, out_f32, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -599,7 +599,9 @@ class Enhancer:
         x 32767 -> int16 (HIP kernels end to end, the chunks of the recording as batches of <= ``max_batch`` through
         :meth:`stream_wav`: H2D of the next batch and D2H of the previous one beside the compute), chunks stitched with the
         padded tail dropped (tester.py:960-969).  Returns int16 [S, L]; ``save_path`` = "<dir>/<wav_name>" also writes
-        ``<save_path>_{s}.wav`` as 24-bit PCM (tester.py:972-974)."""
+        ``<save_path>_{s}.wav`` as 24-bit PCM (tester.py:972-974).  With ``wav_clean=None`` the speaker order is that of
+        each chunk on its own (MISO1 is PIT-trained): for one speaker per output across a long recording use
+        :meth:`enhance_continuous`."""
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -614,19 +616,25 @@ class Enhancer:
         pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
         return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
 
-    def _recording_chunks(self, wav_observe, wav_clean, num_ch_utilize, chunk_size):
-        """enhance_recording's loader side: microphone sub-sampling, the clean sources at ref_ch, 4 s chunks ->
-        (list of float32 [chunk, M], list of float32 [chunk, S] or None, gap)"""
+    def _select_mics(self, wav_observe, num_ch_utilize):
+        """float32 [L, M_all] -> (the microphone indices [0:M:M // num_ch_utilize] (data.py:544), the recording as float32)"""
         obs = np.asarray(wav_observe, dtype=np.float32)
         if obs.ndim != 2 or obs.shape[0] <= obs.shape[1]:
             raise ValueError("wav_observe must be [n_samples, n_mics] with n_samples > n_mics (data.py:510)")
-        L, M_all = obs.shape
+        M_all = obs.shape[1]
         n_use = self.num_ch if num_ch_utilize is None else int(num_ch_utilize)
         if n_use < 1 or n_use > M_all:
             raise ValueError(f"num_ch_utilize must be in [1, {M_all}]")
         mics = list(range(0, M_all, M_all // n_use))                       # data.py:544: [0:M:M // num_ch_utilize]
         if len(mics) != self.num_ch:
             raise ValueError(f"[0:{M_all}:{M_all // n_use}] selects {len(mics)} microphones, the networks take {self.num_ch}")
+        return mics, obs
+
+    def _recording_chunks(self, wav_observe, wav_clean, num_ch_utilize, chunk_size):
+        """enhance_recording's loader side: microphone sub-sampling, the clean sources at ref_ch, 4 s chunks ->
+        (list of float32 [chunk, M], list of float32 [chunk, S] or None, gap)"""
+        mics, obs = self._select_mics(wav_observe, num_ch_utilize)
+        L, M_all = obs.shape
         if int(chunk_size) < 2 * S.HOP or int(chunk_size) % S.HOP:
             raise ValueError(f"chunk_size must be a multiple of the hop ({S.HOP}) and at least two hops")
         obs = obs[:, mics]
@@ -649,11 +657,109 @@ class Enhancer:
         """the K int16 chunks [S, chunk] of one recording -> stitched int16 [S, L]; ``save_path``: the PCM-24 files"""
         out = np.stack([S.stitch_int16([p[s] for p in pcm_chunks], gap) for s in range(self.num_spks)])
         if save_path is not None:
-            import os
-            os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
-            for s in range(self.num_spks):
-                S.write_wav_pcm24(f"{save_path}_{s}.wav", out[s], fs)
+            self._write_speakers(out, save_path, fs)
         return out
+
+    def _write_speakers(self, out, save_path, fs):
+        """int16 [S, L] -> ``<save_path>_{s}.wav`` as 24-bit PCM (tester.py:972-974)"""
+        import os
+        os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
+        for s in range(self.num_spks):
+            S.write_wav_pcm24(f"{save_path}_{s}.wav", out[s], fs)
+
+    def enhance_continuous(self, wav_observe, num_ch_utilize: Optional[int] = None, window: int = 64000,
+                           hop: Optional[int] = None, max_batch: int = 16, save_path: Optional[str] = None,
+                           fs: int = 16000, return_perms: bool = False):
+        """A long recording WITHOUT clean references -> one speaker per output from start to end (continuous separation).
+
+        wav_observe float32 [L, M_all] (as :meth:`enhance_recording` takes it; same microphone sub-sampling).  The recording
+        is cut into windows of ``window`` samples at a hop of ``hop`` (default window // 2; both multiples of 64,
+        window/2 <= hop <= window - 256: :func:`css.plan_windows`), the last one zero-padded.  Every window goes through the
+        fused pass without clean sources (STFT -> MISO1 x M -> shift alignment -> MVDR x S -> MISO3 x S, bit for bit what
+        :meth:`enhance_wav` returns for it alone); the speaker order of window k is linked to window k-1 through their
+        shared frames (``misonet_css_align``: the reference's alignment metric over the overlap, composed along the
+        recording, so the output order is window 0's) and the windows' waveforms are joined by a raised-cosine cross-fade
+        over the overlap (``misonet_css_stitch``).  Windows run in batches of at most ``max_batch`` plus the window carried
+        over from the previous batch: device memory depends on ``max_batch``, not on the recording's length, the host waits
+        only for the oldest of two batches in flight, and the result does not depend on ``max_batch``.
+
+        Returns int16 [S, L] (ndarray) and, with ``return_perms``, P int32 [K, S] (output speaker s of window k = MISO3
+        output P[k, s] of that window).  ``save_path`` also writes ``<save_path>_{s}.wav`` as 24-bit PCM.  A NaN raises
+        FloatingPointError naming the first window that produced it."""
+        import collections
+        from . import css
+        self._ready()
+        if self.model is None:
+            raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
+        mics, obs = self._select_mics(wav_observe, num_ch_utilize)
+        L = obs.shape[0]
+        W = int(window)
+        H = W // 2 if hop is None else int(hop)
+        _, K, Lp = css.plan_windows(L, W, H)
+        nb_max = max(1, int(max_batch))
+        M, Sp, T, F = self.num_ch, self.num_spks, W // S.HOP + 1, N_FREQ
+        padded = np.zeros((Lp, M), dtype=np.float32)
+        padded[:L] = obs[:, mics]
+        dev, lib = self.device, _lib.lib()
+        out = np.empty((Sp, L), dtype=np.int16)
+        with torch.cuda.device(dev):
+            # row 0 of est / y / perm: the window carried over from the previous batch (its spectrogram, waveform and P)
+            est = torch.empty((nb_max + 1, Sp, T, F), dtype=torch.complex64, device=dev)
+            y = torch.empty((nb_max + 1, Sp, W), dtype=torch.float32, device=dev)
+            perm = torch.empty((nb_max + 1, Sp), dtype=torch.int32, device=dev)
+            dist = torch.empty(max(8, css.scratch_bytes(nb_max + 1, Sp, F)), dtype=torch.uint8, device=dev)
+            perms = torch.empty((K, Sp), dtype=torch.int32, device=dev)
+
+            def compute_for(lo, hi):
+                def compute(wav):
+                    nb, c = hi - lo, (1 if lo else 0)         # c: row of window lo
+                    n = c + nb
+                    st = _lib.stream_ptr(dev)
+                    ws = self.workspace(nb, T)
+                    _lib.check(lib.misonet_pipeline_run_wav(self._pipe, wav.data_ptr(), None, nb, W, est[c].data_ptr(), None,
+                                                            None, ws.data_ptr(), ws.numel(), st))
+                    flag = ws[:4].view(torch.int32).clone()
+                    css.align(est[:n], H // S.HOP, perm0=perm[0] if c else None, perm=perm[:n], dist=dist)
+                    _lib.check(lib.misonet_istft(est[c].data_ptr(), nb * Sp, T, None, y[c].data_ptr(), st))
+                    pcm = css.stitch(y[:n], perm[:n], H, c == 0, (L if hi == K else hi * H) - lo * H)
+                    perms[lo:hi].copy_(perm[c:n])
+                    if hi < K and n > 1:
+                        est[0].copy_(est[n - 1])
+                        y[0].copy_(y[n - 1])
+                        perm[0].copy_(perm[n - 1])
+                    return pcm, flag
+                return compute
+
+            ov = _Overlapped(dev, 2)
+            pending = collections.deque()
+
+            def finish(rec, lo, hi):
+                pcm, nan = ov.finish(rec)
+                if nan:
+                    raise FloatingPointError(self._nan_window(padded, lo, hi, W, H))
+                out[:, lo * H: lo * H + pcm.shape[1]] = pcm
+
+            for i, lo in enumerate(range(0, K, nb_max)):
+                hi = min(K, lo + nb_max)
+                while len(pending) >= ov.depth:
+                    finish(*pending.popleft())
+                wav_h = torch.from_numpy(np.stack([padded[k * H: k * H + W] for k in range(lo, hi)]))
+                pending.append((ov.submit(i, (wav_h,), compute_for(lo, hi)), lo, hi))
+            while pending:
+                finish(*pending.popleft())
+            P = perms.cpu().numpy() if return_perms else None
+        if save_path is not None:
+            self._write_speakers(out, save_path, fs)
+        return (out, P) if return_perms else out
+
+    def _nan_window(self, padded, lo, hi, W, H):
+        """the message of a NaN in the batch of windows lo..hi-1: those windows again, one at a time, to name the first"""
+        for k in range(lo, hi):
+            try:
+                self.enhance_wav(torch.from_numpy(padded[k * H: k * H + W][None].copy()).to(self.device), None)
+            except FloatingPointError:
+                return f"libmisonet_hip: NaN in pipeline output of window {k} (samples {k * H}..{k * H + W} of the recording)"
+        return f"libmisonet_hip: NaN in pipeline output of windows {lo}..{hi - 1}"
 
     def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
