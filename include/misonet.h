@@ -107,6 +107,13 @@ int misonet_net_keep_activations(misonet_net* net, int keep);
  * a negative error.  tests/test_lib_abi.py checks that buffers alive at the same step never overlap. */
 int misonet_net_buffer_plan(const misonet_net* net, int n_frames, int max_buffers, long long* offset_bytes,
                             long long* size_bytes, int* first_step, int* last_step);
+/* diagnostic (host only, no GPU; ABI 470): which kernel runs each of the network's 3x3 conv layers in precision mode `mode` --
+ * the encoder stack, then the decoder stack, in launch order (64 layers).  The choice is made once, when the net is created,
+ * from the layer shapes alone; a forward launches exactly these kernels or fails (there is no fall-back).  kind[i]:
+ * 0 DIRECT (conv3x3_mfma, exact f32), 1 W1D (the same kernel in 1-D Winograd form along T), 2 FEW (conv3x3_few), 3 WINO
+ * (conv3x3_wino_f32), 4 X6_FIRST (conv3x3_x6_first), 5 X6 (conv3x3_bf16x6); experiment build only: 6 BF16, 7 BF16_DMA, 8 WINO6.
+ * Returns the number of layers written (<= max_layers), or MISONET_EINVAL for a mode this build of the library does not have. */
+int misonet_net_conv_plan(const misonet_net* net, int mode, int max_layers, int* kind);
 /* test/diagnostic taps: copy an intermediate activation of the LAST forward (still in ws_dev) out as float32
  * [B, C, T, F] in the reference's layout and normalisation.  Names: enc0_conv, enc0..enc6, tcn_out, dec0..dec6.
  * Needs misonet_net_keep_activations(net, 1) BEFORE that forward (MISONET_ESTATE otherwise), except dec6 (the output). */

@@ -17,7 +17,7 @@
 //   ConvTranspose2d s(1,2) p(1,0)                   model.py:67,71        tr2: flipped taps, fin=(f+kf-2)/2 if even
 // Epilogue: + bias, ELU (model.py:412,429,444), raw store, per-(n,co) sum / sum^2 for the instance norm that the
 // NEXT layer applies while staging (model.py:413,430,445).
-#include "kernels.hpp"
+#include "conv_select.hpp"
 #include <stdlib.h>
 #include "conv_epilogue.hpp"
 
@@ -633,42 +633,61 @@ int conv_xcd_env() {
   return v;
 }
 
-hipError_t launch_conv(const ConvArgs& a_in, int n_samples, hipStream_t s) {
+// the kernel's MODE of a layer: 0 stride 1, 1 frequency stride 2, 2 stride-2 transposed, 3 the stride-1 transposed conv on the single
+// bottleneck row (decoder 0: one tap per output row)
+template <class S> static int conv_mode(const S& a) { return a.tr2 ? 2 : (a.sf == 2 ? 1 : ((a.padf == 2 && a.Fin == 1 && !a.out_oct) ? 3 : 0)); }
+// one output row (the encoder's last layer, 64 -> 128 channels on F = 3 -> 1, model.py:50) of the W1D form, MODE 4
+static bool w1d_row(const ConvShape& s) { return !s.tr2 && s.act && s.Fout == 1 && s.Fin == 3 && s.padf == 0 && s.Cout % 128 == 0; }
+
+// W1D takes the activated MODE 1 / 2 / 3 layers, the one-row layer above, and a network's first layer (12 / 16 -> 24 channels: the
+// only shape that may come without activation); planar float32 on both sides
+bool conv_w1d_ok(const ConvShape& s) {
+  if (s.in_oct || s.out_oct) return false;
+  if (conv_mode(s) != 0) return s.act;
+  return !s.transposed && ((s.Cout <= 32 && s.Cin < 3 * CK) || w1d_row(s));
+}
+
+// XCD-aware order deals whole SAMPLES to the 8 XCDs (n % 8 == xcd): with a sample count that is not a multiple of 8 some
+// XCDs get nothing (B = 1: MISO3 runs 2 samples -> 6 of 8 XCDs idle, the first layer took 114 us instead of ~30); the
+// natural (t, f, n) grid is used then
+static int conv_xcd(int n_samples) { return (n_samples % 8 == 0) ? conv_xcd_env() : 0; }
+
+// f32w: the frequency-strided layers (and the first layer) in 1-D Winograd form along T (32-channel groups, 4-row tiles)
+hipError_t launch_conv_w1d(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
-  // XCD-aware order deals whole SAMPLES to the 8 XCDs (n % 8 == xcd): with a sample count that is not a multiple of 8 some
-  // XCDs get nothing (B = 1: MISO3 runs 2 samples -> 6 of 8 XCDs idle, the first layer took 114 us instead of ~30); the
-  // natural (t, f, n) grid is used then
-  const int mode = a.tr2 ? 2 : (a.sf == 2 ? 1 : ((a.padf == 2 && a.Fin == 1 && !a.out_oct) ? 3 : 0));
-  const bool w1d_first = mode == 0 && a.Cout <= 32 && a.Cin < 3 * CK;   // (a network's first layer: 12 / 16 -> 24 channels)
-  const bool w1d_half = ((a.Cin - 1) % CK) < CK / 2;
-  const bool w1d_row = (mode == 0 || mode == 1) && a.act && a.Fout == 1 && a.Fin == 3 && a.padf == 0 && a.Cout % 128 == 0;   // (encoder 6: F = 3 -> 1)
-  if (a.w1d && (a.act || w1d_first) && (mode == 1 || mode == 2 || mode == 3 || w1d_first || w1d_row) && !a.out_oct && !a.in_oct) {
-    // f32w: the frequency-strided layers (and the first layer) in 1-D Winograd form along T (32-channel groups, 4-row tiles)
-    a.cop = 32;
-    a.ncg = (a.Cout + 31) / 32;
-    if (w1d_row) {
-      // one output row (the encoder's last layer, 64 -> 128 channels on F = 3 -> 1, model.py:50): a row per wave would leave three of
-      // four waves idle -- the waves take a 32-channel group each (MODE 4), the staged input serves all four.  The three staged rows
-      // are the three frequency taps whatever the stride
-      a.ncg = a.Cout / 128;
-      a.NR = 3;
-      const dim3 grid4 = conv_grid(a, n_samples, TT, FT, (n_samples % 8 == 0) ? conv_xcd_env() : 0);
-      hipLaunchKernelGGL((conv3x3_mfma<1, 4, 0, false, true>), grid4, dim3(256), conv_lds_bytes(3, 128, a.Cin, 12), s, a);
-      return hipGetLastError();
-    }
-    a.NR = mode == 1 ? 9 : (mode == 2 ? 3 : (mode == 3 ? 1 : 6));
-    const dim3 gridw = conv_grid(a, n_samples, TT, FT, (n_samples % 8 == 0) ? conv_xcd_env() : 0);
-    const size_t ldsw = conv_lds_bytes(a.NR, 32, a.Cin, 12);
-    if (mode == 1) hipLaunchKernelGGL((conv3x3_mfma<1, 1, 0, false, true>), gridw, dim3(256), ldsw, s, a);
-    else if (mode == 2) hipLaunchKernelGGL((conv3x3_mfma<1, 2, 0, false, true>), gridw, dim3(256), ldsw, s, a);
-    else if (mode == 3) hipLaunchKernelGGL((conv3x3_mfma<1, 3, 0, false, true>), gridw, dim3(256), ldsw, s, a);
-    else if (w1d_half) hipLaunchKernelGGL((conv3x3_mfma<1, 0, 0, true, true>), gridw, dim3(256), ldsw, s, a);
-    else hipLaunchKernelGGL((conv3x3_mfma<1, 0, 0, false, true>), gridw, dim3(256), ldsw, s, a);
+  const ConvShape sh = conv_shape(a);
+  if (!conv_w1d_ok(sh) || !a.w1d) return hipErrorInvalidValue;
+  const int mode = conv_mode(a);
+  a.cop = 32;
+  a.ncg = (a.Cout + 31) / 32;
+  if (w1d_row(sh)) {
+    // a row per wave would leave three of four waves idle -- the waves take a 32-channel group each (MODE 4), the staged input
+    // serves all four.  The three staged rows are the three frequency taps whatever the stride
+    a.ncg = a.Cout / 128;
+    a.NR = 3;
+    const dim3 grid4 = conv_grid(a, n_samples, TT, FT, conv_xcd(n_samples));
+    hipLaunchKernelGGL((conv3x3_mfma<1, 4, 0, false, true>), grid4, dim3(256), conv_lds_bytes(3, 128, a.Cin, 12), s, a);
     return hipGetLastError();
   }
+  a.NR = mode == 1 ? 9 : (mode == 2 ? 3 : (mode == 3 ? 1 : 6));
+  const dim3 gridw = conv_grid(a, n_samples, TT, FT, conv_xcd(n_samples));
+  const size_t ldsw = conv_lds_bytes(a.NR, 32, a.Cin, 12);
+  const bool w1d_half = ((a.Cin - 1) % CK) < CK / 2;
+  if (mode == 1) hipLaunchKernelGGL((conv3x3_mfma<1, 1, 0, false, true>), gridw, dim3(256), ldsw, s, a);
+  else if (mode == 2) hipLaunchKernelGGL((conv3x3_mfma<1, 2, 0, false, true>), gridw, dim3(256), ldsw, s, a);
+  else if (mode == 3) hipLaunchKernelGGL((conv3x3_mfma<1, 3, 0, false, true>), gridw, dim3(256), ldsw, s, a);
+  else if (w1d_half) hipLaunchKernelGGL((conv3x3_mfma<1, 0, 0, true, true>), gridw, dim3(256), ldsw, s, a);
+  else hipLaunchKernelGGL((conv3x3_mfma<1, 0, 0, false, true>), gridw, dim3(256), ldsw, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_conv(const ConvArgs& a_in, int n_samples, hipStream_t s) {
+  ConvArgs a = a_in;
+  if (!a.w) return hipErrorInvalidValue;
+  const int mode = conv_mode(a);
   a.NR = mode == 3 ? 1 : (mode == 0 ? 6 : f32_rows(a));
   if (mode == 2 && a.cop != 32) return hipErrorInvalidValue;   // (net.hip packs stride-2 transposed layers in 32-channel groups)
-  const dim3 grid = conv_grid(a, n_samples, TT, mode == 2 ? 2 * FT : FT, (n_samples % 8 == 0) ? conv_xcd_env() : 0);
+  const dim3 grid = conv_grid(a, n_samples, TT, mode == 2 ? 2 * FT : FT, conv_xcd(n_samples));
   const size_t lds = conv_lds_bytes(a.NR, a.cop, a.Cin);
 #define MN_LAUNCH(NCO, MODE) hipLaunchKernelGGL((conv3x3_mfma<NCO, MODE>), grid, dim3(256), lds, s, a)
 #define MN_LAUNCH3(NCO, MODE) hipLaunchKernelGGL((conv3x3_mfma<NCO, MODE, 3>), grid, dim3(256), lds, s, a)

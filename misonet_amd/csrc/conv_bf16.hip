@@ -294,6 +294,7 @@ hipError_t conv_bf16_init() {
 
 hipError_t launch_conv_bf16(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
+  a.NR = conv_rows(a.sf, a.tr2);
   {
     static int dbg = -1;
     if (dbg < 0) dbg = exp_env("MISONET_WS_DEBUG", 0);
@@ -302,7 +303,7 @@ hipError_t launch_conv_bf16(const ConvArgs& a_in, int n_samples, hipStream_t s) 
   const dim3 grid = conv_grid(a, n_samples, TT, FT, conv_xcd_env());
   const size_t lds = bf_lds_bytes(a.NR, a.cop, a.Cin);
   const int mode = a.tr2 ? 2 : (a.sf == 2 ? 1 : 0);
-  if (a.NR != conv_rows(a.sf, a.tr2) || !a.w16) return hipErrorInvalidValue;
+  if (!a.w16) return hipErrorInvalidValue;
   static int tl_env = -1;
   static int tl_done = 0;
   static unsigned long long* tl_buf = nullptr;

@@ -852,7 +852,7 @@ hipError_t launch_conv_bf16_dma(const ConvArgs& a_in, int n_samples, hipStream_t
   if (a.in_oct != 1 && a.in_oct != 4) return hipErrorInvalidValue;
   if (a.out_oct && a.out_oct != a.in_oct) return hipErrorInvalidValue;       // same piece format on both sides
   const bool f16 = a.in_oct == 4;
-  if (a.NR != conv_rows(a.sf, a.tr2)) return hipErrorInvalidValue;
+  a.NR = conv_rows(a.sf, a.tr2);
   {
     static int dbg = -1;
     if (dbg < 0) dbg = exp_env("MISONET_WS_DEBUG", 0);

@@ -33,7 +33,7 @@
 //     and for F <= 4.  The 8-row tile stages 25 % fewer bytes per MFMA than the 4-row tile of the first version (10
 //     rows per 8 instead of 6 per 4, one weight image per 216 instead of 108 MFMAs), which is what makes a chunk
 //     MFMA-bound (see below).
-#include "kernels.hpp"
+#include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 #include "conv_bf16_core.hpp"
 #include <stdio.h>
@@ -861,10 +861,15 @@ __global__ __launch_bounds__(256, 3) void conv3x3_x6_first(const ConvArgs a, con
 #endif
 }
 
+// the first layer: the planar network input, consumed un-normalised, <= 16 in / <= 32 out channels, no activation
+bool conv_x6_first_ok(const ConvShape& s) {
+  return s.net_input && !s.in_oct && !s.transposed && s.sf == 1 && !s.tr2 && !s.act && s.Cin <= 16 && s.Cout <= 32 && s.ident_c >= s.Cin &&
+         (s.out_oct == 0 || s.out_oct == 3);
+}
+
 hipError_t launch_conv_x6_first(const ConvArgs& a_in, const void* wimg, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
-  if (a.in_oct || a.sf != 1 || a.tr2 || a.act || a.Cin > 16 || a.Cout > 32 || a.ident_c < a.Cin || !wimg) return hipErrorInvalidValue;
-  if (a.out_oct && a.out_oct != 3) return hipErrorInvalidValue;
+  if (!conv_x6_first_ok(conv_shape(a, true)) || !wimg) return hipErrorInvalidValue;   // (the caller vouches for the network input)
   static const int dbg = exp_env("MISONET_WS_DEBUG", 0);
   a.dbg = dbg;
   const dim3 grid((a.T + TT - 1) / TT, (a.Fout + 3) / 4, n_samples);

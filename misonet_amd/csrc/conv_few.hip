@@ -15,7 +15,7 @@
 // Workgroup = 4 waves = 16 output rows x 128 frames; wave w owns rows 4 w .. 4 w + 3, lane l frames 2 l, 2 l + 1.  K-chunks
 // of 4 input channels are staged [4][18][132] (instance norm applied on the way, zero padding after it -- the reference's
 // order) into a double-buffered LDS tile; the global loads of chunk k + 1 are in flight while chunk k is computed.
-#include "kernels.hpp"
+#include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 
 namespace mn {
@@ -209,9 +209,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_few(const ConvArgs a) {
   }
 }
 
-bool conv_few_ok(const ConvArgs& a) {
-  return a.wsm != nullptr && !a.act && (a.Cout == 2 || a.Cout == 4) && a.sf == 1 && !a.tr2 && (a.Cin % FW_CK) == 0 && a.Cin <= FW_NRM_MAX &&
-         !a.in_oct && !a.out_oct && a.Fout == a.Fin + 2 * a.padf - 2;
+bool conv_few_ok(const ConvShape& s) {
+  return !s.act && (s.Cout == 2 || s.Cout == 4) && s.sf == 1 && !s.tr2 && (s.Cin % FW_CK) == 0 && s.Cin <= FW_NRM_MAX &&
+         !s.in_oct && !s.out_oct && s.Fout == s.Fin + 2 * s.padf - 2;
 }
 
 static size_t few_lds_bytes(int Cin) { return (size_t)(2 * FW_STAGE) * sizeof(float) + (size_t)Cin * sizeof(float2); }
@@ -224,7 +224,7 @@ hipError_t conv_few_init() {
 
 hipError_t launch_conv_few(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
-  if (!conv_few_ok(a)) return hipErrorInvalidValue;
+  if (!conv_few_ok(conv_shape(a)) || !a.wsm) return hipErrorInvalidValue;
   a.ncg = 1;
   const dim3 grid = conv_grid(a, n_samples, TT, FW_RT, (n_samples % 8 == 0) ? conv_xcd_env() : 0);
   const size_t lds = few_lds_bytes(a.Cin);

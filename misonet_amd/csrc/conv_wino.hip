@@ -35,7 +35,7 @@
 // entry instead of being masked, the weights go global -> LDS by DMA, frame masks exist only in the two ragged column tiles.
 // Epilogue: inverse transform per lane (the 16 positions of a (channel, tile) are 16 accumulator registers of ONE lane),
 // + bias, ELU, centring, 8-byte stores along T, exact statistics (det_stats.hpp) as in conv_epilogue.hpp.
-#include "kernels.hpp"
+#include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 #include "wino_regs.hpp"
 #include <stdio.h>
@@ -829,9 +829,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
 // (act: every DenseBlock conv is followed by ELU + InstanceNorm, model.py:444-445 -- the epilogue has no other form.
 // Cin >= 24: every sample then contributes >= 3 consecutive chunks to a workgroup's stream, which is what the two-parity
 // s_nrm table and the look-back of the DMA waits assume; the network's DenseBlock layers have 24 ... 192 input channels)
-bool conv_wino_ok(const ConvArgs& a) {
-  return a.act && a.Cin >= 3 * WCK && a.Cout <= WCO_MAX && a.sf == 1 && a.padf == 1 && !a.tr2 && a.Fin == a.Fout && (a.Cin % WCK) == 0 && a.Cin <= WNRM_MAX && !a.in_oct &&
-         !a.out_oct && a.ww != nullptr;
+bool conv_wino_ok(const ConvShape& s) {
+  return s.act && s.Cin >= 3 * WCK && s.Cout <= WCO_MAX && s.sf == 1 && s.padf == 1 && !s.tr2 && s.Fin == s.Fout && (s.Cin % WCK) == 0 && s.Cin <= WNRM_MAX && !s.in_oct &&
+         !s.out_oct;
 }
 
 #ifdef MISONET_EXPERIMENTS
@@ -858,7 +858,7 @@ hipError_t conv_wino_init() {
 static hipError_t launch_wino_groups(ConvArgs a, int n_samples, hipStream_t s, bool g16);
 
 hipError_t launch_conv_wino(const ConvArgs& a_in, int n_samples, hipStream_t s) {
-  if (!conv_wino_ok(a_in)) return hipErrorInvalidValue;
+  if (!conv_wino_ok(conv_shape(a_in)) || !a_in.ww) return hipErrorInvalidValue;
   // A layer whose channel count leaves a 16-channel group (the 48-channel dec6.db.c5) runs as two launches: its full 32-channel
   // groups on the 32-row body, the last 16 channels on the 16-row body (a.ww16: their own weight image) -- half of a 32-row
   // MFMA would be padding there.

@@ -28,7 +28,7 @@
 // per position row: it publishes the next row's U quarter (and, in row 2, the next K-step's input) and frees the quarter
 // before; behind it the wave queues the quarter of the same row of the next K-step (and, in row 3, the input two K-steps
 // ahead).
-#include "kernels.hpp"
+#include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 #include "wino_regs.hpp"
 #include <stdio.h>
@@ -500,9 +500,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_x6(const ConvArgs a) {
   }
 }
 
-bool conv_wino6_ok(const ConvArgs& a) {
-  return a.Cin >= 24 && a.Cout <= 128 && a.sf == 1 && a.padf == 1 && !a.tr2 && a.Fin == a.Fout && (a.Cin % 8) == 0 && a.Cin <= XNRM_MAX && !a.in_oct &&
-         !a.out_oct && a.ww6 != nullptr;
+bool conv_wino6_ok(const ConvShape& s) {
+  return s.Cin >= 24 && s.Cout <= 128 && s.sf == 1 && s.padf == 1 && !s.tr2 && s.Fin == s.Fout && (s.Cin % 8) == 0 && s.Cin <= XNRM_MAX && !s.in_oct &&
+         !s.out_oct;
 }
 
 #ifdef MISONET_EXPERIMENTS
@@ -525,7 +525,7 @@ hipError_t conv_wino6_init() {
 
 hipError_t launch_conv_wino6(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
-  if (!conv_wino6_ok(a)) return hipErrorInvalidValue;
+  if (!conv_wino6_ok(conv_shape(a)) || !a.ww6) return hipErrorInvalidValue;
   a.cop = 32;
   a.ncg = (a.Cout + 31) / 32;
   const int cus = device_cus();

@@ -58,7 +58,7 @@ struct ConvArgs {
   int padf;                 // frequency zero padding of the conv form (0, 1, or 2 for a stride-1 transposed conv)
   int tr2;                  // 1: stride-2 transposed conv (fin = (f + kf - 2) / 2 when even)
   int act;                  // 1: ELU + statistics for the following instance norm; 0: raw output
-  int NR;                   // staged input rows per workgroup
+  int NR;                   // staged input rows per workgroup (set by the launcher)
   int ncg;                  // output-channel groups (grid.z = n_samples * ncg)
   int cop;                  // 32 or 64 output channels per group
   // "oct" activation layout of the bf16x3 DMA dataflow (conv_bf16_dma.hip): per sample [hi | lo] halves, each
@@ -113,19 +113,20 @@ inline dim3 conv_grid(ConvArgs& a, int n_samples, int tt, int ft, int xcd) {
 int conv_xcd_env();                          // MISONET_XCD (default 1)
 int device_cus();                            // compute units of the CURRENT device (cached per device, thread-safe); <= 0 on error
 int conv_cop(int Cout);                      // 32 (Cout <= 32) or 64
-int conv_rows(int sf, int tr2);              // NR for the mode
-hipError_t launch_conv(const ConvArgs& a, int n_samples, hipStream_t s);
+int conv_rows(int sf, int tr2);              // staged rows of the row-per-wave geometry (conv_bf16*.hip)
+// Which of these launchers runs a layer: conv_select.hpp (one ConvKind per layer and arithmetic mode, with the launchers' own guards).
+// Every launcher answers hipErrorInvalidValue to a layer its kernel does not take, and sets ConvArgs::NR itself.
+hipError_t launch_conv(const ConvArgs& a, int n_samples, hipStream_t s);       // any shape (needs a.w)
+// f32w, the frequency-strided layers and the first layer in 1-D Winograd form along T (conv.hip W1D; needs a.w1d)
+hipError_t launch_conv_w1d(const ConvArgs& a, int n_samples, hipStream_t s);
 hipError_t conv_init();                      // dynamic-LDS attributes
-// Winograd F(2x2, 3x3) on the fp32 matrix cores for the stride-1 same-padded layers (conv_wino.hip; precision mode "f32w")
-bool conv_wino_ok(const ConvArgs& a);
+// Winograd F(2x2, 3x3) on the fp32 matrix cores for the stride-1 same-padded layers (conv_wino.hip; precision mode "f32w"; needs a.ww)
 hipError_t launch_conv_wino(const ConvArgs& a, int n_samples, hipStream_t s);
 hipError_t conv_wino_init();
 // <= 4 output channels, stride 1, no activation (the network's last layer) on the vector ALU (conv_few.hip; needs a.wsm)
-bool conv_few_ok(const ConvArgs& a);
 hipError_t launch_conv_few(const ConvArgs& a, int n_samples, hipStream_t s);
 hipError_t conv_few_init();
-bool conv_wino6_ok(const ConvArgs& a);
-hipError_t launch_conv_wino6(const ConvArgs& a, int n_samples, hipStream_t s);
+hipError_t launch_conv_wino6(const ConvArgs& a, int n_samples, hipStream_t s);   // conv_wino6.hip (needs a.ww6)
 hipError_t conv_wino6_init();
 hipError_t launch_conv_bf16(const ConvArgs& a, int n_samples, hipStream_t s);   // conv_bf16.hip (needs a.w16)
 hipError_t conv_bf16_init();

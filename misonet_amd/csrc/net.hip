@@ -1,6 +1,6 @@
-// Host runtime of libmisonet_hip.so: layer plan of a MISO trunk (reference model.py:8-111 / 282-395), weight
-// repacking into the kernels' layouts, workspace layout, forward scheduling, and the C ABI of include/misonet.h.
-#include "kernels.hpp"
+// Host runtime of libmisonet_hip.so: layer plan of a MISO trunk (reference model.py:8-111 / 282-395), the weight arena (the
+// images themselves: conv_weights.hip), workspace layout, forward scheduling, and the C ABI of include/misonet.h.
+#include "conv_select.hpp"
 #include "../../include/misonet.h"
 
 #include <math.h>
@@ -111,17 +111,12 @@ struct ConvL {
   bool transposed;
   int wt, bt;                   // tensor indices
   int cop, ncg;
-  long long w_off = 0, b_off = 0;   // offsets (floats) into the device weight arena
-  long long w16_off = 0;            // offset (floats) of the bf16 hi/lo packed weights
-  long long wf_off = 0;             // offset (floats) of the float32 weights in bf16-image order (conv_wprep_k source)
-  long long wf6_off = 0;            // offset (floats) of the float32 weights [cg][chunk of 8][tap][32][8] (conv_wprep6_k source)
-  long long w6s_off = -1;           // first layer only: offset (floats) of the SHARED 3-part bf16 image [chunk][864 units]
-  long long ww_off = -1;            // stride-1 same-padded layers: offset (floats) of the Winograd-domain weights (conv_wino.hip)
-  long long ww6_off = -1;           // the same in three bf16 pieces (conv_wino6.hip)
-  long long ww16_off = -1;          // Cout % 32 == 16: Winograd image of the last 16 channels for the 16-row body (conv_wino.hip G16)
-  long long w1d_off = -1;           // stride-2 convs / transposed convs: 1-D Winograd image along T (conv.hip W1D; f32w mode)
-  long long wsm_off = -1;           // <= 4 output channels, no activation (the last layer): [Cin][9][4] image of conv_few.hip
+  ConvKind kind[CONV_NMODES];       // the layer's kernel per precision mode of the build (conv_select.hpp), filled by build_plan
+  long long img_off[CONV_NKIND];    // commit: offset (floats) into the device weight arena of the image of each kind that occurs in
+                                    // kind[] (and of DIRECT, always); -1: not packed
+  long long b_off = 0;              // ... and of the bias [ncg * cop]
   float wscale = 1.f;               // f16x3: power of two that brings max |W| of the layer to [32, 64)
+  const float* img(const float* w_dev, ConvKind k) const { return w_dev + img_off[(int)k]; }
 };
 
 struct TcnHalf {
@@ -167,17 +162,7 @@ struct misonet_net {
                                  // default: fp32-faithful, what bench.py reports), 4: f16x3 DMA dataflow, 5: f32 MFMA with the
                                  // dense-block convs in Winograd F(2x2, 3x3) form ("f32w": planar float32 layout like mode 0)
 };
-// Product arithmetic modes: 0 "f32", 3 "bf16x6", 5 "f32w".  The measured alternatives that earn nothing (1 / 2 "bf16x3": 16-bit
-// operands, 4 "f16x3": 22-bit operands, 6 "bf16x6w": correct but slower than mode 3 -- DESIGN 3.4) exist only in the experiment
-// build (`make exp`): their kernels (conv_bf16.hip, conv_bf16_dma.hip, conv_wino6.hip), weight images and dispatch are compiled
-// out of the product library, which answers MISONET_EINVAL to them.
-#ifdef MISONET_EXPERIMENTS
-#define MN_ALT_MODES 1
-#else
-#define MN_ALT_MODES 0
-#endif
-// the planar-float32 modes: every activation buffer is float32 [c][f][Tp], instance norm applied while staging
-static inline bool planar_f32(const misonet_net* n) { return n->precision == 0 || n->precision == 5 || n->precision == 6; }
+// (the modes of this build, product 0 / 3 / 5 or all seven: conv_select.hpp conv_mode_built)
 
 static int find_tensor(const misonet_net* n, const std::string& name) {
   for (size_t i = 0; i < n->tensors.size(); ++i)
@@ -199,6 +184,7 @@ static ConvL make_conv(misonet_net* n, const std::string& prefix, int in_buf, in
   L.out_buf = out_buf; L.out_c0 = out_c0; L.Cout = Cout;
   L.transposed = transposed;
   L.act = act;
+  std::fill(L.img_off, L.img_off + CONV_NKIND, -1LL);
   if (transposed) {
     L.tr2 = (sf == 2);
     L.sf = 1;
@@ -226,6 +212,24 @@ static void add_dense(misonet_net* n, std::vector<ConvL>& v, const std::string& 
       v.push_back(make_conv(n, prefix + nm, buf, 0, cin, ident_c, out_buf, out_c0, g2, 1, 1, false, 1));
   }
 }
+
+// precision 2 ("bf16x3") and 3 ("bf16x6"), the DMA dataflows: the dense-block buffers and everything between them travel
+// in the oct layout (2 bf16 parts = the bytes of float32, or 3 parts = 6 bytes per element); the network input/output
+// and the TCN stay planar float32, and so do the F <= 3 bottleneck buffers except in bf16x6.  Returns the ConvArgs::in_oct /
+// out_oct code.
+static inline int buf_oct(int precision, int b) {
+  if (precision < 2 || precision >= 5) return 0;
+  const bool o = (b >= B_E0 && b <= B_E4) || (b >= B_D2 && b <= B_D6) || (b >= B_X2 && b <= B_X6);
+  // bf16x6 also keeps the F <= 3 bottleneck buffers D0 / D1 in its layout (the TCN reads / writes it at its two ends), so
+  // that encoder 6 and decoders 0-1 run on the persistent kernel instead of the one-row-per-wave f32 kernel
+  if (precision == 3 && (b == B_D0 || b == B_D1)) return 3;
+  // f16x3: the first dense-block buffer holds the RAW first-layer output (un-normalised, its scale follows the input), which
+  // two fp16 pieces cannot carry for every input scale nor to 24 bits: it stays in the exact three-bf16 layout and the
+  // layers that read it run on the bf16x6 kernel (its last conv writes the fp16 layout of the next buffer)
+  if (precision == 4 && b == B_E0) return 3;
+  return o ? (precision == 3 ? 3 : (precision == 4 ? 4 : 1)) : 0;
+}
+static inline int buf_oct(const misonet_net* n, int b) { return buf_oct(n->precision, b); }
 
 static int freq_after_conv(int F, int sf) { return (F - 3) / sf + 1; }
 
@@ -343,27 +347,22 @@ static int build_plan(misonet_net* n) {
     n->taps.push_back({nm, B_D0 + i + 1, 0, de[i + 1], true});
   }
   n->taps.push_back({"dec6", B_OUT, 0, c.out_ch, false});
+  // ---- the kernel of every conv layer in every arithmetic mode of the build ----
+  // (MISONET_X6_FIRST=0, experiment build: the first layer of the bf16x6 / f16x3 networks on the exact-f32 kernel of rounds 1-3)
+  static const int x6first_env = exp_env("MISONET_X6_FIRST", 1);
+  for (std::vector<ConvL>* v : {&n->enc, &n->dec})
+    for (ConvL& l : *v)
+      for (int mode = 0; mode < CONV_NMODES; ++mode) {
+        const ConvShape sh = {l.Cin, l.Cout, n->bufs[l.in_buf].F, n->bufs[l.out_buf].F, l.sf, l.padf, l.tr2, l.act, l.transposed,
+                              l.ident_c, l.in_buf == B_IN, buf_oct(mode, l.in_buf), buf_oct(mode, l.out_buf)};
+        l.kind[mode] = conv_mode_built(mode) ? conv_select(sh, mode) : ConvKind::DIRECT;
+        if (l.kind[mode] == ConvKind::X6_FIRST && !x6first_env) l.kind[mode] = ConvKind::DIRECT;
+      }
   return MISONET_OK;
 }
 
 static long long align_up(long long x, long long a) { return (x + a - 1) / a * a; }
 
-// precision 2 ("bf16x3") and 3 ("bf16x6"), the DMA dataflows: the dense-block buffers and everything between them travel
-// in the oct layout (2 bf16 parts = the bytes of float32, or 3 parts = 6 bytes per element); the network input/output
-// and the TCN stay planar float32, and so do the F <= 3 bottleneck buffers except in bf16x6.  Returns the ConvArgs::in_oct /
-// out_oct code.
-static inline int buf_oct(const misonet_net* n, int b) {
-  if (n->precision < 2 || n->precision >= 5) return 0;
-  const bool o = (b >= B_E0 && b <= B_E4) || (b >= B_D2 && b <= B_D6) || (b >= B_X2 && b <= B_X6);
-  // bf16x6 also keeps the F <= 3 bottleneck buffers D0 / D1 in its layout (the TCN reads / writes it at its two ends), so
-  // that encoder 6 and decoders 0-1 run on the persistent kernel instead of the one-row-per-wave f32 kernel
-  if (n->precision == 3 && (b == B_D0 || b == B_D1)) return 3;
-  // f16x3: the first dense-block buffer holds the RAW first-layer output (un-normalised, its scale follows the input), which
-  // two fp16 pieces cannot carry for every input scale nor to 24 bits: it stays in the exact three-bf16 layout and the
-  // layers that read it run on the bf16x6 kernel (its last conv writes the fp16 layout of the next buffer)
-  if (n->precision == 4 && b == B_E0) return 3;
-  return o ? (n->precision == 3 ? 3 : (n->precision == 4 ? 4 : 1)) : 0;
-}
 // floats one sample occupies in buffer b (an oct3 buffer holds 1.5 floats per element; C is a multiple of 8 there)
 static inline long long buf_floats(const misonet_net* n, int Tp, int b) {
   const long long e = (long long)n->bufs[b].C * n->bufs[b].F * Tp;
@@ -471,46 +470,30 @@ static inline float* buf_ptr(const Layout& L, void* ws, int b) {
 static inline dstat_t* stats_base(void* ws) { return reinterpret_cast<dstat_t*>(reinterpret_cast<char*>(ws) + 256); }
 static inline dstat_t* stats_ptr(const Layout& L, void* ws, int b) { return stats_base(ws) + L.stats_off[b]; }
 
+// launch layer c on samples [n0, n0 + nb) with the kernel the plan chose for the current mode (ConvL::kind)
 static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL& c, hipStream_t s, int n0 = 0, int nb = -1) {
-  ConvArgs a;
-  a.in = buf_ptr(L, ws, c.in_buf);
-  a.in_stats = stats_ptr(L, ws, c.in_buf);
-  a.out = buf_ptr(L, ws, c.out_buf);
-  a.out_stats = stats_ptr(L, ws, c.out_buf);
-  a.w = n->w_dev + c.w_off;
-  a.bias = n->w_dev + c.b_off;
-  a.w16 = (MN_ALT_MODES && !planar_f32(n)) ? reinterpret_cast<const unsigned short*>(n->w_dev + c.w16_off) : nullptr;
-  a.ww = (n->precision == 5 && c.ww_off >= 0) ? n->w_dev + c.ww_off : nullptr;
-  a.ww6 = (MN_ALT_MODES && n->precision == 6 && c.ww6_off >= 0) ? n->w_dev + c.ww6_off : nullptr;
-  a.wsm = (planar_f32(n) && c.wsm_off >= 0) ? n->w_dev + c.wsm_off : nullptr;
-  a.w1d = (n->precision == 5 && c.w1d_off >= 0) ? n->w_dev + c.w1d_off : nullptr;
-  a.ww16 = (n->precision == 5 && c.ww16_off >= 0) ? n->w_dev + c.ww16_off : nullptr;
+  const ConvKind kind = c.kind[n->precision];
+  if (nb < 0) nb = L.N;
+  ConvArgs a = {};
   a.in_bstride = bstride(n, L, c.in_buf);
   a.out_bstride = bstride(n, L, c.out_buf);
   a.in_sstride = n->bufs[c.in_buf].C;
   a.out_sstride = n->bufs[c.out_buf].C;
+  a.in = buf_ptr(L, ws, c.in_buf) + (long long)n0 * a.in_bstride;
+  a.out = buf_ptr(L, ws, c.out_buf) + (long long)n0 * a.out_bstride;
+  a.in_stats = stats_ptr(L, ws, c.in_buf) + (long long)n0 * a.in_sstride * 2 * DS_NL;
+  a.out_stats = stats_ptr(L, ws, c.out_buf) + (long long)n0 * a.out_sstride * 2 * DS_NL;
+  a.bias = n->w_dev + c.b_off;
   a.in_c0 = c.in_c0; a.Cin = c.Cin; a.Fin = n->bufs[c.in_buf].F; a.ident_c = c.ident_c;
   a.out_c0 = c.out_c0; a.Cout = c.Cout; a.Fout = n->bufs[c.out_buf].F;
   a.T = L.T; a.Tp = L.Tp;
   a.sf = c.sf; a.padf = c.padf; a.tr2 = c.tr2; a.act = c.act;
-  a.NR = conv_rows(c.sf, c.tr2);
-  a.ncg = c.ncg; a.cop = c.cop;
-  a.dbg = 0;
-  a.dbg_buf = nullptr;
-  a.xcd = 0; a.ntx = a.nty = a.nsamp = 0;
-  a.in_oct = a.out_oct = 0; a.wps = nullptr; a.wps_nstride = 0; a.btab = nullptr; a.btab_nstride = 0;
-  if (nb < 0) nb = L.N;
-  a.in += (long long)n0 * a.in_bstride;
-  a.out += (long long)n0 * a.out_bstride;
-  a.in_stats += (long long)n0 * a.in_sstride * 2 * DS_NL;
-  a.out_stats += (long long)n0 * a.out_sstride * 2 * DS_NL;
   a.in_oct = buf_oct(n, c.in_buf);
   a.out_oct = buf_oct(n, c.out_buf);
-  // bf16x6 / f16x3: the planar-input layers (network input, F <= 3 bottleneck) run on the exact f32 kernel
-  if (n->precision >= 3 && !a.in_oct) a.w16 = nullptr;
+  // output-channel groups: the plan's 32 or 64 channels on the direct kernel, 32 on every other (some of which regroup: conv_select.hpp)
+  a.cop = kind == ConvKind::DIRECT ? c.cop : 32;
+  a.ncg = (c.Cout + a.cop - 1) / a.cop;
   a.wscale = a.descale = 1.f;
-  if (a.in_oct == 4) { a.wscale = c.wscale; a.descale = 1.f / c.wscale; }
-  if (a.w16 || a.in_oct) { a.cop = 32; a.ncg = (c.Cout + 31) / 32; }
   // MISONET_SYNC_DEBUG=1: name every conv launch and wait for it (fault hunting)
   static const int sync_dbg = exp_env("MISONET_SYNC_DEBUG", 0);
   struct SyncDbg {
@@ -523,55 +506,51 @@ static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL
       fprintf(stderr, "%s\n", hipGetErrorString(e));
     }
   } sync_guard{s, a, sync_dbg};
-  // bf16x6 / f16x3 networks: the planar-input first layer in the bf16x6 arithmetic (MISONET_X6_FIRST=0: the exact-f32 kernel
-  // of rounds 1-3, for A/B runs)
-  static const int x6first_env = exp_env("MISONET_X6_FIRST", 1);
-  if (x6first_env && n->precision >= 3 && !a.in_oct && a.out_oct == 3 && c.w6s_off >= 0 && !a.act) {
-    ProfScope ps(s, PK_CONV);
-    HIPCHK(launch_conv_x6_first(a, n->w_dev + c.w6s_off, nb, s));
-    return MISONET_OK;
-  }
-  if (a.in_oct == 3) {
+  // the oct-input kernels read per-sample weights with the input's instance norm folded in: their prep kernel runs first
+  auto prep = [&](hipError_t (*launch_wprep)(const ConvArgs&, const float*, int, hipStream_t)) {
     a.wps = reinterpret_cast<char*>(ws) + L.wps_base + (long long)n0 * L.wps_nstride;
     a.wps_nstride = L.wps_nstride;
     a.btab = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.btab_base) + (long long)n0 * L.btab_nstride;
     a.btab_nstride = L.btab_nstride;
-    {
-      ProfScope pw(s, PK_OTHER);
-      HIPCHK(launch_conv_wprep6(a, n->w_dev + c.wf6_off, nb, s));
-    }
-    ProfScope ps(s, PK_CONV);
-    HIPCHK(launch_conv_bf16x6(a, nb, s));
-    return MISONET_OK;
-  }
+    ProfScope pw(s, PK_OTHER);                                     // its own kind: part of the step, not of the conv kernel
+    return launch_wprep(a, c.img(n->w_dev, kind), nb, s);
+  };
+  hipError_t e = hipSuccess;
+  switch (kind) {
+    case ConvKind::DIRECT: { a.w = c.img(n->w_dev, kind); ProfScope ps(s, PK_CONV); e = launch_conv(a, nb, s); } break;
+    case ConvKind::W1D: { a.w1d = c.img(n->w_dev, kind); ProfScope ps(s, PK_CONV); e = launch_conv_w1d(a, nb, s); } break;
+    case ConvKind::FEW: { a.wsm = c.img(n->w_dev, kind); ProfScope ps(s, PK_CONV); e = launch_conv_few(a, nb, s); } break;
+    case ConvKind::WINO: {
+      a.ww = c.img(n->w_dev, kind);
+      if ((c.Cout & 31) == 16) a.ww16 = a.ww + conv_wino_ww16_at(c.Cin, c.Cout);
+      ProfScope ps(s, PK_CONV);
+      e = launch_conv_wino(a, nb, s);
+    } break;
+    case ConvKind::X6_FIRST: { ProfScope ps(s, PK_CONV); e = launch_conv_x6_first(a, c.img(n->w_dev, kind), nb, s); } break;
+    case ConvKind::X6:
+      e = prep(launch_conv_wprep6);
+      if (e == hipSuccess) { ProfScope ps(s, PK_CONV); e = launch_conv_bf16x6(a, nb, s); }
+      break;
 #if MN_ALT_MODES
-  if (a.in_oct) {
-    a.wps = reinterpret_cast<char*>(ws) + L.wps_base + (long long)n0 * L.wps_nstride;
-    a.wps_nstride = L.wps_nstride;
-    a.btab = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.btab_base) + (long long)n0 * L.btab_nstride;
-    a.btab_nstride = L.btab_nstride;
-    {
-      ProfScope pw(s, PK_OTHER);                                   // its own kind: part of the step, not of the conv kernel
-      HIPCHK(launch_conv_wprep(a, n->w_dev + c.wf_off, nb, s));
-    }
-    ProfScope ps(s, PK_CONV);
-    HIPCHK(launch_conv_bf16_dma(a, nb, s));
-    return MISONET_OK;
-  }
-#else
-  if (a.in_oct) return fail(MISONET_EINVAL, "activation layout %d exists only in the experiment build", a.in_oct);
+    case ConvKind::BF16: {
+      a.w16 = reinterpret_cast<const unsigned short*>(c.img(n->w_dev, kind));
+      ProfScope ps(s, PK_CONV);
+      e = launch_conv_bf16(a, nb, s);
+    } break;
+    case ConvKind::BF16_DMA:
+      if (a.in_oct == 4) { a.wscale = c.wscale; a.descale = 1.f / c.wscale; }
+      e = prep(launch_conv_wprep);
+      if (e == hipSuccess) { ProfScope ps(s, PK_CONV); e = launch_conv_bf16_dma(a, nb, s); }
+      break;
+    case ConvKind::WINO6: { a.ww6 = c.img(n->w_dev, kind); ProfScope ps(s, PK_CONV); e = launch_conv_wino6(a, nb, s); } break;
 #endif
-  {
-    ProfScope ps(s, PK_CONV);
-#if MN_ALT_MODES
-    if (a.w16) HIPCHK(launch_conv_bf16(a, nb, s));
-    else if (a.ww6 && conv_wino6_ok(a)) HIPCHK(launch_conv_wino6(a, nb, s));
-    else
-#endif
-    if (a.wsm && conv_few_ok(a)) HIPCHK(launch_conv_few(a, nb, s));
-    else if (a.ww && conv_wino_ok(a)) HIPCHK(launch_conv_wino(a, nb, s));
-    else HIPCHK(launch_conv(a, nb, s));
+    default: e = hipErrorInvalidValue; break;
   }
+  // a launcher that refuses the layer its kind was chosen for: the selector and the kernel disagree -- never a silent fall-back
+  if (e == hipErrorInvalidValue)
+    return fail(MISONET_EINVAL, "conv kernel kind %d refuses the layer Cin=%d Cout=%d Fin=%d Fout=%d sf=%d padf=%d tr2=%d act=%d in_oct=%d out_oct=%d (mode %d)",
+                (int)kind, a.Cin, a.Cout, a.Fin, a.Fout, a.sf, a.padf, a.tr2, a.act, a.in_oct, a.out_oct, n->precision);
+  HIPCHK(e);
   return MISONET_OK;
 }
 
@@ -678,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 460; }   // 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 470; }   // 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -719,229 +698,6 @@ int misonet_net_set_tensor(misonet_net* n, const char* key, const float* host, l
   return MISONET_OK;
 }
 
-// conv3x3_mfma's weight image [cg][chunk of CK ci][tap = kt * 3 + kf][ci][COP co] (conv-form taps, zero padded)
-static void direct_image(const float* W, int Cin, int Cout, int COP, int ncg, bool transposed, float* w) {
-  struct { int Cin, Cout, ncg; bool transposed; } c = {Cin, Cout, ncg, transposed};
-  const int nchunk = (Cin + CK - 1) / CK;
-  for (int cg = 0; cg < c.ncg; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int kt = 0; kt < 3; ++kt)
-        for (int kf = 0; kf < 3; ++kf)
-          for (int cil = 0; cil < CK; ++cil)
-            for (int col = 0; col < COP; ++col) {
-              const int ci = kc * CK + cil, co = cg * COP + col;
-              float v = 0.f;
-              if (ci < c.Cin && co < c.Cout) {
-                if (c.transposed)   // ConvTranspose2d weight [Cin][Cout][3][3], taps flipped into conv form
-                  v = W[(((long long)ci * c.Cout + co) * 3 + (2 - kt)) * 3 + (2 - kf)];
-                else                // Conv2d weight [Cout][Cin][3][3]
-                  v = W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-              }
-              w[((((long long)cg * nchunk + kc) * 9 + (kt * 3 + kf)) * CK + cil) * COP + col] = v;
-            }
-}
-static void pack_conv(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  const std::vector<float>& Bv = n->tensors[c.bt].host;
-  const int COP = c.cop;
-  direct_image(n->tensors[c.wt].host.data(), c.Cin, c.Cout, c.cop, c.ncg, c.transposed, arena.data() + c.w_off);
-  float* b = arena.data() + c.b_off;
-  for (int co = 0; co < c.ncg * COP; ++co) b[co] = co < c.Cout ? Bv[co] : 0.f;
-}
-
-static inline unsigned short f32_to_bf16_rne(float f) {
-  unsigned int u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-static inline float bf16_to_f32(unsigned short h) {
-  unsigned int u = (unsigned int)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-// bf16x3 path: [cg][chunk of 16 ci][hi|lo][tap][octet h][COP][8] bf16 (conv_bf16.hip)
-static void pack_conv_bf16(const misonet_net* n, ConvL& c, std::vector<float>& arena) {
-  if (!MN_ALT_MODES) return;
-  const std::vector<float>& W = n->tensors[c.wt].host;
-  {
-    // f16x3: a static power of two per layer brings max |W| to [32, 64): with rstd in [2^-6, 2^9] the folded weights
-    // W * rstd stay below fp16's 65504 and the lo pieces of all but negligible weights stay normal
-    float m = 0.f;
-    for (float v : W) m = std::max(m, fabsf(v));
-    c.wscale = (m > 0.f && std::isfinite(m)) ? exp2f(floorf(log2f(64.f / m))) : 1.f;
-  }
-  const int nchunk = (c.Cin + 15) / 16;
-  const int COP = 32;                       // the bf16x3 kernels always work on 32-channel output groups
-  const int ncg16 = (c.Cout + 31) / 32;
-  unsigned short* w = reinterpret_cast<unsigned short*>(arena.data() + c.w16_off);
-  float* wf = arena.data() + c.wf_off;
-  const long long img = 9LL * 2 * COP * 8;
-  for (int cg = 0; cg < ncg16; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int kt = 0; kt < 3; ++kt)
-        for (int kf = 0; kf < 3; ++kf)
-          for (int h = 0; h < 2; ++h)
-            for (int col = 0; col < COP; ++col)
-              for (int e = 0; e < 8; ++e) {
-                const int ci = kc * 16 + 8 * h + e, co = cg * COP + col;
-                float v = 0.f;
-                if (ci < c.Cin && co < c.Cout) {
-                  if (c.transposed) v = W[(((long long)ci * c.Cout + co) * 3 + (2 - kt)) * 3 + (2 - kf)];
-                  else v = W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-                }
-                const unsigned short hi = f32_to_bf16_rne(v);
-                const unsigned short lo = f32_to_bf16_rne(v - bf16_to_f32(hi));
-                const long long base = ((long long)cg * nchunk + kc) * 2 * img;
-                const long long idx = ((((long long)(kt * 3 + kf)) * 2 + h) * COP + col) * 8 + e;
-                w[base + idx] = hi;
-                w[base + img + idx] = lo;
-                wf[((long long)cg * nchunk + kc) * img + idx] = v;
-              }
-}
-
-// bf16x6 path: float32 weights [cg][chunk of 8 ci][tap = kt*3 + kf][32 co][8 ci], zero padded (conv_wprep6_k source)
-static void pack_conv_wf6(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  const std::vector<float>& W = n->tensors[c.wt].host;
-  const int nchunk = (c.Cin + 7) / 8;
-  const int ncg = (c.Cout + 31) / 32;
-  float* wf = arena.data() + c.wf6_off;
-  for (int cg = 0; cg < ncg; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int kt = 0; kt < 3; ++kt)
-        for (int kf = 0; kf < 3; ++kf)
-          for (int col = 0; col < 32; ++col)
-            for (int e = 0; e < 8; ++e) {
-              const int ci = kc * 8 + e, co = cg * 32 + col;
-              float v = 0.f;
-              if (ci < c.Cin && co < c.Cout) {
-                if (c.transposed) v = W[(((long long)ci * c.Cout + co) * 3 + (2 - kt)) * 3 + (2 - kf)];
-                else v = W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-              }
-              wf[((((long long)cg * nchunk + kc) * 9 + (kt * 3 + kf)) * 32 + col) * 8 + e] = v;
-            }
-}
-
-// the first layer's weights as one exact 3-part bf16 image per 8-channel chunk, in conv_wprep6_k's unit order (unit
-// ((kf*3 + p)*2 + kt)*32 + co for kt < 2, 576 + (kf*3 + p)*32 + co for kt = 2; 8 channels per unit): w = hi + mid + lo exactly
-static void pack_conv_w6s(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  if (c.w6s_off < 0) return;
-  const std::vector<float>& W = n->tensors[c.wt].host;
-  const int nchunk = (c.Cin + 7) / 8;
-  unsigned short* img = reinterpret_cast<unsigned short*>(arena.data() + c.w6s_off);
-  for (int kc = 0; kc < nchunk; ++kc)
-    for (int kt = 0; kt < 3; ++kt)
-      for (int kf = 0; kf < 3; ++kf)
-        for (int co = 0; co < 32; ++co)
-          for (int e = 0; e < 8; ++e) {
-            const int ci = kc * 8 + e;
-            const float v = (ci < c.Cin && co < c.Cout) ? W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf] : 0.f;
-            const unsigned short h = f32_to_bf16_rne(v);
-            const float r1 = v - bf16_to_f32(h);
-            const unsigned short m = f32_to_bf16_rne(r1);
-            const unsigned short l = f32_to_bf16_rne(r1 - bf16_to_f32(m));
-            const unsigned short part[3] = {h, m, l};
-            for (int p = 0; p < 3; ++p) {
-              const long long unit = kt < 2 ? ((kf * 3 + p) * 2 + kt) * 32 + co : 576 + (kf * 3 + p) * 32 + co;
-              img[((long long)kc * 864 + unit) * 8 + e] = part[p];
-            }
-          }
-}
-
-// conv_few.hip (the <= 4-channel last layer on the vector ALU): [ci][tap = kt * 3 + kf][4 co] conv-form taps, zero padded
-static void pack_conv_few(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  if (c.wsm_off < 0) return;
-  const std::vector<float>& W = n->tensors[c.wt].host;
-  float* img = arena.data() + c.wsm_off;
-  for (int ci = 0; ci < c.Cin; ++ci)
-    for (int kt = 0; kt < 3; ++kt)
-      for (int kf = 0; kf < 3; ++kf)
-        for (int co = 0; co < 4; ++co) {
-          float v = 0.f;
-          if (co < c.Cout) {
-            if (c.transposed) v = W[(((long long)ci * c.Cout + co) * 3 + (2 - kt)) * 3 + (2 - kf)];
-            else v = W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-          }
-          img[((long long)ci * 9 + (kt * 3 + kf)) * 4 + co] = v;
-        }
-}
-
-// f32w path: Winograd-domain weights U = G g G^T of a stride-1 same-padded conv (conv_wino.hip), G = [1 0 0; .5 .5 .5; .5 -.5 .5;
-// 0 0 1]; position pos = xi * 4 + nu with xi along frequency (kf) and nu along time (kt).  Image order: [cg of 32 co][chunk of
-// 8 ci][pos / 4][ci][co][pos % 4], zero padded past Cout.  Computed in double, rounded once.  Signs: positions with nu = 2
-// carry a minus because the kernel's packed input transform produces -V there (conv_wino.hip, pk_t23); positions with nu = 3
-// and positions with xi = 3 carry one each (both: none) so that the inverse transform A^T M A = sums with a single mixed-sign
-// step per row (conv_wino.hip epilogue: the accumulators hold -M there).
-// conv.hip W1D: U = G g along T per (co, ci, kf), conv-form taps (a transposed conv's are flipped), [cg32][chunk][nu * 3 + kf][ci][32]
-static void w1d_image(const float* W, int Cin, int Cout, bool transposed, float* img) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int nchunk = (Cin + CK - 1) / CK, ncg = (Cout + 31) / 32;
-  for (int cg = 0; cg < ncg; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int nu = 0; nu < 4; ++nu)
-        for (int kf = 0; kf < 3; ++kf)
-          for (int cil = 0; cil < CK; ++cil)
-            for (int col = 0; col < 32; ++col) {
-              const int ci = kc * CK + cil, co = cg * 32 + col;
-              double u = 0.0;
-              if (ci < Cin && co < Cout)
-                for (int kt = 0; kt < 3; ++kt) {
-                  const double g = transposed ? (double)W[(((long long)ci * Cout + co) * 3 + (2 - kt)) * 3 + (2 - kf)]
-                                              : (double)W[(((long long)co * Cin + ci) * 3 + kt) * 3 + kf];
-                  u += G[nu][kt] * g;
-                }
-              img[((((long long)cg * nchunk + kc) * 12 + (nu * 3 + kf)) * CK + cil) * 32 + col] = (float)u;
-            }
-}
-static void wino_image(const float* W, int Cin, int Cout, float* img) {
-  struct { int Cin, Cout; } c = {Cin, Cout};
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int nchunk = c.Cin / 8, ncg = (c.Cout + 31) / 32;
-  for (int cg = 0; cg < ncg; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int cil = 0; cil < 8; ++cil)
-        for (int col = 0; col < 32; ++col) {
-          const int ci = kc * 8 + cil, co = cg * 32 + col;
-          for (int pos = 0; pos < 16; ++pos) {
-            const int xi = pos >> 2, nu = pos & 3;
-            double u = 0.0;
-            if (co < c.Cout)
-              for (int kt = 0; kt < 3; ++kt)
-                for (int kf = 0; kf < 3; ++kf)
-                  u += G[xi][kf] * G[nu][kt] * (double)W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-            const bool minus = (nu == 2) != ((nu == 3) != (xi == 3));
-            img[(((((long long)cg * nchunk + kc) * 4 + (pos >> 2)) * 8 + cil) * 32 + col) * 4 + (pos & 3)] = (float)(minus ? -u : u);
-          }
-        }
-}
-// ... and of output channels [co0, co0 + 16) for the 16-row body: [chunk of 8 ci][K-step s of 4 ci][pos / 4][ci % 4][16 co][pos % 4],
-// the same signs
-static void wino_image16(const float* W, int Cin, int co0, float* img) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int nchunk = Cin / 8;
-  for (int kc = 0; kc < nchunk; ++kc)
-    for (int cil = 0; cil < 8; ++cil)
-      for (int col = 0; col < 16; ++col) {
-        const int ci = kc * 8 + cil, co = co0 + col;
-        for (int pos = 0; pos < 16; ++pos) {
-          const int xi = pos >> 2, nu = pos & 3;
-          double u = 0.0;
-          for (int kt = 0; kt < 3; ++kt)
-            for (int kf = 0; kf < 3; ++kf)
-              u += G[xi][kf] * G[nu][kt] * (double)W[(((long long)co * Cin + ci) * 3 + kt) * 3 + kf];
-          const bool minus = (nu == 2) != ((nu == 3) != (xi == 3));
-          const int s = cil >> 2, kk = cil & 3;
-          img[((((((long long)kc * 2 + s) * 4 + (pos >> 2)) * 4 + kk) * 16 + col) * 4) + (pos & 3)] = (float)(minus ? -u : u);
-        }
-      }
-}
-static void pack_conv_wino(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  if (c.ww_off < 0) return;
-  wino_image(n->tensors[c.wt].host.data(), c.Cin, c.Cout, arena.data() + c.ww_off);
-  if (c.ww16_off >= 0) wino_image16(n->tensors[c.wt].host.data(), c.Cin, c.Cout - 16, arena.data() + c.ww16_off);
-}
-
 // Run-time self-check of the f32w kernel, once per device at the first commit: conv3x3_wino_f32 drives 256 fixed
 // AGPRs and hand-placed wait states through inline asm -- the build guard (tools/check_wino_build.py) covers what the compiler
 // may do to it, this covers the machine: one small layer (40 -> 48 channels, 11 x 70, two samples: ragged row and column tiles, a
@@ -964,17 +720,16 @@ static int wino_selftest() {
   for (float& v : W) v = 0.1f * rnd();
   for (float& v : bias) v = 0.3f * rnd();
   for (float& v : x) v = rnd();
-  const int nchunk = Cin / CK;
-  std::vector<float> wd((size_t)nchunk * 9 * CK * 64), ww((size_t)2 * nchunk * 16 * 8 * 32), ww16((size_t)nchunk * 2048);
-  direct_image(W.data(), Cin, Cout, 64, 1, false, wd.data());
-  wino_image(W.data(), Cin, Cout, ww.data());
-  wino_image16(W.data(), Cin, Cout - 16, ww16.data());
+  const ConvWeights cw = {W.data(), Cin, Cout, false, 64, 1};
+  std::vector<float> wd((size_t)conv_image_floats(ConvKind::DIRECT, cw)), ww((size_t)conv_image_floats(ConvKind::WINO, cw));   // (ww: both bodies' images)
+  conv_image_pack(ConvKind::DIRECT, cw, wd.data());
+  conv_image_pack(ConvKind::WINO, cw, ww.data());
   const size_t out_n = (size_t)N * Cout * F * Tp, st_n = (size_t)N * Cout * 2 * DS_NL;
-  float *dx = nullptr, *dwd = nullptr, *dww = nullptr, *dww16 = nullptr, *db = nullptr, *dy = nullptr;
+  float *dx = nullptr, *dwd = nullptr, *dww = nullptr, *db = nullptr, *dy = nullptr;
   dstat_t* dst = nullptr;
-  auto release = [&]() { (void)hipFree(dx); (void)hipFree(dwd); (void)hipFree(dww); (void)hipFree(dww16); (void)hipFree(db); (void)hipFree(dy); (void)hipFree(dst); };
+  auto release = [&]() { (void)hipFree(dx); (void)hipFree(dwd); (void)hipFree(dww); (void)hipFree(db); (void)hipFree(dy); (void)hipFree(dst); };
   bool ok = hipMalloc(reinterpret_cast<void**>(&dx), x.size() * 4) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dwd), wd.size() * 4) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void**>(&dww), ww.size() * 4) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dww16), ww16.size() * 4) == hipSuccess &&
+            hipMalloc(reinterpret_cast<void**>(&dww), ww.size() * 4) == hipSuccess &&
             hipMalloc(reinterpret_cast<void**>(&db), 128 * 4) == hipSuccess &&
             hipMalloc(reinterpret_cast<void**>(&dy), 2 * out_n * 4) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dst), 2 * st_n * 8) == hipSuccess;
   std::vector<float> y(2 * out_n);
@@ -985,21 +740,20 @@ static int wino_selftest() {
     ok = hipMemcpy(dx, x.data(), x.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(dwd, wd.data(), wd.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(dww, ww.data(), ww.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dww16, ww16.data(), ww16.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(db, b128.data(), 128 * 4, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemset(dy, 0, 2 * out_n * 4) == hipSuccess && hipMemset(dst, 0, 2 * st_n * 8) == hipSuccess;
   }
   if (ok) {
     ConvArgs a = {};
-    a.in = dx; a.in_stats = nullptr; a.w = dwd; a.bias = db; a.ww = dww; a.ww16 = dww16;
+    a.in = dx; a.in_stats = nullptr; a.w = dwd; a.bias = db; a.ww = dww; a.ww16 = dww + conv_wino_ww16_at(Cin, Cout);
     a.in_bstride = (long long)Cin * F * Tp; a.out_bstride = (long long)Cout * F * Tp;
     a.in_sstride = Cin; a.out_sstride = Cout;
     a.in_c0 = 0; a.Cin = Cin; a.Fin = F; a.ident_c = Cin;              // input consumed as it is: no statistics to read
     a.out_c0 = 0; a.Cout = Cout; a.Fout = F; a.T = T; a.Tp = Tp;
-    a.sf = 1; a.padf = 1; a.tr2 = 0; a.act = 1; a.NR = conv_rows(1, 0); a.ncg = 1; a.cop = 64;
+    a.sf = 1; a.padf = 1; a.tr2 = 0; a.act = 1; a.ncg = 1; a.cop = 64;
     a.wscale = a.descale = 1.f;
     a.out = dy; a.out_stats = dst;
-    ok = conv_wino_ok(a) && launch_conv_wino(a, N, nullptr) == hipSuccess;
+    ok = launch_conv_wino(a, N, nullptr) == hipSuccess;
     a.ww = nullptr; a.ww16 = nullptr; a.out = dy + out_n; a.out_stats = dst + st_n;
     ok = ok && launch_conv(a, N, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
          hipMemcpy(y.data(), dy, 2 * out_n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -1029,76 +783,25 @@ static int wino_selftest() {
   return st;
 }
 
-// ... and in the three-piece bf16 form of the bf16x6w mode (conv_wino6.hip): per (cg of 32 co, K-step of 16 ci) four QUARTERS
-// (position rows xi), each [nu][piece h | m | l][lane = co + 32 * (ci / 8 % 2)][8 bf16 = channels 8 * (ci / 8 % 2) .. + 7]: one
-// lane's MFMA A operand is 16 consecutive bytes.  U in double, rounded once to float32, then split exactly at fixed bit
-// positions (top 8 / next 8 / last 8 significant bits).  No sign flips (the kernel's transform is the plain B^T d B).
-static void pack_conv_wino6(const misonet_net* n, const ConvL& c, std::vector<float>& arena) {
-  if (c.ww6_off < 0) return;
-  const std::vector<float>& W = n->tensors[c.wt].host;
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int nk = (c.Cin + 15) / 16, ncg = (c.Cout + 31) / 32;
-  unsigned short* img = reinterpret_cast<unsigned short*>(arena.data() + c.ww6_off);
-  auto top16 = [](float x) { unsigned u; memcpy(&u, &x, 4); return (unsigned short)(u >> 16); };
-  for (int cg = 0; cg < ncg; ++cg)
-    for (int kk = 0; kk < nk; ++kk)
-      for (int pos = 0; pos < 16; ++pos)
-        for (int col = 0; col < 32; ++col)
-          for (int cil = 0; cil < 16; ++cil) {
-            const int ci = kk * 16 + cil, co = cg * 32 + col, xi = pos >> 2, nu = pos & 3;
-            double u = 0.0;
-            if (co < c.Cout && ci < c.Cin)
-              for (int kt = 0; kt < 3; ++kt)
-                for (int kf = 0; kf < 3; ++kf)
-                  u += G[xi][kf] * G[nu][kt] * (double)W[(((long long)co * c.Cin + ci) * 3 + kt) * 3 + kf];
-            const float v = (float)u;
-            unsigned vb; memcpy(&vb, &v, 4);
-            unsigned hb = vb & 0xffff0000u, wb = vb & 0xffffff00u;
-            float h, w; memcpy(&h, &hb, 4); memcpy(&w, &wb, 4);
-            const float m = w - h, l = v - w;
-            const int lane = col + 32 * (cil >> 3), j = cil & 7;
-            const long long q = (((long long)cg * nk + kk) * 4 + xi) * (3 * 4 * 64 * 8);
-            img[q + ((long long)(nu * 3 + 0) * 64 + lane) * 8 + j] = top16(h);
-            img[q + ((long long)(nu * 3 + 1) * 64 + lane) * 8 + j] = top16(m);
-            img[q + ((long long)(nu * 3 + 2) * 64 + lane) * 8 + j] = top16(l);
-          }
-}
-
 int misonet_net_commit(misonet_net* n) {
   if (!n) return fail(MISONET_EINVAL, "null argument");
   for (const Tensor& t : n->tensors)
     if (!t.set) return fail(MISONET_ESTATE, "missing state_dict key '%s'", t.name.c_str());
   long long off = 0;
   auto take = [&off](long long nfl) { long long o = off; off += (nfl + 63) / 64 * 64; return o; };
-  auto place = [&](std::vector<ConvL>& v) {
-    for (ConvL& c : v) {
-      const int nchunk = (c.Cin + CK - 1) / CK;
-      c.w_off = take((long long)c.ncg * nchunk * 9 * CK * c.cop);
+  // per conv layer: the bias, the direct image (always: the exact-f32 mode, the self-check's reference) and the image of every
+  // other kind the plan holds for the layer over the modes of this build
+  auto conv_weights = [n](const ConvL& c) { return ConvWeights{n->tensors[c.wt].host.data(), c.Cin, c.Cout, c.transposed, c.cop, c.ncg}; };
+  for (std::vector<ConvL>* v : {&n->enc, &n->dec})
+    for (ConvL& c : *v) {
+      std::fill(c.img_off, c.img_off + CONV_NKIND, -1LL);
+      c.img_off[(int)ConvKind::DIRECT] = take(conv_image_floats(ConvKind::DIRECT, conv_weights(c)));
       c.b_off = take((long long)c.ncg * c.cop);
-      if (MN_ALT_MODES) {
-        c.w16_off = take((long long)((c.Cout + 31) / 32) * ((c.Cin + 15) / 16) * 2 * 9 * 2 * 32 * 8 / 2);   // u16 -> floats
-        c.wf_off = take((long long)((c.Cout + 31) / 32) * ((c.Cin + 15) / 16) * 9 * 2 * 32 * 8);
+      for (int mode = 0; mode < CONV_NMODES; ++mode) {
+        long long& o = c.img_off[(int)c.kind[mode]];
+        if (conv_mode_built(mode) && o < 0) o = take(conv_image_floats(c.kind[mode], conv_weights(c)));
       }
-      c.wf6_off = take((long long)((c.Cout + 31) / 32) * ((c.Cin + 7) / 8) * 9 * 32 * 8);
-      // the first layer (planar network input, consumed un-normalised, <= 16 in / <= 32 out channels): shared 3-part image
-      if (c.in_buf == B_IN && !c.transposed && c.sf == 1 && c.Cin <= 16 && c.Cout <= 32 && c.ident_c >= c.Cin)
-        c.w6s_off = take((long long)((c.Cin + 7) / 8) * 864 * 4);          // 864 units x 16 bytes = x 4 floats
-      // the DenseBlock convs (stride 1, same padding, Cin a multiple of 8): Winograd-domain image for the f32w mode
-      if (!c.transposed && c.sf == 1 && c.padf == 1 && c.Cin % 8 == 0 && c.Cin <= 256)
-      {
-        c.ww_off = take((long long)((c.Cout + 31) / 32) * (c.Cin / 8) * 16 * 8 * 32);
-        if ((c.Cout & 31) == 16) c.ww16_off = take((long long)(c.Cin / 8) * 2048);
-      }
-      // stride-2 convs / transposed convs, and a network's first layer (12 / 16 -> 24 channels): 1-D Winograd image along T
-      if (((c.tr2 || c.sf == 2) && c.act) || (c.transposed && c.sf == 1 && !c.tr2 && c.padf == 2 && n->bufs[c.in_buf].F == 1 && c.act) || (!c.transposed && c.sf == 1 && c.padf == 0 && n->bufs[c.in_buf].F == 3 && c.Cout % 128 == 0 && c.act) || (!c.transposed && c.sf == 1 && !(c.padf == 2 && n->bufs[c.in_buf].F == 1) && c.Cin < 3 * CK && c.Cout <= 32))
-        c.w1d_off = take((long long)((c.Cout + 31) / 32) * nchunk * 12 * CK * 32);
-      if (c.Cout <= 4 && c.sf == 1 && !c.tr2 && !c.act && c.Cin % 4 == 0 && c.Cin <= 256) c.wsm_off = take((long long)c.Cin * 36);
-      if (MN_ALT_MODES && !c.transposed && c.sf == 1 && c.padf == 1 && c.Cin % 8 == 0 && c.Cin >= 24 && c.Cin <= 256)
-        c.ww6_off = take((long long)((c.Cout + 31) / 32) * ((c.Cin + 15) / 16) * (16 * 3 * 64 * 16 / 4));
     }
-  };
-  place(n->enc);
-  place(n->dec);
   for (TcnBlock& tb : n->tcn)
     for (int h = 0; h < 2; ++h) {
       tb.h[h].o_dw = take(128 * 3);
@@ -1110,10 +813,14 @@ int misonet_net_commit(misonet_net* n) {
       tb.h[h].o_nsh = take(128);
     }
   std::vector<float> arena((size_t)off, 0.f);
-  for (ConvL& c : n->enc) { pack_conv(n, c, arena); pack_conv_bf16(n, c, arena); pack_conv_wf6(n, c, arena); pack_conv_w6s(n, c, arena); pack_conv_wino(n, c, arena); pack_conv_wino6(n, c, arena); }
-  for (ConvL& c : n->enc) if (c.w1d_off >= 0) w1d_image(n->tensors[c.wt].host.data(), c.Cin, c.Cout, c.transposed, arena.data() + c.w1d_off);
-  for (ConvL& c : n->dec) if (c.w1d_off >= 0) w1d_image(n->tensors[c.wt].host.data(), c.Cin, c.Cout, c.transposed, arena.data() + c.w1d_off);
-  for (ConvL& c : n->dec) { pack_conv_few(n, c, arena); pack_conv(n, c, arena); pack_conv_bf16(n, c, arena); pack_conv_wf6(n, c, arena); pack_conv_wino(n, c, arena); pack_conv_wino6(n, c, arena); }
+  for (std::vector<ConvL>* v : {&n->enc, &n->dec})
+    for (ConvL& c : *v) {
+      for (int k = 0; k < CONV_NKIND; ++k)
+        if (c.img_off[k] >= 0) conv_image_pack((ConvKind)k, conv_weights(c), arena.data() + c.img_off[k]);
+      const std::vector<float>& Bv = n->tensors[c.bt].host;
+      for (int co = 0; co < c.ncg * c.cop; ++co) arena[c.b_off + co] = co < c.Cout ? Bv[co] : 0.f;
+      if (MN_ALT_MODES) c.wscale = conv_f16_wscale(n->tensors[c.wt].host.data(), n->tensors[c.wt].numel);
+    }
   for (const TcnBlock& tb : n->tcn)
     for (int h = 0; h < 2; ++h) {
       const TcnHalf& H = tb.h[h];
@@ -1161,8 +868,7 @@ int misonet_net_commit(misonet_net* n) {
 
 int misonet_net_set_precision(misonet_net* n, int mode) {
   if (!n) return fail(MISONET_EINVAL, "null argument");
-  const bool product = (mode == 0 || mode == 3 || mode == 5);
-  if (!product && !(MN_ALT_MODES && mode >= 1 && mode <= 6))
+  if (mode < 0 || mode >= CONV_NMODES || !conv_mode_built(mode))
     return fail(MISONET_EINVAL, "precision mode must be 0 (f32), 3 (bf16x6) or 5 (f32w: f32 with the dense-block convs in Winograd form)%s",
                 MN_ALT_MODES ? "; experiment build: also 1 / 2 (bf16x3), 4 (f16x3), 6 (bf16x6w)"
                              : "; modes 1, 2, 4, 6 exist only in the experiment build (make exp)");
@@ -1184,6 +890,16 @@ int misonet_net_buffer_plan(const misonet_net* n, int n_frames, int max_buffers,
     buf_lifetime(b, first_step[k], last_step[k]);
     if (n->keep_taps) { first_step[k] = 0; last_step[k] = 16; }
   }
+  return k;
+}
+
+int misonet_net_conv_plan(const misonet_net* n, int mode, int max_layers, int* kind) {
+  if (!n || !kind) return fail(MISONET_EINVAL, "null argument");
+  if (mode < 0 || mode >= CONV_NMODES || !conv_mode_built(mode)) return fail(MISONET_EINVAL, "precision mode %d is not in this build", mode);
+  int k = 0;
+  for (const std::vector<ConvL>* v : {&n->enc, &n->dec})
+    for (const ConvL& c : *v)
+      if (k < max_layers) kind[k++] = (int)c.kind[mode];
   return k;
 }
 

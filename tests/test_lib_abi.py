@@ -225,6 +225,68 @@ def test_workspace_plan_never_overlaps_live_buffers(prec):
     lib.misonet_net_destroy(h)
 
 
+# ConvKind codes of misonet_net_conv_plan (include/misonet.h)
+DIRECT, W1D, FEW, WINO, X6_FIRST, X6 = range(6)
+# kernel launches per kind of ONE forward of the 64 conv layers, per product mode (the same for MISO1 and MISO3): f32 runs the
+# last layer (48 -> 4 / 2 channels, no activation) on conv3x3_few and everything else on conv3x3_mfma; f32w the 50 DenseBlock
+# convs on conv3x3_wino_f32, the 13 activated layers outside them and the first layer in the 1-D Winograd form of conv3x3_mfma;
+# bf16x6 the first layer on conv3x3_x6_first and the 63 oct3-input layers on conv3x3_bf16x6
+CONV_PLAN = {0: {DIRECT: 63, FEW: 1}, 5: {WINO: 50, W1D: 13, FEW: 1}, 3: {X6_FIRST: 1, X6: 63}}
+
+
+def _conv_layers():
+    """(has activation, DenseBlock conv) of the 64 conv layers in launch order: encoders, then decoders (model.py:40-73)"""
+    enc = []
+    for b in range(7):
+        enc.append((b > 0, False))                                  # encoders.0.0.conv2d has no activation
+        if b < 5:
+            enc += [(True, True)] * 5
+    dec = []
+    for i in range(7):
+        if i >= 2:
+            dec += [(True, True)] * 5
+        dec.append((i < 6, False))                                  # the last deconv has none
+    return enc + dec
+
+
+@pytest.mark.parametrize("in_ch,out_ch", [(12, 4), (16, 2)])            # MISO1, MISO3
+@pytest.mark.parametrize("mode", [0, 5, 3])                              # f32, f32w, bf16x6
+def test_conv_plan_kernel_per_layer(in_ch, out_ch, mode):
+    """The kernel of every conv layer is decided once, at plan time, from one table (csrc/conv_select.hpp): the per-kind counts
+    are the launch counts of a forward, and nothing falls back silently -- in f32w every DenseBlock conv is WINO and no
+    activated layer is on the direct kernel, in bf16x6 every layer that reads an oct-layout buffer (all but the first) is X6."""
+    L, rc, h = _make(in_ch=in_ch, out_ch=out_ch)
+    assert rc == 0
+    lib = L.lib()
+    kind = (C.c_int * 80)()
+    assert lib.misonet_net_conv_plan(h, mode, 80, kind) == 64
+    kinds = list(kind[:64])
+    assert {k: kinds.count(k) for k in set(kinds)} == CONV_PLAN[mode]
+    layers = _conv_layers()
+    assert len(layers) == 64 and sum(d for _, d in layers) == 50
+    if mode == 5:
+        assert all(k == WINO for k, (_, dense) in zip(kinds, layers) if dense)
+        assert all(k != DIRECT for k, (act, _) in zip(kinds, layers) if act)
+        assert kinds[0] == W1D and kinds[63] == FEW
+    if mode == 3:
+        assert kinds[0] == X6_FIRST and all(k == X6 for k in kinds[1:])      # only the network input is planar
+    if mode == 0:
+        assert kinds[63] == FEW
+    assert lib.misonet_net_conv_plan(h, mode, 10, kind) == 10               # never writes past max_layers
+    lib.misonet_net_destroy(h)
+
+
+def test_conv_plan_rejects_modes_not_in_build():
+    L, rc, h = _make()
+    lib = L.lib()
+    kind = (C.c_int * 64)()
+    for mode in (1, 2, 4, 6, 7, -1):                                     # experiment-build modes and nonsense
+        assert lib.misonet_net_conv_plan(h, mode, 64, kind) == L.EINVAL, mode
+    assert lib.misonet_net_conv_plan(h, 5, 64, None) == L.EINVAL
+    assert lib.misonet_version() >= 470
+    lib.misonet_net_destroy(h)
+
+
 @pytest.mark.parametrize("nt,kind,extra", [("gLN", 1, 56), ("cLN", 2, 56), ("BN", 3, 112)])
 def test_tensor_registry_norm_type_variants(nt, kind, extra):
     """norm_type of the constructors (model.py:9, 283) = the outer norms of the 14 TemporalBlocks (model.py:530,535,570-581):

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Per-layer achieved TFLOP/s of the conv3x3_mfma launches in a rocprofv3 rocpd DB of bench.py (one pipeline step =
-64 conv launches with 6B samples (MISO1) followed by 64 with 2B samples (MISO3)).  usage: conv_layer_report.py db [B] [T]"""
+64 conv launches with 6B samples (MISO1) followed by 64 with 2B samples (MISO3)).  usage: conv_layer_report.py db [B] [T] [precision]
+With a precision (f32 | f32w | bf16x6) every line also names the kernel kind the library's plan holds for the layer
+(misonet_net_conv_plan, host only)."""
+import ctypes
+import os
 import sqlite3
 import sys
 
@@ -28,6 +32,23 @@ def layers(in_ch, out_ch):
     return L
 
 
+KINDS = ("DIRECT", "W1D", "FEW", "WINO", "X6_FIRST", "X6", "BF16", "BF16_DMA", "WINO6")
+
+
+def plan_kinds(precision, in_ch, out_ch):
+    """the ConvKind name of each of the 64 layers of a MISO trunk in `precision`, from the library"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from misonet_amd import _lib
+    lib = _lib.lib()
+    cfg = _lib.Cfg(in_ch, out_ch, (ctypes.c_int * 7)(*EN), (ctypes.c_int * 7)(*DE), 129, 0)
+    net, kind = ctypes.c_void_p(), (ctypes.c_int * 64)()
+    assert lib.misonet_net_create(ctypes.byref(cfg), ctypes.byref(net)) == 0
+    n = lib.misonet_net_conv_plan(net, {"f32": 0, "bf16x6": 3, "f32w": 5}[precision], 64, kind)
+    lib.misonet_net_destroy(net)
+    assert n == 64, n
+    return [KINDS[k] for k in kind]
+
+
 def main():
     db = sqlite3.connect(sys.argv[1])
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 16
@@ -49,6 +70,7 @@ def main():
     assert len(conv) >= 128, len(conv)      # (+ the two launches of the f32w self-check at the first commit)
     last = conv[-128:]
     l1, l3 = layers(12, 4), layers(16, 2)
+    kinds = plan_kinds(sys.argv[4], 12, 4) if len(sys.argv) > 4 else None       # (MISO3's plan has the same kinds)
     print(f"{'layer':14s} {'Cin':>4s} {'Cout':>4s} {'F':>4s} {'ms(MISO1 x%d)' % (6*B):>14s} {'TF/s':>7s} {'ms(MISO3 x%d)' % (2*B):>14s} {'TF/s':>7s}")
     tot = [0, 0, 0, 0]
     for k in range(64):
@@ -58,7 +80,8 @@ def main():
         f3 = 2.0 * cin3 * cout3 * 9 * F * T * 2 * B
         d1, d3 = last[k][1] / 1e6, last[64 + k][1] / 1e6
         tot[0] += d1; tot[1] += f1; tot[2] += d3; tot[3] += f3
-        print(f"{nm:14s} {cin:4d} {cout:4d} {F:4d} {d1:14.3f} {f1 / d1 / 1e9:7.1f} {d3:14.3f} {f3 / d3 / 1e9:7.1f}")
+        print(f"{nm:14s} {cin:4d} {cout:4d} {F:4d} {d1:14.3f} {f1 / d1 / 1e9:7.1f} {d3:14.3f} {f3 / d3 / 1e9:7.1f}"
+              + (f"  {kinds[k]}" if kinds else ""))
     print(f"total MISO1 {tot[0]:.1f} ms {tot[1]/tot[0]/1e9:.1f} TF/s ; MISO3 {tot[2]:.1f} ms {tot[3]/tot[2]/1e9:.1f} TF/s")
 
 
