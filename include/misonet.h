@@ -175,6 +175,37 @@ int misonet_css_align(const void* est_dev, int K, int S, int T, int F, int hop_f
 int misonet_css_stitch(const float* y_dev, const int* perm_dev, int K, int S, int W, int hop, int first,
                        long long n_out, short* out_i16_dev, float* out_f32_dev, misonet_stream stream);
 
+/* ---- scores of separated output against clean references (ABI 480) ------------------------------------------ */
+/* misonet_score_wave: est_dev = E estimates per item, int16 (est_is_i16 != 0; a sample q stands for q / 32767) or float32;
+ *   ref_dev = R references per item, float32.  Both are strided views: element (item b, source s, sample m) lies at
+ *   base[b * sb + s * ss + m * st], strides in elements (int16 [B, S, n] from misonet_istft: (S n, n, 1); a time-major
+ *   [B, n, S]: (n S, 1, S); one microphone c of [B, n, M], passed as base + c: (n M, 0, M) with E = 1).  Sample-contiguous
+ *   views whose rows start 16-byte aligned are read with 16-byte loads.  n_valid_dev int32 [B] (NULL: n): samples
+ *   [n_valid[b], n) of item b are left out (the zero-padded tail of a recording's last chunk).
+ *   stats_dev double [B][E][R][5] receives (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j) over the valid samples, accumulated
+ *   in double (the int16 scale applied once, after the sums) in a fixed order without atomics: bit-reproducible, and the
+ *   block of an item does not depend on B or on its position in the batch.  The statistics are additive over the chunks of
+ *   a recording; SI-SDR, SNR and the best permutation follow from them on the host (misonet_amd/score.py).
+ * misonet_score_spec: the reference's training criterion (criterion.py loss_uPIT / loss_Enhance) per pair of an
+ *   estimate and a reference spectrogram: est_dev / ref_dev complex64 views, element (b, s, t, f) at base[b * sb + s * ss +
+ *   t * st + f], strides in complex elements.  pair_dev double [B][E][R] = sum_{t,f} |Re e - Re r| + |Im e - Im r| +
+ *   | sqrt(Re e^2 + Im e^2 + 1e-8) - |r| |, every term float32, summed in double in a fixed order.  perm_dev int32 [B][R]
+ *   and upit_dev double [B] (either may be NULL; they need E == R): the permutation p with the least sum_i pair[i][p(i)]
+ *   (itertools.permutations order, first minimum) and that sum.
+ * scratch_dev: misonet_score_scratch_bytes(B, E, R, n) / (B, E, R, F) bytes = 8 B max(ceil(x / 4096) (2E + 2R + E R),
+ *   min(x, 1024) E R); less returns MISONET_ENOMEM.  MISONET_EINVAL: a null argument, E outside 1..5, R outside 1..4,
+ *   B outside 1..65535, n < 1, T < 1, F outside 1..1024, a negative stride.  Both calls are asynchronous on the stream,
+ *   allocate nothing and can be captured into a HIP graph. */
+long long misonet_score_scratch_bytes(int B, int E, int R, long long n_or_F);
+int misonet_score_wave(const void* est_dev, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                       const float* ref_dev, long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R,
+                       long long n, const int* n_valid_dev, double* stats_dev, void* scratch_dev,
+                       long long scratch_bytes, misonet_stream stream);
+int misonet_score_spec(const void* est_dev, long long est_sb, long long est_ss, long long est_st, const void* ref_dev,
+                       long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, int T, int F,
+                       double* pair_dev, int* perm_dev, double* upit_dev, void* scratch_dev, long long scratch_bytes,
+                       misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

@@ -62,6 +62,13 @@ SIGNATURES = {
                                     C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_css_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_score_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong]),
+    "misonet_score_wave": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong,
+                                     C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_score_spec": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong,
+                                     C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_pipeline_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.POINTER(C.c_void_p)]),
     "misonet_pipeline_destroy": (C.c_int, [C.c_void_p]),

@@ -215,4 +215,17 @@ struct PitArgs {
 hipError_t launch_pit_dist_k(const PitArgs& p, int S, int K, double* part /*[B*K][F][S][S]*/, hipStream_t s);
 hipError_t launch_pit_pick(const double* part, int F, int S, int n, double* dist /*[n][S][S]*/, int* sel /*[n][S]*/, hipStream_t s);
 
+// Scores of separated output against clean references (score.hip).  Wave statistics: est int16 or float32, ref float32, each
+// a strided view (item, source, sample) in elements (es / rs = the three strides); per-segment partials
+// [B][score_wave_segments(n)][2E + 2R + E R] are folded in segment order into stats [B][E][R][5] =
+// (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j), an int16 estimate scaled by 1 / 32767 once.  1 <= E <= 5, 1 <= R <= 4.
+long long score_wave_segments(long long n);
+hipError_t launch_score_wave(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
+                             int B, int E, int R, long long n, const int* n_valid /*[B] or nullptr*/, double* part,
+                             double* stats, hipStream_t s);
+// The spectral training criterion per pair: p.a = estimates, p.b = references, sm = the source stride; per-bin partials
+// [B][F][E][R] folded in bin order into pair [B][E][R]; perm [B][R] / upit [B] (either may be nullptr; E == R): the uPIT pick
+hipError_t launch_score_spec(const PitArgs& p, int E, int R, double* part, double* pair, int* perm, double* upit,
+                             hipStream_t s);
+
 }  // namespace mn

@@ -657,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 470; }   // 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 480; }   // 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1092,6 +1092,68 @@ int misonet_css_stitch(const float* y, const int* perm, int K, int S, int W, int
   if (n_out < 0 || n_out > cap) return fail(MISONET_EINVAL, "n_out %lld outside [0, %lld]", n_out, cap);
   if (n_out == 0) return MISONET_OK;
   HIPCHK(launch_css_stitch(y, perm, K, S, W, hop, base, n_out, out_i16, out_f32, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- scores against clean references (score.hip) --------------------------------------------------------------------
+// One size serves both entry points: the wave partials [B][ceil(n / 4096)][2E + 2R + E R] and the per-bin partials
+// [B][F][E][R] (F <= 1024), whichever is larger for the value given.
+long long misonet_score_scratch_bytes(int B, int E, int R, long long n_or_F) {
+  if (B <= 0 || E <= 0 || R <= 0 || n_or_F <= 0) return -1;
+  const long long wave = score_wave_segments(n_or_F) * (2LL * E + 2LL * R + (long long)E * R);
+  const long long spec = (n_or_F < 1024 ? n_or_F : 1024) * (long long)E * R;
+  return (long long)B * (wave > spec ? wave : spec) * (long long)sizeof(double);
+}
+
+static int score_ranges(int B, int E, int R) {
+  if (E < 1 || E > 5) return fail(MISONET_EINVAL, "E must be in [1, 5] (got %d): up to 4 speakers and the mixture", E);
+  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
+  if (B < 1 || B > 65535) return fail(MISONET_EINVAL, "B must be in [1, 65535] (got %d)", B);
+  return MISONET_OK;
+}
+
+int misonet_score_wave(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                       const float* ref, long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R,
+                       long long n, const int* n_valid, double* stats, void* scratch, long long scratch_bytes,
+                       misonet_stream stream) {
+  if (!est || !ref || !stats || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = score_ranges(B, E, R)) return rc;
+  if (n < 1 || n > (1LL << 40)) return fail(MISONET_EINVAL, "n must be in [1, 2^40] (got %lld)", n);
+  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
+    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
+  const long long need = misonet_score_scratch_bytes(B, E, R, n);
+  if (scratch_bytes < need)
+    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_score_scratch_bytes(B, E, R, n))", scratch_bytes, need);
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
+  HIPCHK(launch_score_wave(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, reinterpret_cast<double*>(scratch), stats,
+                           reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_score_spec(const void* est, long long est_sb, long long est_ss, long long est_st, const void* ref,
+                       long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, int T, int F,
+                       double* pair, int* perm, double* upit, void* scratch, long long scratch_bytes,
+                       misonet_stream stream) {
+  if (!est || !ref || !pair || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = score_ranges(B, E, R)) return rc;
+  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
+  if (F < 1 || F > 1024) return fail(MISONET_EINVAL, "F must be in [1, 1024] (got %d)", F);
+  if ((perm || upit) && E != R)
+    return fail(MISONET_EINVAL, "the permutation pick needs as many estimates as references (E %d, R %d)", E, R);
+  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
+    return fail(MISONET_EINVAL, "strides must not be negative and the frame strides must be positive");
+  const long long need = misonet_score_scratch_bytes(B, E, R, F);
+  if (scratch_bytes < need)
+    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_score_scratch_bytes(B, E, R, F))", scratch_bytes, need);
+  // complex64 views, strides in complex elements, bins contiguous: element (b, f, source, t) at 2 (b sb + source ss + t st + f)
+  const float* a = reinterpret_cast<const float*>(est);
+  const float* c = reinterpret_cast<const float*>(ref);
+  PitArgs p;
+  p.a = {a, a + 1, 2 * est_sb, 2, 2 * est_ss, (int)(2 * est_st)};
+  p.b = {c, c + 1, 2 * ref_sb, 2, 2 * ref_ss, (int)(2 * ref_st)};
+  p.B = B; p.F = F; p.T = T;
+  HIPCHK(launch_score_spec(p, E, R, reinterpret_cast<double*>(scratch), pair, perm, upit,
+                           reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -163,7 +163,8 @@ class _Overlapped:
             sl["ev_in"] = torch.cuda.Event()
             sl["ev_in"].record(s_in)
         cur.wait_event(sl["ev_in"])
-        res, flag = compute(*[sl[f"d{j}"] if src is not None else None for j, src in enumerate(srcs)])
+        res, flag, *more = compute(*[sl[f"d{j}"] if src is not None else None for j, src in enumerate(srcs)])
+        extra = more[0] if more else None             # a small device tensor that rides the result's D2H (the score sums)
         sl["ev_free"] = torch.cuda.Event()
         sl["ev_free"].record(cur)
         rec = {"pcm_h": sl.get("pcm_h") if to_host else None, "flag_h": sl.get("flag_h"), "res": None if to_host else res}
@@ -178,6 +179,13 @@ class _Overlapped:
                 res.record_stream(s_out)
             rec["flag_h"].copy_(flag, non_blocking=True)
             flag.record_stream(s_out)
+            if extra is not None:
+                ex = sl.get("extra_h")
+                if ex is None or ex.shape != extra.shape or ex.dtype != extra.dtype:
+                    ex = sl["extra_h"] = torch.empty(extra.shape, dtype=extra.dtype, pin_memory=True)
+                ex.copy_(extra, non_blocking=True)
+                extra.record_stream(s_out)
+                rec["extra_h"] = ex
             rec["ev_out"] = torch.cuda.Event()
             rec["ev_out"].record(s_out)
         return rec
@@ -188,6 +196,11 @@ class _Overlapped:
         rec["ev_out"].synchronize()
         res = rec["pcm_h"].numpy().copy() if rec["pcm_h"] is not None else rec["res"]
         return res, int(rec["flag_h"][0]) != 0
+
+    @staticmethod
+    def extra(rec):
+        """after :meth:`finish`: an ndarray copy of the extra block the batch's compute returned, or None"""
+        return rec["extra_h"].numpy().copy() if rec.get("extra_h") is not None else None
 
 
 class Enhancer:
@@ -409,8 +422,13 @@ class Enhancer:
         nothing leaves the device and nothing synchronises (with ``check_nan=False``)."""
         return S.istft_int16(self.enhance_wav(wav, clean_wav, check_nan=check_nan))
 
-    def stream_wav(self, batches, depth: int = 2, check_nan: bool = True):
+    def stream_wav(self, batches, depth: int = 2, check_nan: bool = True, score: bool = False):
         """HOST-resident batches in, int16 waves out, copies overlapped with compute.
+
+        ``score=True``: ``batches`` yields ``(wav, clean_wav, n_valid)`` (n_valid: B ints, the samples of each chunk that
+        count; None = all) and the generator yields ``(pcm, (stats float64 [B, S, S, 5], stats_mix float64 [B, S, 5]))``: the
+        sums of :func:`score.wave_stats` of the int16 result (and of the observation at ``ref_ch``) against ``clean_wav``,
+        launched on the compute stream right behind the iSTFT; the block travels with the result's D2H.
 
         ``batches`` yields ``wav`` or ``(wav, clean_wav)``: CPU float32 tensors [B, n_samples, M] / [B, n_samples, S] (pinned
         or not; un-pinned ones are staged through a pinned buffer of this generator).  For every batch, in order, yields
@@ -438,12 +456,21 @@ class Enhancer:
                 pcm, nan = ov.finish(rec)
                 if check_nan and nan:
                     raise FloatingPointError("libmisonet_hip: NaN in pipeline output")
+                if score:
+                    return pcm, self._score_rows(ov.extra(rec), pcm.shape[0], False)
                 return pcm
 
             for i, item in enumerate(batches):
-                wav_h, clean_h = item if isinstance(item, (tuple, list)) else (item, None)
                 while len(pending) >= depth:                  # slot i % depth still belongs to batch i - depth
                     yield finish(pending.popleft())
+                if score:
+                    wav_h, clean_h, nv = item
+                    if clean_h is None:
+                        raise ValueError("score=True needs the clean sources of every batch")
+                    nv = [wav_h.shape[1]] * wav_h.shape[0] if nv is None else nv
+                    pending.append(ov.submit(i, (wav_h, clean_h, self._nv_bits(nv, torch.float32)), self._wav_pass_score))
+                    continue
+                wav_h, clean_h = item if isinstance(item, (tuple, list)) else (item, None)
                 pending.append(ov.submit(i, (wav_h, clean_h), self._wav_pass))
             while pending:
                 yield finish(pending.popleft())
@@ -455,6 +482,75 @@ class Enhancer:
         T = _lib.lib().misonet_stft_frames(Ls)
         return pcm, self.workspace(B, T)[:4].view(torch.int32).clone()
 
+    # ---- scoring beside the pass (score.py, csrc/score.hip) ----------------------------------------------------------
+    # The per-chunk valid counts reach the device as one more staged input of the batch: int32 bit patterns in a tensor of
+    # the batch's dtype (one element per chunk), copied bit for bit by the H2D copies.
+    @staticmethod
+    def _nv_bits(n_valid, dtype):
+        nv = np.asarray(n_valid, dtype=np.int32).reshape(-1, 1)
+        if dtype == torch.complex64:
+            nv = np.concatenate([nv, np.zeros_like(nv)], axis=1)
+        return torch.from_numpy(np.ascontiguousarray(nv)).view(dtype).reshape(-1, 1)
+
+    @staticmethod
+    def _nv_dev(nv):
+        """the staged bits [N, 1] back as contiguous int32 [N] on the device"""
+        v = nv.view(torch.int32).reshape(nv.shape[0], -1)
+        return v[:, 0].contiguous()
+
+    def _score_rows(self, ex, N, spec):
+        """the flat float64 block of a scored batch of N chunks -> per chunk (stats [S, S, 5], stats_mix [S, 5]) and, for
+        ``spec``, also (pair of the output [S, S], pair of the MISO1 estimate at ref_ch [S, S], its uPIT value)"""
+        Sp = self.num_spks
+        a, b = N * Sp * Sp * 5, N * Sp * 5
+        st, sm = ex[:a].reshape(N, Sp, Sp, 5), ex[a:a + b].reshape(N, Sp, 5)
+        if not spec:
+            return st, sm
+        c = N * Sp * Sp
+        o = a + b
+        return st, sm, ex[o:o + c].reshape(N, Sp, Sp), ex[o + c:o + 2 * c].reshape(N, Sp, Sp), ex[o + 2 * c:o + 2 * c + N]
+
+    def _wav_pass_score(self, wav, clean_wav, nv):
+        """:meth:`_wav_pass` and, right behind its iSTFT on the same stream, the sums of the int16 waves and of the
+        observation at ref_ch against the clean waves (read in place from the time-major inputs)"""
+        from . import score as SC
+        pcm, flag = self._wav_pass(wav, clean_wav)
+        n = pcm.shape[2]
+        nvd = self._nv_dev(nv)
+        ref = clean_wav.transpose(1, 2)[:, :, :n]
+        st = SC.wave_stats(pcm, ref, nvd)
+        sm = SC.wave_stats(wav[:, :n, self.ref_ch:self.ref_ch + 1].transpose(1, 2), ref, nvd)
+        return pcm, flag, torch.cat((st.reshape(-1), sm.reshape(-1)))
+
+    def _spec_pass_score(self, mix, clean, nv):
+        """:meth:`_spec_pass` with scores: the loader carries spectrograms, so the reference waves are the device iSTFT
+        (float32) of the clean spectrograms and of the observation at ref_ch; the spectral criterion of the output
+        (loss_Enhance) and of the MISO1 estimate at ref_ch (loss_uPIT) is taken from the spectrograms themselves"""
+        from . import score as SC
+        N, _, T, _ = mix.shape
+        Sp = self.num_spks
+        out, aux = self.enhance(mix, clean, want_miso1=True, check_nan=False)
+        pcm = S.istft_int16(out)                                                             # [N, S, (T - 1) * 64]
+        refw = S._istft_hip(torch.cat((clean, mix[:, self.ref_ch:self.ref_ch + 1]), dim=1), False)   # [N, S + 1, n]
+        nvd = self._nv_dev(nv)
+        st = SC.wave_stats(pcm, refw[:, :Sp], nvd)
+        sm = SC.wave_stats(refw[:, Sp:], refw[:, :Sp], nvd)
+        pair_o, _ = SC.spec_pairs(out, clean)
+        pair_m, _, val = SC.spec_pairs(aux["miso1"][:, :, self.ref_ch], clean, return_value=True)
+        extra = torch.cat((st.reshape(-1), sm.reshape(-1), pair_o.reshape(-1), pair_m.reshape(-1), val))
+        return pcm, self.workspace(N, T)[:4].view(torch.int32).clone(), extra
+
+    def _recording_score(self, rows, n_valid):
+        """(stats, stats_mix[, pair_out, pair_miso1, upit]) of the chunks of one recording, in order -> :class:`score.Score`"""
+        from . import score as SC
+        st, n = SC.combine([r[0] for r in rows], n_valid)
+        sm, _ = SC.combine([r[1] for r in rows], n_valid)
+        if len(rows[0]) == 2:
+            return SC.from_stats(st, n, sm)
+        # the criterion is a sum over frames and bins: a recording's value is the sum over its chunks
+        le = np.sum([np.diagonal(r[2]) for r in rows], axis=0)
+        return SC.from_stats(st, n, sm, loss_miso1=float(np.sum([r[4] for r in rows])), loss_enhance=le)
+
     def _spec_pass(self, mix, clean):
         """one coalesced Tester_Enhance batch on the current stream: the pass, ONE iSTFT + int16 over its N * S
         spectrograms, and a copy of the pass's NaN flag word (ws[0])"""
@@ -462,7 +558,8 @@ class Enhancer:
         pcm = S.istft_int16(self.enhance(mix, clean, check_nan=False))                      # [N, S, (T - 1) * 64]
         return pcm, self.workspace(N, T)[:4].view(torch.int32).clone()
 
-    def _coalesced(self, items, fill, compute, dtype, max_batch: int, depth: int, label, to_host: bool = True):
+    def _coalesced(self, items, fill, compute, dtype, max_batch: int, depth: int, label, to_host: bool = True,
+                   extra_rows=None):
         """The engine of the coalesced drop-ins: :func:`coalesce.coalesce` over :class:`_Overlapped`.
 
         ``items``: :class:`coalesce.Item` whose ``key`` is the tuple of the per-chunk input shapes (None: input absent);
@@ -471,7 +568,9 @@ class Enhancer:
         staged); ``compute(*device inputs [N, ...])`` -> (result [N, ...], flag) on the current stream.  No per-batch host
         synchronisation: the host waits for the oldest batch in flight only.  Yields completed items in loader order with
         ``item.outputs[split][b]`` = the chunk's result row (ndarray; the device row(s) with ``to_host=False``).  A NaN in a
-        batch raises FloatingPointError naming ``label(chunk)`` of its chunks."""
+        batch raises FloatingPointError naming ``label(chunk)`` of its chunks.  ``extra_rows(block, n)``: ``compute`` returns
+        a third value, a small device block that rides the result's D2H; the function cuts its host copy into per-chunk
+        tuples and a chunk's output becomes ``(result row, *its tuple)``."""
         from .coalesce import coalesce
         depth = max(1, int(depth))
         ov = _Overlapped(self.device, depth)
@@ -499,6 +598,9 @@ class Enhancer:
             if nan:
                 names = list(dict.fromkeys(label(c) for c in chunks))
                 raise FloatingPointError(f"libmisonet_hip: NaN in pipeline output of the batch holding {', '.join(names)}")
+            if extra_rows is not None:
+                parts = extra_rows(ov.extra(rec), len(chunks))
+                return [(res[r],) + tuple(q[r] for q in parts) for r in range(len(chunks))]
             return list(zip(*res)) if isinstance(res, tuple) else list(res)
 
         with torch.cuda.device(self.device):
@@ -585,7 +687,7 @@ class Enhancer:
                             for s in range(self.num_spks)], dim=1)                            # [B,S,T,F]
 
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
-                          max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000) -> np.ndarray:
+                          max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000, score: bool = False):
         """Recording in -> enhanced int16 waves out: the reference's loader item AND its tester body as one device-side
         object (``AudioDataset_Test.__getitem__``, dataloader/data.py:524-597, + ``Tester_Enhance.inference``,
         tester.py:846-975), without host STFT dicts.
@@ -601,12 +703,32 @@ class Enhancer:
         padded tail dropped (tester.py:960-969).  Returns int16 [S, L]; ``save_path`` = "<dir>/<wav_name>" also writes
         ``<save_path>_{s}.wav`` as 24-bit PCM (tester.py:972-974).  With ``wav_clean=None`` the speaker order is that of
         each chunk on its own (MISO1 is PIT-trained): for one speaker per output across a long recording use
-        :meth:`enhance_continuous`."""
+        :meth:`enhance_continuous`.
+
+        ``score=True`` (needs ``wav_clean``): returns ``(pcm, Score)``: the int16 result, bit for bit what ``score=False``
+        returns, and its :class:`score.Score` against the clean sources at ``ref_ch`` (SI-SDR, its improvement over the
+        observation at ``ref_ch``, SNR, the best permutation).  The sums are taken on the device behind the iSTFT of every
+        batch and come back with the int16 waves; the padded tail of the last chunk is left out; the chunks are added on
+        the host in float64.  A chunk's sums do not depend on ``max_batch``."""
+        if score and wav_clean is None:
+            raise ValueError("score=True needs the clean sources (wav_clean)")
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
         pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
         K = len(pieces)
+        if score:
+            nv = [pieces[0].shape[0]] * (K - 1) + [pieces[0].shape[0] - gap]
+
+            def scored_batches():
+                for lo in range(0, K, max_batch):
+                    yield (torch.from_numpy(np.stack(pieces[lo:lo + max_batch])),
+                           torch.from_numpy(np.stack(cpieces[lo:lo + max_batch])), nv[lo:lo + max_batch])
+
+            got = list(self.stream_wav(scored_batches(), score=True))
+            pcm = np.concatenate([g[0] for g in got], axis=0)
+            rows = [(g[1][0][b], g[1][1][b]) for g in got for b in range(g[0].shape[0])]
+            return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs), self._recording_score(rows, nv)
 
         def batches():
             for lo in range(0, K, max_batch):
@@ -763,7 +885,7 @@ class Enhancer:
 
     def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
-                           depth: int = 2) -> Dict[str, np.ndarray]:
+                           depth: int = 2, score: bool = False) -> Dict[str, np.ndarray]:
         """:meth:`enhance_recording` over many recordings, with every launch filled across them.
 
         ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
@@ -773,7 +895,8 @@ class Enhancer:
         ``depth`` batches in flight); the int16 chunks are scattered back and every recording stitched.  ``save_path``: a
         directory; recording ``name`` is written as ``<save_path>/<name>_{s}.wav``.  Returns {name: int16 [S, L]} in input
         order; each recording bit for bit what :meth:`enhance_recording` returns for it alone (results do not depend on the
-        batch)."""
+        batch).  ``score=True`` (every recording needs its clean sources): {name: (int16 [S, L], Score)}, each
+        pair bit for bit what :meth:`enhance_recording` returns with ``score=True``."""
         import os
         from .coalesce import Item
         self._ready()
@@ -782,25 +905,38 @@ class Enhancer:
 
         def items():
             for i, (wav_observe, wav_clean, name) in enumerate(recordings):
+                if score and wav_clean is None:
+                    raise ValueError(f"score=True needs the clean sources (wav_clean) of every recording ({name} has none)")
                 pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
                 key = (pieces[0].shape, cpieces[0].shape if cpieces is not None else None)
+                if score:
+                    key = key + ((1,),)                              # the chunk's valid count rides as a third input
                 yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name))
 
         def fill(c, rows):
-            pieces, cpieces, _, _ = c.item.payload
+            pieces, cpieces, gap, _ = c.item.payload
             rows[0].copy_(torch.from_numpy(pieces[c.split]))
             if rows[1] is not None:
                 rows[1].copy_(torch.from_numpy(cpieces[c.split]))
+            if score:
+                n = pieces[0].shape[0]
+                rows[2].copy_(self._nv_bits([n - gap if c.split == len(pieces) - 1 else n], torch.float32)[0])
 
         results = {}
-        for it in self._coalesced(items(), fill, self._wav_pass, torch.float32, max_batch, depth,
-                                  lambda c: str(c.item.payload[3])):
-            _, _, gap, name = it.payload
+        for it in self._coalesced(items(), fill, self._wav_pass_score if score else self._wav_pass, torch.float32, max_batch,
+                                  depth, lambda c: str(c.item.payload[3]),
+                                  extra_rows=(lambda ex, n: self._score_rows(ex, n, False)) if score else None):
+            pieces, _, gap, name = it.payload
             path = os.path.join(save_path, str(name)) if save_path is not None else None
-            results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
+            if score:
+                n = pieces[0].shape[0]
+                pcm = self._finish_recording([o[0][0] for o in it.outputs], gap, path, fs)
+                results[name] = (pcm, self._recording_score([o[0][1:] for o in it.outputs], [n] * (len(pieces) - 1) + [n - gap]))
+            else:
+                results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
         return results
 
-    def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2):
+    def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2, score=False):
         """Drop-in for ``Tester_Enhance.inference(data_loader, saveDir)`` (tester.py:846-975): the loader yields
         ``(split_observe_dict, split_clean_s0_dict, split_clean_s1_dict, gap, wav_name)`` with dict values complex
         ``[B, Ch, T, F]`` keyed '0', '1', ... (dataloader/data.py:524-597).  Every split runs through
@@ -811,9 +947,25 @@ class Enhancer:
         T and the end of the loader flush a shorter one), staged in pinned slots, with no host synchronisation per batch
         (at most ``depth`` batches in flight, the NaN flag word travels with each batch's D2H).  ``coalesce=False``: one
         item at a time, its splits in groups of at most ``max_batch``.  Both return and write the same bits (results do not
-        depend on the batch)."""
+        depend on the batch).
+
+        ``score=True``: the return value is unchanged and ``<saveDir>/scores.json`` is written: ``{wav_name:
+        Score.as_dict()}`` plus a ``"mean"`` entry over the valid speakers.  The loader carries spectrograms, so the
+        reference waves are the device iSTFT (float32) of the clean spectrograms at ``ref_ch`` and the mixture row that of
+        the observation at ``ref_ch``; ``loss_enhance`` / ``loss_miso1`` are criterion.py's ``loss_Enhance`` of the output
+        and ``loss_uPIT`` of the MISO1 estimate at ``ref_ch``, summed over the recording's chunks."""
         import os
         os.makedirs(saveDir, exist_ok=True)
+        if score:
+            scores = {}
+            if coalesce:
+                results = self._inference_coalesced(data_loader, saveDir, fs, write, max_batch, depth, scores)
+            else:
+                results = {}
+                for item in data_loader:                         # one item at a time: its chunks never share a launch
+                    results.update(self._inference_coalesced([item], saveDir, fs, write, max_batch, depth, scores))
+            self._write_scores(saveDir, scores)
+            return results
         if coalesce:
             return self._inference_coalesced(data_loader, saveDir, fs, write, max_batch, depth)
         results = {}
@@ -895,6 +1047,26 @@ class Enhancer:
             names = [wav_name] * B if isinstance(wav_name, str) else list(wav_name)
             yield Item(i, B, K, ((M, T, F), (self.num_spks, T, F)), dict(obs=obs, s0=s0, s1=s1, gaps=gaps, names=names))
 
+    def _tap_references(self, data_loader, refs):
+        """Passes the loader's items through and leaves in ``refs[wav_name]`` the reference waves of every recording:
+        float32 [S + 1, n] on the host, the iSTFT (device) of the clean spectrograms at ref_ch and, last row, of the
+        observation at ref_ch, the chunks stitched with the padded tail dropped."""
+        for item in data_loader:
+            obs_d, s0_d, s1_d, gap, wav_name = item
+            K = len(obs_d)
+            with torch.cuda.device(self.device):
+                spec = torch.stack([torch.stack([torch.as_tensor(s0_d[str(k)])[:, self.ref_ch],
+                                                 torch.as_tensor(s1_d[str(k)])[:, self.ref_ch],
+                                                 torch.as_tensor(obs_d[str(k)])[:, self.ref_ch]], dim=1)
+                                    for k in range(K)], dim=1).to(self.device)               # [B, K, S + 1, T, F]
+                w = S._istft_hip(spec, False).permute(0, 2, 1, 3)                              # [B, S + 1, K, n]
+                w = w.reshape(w.shape[0], w.shape[1], -1).cpu().numpy()
+            for b in range(w.shape[0]):
+                g = int(gap[b]) if hasattr(gap, "__len__") else int(gap)
+                name = wav_name if isinstance(wav_name, str) else wav_name[b]
+                refs[name] = w[b, :, : w.shape[2] - g]
+            yield item
+
     def _fill_spec(self, c, rows):
         """stage one loader chunk: the observation [M,T,F] and the clean sources at ref_ch [S,T,F] (tester.py:889-890)"""
         p = c.item.payload
@@ -902,12 +1074,47 @@ class Enhancer:
         rows[1][0].copy_(p["s0"][c.split][c.b, self.ref_ch])
         rows[1][1].copy_(p["s1"][c.split][c.b, self.ref_ch])
 
-    def _inference_coalesced(self, data_loader, saveDir, fs, write, max_batch, depth):
+    @staticmethod
+    def _write_scores(saveDir, scores):
+        """``<saveDir>/scores.json``: {wav_name: Score.as_dict()} and the "mean" entry"""
+        import json
+        import os
+        from . import score as SC
+        doc = {str(name): sc.as_dict() for name, sc in scores.items()}
+        doc["mean"] = SC.mean_of(list(scores.values()))
+        with open(os.path.join(saveDir, "scores.json"), "w") as fh:
+            json.dump(doc, fh, indent=1)
+
+    def _inference_coalesced(self, data_loader, saveDir, fs, write, max_batch, depth, scores=None):
         import os
         results = {}
-        for it in self._coalesced(self._loader_items(data_loader), self._fill_spec, self._spec_pass, torch.complex64,
-                                  max_batch, depth, lambda c: str(c.item.payload["names"][c.b])):
+        items = self._loader_items(data_loader)
+        if scores is None:
+            batches = self._coalesced(items, self._fill_spec, self._spec_pass, torch.complex64, max_batch, depth,
+                                      lambda c: str(c.item.payload["names"][c.b]))
+        else:
+            def keyed(src):
+                for it in src:
+                    it.key = tuple(it.key) + ((1,),)               # the chunk's valid count rides as a third input
+                    yield it
+
+            def fill(c, rows):
+                self._fill_spec(c, rows)
+                n = (c.item.key[0][1] - 1) * S.HOP
+                last = c.split == c.item.n_split - 1
+                rows[2].copy_(self._nv_bits([n - c.item.payload["gaps"][c.b] if last else n], torch.complex64)[0])
+
+            batches = self._coalesced(keyed(items), fill, self._spec_pass_score, torch.complex64, max_batch, depth,
+                                      lambda c: str(c.item.payload["names"][c.b]),
+                                      extra_rows=lambda ex, n: self._score_rows(ex, n, True))
+        for it in batches:
             p = it.payload
+            if scores is not None:
+                n = (it.key[0][1] - 1) * S.HOP
+                for b in range(it.n_b):
+                    nv = [n] * (it.n_split - 1) + [n - p["gaps"][b]]
+                    scores[p["names"][b]] = self._recording_score([it.outputs[k][b][1:] for k in range(it.n_split)], nv)
+                it.outputs = [[row[0] for row in split] for split in it.outputs]
             for b in range(it.n_b):
                 wav = np.stack([S.stitch_int16([it.outputs[k][b][s] for k in range(it.n_split)], p["gaps"][b])
                                 for s in range(self.num_spks)])                               # [S, n_total]

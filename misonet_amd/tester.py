@@ -46,6 +46,7 @@ class Tester_Enhance(object):
             model_sep.cuda(device)
             model.cuda(device)
         self._enh = Enhancer(model_sep.eval(), model.eval(), num_spks=self.num_spks, ref_ch=self.ref_ch)
+        self.score = False           # True: inference() also writes <saveDir>/scores.json (Enhancer.inference, score=True)
 
     def test(self):
         """tester.py:827-844: development set into ``cv_dev93``, test set into ``test_eval92``."""
@@ -58,7 +59,7 @@ class Tester_Enhance(object):
 
     def inference(self, data_loader, saveDir):
         """tester.py:846-975; returns {wav_name: int16 [num_spks, n_samples]} besides writing the files."""
-        return self._enh.inference(data_loader, saveDir, fs=self.fs)
+        return self._enh.inference(data_loader, saveDir, fs=self.fs, score=bool(self.score))
 
 
 class Tester_Beamforming(object):
@@ -97,6 +98,7 @@ class Tester_Beamforming(object):
         if isinstance(device, int):
             model.cuda(device)
         self._enh = Enhancer(model.eval(), None, num_spks=self.num_spks, ref_ch=self.ref_ch)
+        self.score = False           # True: inference() also writes <saveDir>/scores.json for the beamformer output
 
     def test(self):
         """tester.py:289-325: the training set into ``train_si284`` when ``tr_inference_flag``, else the development set into
@@ -119,7 +121,25 @@ class Tester_Beamforming(object):
         (:mod:`misonet_amd.coalesce`, at most ``depth`` batches in flight, no host synchronisation per batch).  Chunk-wise
         (``utterance_flag = False``): separation, MVDR, one iSTFT + int16 and one D2H per batch.  Utterance-wise: once all
         of a recording's chunks are separated, the tail of :meth:`Enhancer.beamform_utterance` runs on its slice.
-        ``coalesce=False``: one item at a time.  Both return and write the same bits."""
+        ``coalesce=False``: one item at a time.  Both return and write the same bits.
+
+        With ``self.score`` set, ``<saveDir>/scores.json`` is written as :meth:`Enhancer.inference` writes it, for the int16
+        beamformer output that goes into the files (:func:`misonet_amd.score.score_waves`; the reference waves are the
+        device iSTFT of the clean spectrograms at ``ref_ch``, stitched as the output is; no spectral criterion: the
+        beamformer has none)."""
+        if self.score:
+            from . import score as SC
+            refs, scores = {}, {}
+            results = self._inference(self._enh._tap_references(data_loader, refs), saveDir, write, coalesce, max_batch, depth)
+            for name, wav in results.items():
+                ref = refs.pop(name)
+                n = min(wav.shape[1], ref.shape[1])      # utterance-wise output is padded to whole hops: not the recording
+                scores[name] = SC.score_waves(wav[:, :n], ref[:-1, :n], ref[-1, :n], fs=self.fs, device=self._enh.device)
+            self._enh._write_scores(saveDir, scores)
+            return results
+        return self._inference(data_loader, saveDir, write, coalesce, max_batch, depth)
+
+    def _inference(self, data_loader, saveDir, write, coalesce, max_batch, depth):
         import numpy as np
         import torch
         os.makedirs(saveDir, exist_ok=True)

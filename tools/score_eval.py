@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Scores a directory of separated wav files against a directory of clean ones, on the device.
+
+    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json]
+
+EST_DIR holds ``<name>_{s}.wav`` (what ``enhance_recording(save_path=...)`` / ``inference`` write: 24-bit or 16-bit PCM, mono);
+REF_DIR holds the clean sources under the same names (``<name>_{s}.wav``, any channel count: channel ``--ref-ch`` is used)
+and, there or in ``--mix-dir``, the observation as ``<name>.wav`` (optional: without it no SI-SDR improvement is reported).
+Prints (or writes) the JSON ``Enhancer.inference(..., score=True)`` writes: ``{name: Score.as_dict()}`` plus ``"mean"``.
+Definitions: INTEGRATION.md 4d.  Lengths may differ by the padding of the last hop: the common length is scored.
+"""
+import argparse
+import json
+import os
+import re
+import sys
+import wave
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def read_wav(path):
+    """PCM wav (16 or 24 bit) -> (float32 [n, ch] in [-1, 1), int16 [n, ch] when the file holds int16 << 8 or int16, fs)"""
+    from misonet_amd.stft import read_wav_pcm24
+    with wave.open(path, "rb") as w:
+        width, ch, fs, n = w.getsampwidth(), w.getnchannels(), w.getframerate(), w.getnframes()
+        raw = w.readframes(n) if width == 2 else None
+    if width == 3:
+        v, fs = read_wav_pcm24(path)
+        i16 = (v >> 8).astype(np.int16) if not np.any(v & 0xFF) else None
+        return (v / float(1 << 23)).astype(np.float32), i16, fs
+    if width == 2:
+        q = np.frombuffer(raw, dtype="<i2").reshape(n, ch)
+        return (q / 32768.0).astype(np.float32), q.copy(), fs
+    raise ValueError(f"{path}: {8 * width}-bit PCM is not supported (16 or 24)")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("est_dir")
+    ap.add_argument("ref_dir")
+    ap.add_argument("--num-spks", type=int, default=2)
+    ap.add_argument("--ref-ch", type=int, default=0)
+    ap.add_argument("--mix-dir", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    from misonet_amd import score
+    pat = re.compile(r"^(.*)_0\.wav$")
+    names = sorted(m.group(1) for m in map(pat.match, os.listdir(a.est_dir)) if m)
+    if not names:
+        raise SystemExit(f"no <name>_0.wav in {a.est_dir}")
+    scores = {}
+    for name in names:
+        est, ref = [], []
+        for s in range(a.num_spks):
+            f32, i16, _ = read_wav(os.path.join(a.est_dir, f"{name}_{s}.wav"))
+            est.append(i16[:, 0] if i16 is not None else f32[:, 0])       # the library's own files: int16, scored as such
+            ref.append(read_wav(os.path.join(a.ref_dir, f"{name}_{s}.wav"))[0][:, a.ref_ch])
+        mix_path = os.path.join(a.mix_dir or a.ref_dir, f"{name}.wav")
+        mix = read_wav(mix_path)[0][:, a.ref_ch] if os.path.exists(mix_path) else None
+        n = min([len(x) for x in est + ref] + ([len(mix)] if mix is not None else []))
+        if any(x.dtype != est[0].dtype for x in est):
+            est = [x.astype(np.float32) / (32767.0 if x.dtype == np.int16 else 1.0) for x in est]
+        scores[name] = score.score_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
+                                         mix[:n] if mix is not None else None)
+    doc = {name: sc.as_dict() for name, sc in scores.items()}
+    doc["mean"] = score.mean_of(list(scores.values()))
+    text = json.dumps(doc, indent=1)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text)
+    else:
+        print(text)
+
+
+if __name__ == "__main__":
+    main()
