@@ -206,6 +206,33 @@ int misonet_score_spec(const void* est_dev, long long est_sb, long long est_ss, 
                        double* pair_dev, int* perm_dev, double* upit_dev, void* scratch_dev, long long scratch_bytes,
                        misonet_stream stream);
 
+/* ---- BSS-eval SDR / SIR / SAR: the energies of the projections (ABI 490) ------------------------------------------ */
+/* The metric of Vincent et al. 2006 (mir_eval.separation.bss_eval_sources): an estimate is projected onto the span of all
+ * references delayed by 0 .. Q - 1 samples.  All arithmetic is float64; every signal is zero outside [0, n_valid).
+ * misonet_bss_corr: the views, n_valid_dev and the int16 rule of misonet_score_wave.  Rrr_dev double [B][R][R][Q]:
+ *   Rrr[j][k][a] = sum_t r_j[t] r_k[t + a]; Rre_dev double [B][R][E][Q]: Rre[j][i][a] = sum_t r_j[t] e_i[t + a]; Eee_dev
+ *   double [B][E] = sum_t e_i[t]^2.  The products (exact in float64) are added over fixed 4096-sample segments on the
+ *   float64 matrix pipe and the segments in segment order: bit-reproducible, independent of B and of the item's position.
+ * misonet_bss_solve: G [R Q, R Q] with G[(j,a),(k,b)] = sum_t r_j[t - a] r_k[t - b] (block Toeplitz from Rrr), D_i = the
+ *   Rre[.][i][.] stacked.  A_dev double [B][E] = D_i^T G^-1 D_i (the energy of the projection on all references), T_dev double
+ *   [B][E][R] = d_ij^T G_jj^-1 d_ij (on reference j alone), by a blocked Cholesky factorisation whose forward substitution
+ *   rides as extra rows.  A reference with Rrr[j][j][0] == 0 leaves the span (identity block, zero right-hand side: T = 0).
+ *   info_dev int32 [B]: -1, or the first row of G whose pivot was <= 2^-40 of the matching diagonal entry of G or not finite;
+ *   then every T and A of that item is NaN.  Eee_dev is not read by the kernels: SDR_ij = T / (Eee - T), SIR_ij = T / (A - T),
+ *   SAR_i = A / (Eee - A) are formed on the host (misonet_amd/score.py).
+ * scratch_dev: misonet_bss_scratch_bytes(B, E, R, n, Q) = 8 B max(ceil((n + 15) / 4096) (R R + R E + E) Q,
+ *   (R Q + 4) R Q + R (Q + 4) Q) bytes (host only; misonet_bss_solve needs the value for n = 1); less returns MISONET_ENOMEM.
+ *   MISONET_EINVAL (the size function: -1): a null argument, E or R outside 1..4, B outside 1..4096, Q outside 16..1024 or no
+ *   multiple of 16, n outside 1..2^24, a negative stride.  Both calls are asynchronous on the stream and allocate nothing. */
+long long misonet_bss_scratch_bytes(int B, int E, int R, long long n, int Q);
+int misonet_bss_corr(const void* est_dev, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                     const float* ref_dev, long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R,
+                     long long n, const int* n_valid_dev, int Q, double* Rrr_dev, double* Rre_dev, double* Eee_dev,
+                     void* scratch_dev, long long scratch_bytes, misonet_stream stream);
+int misonet_bss_solve(const double* Rrr_dev, const double* Rre_dev, const double* Eee_dev, int B, int E, int R, int Q,
+                      double* T_dev, double* A_dev, int* info_dev, void* scratch_dev, long long scratch_bytes,
+                      misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

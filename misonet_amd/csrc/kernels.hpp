@@ -228,4 +228,16 @@ hipError_t launch_score_wave(const void* est, int est_is_i16, const long long* e
 hipError_t launch_score_spec(const PitArgs& p, int E, int R, double* part, double* pair, int* perm, double* upit,
                              hipStream_t s);
 
+// BSS-eval energies (bss.hip).  Lagged correlations over the same strided views as launch_score_wave: per-segment partials
+// [B][bss_corr_segments(n)][R R + R E + E][Q] folded in segment order into Rrr [B][R][R][Q], Rre [B][R][E][Q], Eee [B][E].
+// The systems: per item bss_solve_doubles(R, Q) doubles of scratch; T [B][E][R], A [B][E], info [B] (-1, or the first row
+// whose pivot failed).  1 <= E, R <= 4, 16 | Q, 16 <= Q <= 1024.
+long long bss_corr_segments(long long n);
+long long bss_solve_doubles(int R, int Q);
+hipError_t launch_bss_corr(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs, int B,
+                           int E, int R, long long n, const int* n_valid /*[B] or nullptr*/, int Q, double* part, double* Rrr,
+                           double* Rre, double* Eee, hipStream_t s);
+hipError_t launch_bss_solve(const double* Rrr, const double* Rre, int B, int E, int R, int Q, double* T, double* A, int* info,
+                            double* scratch, hipStream_t s);
+
 }  // namespace mn

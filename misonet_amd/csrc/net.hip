@@ -657,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 480; }   // 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 490; }   // 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1154,6 +1154,54 @@ int misonet_score_spec(const void* est, long long est_sb, long long est_ss, long
   p.B = B; p.F = F; p.T = T;
   HIPCHK(launch_score_spec(p, E, R, reinterpret_cast<double*>(scratch), pair, perm, upit,
                            reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- BSS-eval energies (bss.hip) -----------------------------------------------------------------------------------------
+static int bss_ranges(int B, int E, int R, int Q) {
+  if (E < 1 || E > 4) return fail(MISONET_EINVAL, "E must be in [1, 4] (got %d)", E);
+  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
+  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
+  if (Q < 16 || Q > 1024 || Q % 16) return fail(MISONET_EINVAL, "Q must be a multiple of 16 in [16, 1024] (got %d)", Q);
+  return MISONET_OK;
+}
+
+// One size serves both calls: the correlation partials [B][ceil((n + 15) / 4096)][R R + R E + E][Q] and the systems of an item,
+// (R Q + 4) R Q + R (Q + 4) Q doubles, whichever is larger.
+long long misonet_bss_scratch_bytes(int B, int E, int R, long long n, int Q) {
+  if (B < 1 || B > 4096 || E < 1 || E > 4 || R < 1 || R > 4 || Q < 16 || Q > 1024 || Q % 16 || n < 1 || n > (1LL << 24)) return -1;
+  const long long corr = bss_corr_segments(n) * ((long long)R * R + (long long)R * E + E) * Q;
+  const long long sys = bss_solve_doubles(R, Q);
+  return (long long)B * (corr > sys ? corr : sys) * (long long)sizeof(double);
+}
+
+int misonet_bss_corr(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st, const float* ref,
+                     long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, long long n,
+                     const int* n_valid, int Q, double* Rrr, double* Rre, double* Eee, void* scratch,
+                     long long scratch_bytes, misonet_stream stream) {
+  if (!est || !ref || !Rrr || !Rre || !Eee || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
+    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
+  const long long need = misonet_bss_scratch_bytes(B, E, R, n, Q);
+  if (scratch_bytes < need)
+    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_bss_scratch_bytes(B, E, R, n, Q))", scratch_bytes, need);
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
+  HIPCHK(launch_bss_corr(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, Q, reinterpret_cast<double*>(scratch), Rrr, Rre,
+                         Eee, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_bss_solve(const double* Rrr, const double* Rre, const double* Eee, int B, int E, int R, int Q, double* T, double* A,
+                      int* info, void* scratch, long long scratch_bytes, misonet_stream stream) {
+  if (!Rrr || !Rre || !Eee || !T || !A || !info || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
+  const long long need = misonet_bss_scratch_bytes(B, E, R, 1, Q);
+  if (scratch_bytes < need)
+    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_bss_scratch_bytes(B, E, R, 1, Q))", scratch_bytes, need);
+  HIPCHK(launch_bss_solve(Rrr, Rre, B, E, R, Q, T, A, info, reinterpret_cast<double*>(scratch),
+                          reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -1,7 +1,9 @@
 """Scores of separated output against clean references: SI-SDR and its improvement over the mixture, SNR, the best
 permutation, and the reference's training criterion (criterion.py ``loss_uPIT`` / ``loss_Enhance``).  The sums run on the
 device (csrc/score.hip, C ABI ``misonet_score_wave`` / ``misonet_score_spec``); the handful of doubles they leave is turned
-into dB on the host.  tests/score_ref.py restates every definition in NumPy.
+into dB on the host.  tests/score_ref.py restates every definition in NumPy.  BSS-eval SDR, SIR and SAR (Vincent et al. 2006,
+the figures SMS-WSJ tabulates) come from the energies of two projections (csrc/bss.hip, C ABI ``misonet_bss_corr`` /
+``misonet_bss_solve``; :class:`BssEval`, INTEGRATION.md 4e, restated in tests/bss_ref.py).
 
 Definitions:
   * stats[i][j] = (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j) over the valid samples; additive over the chunks of a recording;
@@ -267,3 +269,286 @@ def score_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Score:
     st, n = combine(blocks_e, ns)
     sm = combine(blocks_m, ns)[0] if mix is not None else None
     return from_stats(st, n, sm)
+
+
+# ---- BSS-eval SDR / SIR / SAR ------------------------------------------------------------------------
+# float64 throughout, every signal zero outside [0, n); references r_j, estimates e_i, filter length Q:
+#   Rrr[j][k][a] = S_t r_j[t] r_k[t + a], Rre[j][i][a] = S_t r_j[t] e_i[t + a], a in [0, Q), Eee[i] = S_t e_i[t]^2;
+#   G [R Q, R Q]: G[(j,a),(k,b)] = S_t r_j[t - a] r_k[t - b]; D_i = the Rre[.][i][.] stacked;
+#   A_i = D_i^T G^-1 D_i (projection on all references), T_ij = d_ij^T G_jj^-1 d_ij (on reference j alone);
+#   SDR_ij = 10 log10(T_ij / max(Eee_i - T_ij, 0)), SIR_ij = 10 log10(T_ij / max(A_i - T_ij, 0)),
+#   SAR_i = 10 log10(A_i / max(Eee_i - A_i, 0)): mir_eval's figures, the projections being orthogonal.
+BSS_SCRATCH_CAP = 1 << 30    # bytes of device scratch per call of bss_solve / bss_corr: larger batches go in groups
+
+
+@dataclasses.dataclass
+class BssEval:
+    """BSS-eval figures of one recording, speaker j = reference j, dB.  ``ok = False``: the factorisation met a pivot
+    <= 2^-40 of its diagonal entry (linearly dependent references) and every figure is NaN."""
+    sdr: np.ndarray                       # [S] SDR(e_j, r_j)
+    sir: np.ndarray                       # [S] SIR(e_j, r_j)
+    sar: np.ndarray                       # [S] SAR(e_j)
+    valid: np.ndarray                     # [S] bool: reference j is not silent (a silent one leaves the span; NaN SDR / SIR)
+    ok: bool
+    perm_best: List[int]                  # p[j] = the estimate of reference j in the assignment with the largest mean SIR
+    sdr_best: np.ndarray                  # [S] SDR(e_p[j], r_j)
+    sir_best: np.ndarray                  # [S] SIR(e_p[j], r_j)
+    sar_best: np.ndarray                  # [S] SAR(e_p[j])
+    sdr_mix: Optional[np.ndarray]         # [S] SDR(mixture, r_j), or None without a mixture
+    sdri: Optional[np.ndarray]            # [S] sdr - sdr_mix
+    filt_len: int
+    n_samples: int
+
+    def as_dict(self) -> dict:
+        def lst(x):
+            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
+        return dict(sdr=lst(self.sdr), sir=lst(self.sir), sar=lst(self.sar), valid=[bool(v) for v in self.valid],
+                    ok=bool(self.ok), perm_best=[int(p) for p in self.perm_best], sdr_best=lst(self.sdr_best),
+                    sir_best=lst(self.sir_best), sar_best=lst(self.sar_best), sdr_mix=lst(self.sdr_mix), sdri=lst(self.sdri),
+                    filt_len=int(self.filt_len), n_samples=int(self.n_samples))
+
+
+def _db_ratio(num, den):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 10.0 * np.log10(num / np.maximum(den, 0.0))
+
+
+def bss_from_energies(T, A, Eee, valid=None, ok: bool = True, T_mix=None, Eee_mix=None, filt_len: int = 512,
+                      n_samples: int = 0) -> BssEval:
+    """T float64 [S estimates, S references], A [S], Eee [S] (:func:`bss_solve` / :func:`bss_corr` of one recording) ->
+    :class:`BssEval`.  ``valid`` bool [S] (None: all): reference j is not silent; ``ok``: the factorisation succeeded;
+    ``T_mix`` [S] and ``Eee_mix`` (scalar): the energies of the mixture scored as a single estimate.  Host, float64, no GPU."""
+    T = np.asarray(T, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1]:
+        raise ValueError("T must be [S, S] (estimates x references)")
+    S = T.shape[0]
+    A = np.asarray(A, dtype=np.float64).reshape(-1)
+    Eee = np.asarray(Eee, dtype=np.float64).reshape(-1)
+    if A.shape != (S,) or Eee.shape != (S,):
+        raise ValueError("A and Eee must hold one entry per estimate")
+    valid = np.ones(S, dtype=bool) if valid is None else np.asarray(valid, dtype=bool).reshape(-1)
+    if valid.shape != (S,):
+        raise ValueError("valid must hold one entry per reference")
+    if (T_mix is None) != (Eee_mix is None):
+        raise ValueError("T_mix and Eee_mix go together")
+    sdr_m = np.where(valid[None, :], _db_ratio(T, Eee[:, None] - T), np.nan)
+    sir_m = np.where(valid[None, :], _db_ratio(T, A[:, None] - T), np.nan)
+    sar_v = _db_ratio(A, Eee - A)
+    mix_v = None
+    if T_mix is not None:
+        tm = np.asarray(T_mix, dtype=np.float64).reshape(-1)
+        if tm.shape != (S,):
+            raise ValueError("T_mix must hold one entry per reference")
+        mix_v = np.where(valid, _db_ratio(tm, float(Eee_mix) - tm), np.nan)
+    if not ok:
+        sdr_m, sir_m, sar_v = np.full((S, S), np.nan), np.full((S, S), np.nan), np.full(S, np.nan)
+        mix_v = None if mix_v is None else np.full(S, np.nan)
+    p = best_perm(sir_m)
+    idx = np.arange(S)
+    sdr = sdr_m[idx, idx]
+    return BssEval(sdr=sdr, sir=sir_m[idx, idx], sar=sar_v.copy(), valid=valid, ok=bool(ok), perm_best=p,
+                   sdr_best=np.array([sdr_m[p[j], j] for j in range(S)]), sir_best=np.array([sir_m[p[j], j] for j in range(S)]),
+                   sar_best=np.array([sar_v[p[j]] for j in range(S)]), sdr_mix=mix_v,
+                   sdri=None if mix_v is None else sdr - mix_v, filt_len=int(filt_len), n_samples=int(n_samples))
+
+
+def bss_mean_of(evals: Sequence[BssEval]) -> dict:
+    """The ``"bss"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers of the
+    recordings whose factorisation succeeded."""
+    out = {}
+    for key in ("sdr", "sir", "sar", "sdr_best", "sir_best", "sar_best", "sdr_mix", "sdri"):
+        vals = [float(getattr(e, key)[j]) for e in evals if e.ok and getattr(e, key) is not None
+                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
+        out[key] = float(np.mean(vals)) if vals else None
+    out["n_recordings"] = len(evals)
+    out["n_failed"] = int(sum(1 for e in evals if not e.ok))
+    return out
+
+
+def bss_scratch_bytes(B: int, E: int, R: int, n: int, filt_len: int = 512) -> int:
+    """bytes of scratch for :func:`bss_corr` (n samples) and :func:`bss_solve` (n = 1):
+    8 B max(ceil((n + 15) / 4096) (R R + R E + E) Q, (R Q + 4) R Q + R (Q + 4) Q); negative outside the limits"""
+    return int(_lib.lib().misonet_bss_scratch_bytes(int(B), int(E), int(R), int(n), int(filt_len)))
+
+
+def _bss_limits(E, R, Q, n=1):
+    if not (1 <= E <= 4 and 1 <= R <= 4):
+        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+    if not (16 <= Q <= 1024) or Q % 16:
+        raise ValueError(f"filt_len must be a multiple of 16 in [16, 1024] (got {Q})")
+    if not (1 <= n <= 1 << 24):
+        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
+
+
+def _bss_groups(B, per_item):
+    g = max(1, min(B, 4096, BSS_SCRATCH_CAP // max(1, per_item)))
+    return [(lo, min(B, lo + g)) for lo in range(0, B, g)]
+
+
+def bss_corr(est, ref, n_valid=None, filt_len: int = 512):
+    """est int16 or float32 [B, E, n], ref float32 [B, R, n] (device views as :func:`wave_stats` takes them), n_valid int32
+    [B] (device) or None.  Returns float64 (Rrr [B, R, R, Q], Rre [B, R, E, Q], Eee [B, E]).  Asynchronous on the current
+    stream; an item's block does not depend on the batch."""
+    import torch
+    est = _wave_view(est, "est", (torch.int16, torch.float32))
+    ref = _wave_view(ref, "ref", (torch.float32,))
+    B, E, n = est.shape
+    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
+        raise ValueError("est and ref must agree in B, n and device")
+    R, Q = ref.shape[1], int(filt_len)
+    _bss_limits(E, R, Q, n)
+    if B < 1:
+        raise ValueError("at least one item")
+    dev = est.device
+    if n_valid is not None:
+        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
+                or n_valid.numel() != B or not n_valid.is_contiguous():
+            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    Rrr = torch.empty((B, R, R, Q), dtype=torch.float64, device=dev)
+    Rre = torch.empty((B, R, E, Q), dtype=torch.float64, device=dev)
+    Eee = torch.empty((B, E), dtype=torch.float64, device=dev)
+    L = _lib.lib()
+    groups = _bss_groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, n, Q)))
+    nb = int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, n, Q))
+    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for lo, hi in groups:
+            e, r = est[lo:hi], ref[lo:hi]
+            _lib.check(L.misonet_bss_corr(e.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
+                                          est.stride(2), r.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), hi - lo,
+                                          E, R, n, n_valid[lo:hi].data_ptr() if n_valid is not None else None, Q,
+                                          Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(), Eee[lo:hi].data_ptr(),
+                                          scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    return Rrr, Rre, Eee
+
+
+def bss_solve(Rrr, Rre, Eee):
+    """Rrr float64 [B, R, R, Q], Rre [B, R, E, Q], Eee [B, E] (device, contiguous) -> (T float64 [B, E, R], A [B, E], info
+    int32 [B]): the energies of the projections of estimate i on reference j alone and on all references, by a blocked
+    Cholesky factorisation per item; info = -1, or the first row of G whose pivot failed (then T and A of the item are NaN).
+    Asynchronous on the current stream; batches whose systems exceed 1 GiB of scratch run in groups."""
+    import torch
+    for x, name, nd in ((Rrr, "Rrr", 4), (Rre, "Rre", 4), (Eee, "Eee", 2)):
+        if not isinstance(x, torch.Tensor) or x.dim() != nd or x.dtype != torch.float64 or not x.is_cuda \
+                or not x.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 device tensor of {nd} dimensions")
+    B, R, R2, Q = Rrr.shape
+    E = Rre.shape[2]
+    if R2 != R or tuple(Rre.shape) != (B, R, E, Q) or tuple(Eee.shape) != (B, E) or Rre.device != Rrr.device \
+            or Eee.device != Rrr.device:
+        raise ValueError("Rrr [B, R, R, Q], Rre [B, R, E, Q] and Eee [B, E] must agree")
+    _bss_limits(E, R, Q)
+    if B < 1:
+        raise ValueError("at least one item")
+    dev = Rrr.device
+    T = torch.empty((B, E, R), dtype=torch.float64, device=dev)
+    A = torch.empty((B, E), dtype=torch.float64, device=dev)
+    info = torch.empty((B,), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    groups = _bss_groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, 1, Q)))
+    nb = int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, 1, Q))
+    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for lo, hi in groups:
+            _lib.check(L.misonet_bss_solve(Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(), Eee[lo:hi].data_ptr(), hi - lo, E, R,
+                                           Q, T[lo:hi].data_ptr(), A[lo:hi].data_ptr(), info[lo:hi].data_ptr(),
+                                           scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    return T, A, info
+
+
+def bss_energies(est, ref, mix=None, n_valid=None, filt_len: int = 512):
+    """est int16 / float32 [B, S, n], ref float32 [B, S, n], mix float32 [B, 1, n] or None (device views), n_valid int32 [B] or
+    None -> a device float64 block [B, W]: per item T [S, S], A [S], Eee [S], Rrr[j][j][0] [S] (0: reference j is silent),
+    info and, with a mixture, T_mix [S] and Eee_mix (the mixture scored as a one-estimate call): what :func:`bss_unpack`
+    reads.  Everything is queued on the current stream; nothing synchronises."""
+    import torch
+    Rrr, Rre, Eee = bss_corr(est, ref, n_valid, filt_len)
+    T, A, info = bss_solve(Rrr, Rre, Eee)
+    B = est.shape[0]
+    if est.shape[1] != ref.shape[1]:
+        raise ValueError("as many estimates as references")
+    idx = torch.arange(ref.shape[1], device=est.device)
+    cols = [T.reshape(B, -1), A, Eee, Rrr[:, idx, idx, 0], info.to(torch.float64)[:, None]]
+    if mix is not None:
+        _, Rrm, Emm = bss_corr(mix, ref, n_valid, filt_len)
+        Tm, _, _ = bss_solve(Rrr, Rrm, Emm)
+        cols += [Tm.reshape(B, -1), Emm]
+    return torch.cat(cols, dim=1)
+
+
+def bss_unpack(row, S: int, filt_len: int, n_samples: int) -> BssEval:
+    """one host row of :func:`bss_energies` -> :class:`BssEval`"""
+    row = np.asarray(row, dtype=np.float64)
+    o = S * S
+    T, A, Eee, rr0, info = row[:o].reshape(S, S), row[o:o + S], row[o + S:o + 2 * S], row[o + 2 * S:o + 3 * S], row[o + 3 * S]
+    o += 3 * S + 1
+    tm = em = None
+    if row.shape[0] > o:
+        tm, em = row[o:o + S], row[o + S]
+    return bss_from_energies(T, A, Eee, valid=rr0 != 0, ok=not info >= 0, T_mix=tm, Eee_mix=em, filt_len=filt_len,
+                             n_samples=n_samples)
+
+
+def bss_queue(items, filt_len: int, dev, pinned: bool = False):
+    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
+    same S and all or none with a mixture; any lengths) -> the device block [len(items), W] of :func:`bss_energies`, queued
+    on the current stream of ``dev``.  Several recordings go as one batch, zero-padded to the longest with ``n_valid`` set: a
+    row is bit for bit what the recording gives alone.  ``pinned``: host inputs go through pinned memory and asynchronous
+    copies, so that the caller is not held up."""
+    import torch
+    recs = []
+    for est, clean, mix in items:
+        est, clean = torch.as_tensor(est), torch.as_tensor(clean)
+        if est.dim() != 2 or clean.dim() != 2 or est.shape != clean.shape:
+            raise ValueError("est and clean must both be [S, L]")
+        if est.dtype != torch.int16:
+            est = est.to(torch.float32)
+        if mix is not None:
+            mix = torch.as_tensor(mix).to(torch.float32).reshape(-1)
+            if mix.numel() != est.shape[1]:
+                raise ValueError("mix must hold L samples")
+        recs.append((est, clean.to(torch.float32), mix))
+    if not recs:
+        raise ValueError("at least one recording")
+    S, G = recs[0][0].shape[0], len(recs)
+    if any(r[0].shape[0] != S for r in recs) or any((r[2] is None) != (recs[0][2] is None) for r in recs):
+        raise ValueError("every recording must have the same number of speakers, and all or none a mixture")
+    for r in recs:
+        _bss_limits(S, S, int(filt_len), r[0].shape[1])
+    if any(r[0].dtype != recs[0][0].dtype for r in recs):
+        raise ValueError("int16 and float32 estimates cannot share a batch")
+    with_mix = recs[0][2] is not None
+
+    def up(x):
+        if x.device.type == "cpu" and pinned:
+            return x.contiguous().pin_memory().to(dev, non_blocking=True)
+        return x.to(dev).contiguous()
+
+    with torch.cuda.device(dev):
+        if G == 1:
+            est, clean, mix = recs[0]
+            return bss_energies(up(est)[None], up(clean)[None], up(mix)[None, None] if with_mix else None, None, int(filt_len))
+        lens = [int(r[0].shape[1]) for r in recs]
+        n = max(lens)
+
+        def padded(k, rows, dtype):
+            buf = torch.zeros((G, rows, n), dtype=dtype, pin_memory=pinned)
+            for g, r in enumerate(recs):
+                buf[g, :, :lens[g]].copy_(r[k].reshape(rows, -1))
+            return buf.to(dev, non_blocking=pinned)
+
+        nv = torch.tensor(lens, dtype=torch.int32)
+        nv = (nv.pin_memory() if pinned else nv).to(dev, non_blocking=pinned)
+        return bss_energies(padded(0, S, recs[0][0].dtype), padded(1, S, torch.float32),
+                            padded(2, 1, torch.float32) if with_mix else None, nv, int(filt_len))
+
+
+def bss_eval_waves(est, clean, mix=None, filt_len: int = 512, device=None) -> BssEval:
+    """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
+    :class:`BssEval` (1 <= S <= 4, L <= 2^24): the counterpart of :func:`score_waves` for BSS-eval SDR, SIR and SAR, for the
+    output of ``enhance_continuous`` and for files read back from disk."""
+    import torch
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    est = torch.as_tensor(est)
+    row = bss_queue([(est, clean, mix)], filt_len, dev)[0].cpu().numpy()
+    return bss_unpack(row, int(est.shape[0]), int(filt_len), int(est.shape[1]))

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Scores a directory of separated wav files against a directory of clean ones, on the device.
 
-    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json]
+    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]]
 
 EST_DIR holds ``<name>_{s}.wav`` (what ``enhance_recording(save_path=...)`` / ``inference`` write: 24-bit or 16-bit PCM, mono);
 REF_DIR holds the clean sources under the same names (``<name>_{s}.wav``, any channel count: channel ``--ref-ch`` is used)
 and, there or in ``--mix-dir``, the observation as ``<name>.wav`` (optional: without it no SI-SDR improvement is reported).
 Prints (or writes) the JSON ``Enhancer.inference(..., score=True)`` writes: ``{name: Score.as_dict()}`` plus ``"mean"``.
+``--bss`` adds BSS-eval SDR, SIR and SAR (``BssEval.as_dict()``, INTEGRATION.md 4e, filters of ``--filt-len`` taps) as a
+``"bss"`` entry of every recording and of ``"mean"``; without the flag the output is what it always was.
 Definitions: INTEGRATION.md 4d.  Lengths may differ by the padding of the last hop: the common length is scored.
 """
 import argparse
@@ -47,13 +49,15 @@ def main(argv=None):
     ap.add_argument("--ref-ch", type=int, default=0)
     ap.add_argument("--mix-dir", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bss", action="store_true", help="also BSS-eval SDR / SIR / SAR")
+    ap.add_argument("--filt-len", type=int, default=512, help="taps of the BSS-eval projection filters")
     a = ap.parse_args(argv)
     from misonet_amd import score
     pat = re.compile(r"^(.*)_0\.wav$")
     names = sorted(m.group(1) for m in map(pat.match, os.listdir(a.est_dir)) if m)
     if not names:
         raise SystemExit(f"no <name>_0.wav in {a.est_dir}")
-    scores = {}
+    scores, evals = {}, {}
     for name in names:
         est, ref = [], []
         for s in range(a.num_spks):
@@ -67,8 +71,15 @@ def main(argv=None):
             est = [x.astype(np.float32) / (32767.0 if x.dtype == np.int16 else 1.0) for x in est]
         scores[name] = score.score_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
                                          mix[:n] if mix is not None else None)
+        if a.bss:
+            evals[name] = score.bss_eval_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
+                                               mix[:n] if mix is not None else None, filt_len=a.filt_len)
     doc = {name: sc.as_dict() for name, sc in scores.items()}
     doc["mean"] = score.mean_of(list(scores.values()))
+    if a.bss:
+        for name, ev in evals.items():
+            doc[name]["bss"] = ev.as_dict()
+        doc["mean"]["bss"] = score.bss_mean_of(list(evals.values()))
     text = json.dumps(doc, indent=1)
     if a.out:
         with open(a.out, "w") as fh:
