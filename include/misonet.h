@@ -233,6 +233,41 @@ int misonet_bss_solve(const double* Rrr_dev, const double* Rre_dev, const double
                       double* T_dev, double* A_dev, int* info_dev, void* scratch_dev, long long scratch_bytes,
                       misonet_stream stream);
 
+/* ---- STOI and ESTOI: the intelligibility figures (ABI 500) --------------------------------------------------------- */
+/* STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) of an estimate y against a clean reference x, step for step what
+ * pystoi does (INTEGRATION.md 4f has the definition in full; tests/stoi_ref.py restates it): both signals resampled to
+ * 10 kHz, the frames of 256 samples whose energy lies more than 40 dB under the loudest frame OF THE REFERENCE removed from
+ * both, the kept frames overlap-added and framed again, a 512-point transform per frame, 15 third-octave bands from 150 Hz,
+ * and over every run of 30 frames the clipped band-wise correlation (STOI) and the row- and column-normalised correlation
+ * (ESTOI).  All arithmetic is float64, without atomics and in a fixed order: bit-reproducible, independent of B and of the
+ * item's position in the batch.
+ * misonet_stoi_resampled_len: ceil(n p / q) with p / q = 10000 / fs, the length at 10 kHz (host only); -1 for fs other than
+ *   8000, 10000, 16000 or n outside 1..2^24.  misonet_stoi_taps: the number of polyphase taps 2 Lh + 1 (581 for 16 kHz, 365
+ *   for 8 kHz, 1 for 10 kHz; host only), and, where taps_host is not NULL, the taps g[k] = p h[k - Lh] / sum h themselves.
+ * misonet_stoi_resample: the views, n_valid_dev and the int16 rule of misonet_score_wave; mix_dev (may be NULL) float32, item
+ *   b sample m at mix_dev[b * mix_sb + m * mix_st].  x10_dev double [B][R + E (+ 1)][n10], n10 = misonet_stoi_resampled_len(n,
+ *   fs): the references, the estimates and the mixture at 10 kHz, x10[m] = sum_j x[j] g[m q - j p + Lh] with j ascending, zero
+ *   past the item's own length; len10_dev int32 [B] = that length, ceil(n_valid p / q).  Every signal is resampled once.
+ * misonet_stoi_measure: x10_dev as above (NS signals per item, the first R of them the references), len10_dev int32 [B] or
+ *   NULL (n10).  out_dev double [B][NS - R][R][2] = (STOI, ESTOI) of estimate i against reference j, both 1e-5 where fewer
+ *   than 30 frames are kept; frames_dev int32 [B][R][3] = (frames, kept frames, 1 if any sample of the reference is not
+ *   zero).  The number of kept frames never leaves the device: the grids are sized by all frames.
+ * scratch_dev: misonet_stoi_scratch_bytes(B, NS, R, n10) bytes (host only) = 8 B (R f + 15 R (NS - R + 1) f + 2 R (NS - R)
+ *   max(f - 29, 1) + R ceil(f / 2)) with f = max(frames of n10, 1); less returns MISONET_ENOMEM.  MISONET_EINVAL (the size
+ *   function: -1): a null argument, E or R outside 1..4, NS - R outside 1..5, B outside 1..4096, n outside 1..2^24, n10 outside
+ *   1..5 * 2^22, another rate, a negative stride.  The first call on a device builds a table of 1715 doubles (window,
+ *   twiddles, taps: one allocation and one synchronous copy); after that both calls are asynchronous on the stream and
+ *   allocate nothing. */
+long long misonet_stoi_resampled_len(long long n, int fs);
+int misonet_stoi_taps(int fs, double* taps_host);
+long long misonet_stoi_scratch_bytes(int B, int NS, int R, long long n10);
+int misonet_stoi_resample(const void* est_dev, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                          const float* ref_dev, long long ref_sb, long long ref_ss, long long ref_st, const float* mix_dev,
+                          long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid_dev, int fs,
+                          double* x10_dev, int* len10_dev, misonet_stream stream);
+int misonet_stoi_measure(const double* x10_dev, const int* len10_dev, int B, int NS, int R, long long n10, double* out_dev,
+                         int* frames_dev, void* scratch_dev, long long scratch_bytes, misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

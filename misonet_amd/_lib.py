@@ -75,6 +75,15 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_bss_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_stoi_resampled_len": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "misonet_stoi_taps": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
+    "misonet_stoi_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong]),
+    "misonet_stoi_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p,
+                                        C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong,
+                                        C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "misonet_stoi_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_pipeline_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.POINTER(C.c_void_p)]),
     "misonet_pipeline_destroy": (C.c_int, [C.c_void_p]),

@@ -240,4 +240,22 @@ hipError_t launch_bss_corr(const void* est, int est_is_i16, const long long* es,
 hipError_t launch_bss_solve(const double* Rrr, const double* Rre, int B, int E, int R, int Q, double* T, double* A, int* info,
                             double* scratch, hipStream_t s);
 
+// STOI / ESTOI (stoi.hip).  The table (stoi_table_count() doubles, built on the host): the window, the
+// twiddles of the 512-point transform and the polyphase taps of 16, 8 and 10 kHz.  The resampler reads the strided views of
+// launch_score_wave (ms = the item and sample strides of the mixture, which may be nullptr) and writes x10 [B][R + E (+ 1)][n10]
+// (references, estimates, mixture) and len10 [B].  The measure: per item stoi_item_doubles(NS, R, n10) doubles of scratch;
+// out [B][NS - R][R][2] = (STOI, ESTOI), meta [B][R][3] = (frames, kept frames, any sample != 0).
+int stoi_table_count();
+void stoi_build_table(double* t);
+int stoi_taps(int fs);            // 2 Lh + 1, or -1 for a rate that is not served
+int stoi_tap_offset(int fs);      // where those taps start in the table, or -1
+long long stoi_resampled_len(long long n, int fs);
+long long stoi_item_doubles(int NS, int R, long long n10);
+hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
+                                const float* mix, const long long* ms, int B, int E, int R, long long n,
+                                const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* x10, int* len10,
+                                hipStream_t s);
+hipError_t launch_stoi_measure(const double* x10, const int* len10 /*[B] or nullptr*/, int B, int NS, int R, long long n10,
+                               const double* table, double* out, int* meta, double* scratch, hipStream_t s);
+
 }  // namespace mn

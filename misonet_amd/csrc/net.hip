@@ -657,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 490; }   // 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 500; }   // 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1202,6 +1202,87 @@ int misonet_bss_solve(const double* Rrr, const double* Rre, const double* Eee, i
     return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_bss_scratch_bytes(B, E, R, 1, Q))", scratch_bytes, need);
   HIPCHK(launch_bss_solve(Rrr, Rre, B, E, R, Q, T, A, info, reinterpret_cast<double*>(scratch),
                           reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- STOI / ESTOI (stoi.hip) ------------------------------------------------------------------------------------------------
+// the table of the current device (window, twiddles, polyphase taps), built on first use: that one call allocates and copies
+// synchronously; every later call only queues kernels
+static std::atomic<double*> g_stoi_tab[MAX_DEV] = {};
+static std::mutex g_stoi_mu;
+static int get_stoi_table(const double** out) {
+  const int d = cur_dev();
+  if (!g_stoi_tab[d].load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lk(g_stoi_mu);
+    if (!g_stoi_tab[d].load(std::memory_order_acquire)) {
+      std::vector<double> t((size_t)stoi_table_count());
+      stoi_build_table(t.data());
+      double* p = nullptr;
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), t.size() * sizeof(double)));
+      HIPCHK(hipMemcpy(p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
+      g_stoi_tab[d].store(p, std::memory_order_release);
+    }
+  }
+  *out = g_stoi_tab[d].load(std::memory_order_acquire);
+  return MISONET_OK;
+}
+
+long long misonet_stoi_resampled_len(long long n, int fs) { return stoi_resampled_len(n, fs); }
+
+int misonet_stoi_taps(int fs, double* taps_host) {
+  const int nt = stoi_taps(fs);
+  if (nt < 0) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
+  if (taps_host) {
+    std::vector<double> t((size_t)stoi_table_count());
+    stoi_build_table(t.data());
+    const int off = stoi_tap_offset(fs);
+    for (int i = 0; i < nt; ++i) taps_host[i] = t[(size_t)off + i];
+  }
+  return nt;
+}
+
+static bool stoi_ranges_ok(int B, int NS, int R, long long n10) {
+  return B >= 1 && B <= 4096 && R >= 1 && R <= 4 && NS - R >= 1 && NS - R <= 5 && n10 >= 1 && n10 <= 5 * (1LL << 22);
+}
+
+long long misonet_stoi_scratch_bytes(int B, int NS, int R, long long n10) {
+  if (!stoi_ranges_ok(B, NS, R, n10)) return -1;
+  return (long long)B * stoi_item_doubles(NS, R, n10) * (long long)sizeof(double);
+}
+
+int misonet_stoi_resample(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                          const float* ref, long long ref_sb, long long ref_ss, long long ref_st, const float* mix,
+                          long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid, int fs,
+                          double* x10, int* len10, misonet_stream stream) {
+  if (!est || !ref || !x10 || !len10) return fail(MISONET_EINVAL, "null argument");
+  if (E < 1 || E > 4) return fail(MISONET_EINVAL, "E must be in [1, 4] (got %d)", E);
+  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
+  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
+  if (fs != 8000 && fs != 10000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1 || (mix && (mix_sb < 0 || mix_st < 1)))
+    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
+  const double* tab;
+  if (const int rc = get_stoi_table(&tab)) return rc;
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
+  HIPCHK(launch_stoi_resample(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, x10, len10,
+                              reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_stoi_measure(const double* x10, const int* len10, int B, int NS, int R, long long n10, double* out, int* frames,
+                         void* scratch, long long scratch_bytes, misonet_stream stream) {
+  if (!x10 || !out || !frames || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (!stoi_ranges_ok(B, NS, R, n10))
+    return fail(MISONET_EINVAL, "1 <= B <= 4096, 1 <= R <= 4, 1 <= NS - R <= 5, 1 <= n10 <= 5 * 2^22 (got %d, %d, %d, %lld)", B,
+                R, NS - R, n10);
+  const long long need = misonet_stoi_scratch_bytes(B, NS, R, n10);
+  if (scratch_bytes < need)
+    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_stoi_scratch_bytes(B, NS, R, n10))", scratch_bytes, need);
+  const double* tab;
+  if (const int rc = get_stoi_table(&tab)) return rc;
+  HIPCHK(launch_stoi_measure(x10, len10, B, NS, R, n10, tab, out, frames, reinterpret_cast<double*>(scratch),
+                             reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

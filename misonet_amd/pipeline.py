@@ -688,7 +688,7 @@ class Enhancer:
 
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                           max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000, score: bool = False,
-                          bss: bool = False, bss_filt_len: int = 512):
+                          bss: bool = False, bss_filt_len: int = 512, stoi: bool = False):
         """Recording in -> enhanced int16 waves out: the reference's loader item AND its tester body as one device-side
         object (``AudioDataset_Test.__getitem__``, dataloader/data.py:524-597, + ``Tester_Enhance.inference``,
         tester.py:846-975), without host STFT dicts.
@@ -716,11 +716,22 @@ class Enhancer:
         of ``bss=False``.  :class:`score.BssEval` holds BSS-eval SDR, SIR and SAR (the figures SMS-WSJ tabulates,
         INTEGRATION.md 4e) of the stitched int16 result against the clean sources at ``ref_ch`` with filters of
         ``bss_filt_len`` taps, the observation at ``ref_ch`` as the mixture: what
-        ``score.bss_eval_waves(pcm, clean[:, :, ref_ch], mix)`` returns."""
+        ``score.bss_eval_waves(pcm, clean[:, :, ref_ch], mix)`` returns.
+
+        ``stoi=True`` (needs ``score=True``): a :class:`score.Stoi` is appended as the last element of the returned tuple,
+        ``(pcm, Score, Stoi)`` or ``(pcm, Score, BssEval, Stoi)``; everything before it keeps its bits.  It holds STOI and
+        ESTOI of the stitched int16 result against the clean sources at ``ref_ch`` at rate ``fs`` (8000,
+        10000 or 16000), the observation at ``ref_ch`` as the mixture: what
+        ``score.stoi_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns."""
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
+        if stoi and not score:
+            raise ValueError("stoi=True needs score=True (and the clean sources)")
         if score and wav_clean is None:
             raise ValueError("score=True needs the clean sources (wav_clean)")
+        if stoi:
+            from . import score as SC
+            SC.check_stoi_fs(fs)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -738,11 +749,16 @@ class Enhancer:
             pcm = np.concatenate([g[0] for g in got], axis=0)
             rows = [(g[1][0][b], g[1][1][b]) for g in got for b in range(g[0].shape[0])]
             out, sc = self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs), self._recording_score(rows, nv)
-            if not bss:
+            if not bss and not stoi:
                 return out, sc
             from . import score as SC
-            clean, mix = self._bss_refs(wav_observe, wav_clean, num_ch_utilize)
-            return out, sc, SC.bss_eval_waves(out, clean, mix, filt_len=bss_filt_len, device=self.device)
+            clean, mix = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
+            res = (out, sc)
+            if bss:
+                res = res + (SC.bss_eval_waves(out, clean, mix, filt_len=bss_filt_len, device=self.device),)
+            if stoi:
+                res = res + (SC.stoi_waves(out, clean, mix, fs=fs, device=self.device),)
+            return res
 
         def batches():
             for lo in range(0, K, max_batch):
@@ -752,8 +768,8 @@ class Enhancer:
         pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
         return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
 
-    def _bss_refs(self, wav_observe, wav_clean, num_ch_utilize):
-        """the references of BSS-eval for one recording: (the clean sources at ref_ch of the sub-sampled array, float32
+    def _wave_refs(self, wav_observe, wav_clean, num_ch_utilize):
+        """the references of BSS-eval and STOI for one recording: (the clean sources at ref_ch of the sub-sampled array, float32
         [S, L]; the observation there, float32 [L])"""
         mics, obs = self._select_mics(wav_observe, num_ch_utilize)
         m = mics[self.ref_ch]
@@ -904,12 +920,12 @@ class Enhancer:
                 return f"libmisonet_hip: NaN in pipeline output of window {k} (samples {k * H}..{k * H + W} of the recording)"
         return f"libmisonet_hip: NaN in pipeline output of windows {lo}..{hi - 1}"
 
-    BSS_GROUP = 16      # recordings per BSS-eval batch of enhance_recordings: 0.53 ms each at 16 against 6.1 ms one by one
+    BSS_GROUP = 16      # recordings per BSS-eval / STOI batch of enhance_recordings: 0.53 ms each at 16 against 6.1 ms one by one
 
     def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
                            depth: int = 2, score: bool = False, bss: bool = False,
-                           bss_filt_len: int = 512) -> Dict[str, np.ndarray]:
+                           bss_filt_len: int = 512, stoi: bool = False) -> Dict[str, np.ndarray]:
         """:meth:`enhance_recording` over many recordings, with every launch filled across them.
 
         ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
@@ -924,11 +940,18 @@ class Enhancer:
         {name: (int16 [S, L], Score, BssEval)}.  The stitched recordings are queued for BSS-eval in groups of
         ``BSS_GROUP`` on a stream of their own (pinned copies, the correlation and factorisation kernels of csrc/bss.hip,
         one batch per group: a recording's figures do not depend on the group) and nothing waits for them until every
-        recording has gone through: the pass is not stalled."""
+        recording has gone through: the pass is not stalled.  ``stoi=True`` (needs ``score=True``): a :class:`score.Stoi`
+        (STOI and ESTOI at rate ``fs``, csrc/stoi.hip) is appended as the last element of every tuple, queued in the same
+        groups on the same side stream; everything before it keeps its bits."""
         import os
         from .coalesce import Item
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
+        if stoi and not score:
+            raise ValueError("stoi=True needs score=True (and the clean sources)")
+        if stoi:
+            from . import score as SC
+            SC.check_stoi_fs(fs)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -941,8 +964,8 @@ class Enhancer:
                 key = (pieces[0].shape, cpieces[0].shape if cpieces is not None else None)
                 if score:
                     key = key + ((1,),)                              # the chunk's valid count rides as a third input
-                if bss:
-                    bss_refs[i] = self._bss_refs(wav_observe, wav_clean, num_ch_utilize)
+                if bss or stoi:
+                    side_refs[i] = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
                 yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name))
 
         def fill(c, rows):
@@ -955,16 +978,17 @@ class Enhancer:
                 rows[2].copy_(self._nv_bits([n - gap if c.split == len(pieces) - 1 else n], torch.float32)[0])
 
         results = {}
-        bss_refs, bss_wait, bss_done = {}, [], []
-        if bss:
+        side_refs, side_wait, side_done = {}, [], []
+        if bss or stoi:
             from . import score as SC
             side = torch.cuda.Stream(self.device)
 
-            def bss_flush():
+            def side_flush():
                 with torch.cuda.stream(side):
-                    bss_done.append(([w[0] for w in bss_wait],
-                                     SC.bss_queue([w[1:] for w in bss_wait], bss_filt_len, self.device, pinned=True)))
-                bss_wait.clear()
+                    side_done.append(([w[0] for w in side_wait],) + SC.side_queue(
+                        [w[1:] for w in side_wait], self.device, pinned=True, bss_filt_len=bss_filt_len if bss else None,
+                        stoi_fs=fs if stoi else None))                 # one padded, pinned batch serves both
+                side_wait.clear()
         for it in self._coalesced(items(), fill, self._wav_pass_score if score else self._wav_pass, torch.float32, max_batch,
                                   depth, lambda c: str(c.item.payload[3]),
                                   extra_rows=(lambda ex, n: self._score_rows(ex, n, False)) if score else None):
@@ -974,20 +998,24 @@ class Enhancer:
                 n = pieces[0].shape[0]
                 pcm = self._finish_recording([o[0][0] for o in it.outputs], gap, path, fs)
                 results[name] = (pcm, self._recording_score([o[0][1:] for o in it.outputs], [n] * (len(pieces) - 1) + [n - gap]))
-                if bss:
-                    bss_wait.append((name, pcm) + bss_refs.pop(it.index))
-                    if len(bss_wait) >= self.BSS_GROUP:
-                        bss_flush()
+                if bss or stoi:
+                    side_wait.append((name, pcm) + side_refs.pop(it.index))
+                    if len(side_wait) >= self.BSS_GROUP:
+                        side_flush()
             else:
                 results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
-        if bss:
-            if bss_wait:
-                bss_flush()
+        if bss or stoi:
+            if side_wait:
+                side_flush()
             side.synchronize()
-            for names, block in bss_done:
-                for name, row in zip(names, block.cpu().numpy()):
-                    pcm, sc = results[name]
-                    results[name] = (pcm, sc, SC.bss_unpack(row, self.num_spks, int(bss_filt_len), pcm.shape[1]))
+            for names, block, sblock in side_done:
+                if bss:
+                    for name, row in zip(names, block.cpu().numpy()):
+                        pcm, sc = results[name]
+                        results[name] = (pcm, sc, SC.bss_unpack(row, self.num_spks, int(bss_filt_len), pcm.shape[1]))
+                if stoi:
+                    for name, row in zip(names, sblock.cpu().numpy()):
+                        results[name] = results[name] + (SC.stoi_unpack(row, self.num_spks, int(fs), results[name][0].shape[1]),)
         return results
 
     def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2, score=False):

@@ -3,7 +3,9 @@ permutation, and the reference's training criterion (criterion.py ``loss_uPIT`` 
 device (csrc/score.hip, C ABI ``misonet_score_wave`` / ``misonet_score_spec``); the handful of doubles they leave is turned
 into dB on the host.  tests/score_ref.py restates every definition in NumPy.  BSS-eval SDR, SIR and SAR (Vincent et al. 2006,
 the figures SMS-WSJ tabulates) come from the energies of two projections (csrc/bss.hip, C ABI ``misonet_bss_corr`` /
-``misonet_bss_solve``; :class:`BssEval`, INTEGRATION.md 4e, restated in tests/bss_ref.py).
+``misonet_bss_solve``; :class:`BssEval`, INTEGRATION.md 4e, restated in tests/bss_ref.py).  STOI and ESTOI, the intelligibility
+figures, are computed whole on the device (csrc/stoi.hip, C ABI ``misonet_stoi_resample`` / ``misonet_stoi_measure``;
+:class:`Stoi`, INTEGRATION.md 4f, restated in tests/stoi_ref.py).
 
 Definitions:
   * stats[i][j] = (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j) over the valid samples; additive over the chunks of a recording;
@@ -489,12 +491,10 @@ def bss_unpack(row, S: int, filt_len: int, n_samples: int) -> BssEval:
                              n_samples=n_samples)
 
 
-def bss_queue(items, filt_len: int, dev, pinned: bool = False):
-    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
-    same S and all or none with a mixture; any lengths) -> the device block [len(items), W] of :func:`bss_energies`, queued
-    on the current stream of ``dev``.  Several recordings go as one batch, zero-padded to the longest with ``n_valid`` set: a
-    row is bit for bit what the recording gives alone.  ``pinned``: host inputs go through pinned memory and asynchronous
-    copies, so that the caller is not held up."""
+def _wave_batch(items, dev, pinned, limits):
+    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) -> the device tensors
+    (est [G, S, n], clean [G, S, n], mix [G, 1, n] or None, n_valid int32 [G] or None for a single recording), zero-padded to
+    the longest; ``limits(S, L)`` raises for what the caller does not take.  Must run under ``torch.cuda.device(dev)``."""
     import torch
     recs = []
     for est, clean, mix in items:
@@ -514,7 +514,7 @@ def bss_queue(items, filt_len: int, dev, pinned: bool = False):
     if any(r[0].shape[0] != S for r in recs) or any((r[2] is None) != (recs[0][2] is None) for r in recs):
         raise ValueError("every recording must have the same number of speakers, and all or none a mixture")
     for r in recs:
-        _bss_limits(S, S, int(filt_len), r[0].shape[1])
+        limits(S, r[0].shape[1])
     if any(r[0].dtype != recs[0][0].dtype for r in recs):
         raise ValueError("int16 and float32 estimates cannot share a batch")
     with_mix = recs[0][2] is not None
@@ -524,23 +524,49 @@ def bss_queue(items, filt_len: int, dev, pinned: bool = False):
             return x.contiguous().pin_memory().to(dev, non_blocking=True)
         return x.to(dev).contiguous()
 
+    if G == 1:
+        est, clean, mix = recs[0]
+        return up(est)[None], up(clean)[None], up(mix)[None, None] if with_mix else None, None
+    lens = [int(r[0].shape[1]) for r in recs]
+    n = max(lens)
+
+    def padded(k, rows, dtype):
+        buf = torch.zeros((G, rows, n), dtype=dtype, pin_memory=pinned)
+        for g, r in enumerate(recs):
+            buf[g, :, :lens[g]].copy_(r[k].reshape(rows, -1))
+        return buf.to(dev, non_blocking=pinned)
+
+    nv = torch.tensor(lens, dtype=torch.int32)
+    nv = (nv.pin_memory() if pinned else nv).to(dev, non_blocking=pinned)
+    return (padded(0, S, recs[0][0].dtype), padded(1, S, torch.float32), padded(2, 1, torch.float32) if with_mix else None, nv)
+
+
+def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = None, stoi_fs: Optional[int] = None):
+    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
+    same S and all or none with a mixture; any lengths) -> (the device block [len(items), W] of :func:`bss_energies` for
+    filters of ``bss_filt_len`` taps, that of :func:`stoi_block` at rate ``stoi_fs``), either None where its argument is
+    None, queued on the current stream of ``dev``.  Several recordings go as one batch, zero-padded to the longest with
+    ``n_valid`` set, and the batch is built and copied once for both: a row is bit for bit what the recording gives
+    alone.  ``pinned``: host inputs go through pinned memory and asynchronous copies, so that the caller is not held up."""
+    import torch
+    if stoi_fs is not None:
+        stoi_fs = check_stoi_fs(stoi_fs)
+
+    def limits(S, L):
+        if bss_filt_len is not None:
+            _bss_limits(S, S, int(bss_filt_len), L)
+        if stoi_fs is not None:
+            _stoi_limits(S, L)
+
     with torch.cuda.device(dev):
-        if G == 1:
-            est, clean, mix = recs[0]
-            return bss_energies(up(est)[None], up(clean)[None], up(mix)[None, None] if with_mix else None, None, int(filt_len))
-        lens = [int(r[0].shape[1]) for r in recs]
-        n = max(lens)
+        est, clean, mix, nv = _wave_batch(items, dev, pinned, limits)
+        return (bss_energies(est, clean, mix, nv, int(bss_filt_len)) if bss_filt_len is not None else None,
+                stoi_block(est, clean, mix, nv, stoi_fs) if stoi_fs is not None else None)
 
-        def padded(k, rows, dtype):
-            buf = torch.zeros((G, rows, n), dtype=dtype, pin_memory=pinned)
-            for g, r in enumerate(recs):
-                buf[g, :, :lens[g]].copy_(r[k].reshape(rows, -1))
-            return buf.to(dev, non_blocking=pinned)
 
-        nv = torch.tensor(lens, dtype=torch.int32)
-        nv = (nv.pin_memory() if pinned else nv).to(dev, non_blocking=pinned)
-        return bss_energies(padded(0, S, recs[0][0].dtype), padded(1, S, torch.float32),
-                            padded(2, 1, torch.float32) if with_mix else None, nv, int(filt_len))
+def bss_queue(items, filt_len: int, dev, pinned: bool = False):
+    """:func:`side_queue` for BSS-eval alone: the device block [len(items), W] of :func:`bss_energies`"""
+    return side_queue(items, dev, pinned, bss_filt_len=filt_len)[0]
 
 
 def bss_eval_waves(est, clean, mix=None, filt_len: int = 512, device=None) -> BssEval:
@@ -552,3 +578,256 @@ def bss_eval_waves(est, clean, mix=None, filt_len: int = 512, device=None) -> Bs
     est = torch.as_tensor(est)
     row = bss_queue([(est, clean, mix)], filt_len, dev)[0].cpu().numpy()
     return bss_unpack(row, int(est.shape[0]), int(filt_len), int(est.shape[1]))
+
+
+# ---- STOI and ESTOI ----------------------------------------------------------------------------------
+# x the clean reference, y the estimate, float64 throughout: both to 10 kHz (polyphase, Kaiser window), the frames of 256 whose
+# energy is more than 40 dB under the loudest frame of x dropped from both, the kept frames overlap-added and framed again,
+# 512-point transform, 15 third-octave bands, segments of 30 frames; STOI = the mean clipped band-wise correlation, ESTOI =
+# the mean correlation of the row- and column-normalised segments.
+STOI_RATES = (8000, 10000, 16000)
+STOI_SEG = 30                 # frames per segment: fewer kept frames give 1e-5 and ``valid = False``
+STOI_SCRATCH_CAP = 1 << 30    # bytes of device memory per group of stoi_block: larger batches go in groups
+
+
+@dataclasses.dataclass
+class Stoi:
+    """STOI and ESTOI of one recording, speaker j = reference j.  ``valid[j] = False``: reference j is silent (NaN) or keeps
+    fewer than 30 frames (1e-5, as pystoi answers)."""
+    stoi: np.ndarray                      # [S] STOI(e_j, r_j)
+    estoi: np.ndarray                     # [S] ESTOI(e_j, r_j)
+    valid: np.ndarray                     # [S] bool
+    perm_best: List[int]                  # p[j] = the estimate of reference j in the assignment with the largest summed STOI
+    stoi_best: np.ndarray                 # [S] STOI(e_p[j], r_j)
+    estoi_best: np.ndarray                # [S] ESTOI(e_p[j], r_j)
+    stoi_mix: Optional[np.ndarray]        # [S] STOI(mixture, r_j), or None without a mixture
+    estoi_mix: Optional[np.ndarray]       # [S]
+    stoi_i: Optional[np.ndarray]          # [S] stoi - stoi_mix
+    estoi_i: Optional[np.ndarray]         # [S] estoi - estoi_mix
+    frames: np.ndarray                    # [S] int: frames of reference j at 10 kHz
+    frames_kept: np.ndarray               # [S] int: those within 40 dB of its loudest frame
+    fs: int
+    n_samples: int
+
+    def as_dict(self) -> dict:
+        def lst(x):
+            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
+        return dict(stoi=lst(self.stoi), estoi=lst(self.estoi), valid=[bool(v) for v in self.valid],
+                    perm_best=[int(p) for p in self.perm_best], stoi_best=lst(self.stoi_best), estoi_best=lst(self.estoi_best),
+                    stoi_mix=lst(self.stoi_mix), estoi_mix=lst(self.estoi_mix), stoi_i=lst(self.stoi_i),
+                    estoi_i=lst(self.estoi_i), frames=[int(v) for v in self.frames],
+                    frames_kept=[int(v) for v in self.frames_kept], fs=int(self.fs), n_samples=int(self.n_samples))
+
+
+def stoi_from_matrices(stoi_m, estoi_m, frames, frames_kept, nonsilent, stoi_mix=None, estoi_mix=None, fs: int = 16000,
+                       n_samples: int = 0) -> Stoi:
+    """stoi_m / estoi_m float64 [S estimates, S references] as the device leaves them, frames / frames_kept int [S], nonsilent
+    bool [S] (reference j has a sample that is not zero), stoi_mix / estoi_mix [S] or None -> :class:`Stoi`.  The rules of the
+    edges are applied here: a silent reference gives NaN, fewer than 30 kept frames 1e-5, neither is valid.  The definition
+    calls a reference silent when sum x^2 == 0 over the input; ``nonsilent`` as the device reports it says that a sample of
+    the reference at 10 kHz differs from zero.  The two agree unless a non-zero input resamples to exact zeros everywhere,
+    which the filter's non-zero taps rule out for float32 input short of cancellation to the last bit.  Host, no GPU."""
+    sm, em = np.array(stoi_m, dtype=np.float64), np.array(estoi_m, dtype=np.float64)
+    if sm.ndim != 2 or sm.shape[0] != sm.shape[1] or em.shape != sm.shape:
+        raise ValueError("stoi_m and estoi_m must both be [S, S] (estimates x references)")
+    S = sm.shape[0]
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+    kept = np.asarray(frames_kept, dtype=np.int64).reshape(-1)
+    ns = np.asarray(nonsilent, dtype=bool).reshape(-1)
+    if frames.shape != (S,) or kept.shape != (S,) or ns.shape != (S,):
+        raise ValueError("frames, frames_kept and nonsilent must hold one entry per reference")
+    if (stoi_mix is None) != (estoi_mix is None):
+        raise ValueError("stoi_mix and estoi_mix go together")
+    short = kept < STOI_SEG
+    sm = np.where(ns[None, :], np.where(short[None, :], 1e-5, sm), np.nan)
+    em = np.where(ns[None, :], np.where(short[None, :], 1e-5, em), np.nan)
+    mix_s = mix_e = None
+    if stoi_mix is not None:
+        mix_s, mix_e = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (stoi_mix, estoi_mix))
+        if mix_s.shape != (S,) or mix_e.shape != (S,):
+            raise ValueError("stoi_mix and estoi_mix must hold one entry per reference")
+        mix_s = np.where(ns, np.where(short, 1e-5, mix_s), np.nan)
+        mix_e = np.where(ns, np.where(short, 1e-5, mix_e), np.nan)
+    p = best_perm(sm)
+    idx = np.arange(S)
+    own_s, own_e = sm[idx, idx], em[idx, idx]
+    return Stoi(stoi=own_s, estoi=own_e, valid=ns & ~short, perm_best=p, stoi_best=np.array([sm[p[j], j] for j in range(S)]),
+                estoi_best=np.array([em[p[j], j] for j in range(S)]), stoi_mix=mix_s, estoi_mix=mix_e,
+                stoi_i=None if mix_s is None else own_s - mix_s, estoi_i=None if mix_e is None else own_e - mix_e,
+                frames=frames, frames_kept=kept, fs=int(fs), n_samples=int(n_samples))
+
+
+def stoi_mean_of(items: Sequence[Stoi]) -> dict:
+    """The ``"stoi"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers"""
+    out = {}
+    for key in ("stoi", "estoi", "stoi_best", "estoi_best", "stoi_mix", "estoi_mix", "stoi_i", "estoi_i"):
+        vals = [float(getattr(e, key)[j]) for e in items if getattr(e, key) is not None
+                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
+        out[key] = float(np.mean(vals)) if vals else None
+    out["n_recordings"] = len(items)
+    out["n_speakers_valid"] = int(sum(int(np.sum(e.valid)) for e in items))
+    return out
+
+
+def check_stoi_fs(fs):
+    if int(fs) != fs or int(fs) not in STOI_RATES:
+        raise ValueError(f"STOI is defined here for fs = 8000, 10000 or 16000 Hz (got {fs})")
+    return int(fs)
+
+
+def stoi_resampled_len(n: int, fs: int) -> int:
+    """ceil(n p / q), p / q = 10000 / fs: the length at 10 kHz; negative outside the limits (n <= 2^24, the three rates)"""
+    return int(_lib.lib().misonet_stoi_resampled_len(int(n), int(fs)))
+
+
+def stoi_taps(fs: int) -> np.ndarray:
+    """the polyphase taps g[k] = p h[k - Lh] / sum h of rate fs as the library builds them (host, no GPU): 581 for 16 kHz,
+    365 for 8 kHz, the single 1.0 for 10 kHz"""
+    import ctypes as C
+    L = _lib.lib()
+    n = int(L.misonet_stoi_taps(check_stoi_fs(fs), None))
+    buf = (C.c_double * n)()
+    L.misonet_stoi_taps(int(fs), buf)
+    return np.array(buf, dtype=np.float64)
+
+
+def stoi_scratch_bytes(B: int, NS: int, R: int, n10: int) -> int:
+    """bytes of scratch for :func:`stoi_measure` over NS signals per item (R references first) of n10 samples at 10 kHz:
+    8 B (R f + 15 R (NS - R + 1) f + 2 R (NS - R) max(f - 29, 1) + R ceil(f / 2)), f = max(frames, 1); negative outside the
+    limits"""
+    return int(_lib.lib().misonet_stoi_scratch_bytes(int(B), int(NS), int(R), int(n10)))
+
+
+def stoi_resample(est, ref, mix=None, n_valid=None, fs: int = 16000):
+    """est int16 or float32 [B, E, n], ref float32 [B, R, n] (device views as :func:`wave_stats` takes them), mix float32
+    [B, 1, n] or None, n_valid int32 [B] (device) or None.  Returns (x10 float64 [B, R + E (+ 1), n10]: the references, the
+    estimates and the mixture at 10 kHz, zero past an item's own length; len10 int32 [B] = ceil(n_valid p / q)).
+    Asynchronous on the current stream; an item's rows do not depend on the batch."""
+    import torch
+    fs = check_stoi_fs(fs)
+    est = _wave_view(est, "est", (torch.int16, torch.float32))
+    ref = _wave_view(ref, "ref", (torch.float32,))
+    B, E, n = est.shape
+    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
+        raise ValueError("est and ref must agree in B, n and device")
+    R = ref.shape[1]
+    if not (1 <= E <= 4 and 1 <= R <= 4):
+        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+    if not (1 <= n <= 1 << 24):
+        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
+    if B < 1 or B > 4096:
+        raise ValueError("1 <= B <= 4096 items")
+    dev = est.device
+    if mix is not None:
+        mix = _wave_view(mix, "mix", (torch.float32,))
+        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
+            raise ValueError("mix must be [B, 1, n] on the device of est")
+    if n_valid is not None:
+        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
+                or n_valid.numel() != B or not n_valid.is_contiguous():
+            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    L = _lib.lib()
+    n10 = int(L.misonet_stoi_resampled_len(n, fs))
+    x10 = torch.empty((B, R + E + (1 if mix is not None else 0), n10), dtype=torch.float64, device=dev)
+    len10 = torch.empty((B,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.misonet_stoi_resample(est.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
+                                           est.stride(2), ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
+                                           mix.data_ptr() if mix is not None else None,
+                                           mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
+                                           B, E, R, n, n_valid.data_ptr() if n_valid is not None else None, fs,
+                                           x10.data_ptr(), len10.data_ptr(), _lib.stream_ptr(dev)))
+    return x10, len10
+
+
+def stoi_measure(x10, len10, R: int):
+    """x10 float64 [B, NS, n10] (device, contiguous; the first R signals of an item are its references, the others are
+    measured against each of them), len10 int32 [B] (device) or None -> (out float64 [B, NS - R, R, 2] = (STOI, ESTOI) of
+    estimate i against reference j, 1e-5 where fewer than 30 frames are kept; frames int32 [B, R, 3] = (frames, kept frames,
+    1 if the reference has a sample that is not zero)).  Asynchronous on the current stream: the number of kept frames
+    stays on the device."""
+    import torch
+    if not isinstance(x10, torch.Tensor) or x10.dim() != 3 or x10.dtype != torch.float64 or not x10.is_cuda \
+            or not x10.is_contiguous():
+        raise ValueError("x10 must be a contiguous float64 device tensor [B, signals, n10]")
+    B, NS, n10 = x10.shape
+    R = int(R)
+    dev = x10.device
+    if len10 is not None:
+        if not isinstance(len10, torch.Tensor) or len10.dtype != torch.int32 or len10.device != dev or len10.numel() != B \
+                or not len10.is_contiguous():
+            raise ValueError(f"len10 must be a contiguous int32 device tensor of {B} entries")
+    L = _lib.lib()
+    nb = int(L.misonet_stoi_scratch_bytes(B, NS, R, n10))
+    if nb < 0:
+        raise ValueError(f"1 <= B <= 4096, 1 <= R <= 4, 1 <= NS - R <= 5, 1 <= n10 <= 5 * 2^22 (got {B}, {R}, {NS - R}, {n10})")
+    out = torch.empty((B, NS - R, R, 2), dtype=torch.float64, device=dev)
+    frames = torch.empty((B, R, 3), dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.misonet_stoi_measure(x10.data_ptr(), len10.data_ptr() if len10 is not None else None, B, NS, R, n10,
+                                          out.data_ptr(), frames.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                          _lib.stream_ptr(dev)))
+    return out, frames
+
+
+def stoi_block(est, ref, mix=None, n_valid=None, fs: int = 16000):
+    """est int16 / float32 [B, S, n], ref float32 [B, S, n], mix float32 [B, 1, n] or None (device views), n_valid int32 [B] or
+    None -> a device float64 block [B, W]: per item the (STOI, ESTOI) of every (estimate, reference) pair ([S (+ 1), S, 2], the
+    mixture as the last estimate) and (frames, kept, not silent) per reference: what :func:`stoi_unpack` reads.  Everything
+    is queued on the current stream; nothing synchronises.  Batches beyond 1 GiB of device memory run in groups."""
+    import torch
+    B, E, n = est.shape
+    R = ref.shape[1]
+    NS = R + E + (1 if mix is not None else 0)
+    n10 = stoi_resampled_len(n, check_stoi_fs(fs))
+    per = 8 * NS * max(n10, 1) + max(stoi_scratch_bytes(1, NS, R, max(n10, 1)), 0)
+    g = max(1, min(B, STOI_SCRATCH_CAP // max(1, per)))
+    rows = []
+    for lo in range(0, B, g):
+        hi = min(B, lo + g)
+        x10, len10 = stoi_resample(est[lo:hi], ref[lo:hi], mix[lo:hi] if mix is not None else None,
+                                   n_valid[lo:hi] if n_valid is not None else None, fs)
+        out, frames = stoi_measure(x10, len10, R)
+        rows.append(torch.cat([out.reshape(hi - lo, -1), frames.to(torch.float64).reshape(hi - lo, -1)], dim=1))
+    return rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+
+
+def stoi_unpack(row, S: int, fs: int, n_samples: int) -> Stoi:
+    """one host row of :func:`stoi_block` -> :class:`Stoi`"""
+    row = np.asarray(row, dtype=np.float64)
+    E = (row.shape[0] - 3 * S) // (2 * S)
+    if E not in (S, S + 1) or row.shape[0] != 2 * S * E + 3 * S:
+        raise ValueError("not a row of stoi_block for this number of speakers")
+    fig = row[:2 * S * E].reshape(E, S, 2)
+    meta = row[2 * S * E:].reshape(S, 3)
+    mix = fig[S] if E > S else None
+    return stoi_from_matrices(fig[:S, :, 0], fig[:S, :, 1], meta[:, 0], meta[:, 1], meta[:, 2] != 0,
+                              None if mix is None else mix[:, 0], None if mix is None else mix[:, 1], fs=fs,
+                              n_samples=n_samples)
+
+
+def _stoi_limits(S, L):
+    if not (1 <= S <= 4):
+        raise ValueError(f"1 <= S <= 4 speakers (got {S})")
+    if not (1 <= L <= 1 << 24):
+        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
+
+
+def stoi_queue(items, fs: int, dev, pinned: bool = False):
+    """:func:`side_queue` for STOI / ESTOI alone: the device block [len(items), W] of :func:`stoi_block`"""
+    return side_queue(items, dev, pinned, stoi_fs=fs)[1]
+
+
+def stoi_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Stoi:
+    """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
+    :class:`Stoi` (1 <= S <= 4, L <= 2^24, fs 8000, 10000 or 16000): the counterpart of :func:`score_waves` for STOI and
+    ESTOI, for the output of ``enhance_continuous`` and for files read back from disk."""
+    import torch
+    fs = check_stoi_fs(fs)
+    est = torch.as_tensor(est)
+    if est.dim() == 2:
+        _stoi_limits(int(est.shape[0]), int(est.shape[1]))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    row = stoi_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
+    return stoi_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Scores a directory of separated wav files against a directory of clean ones, on the device.
 
-    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]]
+    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]] [--stoi]
 
 EST_DIR holds ``<name>_{s}.wav`` (what ``enhance_recording(save_path=...)`` / ``inference`` write: 24-bit or 16-bit PCM, mono);
 REF_DIR holds the clean sources under the same names (``<name>_{s}.wav``, any channel count: channel ``--ref-ch`` is used)
 and, there or in ``--mix-dir``, the observation as ``<name>.wav`` (optional: without it no SI-SDR improvement is reported).
 Prints (or writes) the JSON ``Enhancer.inference(..., score=True)`` writes: ``{name: Score.as_dict()}`` plus ``"mean"``.
 ``--bss`` adds BSS-eval SDR, SIR and SAR (``BssEval.as_dict()``, INTEGRATION.md 4e, filters of ``--filt-len`` taps) as a
-``"bss"`` entry of every recording and of ``"mean"``; without the flag the output is what it always was.
+``"bss"`` entry of every recording and of ``"mean"``; ``--stoi`` adds STOI and ESTOI (``Stoi.as_dict()``, INTEGRATION.md 4f, at
+the rate the files carry: 8, 10 or 16 kHz) as a ``"stoi"`` entry likewise; without the flags the output is what it always was.
 Definitions: INTEGRATION.md 4d.  Lengths may differ by the padding of the last hop: the common length is scored.
 """
 import argparse
@@ -51,17 +52,19 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--bss", action="store_true", help="also BSS-eval SDR / SIR / SAR")
     ap.add_argument("--filt-len", type=int, default=512, help="taps of the BSS-eval projection filters")
+    ap.add_argument("--stoi", action="store_true", help="also STOI and ESTOI (the rate comes from the files)")
     a = ap.parse_args(argv)
     from misonet_amd import score
     pat = re.compile(r"^(.*)_0\.wav$")
     names = sorted(m.group(1) for m in map(pat.match, os.listdir(a.est_dir)) if m)
     if not names:
         raise SystemExit(f"no <name>_0.wav in {a.est_dir}")
-    scores, evals = {}, {}
+    scores, evals, stois = {}, {}, {}
     for name in names:
-        est, ref = [], []
+        est, ref, rates = [], [], set()
         for s in range(a.num_spks):
-            f32, i16, _ = read_wav(os.path.join(a.est_dir, f"{name}_{s}.wav"))
+            f32, i16, fs = read_wav(os.path.join(a.est_dir, f"{name}_{s}.wav"))
+            rates.add(int(fs))
             est.append(i16[:, 0] if i16 is not None else f32[:, 0])       # the library's own files: int16, scored as such
             ref.append(read_wav(os.path.join(a.ref_dir, f"{name}_{s}.wav"))[0][:, a.ref_ch])
         mix_path = os.path.join(a.mix_dir or a.ref_dir, f"{name}.wav")
@@ -74,12 +77,21 @@ def main(argv=None):
         if a.bss:
             evals[name] = score.bss_eval_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
                                                mix[:n] if mix is not None else None, filt_len=a.filt_len)
+        if a.stoi:
+            if len(rates) != 1:
+                raise SystemExit(f"{name}: the estimates disagree about the rate ({sorted(rates)})")
+            stois[name] = score.stoi_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
+                                           mix[:n] if mix is not None else None, fs=rates.pop())
     doc = {name: sc.as_dict() for name, sc in scores.items()}
     doc["mean"] = score.mean_of(list(scores.values()))
     if a.bss:
         for name, ev in evals.items():
             doc[name]["bss"] = ev.as_dict()
         doc["mean"]["bss"] = score.bss_mean_of(list(evals.values()))
+    if a.stoi:
+        for name, st in stois.items():
+            doc[name]["stoi"] = st.as_dict()
+        doc["mean"]["stoi"] = score.stoi_mean_of(list(stois.values()))
     text = json.dumps(doc, indent=1)
     if a.out:
         with open(a.out, "w") as fh:
