@@ -121,9 +121,11 @@ int misonet_net_tap_shape(const misonet_net* net, const char* name, int* C, int*
 int misonet_net_tap(misonet_net* net, const char* name, const void* ws_dev, int B, int T, float* dst_dev,
                     misonet_stream stream);
 
-/* ---- MVDR: Tester_Enhance.Apply_Beamforming(source_stft, mix_stft, epsi) (tester.py:1071-1136) ---------- */
+/* ---- beamforming: Tester_Enhance.Apply_Beamforming(source_stft, mix_stft, epsi) (tester.py:1071-1136) and the
+ * settings its author kept beside it (MPDR, conditioning, trace normalisation, BAN; GEV from the nn-gev family) ---- */
 /* src_dev, mix_dev: complex64 [B, F, M, T] contiguous (the reference passes permuted views, tester.py:921-923);
- * out_dev: complex64 [B, T, F] (tester.py:1134).  M <= 8. */
+ * out_dev: complex64 [B, T, F] (tester.py:1134).  2 <= M <= 8.  misonet_mvdr is the reference's live path: residual-noise
+ * MVDR, steering vector from the principal eigenvector of Phi_s, sequential phase correction, eps I loading. */
 long long misonet_mvdr_workspace_bytes(int B, int F, int M);
 int misonet_mvdr(const void* src_dev, const void* mix_dev, int B, int F, int M, int T, float epsi,
                  void* out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
@@ -131,6 +133,46 @@ int misonet_mvdr(const void* src_dev, const void* mix_dev, int B, int F, int M, 
  * both complex128 [B,F,M], to device buffers (either may be NULL) */
 int misonet_mvdr_debug(const void* ws_dev, int B, int F, int M, void* steer_c128_dev, void* w_c128_dev,
                        misonet_stream stream);
+
+/* ---- selectable beamformers (ABI 510) ------------------------------------------------------------------------------
+ * Phi_s = S S^H / T and Phi_n = N N^H / T are accumulated, made Hermitian and divided by T as above (tester.py:1091-1100);
+ * everything after the reduced covariances is float64, per bin, without atomics: bit-reproducible and independent of B.
+ *   noise            0 "residual": N = Y - S (tester.py:1095);  1 "mix": N = Y (tester.py:1096: MPDR, "MP-GEV")
+ *   condition        gamma >= 0: Phi_n <- (Phi_n + gamma tr(Phi_n) / M I) / (1 + gamma), PER BIN (equation 2.3 of the paper
+ *                    that tester.py:1170 cites; the reference's dead code takes the trace of a whole [F, M, M] slab)
+ *   trace_normalize  Phi_n <- Phi_n / tr(Phi_n) (tester.py:1099), after the conditioning
+ *   epsi             Phi_n' = Phi_n + epsi I, last (tester.py:1221)
+ *   kind             0 "mvdr": the solve of misonet_mvdr: d from Phi_s, d / d[0], sqrt(M / ||d||), phase correction along f,
+ *                      w = Phi_n'^-1 d / (d^H Phi_n'^-1 d);
+ *                    1 "souden": G = Phi_n'^-1 Phi_s, w = G[:, ref_ch] / tr(G); w = 0 where tr(G) == 0;
+ *                    2 "gev": the eigenvector of the largest lambda in Phi_s w = lambda Phi_n' w (Cholesky Phi_n' = L L^H,
+ *                      C = L^-1 Phi_s L^-H, cyclic Jacobi on C, w = L^-H u), scaled to w^H Phi_n' w = 1 and rotated PER BIN so
+ *                      that (Phi_n' w)[ref_ch] is real and >= 0 (left as it is where that entry is 0).  A Cholesky pivot that
+ *                      is not positive gives a non-finite w; nothing is clamped.
+ *   ban              w <- w sqrt|w^H Phi_n' Phi_n' w| / |w^H Phi_n' w| (tester.py:1196-1208 with eps = 0); w stays where the
+ *                    denominator is 0
+ *   ref_ch           0 <= ref_ch < M: the reference microphone of "souden" and "gev"
+ * With the defaults of misonet_bf_opts_default every output bit of misonet_beamform is that of misonet_mvdr.
+ * Bad fields (unknown kind or noise, negative or non-finite condition or epsi, ref_ch outside [0, M)) are refused on the
+ * host with MISONET_EINVAL and a message (the size function: -1), before any launch. */
+typedef struct {
+  int kind;
+  int noise;
+  double condition;
+  int trace_normalize;
+  float epsi;
+  int ban;
+  int ref_ch;
+} misonet_bf_opts;
+int misonet_bf_opts_default(misonet_bf_opts* opts);      /* mvdr, residual, 0, 0, 1e-6f, 0, 0 */
+long long misonet_beamform_workspace_bytes(int B, int F, int M, const misonet_bf_opts* opts);
+int misonet_beamform(const void* src_dev, const void* mix_dev, int B, int F, int M, int T, const misonet_bf_opts* opts,
+                     void* out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_beamform, copy the weights w complex128 [B, F, M] and, for "gev", lambda_max float64 [B, F]
+ * (MISONET_EINVAL for lambda of another kind) to device buffers (either may be NULL).  For "mvdr" misonet_mvdr_debug reads
+ * the same workspace. */
+int misonet_beamform_debug(const void* ws_dev, int B, int F, int M, const misonet_bf_opts* opts, void* w_c128_dev,
+                           double* lambda_dev, misonet_stream stream);
 
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
@@ -280,6 +322,13 @@ int misonet_stoi_measure(const double* x10_dev, const int* len10_dev, int B, int
 int misonet_pipeline_create(misonet_net* miso1, misonet_net* miso3, int num_mic, int num_spk, int ref_ch,
                             float epsi, misonet_pipeline** out);
 int misonet_pipeline_destroy(misonet_pipeline* p);
+/* ABI 510: the beamformer of step "MVDR per speaker" (misonet_pipeline_create sets the defaults with its own epsi and
+ * ref_ch 0).  Legal between runs; the workspace size depends on the kind, so misonet_pipeline_workspace_bytes must be asked
+ * again.  MISONET_EINVAL for bad fields (as misonet_beamform, M = num_mic).  The options are kernel arguments: a HIP graph
+ * captured from a run keeps the options it was captured with, and the library holds no graph itself, so no call order can
+ * make this return MISONET_ESTATE; the owner of a captured graph captures again (misonet_amd.Enhancer refuses the change
+ * while one of its captured passes is alive). */
+int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* opts);
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T);
 /* mix_dev complex64 [B,M,T,F]; clean_dev complex64 [B,S,T,F] or NULL; out_dev complex64 [B,S,T,F] (MISO3);
  * optional outputs (may be NULL): bf_dev complex64 [B,S,T,F] (MVDR), miso1_dev complex64 [B,S,M,T,F] (aligned).
@@ -320,8 +369,8 @@ int misonet_stft(const float* wav_dev, int B, int n_samples, int M, void* out_de
 int misonet_istft(const void* spec_dev, int N, int T, void* out_i16_dev, float* out_f32_dev, misonet_stream stream);
 
 /* ---- per-launch timing (bench.py roofline leg): while enabled, the library brackets every conv launch, the TCN
- * section and the MVDR section of each forward with HIP events on the caller's stream.  kinds: 0 = 3x3 conv kernel
- * launches, 1 = TCN sections, 2 = MVDR sections, 3 = other (conv_wprep_k, the per-sample weight preparation of the
+ * section and the beamforming section of each forward with HIP events on the caller's stream.  kinds: 0 = 3x3 conv kernel
+ * launches, 1 = TCN sections, 2 = beamforming sections (whichever beamformer is set), 3 = other (conv_wprep_k, the per-sample weight preparation of the
  * DMA dataflow).  State is per device (the current device at the call); misonet_profile_end synchronises and sums. */
 int misonet_profile_begin(int max_launches);
 int misonet_profile_end(double* ms_by_kind /*[4]*/, long long* launches_by_kind /*[4]*/);

@@ -3,12 +3,13 @@
 Host-side mirror of the reference call surface:
   MISO_1, MISO_3            (reference model.py:8-111, 282-395)
   Apply_Beamforming         (reference tester.py:1071-1136)
+  Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
 library raises -- there is no CPU fallback.
 """
-__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Enhancer", "weights"]
+__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Enhancer", "weights"]
 
 
 def __getattr__(name):
@@ -18,6 +19,9 @@ def __getattr__(name):
     if name == "Apply_Beamforming":
         from .beamform import Apply_Beamforming
         return Apply_Beamforming
+    if name == "Beamformer":
+        from .beamform import Beamformer
+        return Beamformer
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

@@ -26,6 +26,12 @@ class Cfg(C.Structure):
                 ("n_freq", C.c_int), ("tcn_norm", C.c_int)]       # tcn_norm: 0 IN, 1 gLN, 2 cLN, 3 BatchNorm1d (ABI 400)
 
 
+class BfOpts(C.Structure):
+    """misonet_bf_opts (ABI 510): kind 0 mvdr / 1 souden / 2 gev, noise 0 residual / 1 mix"""
+    _fields_ = [("kind", C.c_int), ("noise", C.c_int), ("condition", C.c_double), ("trace_normalize", C.c_int),
+                ("epsi", C.c_float), ("ban", C.c_int), ("ref_ch", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -54,6 +60,13 @@ SIGNATURES = {
     "misonet_mvdr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_mvdr_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_bf_opts_default": (C.c_int, [C.POINTER(BfOpts)]),
+    "misonet_beamform_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.POINTER(BfOpts)]),
+    "misonet_beamform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BfOpts), C.c_void_p,
+                                   C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_beamform_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(BfOpts), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "misonet_pipeline_set_beamformer": (C.c_int, [C.c_void_p, C.POINTER(BfOpts)]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

@@ -1,13 +1,17 @@
 """Host-side mirror of the reference's array-processing calls on the inference path.
 
-``Apply_Beamforming(source_stft, mix_stft, epsi)``  -- reference tester.py:1071-1136 (MVDR per frequency bin)
+``Apply_Beamforming(source_stft, mix_stft, epsi)``  -- reference tester.py:1071-1136 (MVDR per frequency bin); keywords
+                                                       select the other beamformers (:class:`Beamformer`)
 ``pit_select(anchor, cand)``                        -- reference tester.py:1043-1065 / 889-915 (PIT over all S! permutations)
 
-Both run as HIP kernels through the C ABI (misonet_mvdr / misonet_pit_select in include/misonet.h).
+Both run as HIP kernels through the C ABI (misonet_beamform / misonet_pit_select in include/misonet.h).
 """
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import math
+from typing import Optional
 
 import numpy as np
 import torch
@@ -25,13 +29,90 @@ def _dev_c64(x, device):
     return t.to(torch.complex64).contiguous(), was_numpy
 
 
-def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debug=False):
-    """MVDR beamforming, same arguments and result as Tester_Enhance.Apply_Beamforming (tester.py:1071-1136).
+KINDS = ("mvdr", "souden", "gev")
+NOISES = ("residual", "mix")
+
+
+@dataclasses.dataclass(frozen=True)
+class Beamformer:
+    """One plain-data description of a beamformer (``misonet_bf_opts`` of include/misonet.h), used by every layer.
+
+    kind             "mvdr" (the reference's live path, tester.py:1071-1136), "souden" (w = G[:, ref_ch] / tr G with
+                     G = Phi_n'^-1 Phi_s) or "gev" (principal generalised eigenvector of (Phi_s, Phi_n'), w^H Phi_n' w = 1,
+                     (Phi_n' w)[ref_ch] real and >= 0 per bin)
+    noise            "residual": Phi_n from Y - S (tester.py:1095); "mix": from Y (tester.py:1096, MPDR / "MP-GEV")
+    condition        gamma >= 0: Phi_n <- (Phi_n + gamma tr(Phi_n) / M I) / (1 + gamma), per bin
+    trace_normalize  Phi_n <- Phi_n / tr(Phi_n) (tester.py:1099), after the conditioning
+    epsi             Phi_n' = Phi_n + epsi I, last (tester.py:1221); None = the default of the call that uses the options
+    ban              blind analytic normalisation of w (tester.py:1186-1208)
+    ref_ch           reference microphone of "souden" and "gev"
+    """
+    kind: str = "mvdr"
+    noise: str = "residual"
+    condition: float = 0.0
+    trace_normalize: bool = False
+    epsi: Optional[float] = None
+    ban: bool = False
+    ref_ch: int = 0
+
+    @classmethod
+    def of(cls, spec) -> "Beamformer":
+        """None (the defaults), a Beamformer, a kind name, or a dict of the fields above"""
+        if spec is None:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            return cls(kind=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown beamformer field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("beamformer must be None, a Beamformer, a kind name or a dict of its fields")
+
+    def with_epsi(self, default: float) -> "Beamformer":
+        return self if self.epsi is not None else dataclasses.replace(self, epsi=float(default))
+
+    def validate(self, num_mic: Optional[int] = None) -> "Beamformer":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        if self.kind not in KINDS:
+            raise ValueError(f"beamformer kind {self.kind!r}: one of {KINDS}")
+        if self.noise not in NOISES:
+            raise ValueError(f"beamformer noise {self.noise!r}: one of {NOISES}")
+        if not (isinstance(self.condition, (int, float)) and math.isfinite(self.condition) and self.condition >= 0):
+            raise ValueError(f"beamformer condition (gamma) must be finite and >= 0, got {self.condition!r}")
+        if self.epsi is not None and not (math.isfinite(self.epsi) and self.epsi >= 0):
+            raise ValueError(f"beamformer epsi must be finite and >= 0, got {self.epsi!r}")
+        if int(self.ref_ch) != self.ref_ch or self.ref_ch < 0 or (num_mic is not None and self.ref_ch >= num_mic):
+            raise ValueError(f"beamformer ref_ch {self.ref_ch!r} outside [0, {num_mic if num_mic is not None else 'M'})")
+        return self
+
+    def c_opts(self, epsi_default: float = 1e-6) -> "_lib.BfOpts":
+        return _lib.BfOpts(KINDS.index(self.kind), NOISES.index(self.noise), float(self.condition),
+                           int(bool(self.trace_normalize)), float(self.epsi if self.epsi is not None else epsi_default),
+                           int(bool(self.ban)), int(self.ref_ch))
+
+
+def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debug=False, *, beamformer="mvdr",
+                      noise="residual", condition=0.0, trace_normalize=False, ban=False, ref_ch=0):
+    """Beamforming, same arguments and (with the keyword defaults) same result as Tester_Enhance.Apply_Beamforming
+    (tester.py:1071-1136: residual-noise MVDR).
 
     source_stft, mix_stft: complex [B, F, Ch, T] (np.ndarray as in the reference, or torch tensors; permuted
     views are fine).  Returns a torch complex64 tensor [B, T, F]: on the CPU when the inputs were ndarrays (the
     reference returns torch.from_numpy(...)), on the device when they were device tensors.  Inputs are not modified.
+
+    The keywords are the fields of :class:`Beamformer` (``beamformer`` = its ``kind``, or a whole Beamformer / dict, whose
+    ``epsi``, when set, wins over the positional one).  ``return_debug`` adds what the kind has, complex128 / float64 on
+    the device: "mvdr" ``steer1`` and ``w`` [B, F, Ch]; "souden" ``w``; "gev" ``w`` and ``lam`` [B, F] (lambda_max).
     """
+    if isinstance(beamformer, str):
+        bf = Beamformer(kind=beamformer, noise=noise, condition=condition, trace_normalize=trace_normalize, epsi=epsi,
+                        ban=ban, ref_ch=ref_ch)
+    else:
+        bf = Beamformer.of(beamformer).with_epsi(epsi)
+    bf.validate(np.shape(source_stft)[2] if np.ndim(source_stft) == 4 else None)     # before any copy or launch
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     src, np_in = _dev_c64(source_stft, device)
@@ -39,20 +120,31 @@ def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debu
     if src.shape != mix.shape or src.dim() != 4:
         raise ValueError(f"source_stft {tuple(src.shape)} and mix_stft {tuple(mix.shape)} must both be [B, F, Ch, T]")
     B, F, M, T = src.shape
+    opts = bf.c_opts()
     L = _lib.lib()
-    nws = L.misonet_mvdr_workspace_bytes(B, F, M)
+    nws = L.misonet_beamform_workspace_bytes(B, F, M, C.byref(opts))
+    if nws < 0:
+        _lib.check(_lib.EINVAL)
     ws = torch.empty(max(int(nws), 8), dtype=torch.uint8, device=src.device)
     out = torch.empty((B, T, F), dtype=torch.complex64, device=src.device)
     with torch.cuda.device(src.device):
         st = _lib.stream_ptr(src.device)
-        _lib.check(L.misonet_mvdr(src.data_ptr(), mix.data_ptr(), B, F, M, T, float(epsi), out.data_ptr(), ws.data_ptr(),
-                                  ws.numel(), st))
+        _lib.check(L.misonet_beamform(src.data_ptr(), mix.data_ptr(), B, F, M, T, C.byref(opts), out.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), st))
         dbg = None
         if return_debug:
-            steer = torch.empty((B, F, M), dtype=torch.complex128, device=src.device)
             w = torch.empty((B, F, M), dtype=torch.complex128, device=src.device)
-            _lib.check(L.misonet_mvdr_debug(ws.data_ptr(), B, F, M, steer.data_ptr(), w.data_ptr(), st))
-            dbg = dict(steer1=steer, w=w)
+            dbg = dict(w=w)
+            if bf.kind == "mvdr":
+                steer = torch.empty((B, F, M), dtype=torch.complex128, device=src.device)
+                _lib.check(L.misonet_mvdr_debug(ws.data_ptr(), B, F, M, steer.data_ptr(), w.data_ptr(), st))
+                dbg = dict(steer1=steer, w=w)
+            else:
+                lam = torch.empty((B, F), dtype=torch.float64, device=src.device) if bf.kind == "gev" else None
+                _lib.check(L.misonet_beamform_debug(ws.data_ptr(), B, F, M, C.byref(opts), w.data_ptr(),
+                                                    lam.data_ptr() if lam is not None else None, st))
+                if lam is not None:
+                    dbg["lam"] = lam
     if np_in:
         out = out.cpu()
     return (out, dbg) if return_debug else out

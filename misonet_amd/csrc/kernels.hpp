@@ -189,8 +189,9 @@ struct CView {
   const float* re; const float* im;
   long long sb, sf, sm; int st;
 };
+enum { BF_MVDR = 0, BF_SOUDEN = 1, BF_GEV = 2 };
 struct MvdrArgs {
-  CView mix;              // observation Y
+  CView mix;             // observation Y
   const float* est;       // planar MISO1 output buffer [B*M][2S][F][Tp] (pipeline mode) or nullptr
   long long est_bstride;  // floats per sample
   const int* sel;         // [B][M][S]: estimated-speaker index to use for (b, mic m, aligned speaker j), or nullptr
@@ -198,12 +199,23 @@ struct MvdrArgs {
   int S;                  // speakers handled per utterance (grid.z)
   int B, F, M, T, Tp;
   float epsi;
+  // the beamformer (misonet_bf_opts, already validated on the host); the defaults are the reference's live path
+  int kind = BF_MVDR;     // BF_MVDR / BF_SOUDEN / BF_GEV
+  int noise_mix = 0;      // 1: Phi_n from Y instead of Y - S (MPDR, tester.py:1096)
+  int trace_norm = 0;     // Phi_n <- Phi_n / tr(Phi_n) (tester.py:1099)
+  int ban = 0;            // blind analytic normalisation of w (tester.py:1186-1208)
+  int bf_ref = 0;         // reference microphone of souden / gev
+  double condition = 0.0; // gamma: Phi_n <- (Phi_n + gamma tr(Phi_n) / M I) / (1 + gamma), per bin
 };
 long long mvdr_ws_bytes(int B, int S, int F, int M);
+// workspace of launch_mvdr for a kind: mvdr_ws_bytes, for souden / gev followed by Phi_s [B][S][F][M][M] and lambda_max [B][S][F]
+long long bf_ws_bytes(int B, int S, int F, int M, int kind);
 // out: complex, element (b, spk, t, f) at out_re[b*ob + spk*os + t*ot + f*of]
 struct COut { float* re; float* im; long long ob, os, ot, of; };
 hipError_t launch_mvdr(const MvdrArgs& a, const COut& out, void* ws, hipStream_t s);
 hipError_t launch_mvdr_debug(const void* ws, int B, int S, int F, int M, double* steer, double* w, hipStream_t s);
+// w complex128 [B][S][F][M] and (gev only) lambda_max float64 [B][S][F] of the last launch_mvdr in ws; either may be null
+hipError_t launch_bf_debug(const void* ws, int B, int S, int F, int M, double* w, double* lam, hipStream_t s);
 
 // dist[b][i][j] = sum_{t,f} | |A_i| - |B_j| | for S = 1..4 speakers: per-bin float64 partials, added in bin order (bit-
 // reproducible); then sel = the cheapest of the S! permutations (itertools order, first minimum).

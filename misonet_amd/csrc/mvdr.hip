@@ -9,6 +9,11 @@
 //   k2 mvdr_solve   : sequential-in-f phase correction               (tester.py:1154-1167)
 //                     w = (Phi_n + eps I)^-1 d / (d^H (Phi_n + eps I)^-1 d)   (tester.py:1211-1225)
 //   k3 mvdr_apply   : out[t] = sum_m conj(w_m) Y_m[t]                (tester.py:1227-1228)
+// The other beamformers (misonet_bf_opts) share k1 and k3: k1 takes Phi_n from Y instead of Y - S for noise = mix
+// (tester.py:1096) and, for souden / gev, writes Phi_s beside Phi_n and leaves the eigen-solve out (bf_scm: the same body with MIX);
+//   k2' bf_solve    : one wave per (b, spk, f), no dependence from bin to bin: Phi_n' (conditioning, trace normalisation,
+//                     eps I), Cholesky Phi_n' = L L^H, souden w = (Phi_n'^-1 Phi_s)[:, ref] / tr or gev C = L^-1 Phi_s L^-H,
+//                     Jacobi, w = L^-H u with the phase fixed per bin; blind analytic normalisation (tester.py:1186-1208)
 #include "kernels.hpp"
 
 namespace mn {
@@ -38,6 +43,17 @@ __host__ __device__ inline long long ws_w(int B, int S, int F, int M) {
 long long mvdr_ws_bytes(int B, int S, int F, int M) {
   return (ws_w(B, S, F, M) + (long long)B * S * F * M * 2) * (long long)sizeof(double);
 }
+// souden / gev append: phis [B][S][F][M][M][2] | lam [B][S][F]
+__host__ __device__ inline long long ws_phis(int B, int S, int F, int M) {
+  return ws_w(B, S, F, M) + (long long)B * S * F * M * 2;
+}
+__host__ __device__ inline long long ws_lam(int B, int S, int F, int M) {
+  return ws_phis(B, S, F, M) + (long long)B * S * F * M * M * 2;
+}
+long long bf_ws_bytes(int B, int S, int F, int M, int kind) {
+  if (kind == BF_MVDR) return mvdr_ws_bytes(B, S, F, M);
+  return (ws_lam(B, S, F, M) + (long long)B * S * F) * (long long)sizeof(double);
+}
 
 // source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f
 __device__ inline void src_row(const MvdrArgs& a, int b, int f, int m, int spk, const float*& re, const float*& im,
@@ -58,289 +74,296 @@ __device__ inline void src_row(const MvdrArgs& a, int b, int f, int m, int spk, 
   }
 }
 
+// Complex Jacobi on the Hermitian s_A with a PARALLEL (round-robin) ordering; eigenvectors accumulate in the columns of
+// s_V.  A sweep is ME - 1 rounds of M / 2 DISJOINT pivot pairs; disjoint rotations commute, so a round applies
+// A <- R^H A R with R = R_1 R_2 .. in three phases separated by barriers: (0) every lane of pair j computes that
+// pair's rotation from the untouched matrix, (1) lane (j, k) updates row k of the columns (p_j, q_j) of A and V,
+// (2) lane (j, k) updates column k of the rows (p_j, q_j) of A.  M (M - 1) / 2 rotations of a sweep cost ME - 1 round
+// latencies instead of M (M - 1) / 2: the 6 x 6 problem was ~280 of the kernel's 320 us of dependent float64 work.
+// Every thread of the workgroup calls it (it holds barriers), after a barrier that follows the writes of s_A and s_V = I.
 template <int M>
-__global__ __launch_bounds__(256) void mvdr_scm_eig(const MvdrArgs a, double* ws) {
-  constexpr int NT = M * (M + 1) / 2;
-  __shared__ double s_part[4][2 * NT * 2];
-  __shared__ double s_A[M][M][2];
-  __shared__ double s_V[M][M][2];
-  const int f = blockIdx.x, b = blockIdx.y, spk = blockIdx.z;
-  const int tid = threadIdx.x;
-  const float *sre[M], *sim[M], *yre[M], *yim[M];
-  int sst = 1;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    src_row(a, b, f, m, spk, sre[m], sim[m], sst);
-    const long long off = (long long)b * a.mix.sb + (long long)f * a.mix.sf + (long long)m * a.mix.sm;
-    yre[m] = a.mix.re + off;
-    yim[m] = a.mix.im + off;
-  }
-  const int yst = a.mix.st;
-  float ps[NT][2], pn[NT][2];
-#pragma unroll
-  for (int i = 0; i < NT; ++i) { ps[i][0] = ps[i][1] = pn[i][0] = pn[i][1] = 0.f; }
-  const int nthr = blockDim.x, nw = nthr >> 6;
-  for (int t = tid; t < a.T; t += nthr) {
-    float xr[M], xi[M], nr[M], ni[M];
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-      xr[m] = sre[m][(long long)t * sst];
-      xi[m] = sim[m][(long long)t * sst];
-      nr[m] = yre[m][(long long)t * yst] - xr[m];      // noise = mix - source (tester.py:1095)
-      ni[m] = yim[m][(long long)t * yst] - xi[m];
-    }
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < M; ++i)
-#pragma unroll
-      for (int j = 0; j <= i; ++j, ++k) {
-        ps[k][0] += xr[i] * xr[j] + xi[i] * xi[j];
-        ps[k][1] += xi[i] * xr[j] - xr[i] * xi[j];
-        pn[k][0] += nr[i] * nr[j] + ni[i] * ni[j];
-        pn[k][1] += ni[i] * nr[j] - nr[i] * ni[j];
+__device__ __forceinline__ void jacobi_hermitian(double (&s_A)[M][M][2], double (&s_V)[M][M][2], const int tid) {
+  constexpr int ME = (M + 1) & ~1;                       // players of the tournament (a dummy when M is odd)
+  constexpr int NPR = ME / 2;                            // pairs per round
+  const int pj = tid / M, pk = tid - pj * M;             // this lane's pair slot and index (valid when pj < NPR)
+  double scale = 0.0;
+  for (int i = 0; i < M; ++i) scale += fabs(s_A[i][i][0]);
+  for (int sweep = 0; sweep < 16; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < M; ++p)
+      for (int q = p + 1; q < M; ++q) off += s_A[p][q][0] * s_A[p][q][0] + s_A[p][q][1] * s_A[p][q][1];
+    if (off <= 1e-28 * scale * scale || off == 0.0) break;    // uniform: every lane reads the same elements
+    for (int rd = 0; rd < ME - 1; ++rd) {
+      // circle method: slot 0 pairs the fixed player ME - 1 with rd, slot i pairs (rd + i) with (rd - i) modulo ME - 1
+      int p = 0, q = 0;
+      bool act = pj < NPR;
+      if (act) {
+        if (pj == 0) { p = rd; q = ME - 1; }
+        else { p = (rd + pj) % (ME - 1); q = (rd - pj + (ME - 1)) % (ME - 1); }
+        if (p > q) { const int t = p; p = q; q = t; }
+        act = q < M;                                     // the dummy player sits out
       }
-  }
-  // block reduction in float64
-  const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int k = 0; k < NT; ++k)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      double v1 = ps[k][c], v2 = pn[k][c];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) {
-        v1 += __shfl_xor(v1, m, 64);
-        v2 += __shfl_xor(v2, m, 64);
+      cd Rpp = {1.0, 0.0}, Rpq = {0.0, 0.0}, Rqp = {0.0, 0.0}, Rqq = {1.0, 0.0};
+      if (act) {
+        const cd apq = {s_A[p][q][0], s_A[p][q][1]};
+        const double g = sqrt(cabs2(apq));
+        if (g > 1e-300) {
+          const double app = s_A[p][p][0], aqq = s_A[q][q][0];
+          const double tau = (aqq - app) / (2.0 * g);
+          const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+          const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = tt * cs;
+          const cd ph = {apq.re / g, apq.im / g};        // e^{i phi}
+          // R restricted to (p,q): Rpp = c, Rpq = s, Rqp = -s e^{-i phi}, Rqq = c e^{-i phi}
+          Rpp = {cs, 0.0}; Rpq = {sn, 0.0};
+          Rqp = {-sn * ph.re, sn * ph.im}; Rqq = {cs * ph.re, -cs * ph.im};
+        } else {
+          act = false;
+        }
       }
-      if (lane == 0) {
-        s_part[wave][(k * 2 + c)] = v1;
-        s_part[wave][2 * NT + (k * 2 + c)] = v2;
+      __syncthreads();                                   // every lane has read its pivot before anyone overwrites it
+      if (act) {                                         // A <- A R (columns p, q), V <- V R: row k = pk
+        const int k = pk;
+        const cd akp = {s_A[k][p][0], s_A[k][p][1]}, akq = {s_A[k][q][0], s_A[k][q][1]};
+        const cd np_ = cadd(cmul(akp, Rpp), cmul(akq, Rqp));
+        const cd nq_ = cadd(cmul(akp, Rpq), cmul(akq, Rqq));
+        s_A[k][p][0] = np_.re; s_A[k][p][1] = np_.im;
+        s_A[k][q][0] = nq_.re; s_A[k][q][1] = nq_.im;
+        const cd vkp = {s_V[k][p][0], s_V[k][p][1]}, vkq = {s_V[k][q][0], s_V[k][q][1]};
+        const cd vp_ = cadd(cmul(vkp, Rpp), cmul(vkq, Rqp));
+        const cd vq_ = cadd(cmul(vkp, Rpq), cmul(vkq, Rqq));
+        s_V[k][p][0] = vp_.re; s_V[k][p][1] = vp_.im;
+        s_V[k][q][0] = vq_.re; s_V[k][q][1] = vq_.im;
       }
-    }
-  __syncthreads();
-  const double invT = 1.0 / (double)a.T;
-  const long long idx = ((long long)(b * a.S + spk) * a.F + f);
-  for (int e = tid; e < 2 * NT * 2; e += nthr) {
-    double v = 0.0;
-    for (int w = 0; w < nw; ++w) v += s_part[w][e];
-    v *= invT;
-    const int which = e / (2 * NT);            // 0: Phi_s, 1: Phi_n
-    const int kc = e - which * 2 * NT;
-    const int k = kc >> 1, c = kc & 1;
-    // k -> (i, j), i >= j
-    int i = 0, rem = k;
-    while (rem > i) { rem -= (i + 1); ++i; }
-    const int j = rem;
-    if (which == 0) {
-      s_A[i][j][c] = v;
-      s_A[j][i][c] = c ? -v : v;
-      if (i == j && c) s_A[i][i][1] = 0.0;
-    } else {
-      double* pn_o = ws + ws_phin(a.B, a.S, a.F, M) + idx * (M * M * 2);
-      pn_o[(i * M + j) * 2 + c] = (i == j && c) ? 0.0 : v;
-      if (i != j) pn_o[(j * M + i) * 2 + c] = c ? -v : v;
-    }
-  }
-  for (int e = tid; e < M * M; e += nthr) {
-    const int i = e / M, j = e - i * M;
-    s_V[i][j][0] = (i == j) ? 1.0 : 0.0;
-    s_V[i][j][1] = 0.0;
-  }
-  __syncthreads();
-  // Complex Jacobi on the Hermitian s_A with a PARALLEL (round-robin) ordering; eigenvectors accumulate in the columns of
-  // s_V.  A sweep is ME - 1 rounds of M / 2 DISJOINT pivot pairs; disjoint rotations commute, so a round applies
-  // A <- R^H A R with R = R_1 R_2 .. in three phases separated by barriers: (0) every lane of pair j computes that
-  // pair's rotation from the untouched matrix, (1) lane (j, k) updates row k of the columns (p_j, q_j) of A and V,
-  // (2) lane (j, k) updates column k of the rows (p_j, q_j) of A.  M (M - 1) / 2 rotations of a sweep cost ME - 1 round
-  // latencies instead of M (M - 1) / 2: the 6 x 6 problem was ~280 of the kernel's 320 us of dependent float64 work.
-  {
-    constexpr int ME = (M + 1) & ~1;                       // players of the tournament (a dummy when M is odd)
-    constexpr int NPR = ME / 2;                            // pairs per round
-    const int pj = tid / M, pk = tid - pj * M;             // this lane's pair slot and index (valid when pj < NPR)
-    double scale = 0.0;
-    for (int i = 0; i < M; ++i) scale += fabs(s_A[i][i][0]);
-    for (int sweep = 0; sweep < 16; ++sweep) {
-      double off = 0.0;
-      for (int p = 0; p < M; ++p)
-        for (int q = p + 1; q < M; ++q) off += s_A[p][q][0] * s_A[p][q][0] + s_A[p][q][1] * s_A[p][q][1];
-      if (off <= 1e-28 * scale * scale || off == 0.0) break;    // uniform: every lane reads the same elements
-      for (int rd = 0; rd < ME - 1; ++rd) {
-        // circle method: slot 0 pairs the fixed player ME - 1 with rd, slot i pairs (rd + i) with (rd - i) modulo ME - 1
-        int p = 0, q = 0;
-        bool act = pj < NPR;
-        if (act) {
-          if (pj == 0) { p = rd; q = ME - 1; }
-          else { p = (rd + pj) % (ME - 1); q = (rd - pj + (ME - 1)) % (ME - 1); }
-          if (p > q) { const int t = p; p = q; q = t; }
-          act = q < M;                                     // the dummy player sits out
-        }
-        cd Rpp = {1.0, 0.0}, Rpq = {0.0, 0.0}, Rqp = {0.0, 0.0}, Rqq = {1.0, 0.0};
-        if (act) {
-          const cd apq = {s_A[p][q][0], s_A[p][q][1]};
-          const double g = sqrt(cabs2(apq));
-          if (g > 1e-300) {
-            const double app = s_A[p][p][0], aqq = s_A[q][q][0];
-            const double tau = (aqq - app) / (2.0 * g);
-            const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = tt * cs;
-            const cd ph = {apq.re / g, apq.im / g};        // e^{i phi}
-            // R restricted to (p,q): Rpp = c, Rpq = s, Rqp = -s e^{-i phi}, Rqq = c e^{-i phi}
-            Rpp = {cs, 0.0}; Rpq = {sn, 0.0};
-            Rqp = {-sn * ph.re, sn * ph.im}; Rqq = {cs * ph.re, -cs * ph.im};
-          } else {
-            act = false;
-          }
-        }
-        __syncthreads();                                   // every lane has read its pivot before anyone overwrites it
-        if (act) {                                         // A <- A R (columns p, q), V <- V R: row k = pk
-          const int k = pk;
-          const cd akp = {s_A[k][p][0], s_A[k][p][1]}, akq = {s_A[k][q][0], s_A[k][q][1]};
-          const cd np_ = cadd(cmul(akp, Rpp), cmul(akq, Rqp));
-          const cd nq_ = cadd(cmul(akp, Rpq), cmul(akq, Rqq));
-          s_A[k][p][0] = np_.re; s_A[k][p][1] = np_.im;
-          s_A[k][q][0] = nq_.re; s_A[k][q][1] = nq_.im;
-          const cd vkp = {s_V[k][p][0], s_V[k][p][1]}, vkq = {s_V[k][q][0], s_V[k][q][1]};
-          const cd vp_ = cadd(cmul(vkp, Rpp), cmul(vkq, Rqp));
-          const cd vq_ = cadd(cmul(vkp, Rpq), cmul(vkq, Rqq));
-          s_V[k][p][0] = vp_.re; s_V[k][p][1] = vp_.im;
-          s_V[k][q][0] = vq_.re; s_V[k][q][1] = vq_.im;
-        }
-        __syncthreads();
-        if (act) {                                         // A <- R^H A (rows p, q): column k = pk
-          const int k = pk;
-          const cd apk = {s_A[p][k][0], s_A[p][k][1]}, aqk = {s_A[q][k][0], s_A[q][k][1]};
-          const cd np_ = cadd(cmul(cconj(Rpp), apk), cmul(cconj(Rqp), aqk));
-          const cd nq_ = cadd(cmul(cconj(Rpq), apk), cmul(cconj(Rqq), aqk));
-          s_A[p][k][0] = np_.re; s_A[p][k][1] = np_.im;
-          s_A[q][k][0] = nq_.re; s_A[q][k][1] = nq_.im;
-        }
-        __syncthreads();
-        if (act && pk == 0) {
-          s_A[p][q][0] = s_A[p][q][1] = 0.0;
-          s_A[q][p][0] = s_A[q][p][1] = 0.0;
-          s_A[p][p][1] = 0.0;
-          s_A[q][q][1] = 0.0;
-        }
-        __syncthreads();
+      __syncthreads();
+      if (act) {                                         // A <- R^H A (rows p, q): column k = pk
+        const int k = pk;
+        const cd apk = {s_A[p][k][0], s_A[p][k][1]}, aqk = {s_A[q][k][0], s_A[q][k][1]};
+        const cd np_ = cadd(cmul(cconj(Rpp), apk), cmul(cconj(Rqp), aqk));
+        const cd nq_ = cadd(cmul(cconj(Rpq), apk), cmul(cconj(Rqq), aqk));
+        s_A[p][k][0] = np_.re; s_A[p][k][1] = np_.im;
+        s_A[q][k][0] = nq_.re; s_A[q][k][1] = nq_.im;
       }
-    }
-  }
-  if (tid == 0) {
-    int best = 0;                                         // argmax eigenvalue, first on ties (tester.py:1110)
-    for (int i = 1; i < M; ++i)
-      if (s_A[i][i][0] > s_A[best][best][0]) best = i;
-    cd v[M];
-    for (int i = 0; i < M; ++i) v[i] = {s_V[i][best][0], s_V[i][best][1]};
-    const cd v0 = v[0];
-    double nrm = 0.0;
-    for (int i = 0; i < M; ++i) {
-      v[i] = cdiv(v[i], v0);                              // tester.py:1119
-      nrm += cabs2(v[i]);
-    }
-    const double sc = sqrt((double)M / sqrt(nrm));        // tester.py:1123: sqrt(M / ||d||)
-    double* o = ws + ws_steer0(a.B, a.S, a.F, M) + idx * (M * 2);
-    for (int i = 0; i < M; ++i) {
-      o[i * 2 + 0] = v[i].re * sc;
-      o[i * 2 + 1] = v[i].im * sc;
+      __syncthreads();
+      if (act && pk == 0) {
+        s_A[p][q][0] = s_A[p][q][1] = 0.0;
+        s_A[q][p][0] = s_A[q][p][1] = 0.0;
+        s_A[p][p][1] = 0.0;
+        s_A[q][q][1] = 0.0;
+      }
+      __syncthreads();
     }
   }
 }
 
-// one workgroup per (b, spk): thread 0 runs the sequential phase correction over f, then thread f solves bin f
+// For souden and gev (a.kind, uniform) Phi_s goes to the workspace beside Phi_n and the eigen-solve is left to bf_solve.
+// bf_scm is the same kernel with Phi_n from the observation itself (MIX: MPDR, tester.py:1096).
+template <int M>
+__global__ __launch_bounds__(256) void mvdr_scm_eig(const MvdrArgs a, double* ws) {
+  constexpr bool MIX = false;
+#include "mvdr_scm_body.inc"
+}
+template <int M>
+__global__ __launch_bounds__(256) void bf_scm(const MvdrArgs a, double* ws) {
+  constexpr bool MIX = true;
+#include "mvdr_scm_body.inc"
+}
+
+// Phi_n' of one bin from the stored Phi_n [M][M][2]: conditioning (Phi_n + gamma tr / M I) / (1 + gamma), then the division by
+// the trace of that (tester.py:1099), then eps I (tester.py:1221).  With gamma = 0 and no trace normalisation every step but
+// the last is exact (+ 0, / 1).
+struct PhinPrime {
+  double add, div1, div2, eps;
+  template <int M>
+  __device__ inline void init(const double* pn, double cond, int tn, double epsi) {
+    double tr = 0.0;
+    for (int k = 0; k < M; ++k) tr += pn[(k * M + k) * 2];
+    add = cond * tr / (double)M;
+    div1 = 1.0 + cond;
+    div2 = 1.0;
+    if (tn) {
+      double t2 = 0.0;
+      for (int k = 0; k < M; ++k) t2 += (pn[(k * M + k) * 2] + add) / div1;
+      div2 = t2;
+    }
+    eps = epsi;
+  }
+  template <int M>
+  __device__ inline cd at(const double* pn, int i, int j) const {
+    cd v = {pn[(i * M + j) * 2], pn[(i * M + j) * 2 + 1]};
+    if (i == j) v.re += add;
+    v.re = v.re / div1 / div2;
+    v.im = v.im / div1 / div2;
+    if (i == j) v.re += eps;
+    return v;
+  }
+};
+
+// blind analytic normalisation (tester.py:1196-1208, eps = 0): w <- w sqrt|w^H N N w| / |w^H N w| with N = Phi_n' Hermitian,
+// so w^H N N w = ||N w||^2; a zero denominator leaves w as it is.  N(i, j) returns element (i, j).
+template <int M, class NF>
+__device__ inline void ban_scale(cd (&w)[M], NF N) {
+  cd den = {0.0, 0.0};
+  double num = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    cd v = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < M; ++j) v = cadd(v, cmul(N(i, j), w[j]));
+    num += cabs2(v);
+    den = cadd(den, cmul(cconj(w[i]), v));
+  }
+  const double d = sqrt(cabs2(den));
+  if (d == 0.0) return;
+  const double g = sqrt(num) / d;
+#pragma unroll
+  for (int i = 0; i < M; ++i) { w[i].re *= g; w[i].im *= g; }
+}
+
+// one workgroup per (b, spk): thread 0 runs the sequential phase correction over f, then thread f solves bin f.
+// mvdr_solve_ext compiles in the options beyond the reference's live path: conditioning, trace normalisation, BAN.
 template <int M>
 __global__ __launch_bounds__(256) void mvdr_solve(int B, int S, int F, double epsi, double* ws) {
-  extern __shared__ double s_d[];     // [F][M][2]
-  const int b = blockIdx.x, spk = blockIdx.y;
+  constexpr bool EXT = false;
+  constexpr double cond = 0.0;
+  constexpr int tn = 0, ban = 0;
+#include "mvdr_solve_body.inc"
+}
+template <int M>
+__global__ __launch_bounds__(256) void mvdr_solve_ext(int B, int S, int F, double epsi, double* ws, double cond, int tn,
+                                                      int ban) {
+  constexpr bool EXT = true;
+#include "mvdr_solve_body.inc"
+}
+
+// souden / gev: one single-wave workgroup per (b, spk, f), as mvdr_scm_eig -- nothing depends on another bin.  All float64.
+//   N = Phi_n' (PhinPrime), Cholesky N = L L^H: column j by lane j (diagonal) and lanes i > j (below it).  A pivot <= 0 gives
+//   sqrt(< 0) = NaN or a division by 0: the non-finite w is what the caller sees, nothing is clamped.
+//   X = L^-1 Phi_s: lane j owns column j (forward substitution).
+//   souden: G = L^-H X, again a column per lane; w = G[:, ref] / tr(G), 0 where tr(G) == 0.
+//   gev:    C = X L^-H = (L^-1 X^H)^H, lane j owns row j; Jacobi on C; w = L^-H u, w^H N w = 1,
+//           (N w)[ref] real and >= 0; lambda_max beside it.
+template <int M, int KIND>
+__global__ __launch_bounds__(64) void bf_solve(int B, int S, int F, double epsi, double cond, int tn, int ban, int ref,
+                                               double* ws) {
+  __shared__ double s_N[M][M][2];
+  __shared__ double s_L[M][M][2];
+  __shared__ double s_A[M][M][2];
+  __shared__ double s_C[M][M][2];
+  __shared__ double s_V[M][M][2];
+  const int f = blockIdx.x, b = blockIdx.y, spk = blockIdx.z;
   const int tid = threadIdx.x;
-  const long long base = (long long)(b * S + spk) * F;
-  const double* d0 = ws + ws_steer0(B, S, F, M) + base * (M * 2);
-  for (int i = tid; i < F * M * 2; i += blockDim.x) s_d[i] = d0[i];
+  const long long idx = ((long long)(b * S + spk) * F + f);
+  const double* pn = ws + ws_phin(B, S, F, M) + idx * (M * M * 2);
+  const double* ps = ws + ws_phis(B, S, F, M) + idx * (M * M * 2);
+  PhinPrime P;
+  P.init<M>(pn, cond, tn, epsi);
+  for (int e = tid; e < M * M; e += 64) {
+    const int i = e / M, j = e - i * M;
+    const cd v = P.at<M>(pn, i, j);
+    s_N[i][j][0] = v.re; s_N[i][j][1] = v.im;
+    s_A[i][j][0] = ps[e * 2]; s_A[i][j][1] = ps[e * 2 + 1];
+    s_L[i][j][0] = 0.0; s_L[i][j][1] = 0.0;
+    s_V[i][j][0] = (i == j) ? 1.0 : 0.0; s_V[i][j][1] = 0.0;
+  }
   __syncthreads();
-  // sequential-in-f phase correction (tester.py:1161-1167): bin f is rotated by the phase of <d[f], d_corrected[f-1]>.
-  // The dependence from bin to bin is kept exactly; inside a bin lane m < M owns microphone m (the M products and the M
-  // rotations run on M lanes, the sum over m is a butterfly over 8 lanes with zeros in the unused ones).
-  if (tid < 8) {
-    const int m = tid;
-    const bool live = m < M;
-    cd prv = live ? cd{s_d[m * 2], s_d[m * 2 + 1]} : cd{0.0, 0.0};
-    for (int f = 1; f < F; ++f) {
-      const cd cur = live ? cd{s_d[(f * M + m) * 2], s_d[(f * M + m) * 2 + 1]} : cd{0.0, 0.0};
-      cd z = cmulc(cur, prv);
-#pragma unroll
-      for (int w = 4; w >= 1; w >>= 1) {
-        z.re += __shfl_xor(z.re, w, 8);
-        z.im += __shfl_xor(z.im, w, 8);
-      }
-      const double az = sqrt(cabs2(z));
-      cd rot = {1.0, 0.0};                                // exp(-j angle(z)); angle(0) = 0
-      if (az > 0.0) rot = {z.re / az, -z.im / az};
-      prv = cmul(cur, rot);
-      if (live) {
-        s_d[(f * M + m) * 2] = prv.re;
-        s_d[(f * M + m) * 2 + 1] = prv.im;
-      }
+  for (int j = 0; j < M; ++j) {                            // Cholesky, left-looking: column j from the columns before it
+    if (tid == j) {
+      double d = s_N[j][j][0];
+      for (int k = 0; k < j; ++k) d -= s_L[j][k][0] * s_L[j][k][0] + s_L[j][k][1] * s_L[j][k][1];
+      s_L[j][j][0] = sqrt(d);                              // d <= 0: NaN, or a division by zero below
+    }
+    __syncthreads();
+    if (tid > j && tid < M) {
+      const int i = tid;
+      cd acc = {s_N[i][j][0], s_N[i][j][1]};
+      for (int k = 0; k < j; ++k)
+        acc = csub(acc, cmulc(cd{s_L[i][k][0], s_L[i][k][1]}, cd{s_L[j][k][0], s_L[j][k][1]}));
+      const double ljj = s_L[j][j][0];
+      s_L[i][j][0] = acc.re / ljj; s_L[i][j][1] = acc.im / ljj;
+    }
+    __syncthreads();
+  }
+  if (tid < M) {                                           // X = L^-1 Phi_s, column tid, in place
+    const int j = tid;
+    for (int i = 0; i < M; ++i) {
+      cd acc = {s_A[i][j][0], s_A[i][j][1]};
+      for (int k = 0; k < i; ++k) acc = csub(acc, cmul(cd{s_L[i][k][0], s_L[i][k][1]}, cd{s_A[k][j][0], s_A[k][j][1]}));
+      const double lii = s_L[i][i][0];
+      s_A[i][j][0] = acc.re / lii; s_A[i][j][1] = acc.im / lii;
     }
   }
   __syncthreads();
-  double* d1 = ws + ws_steer1(B, S, F, M) + base * (M * 2);
-  for (int i = tid; i < F * M * 2; i += blockDim.x) d1[i] = s_d[i];
-  for (int f = tid; f < F; f += blockDim.x) {
-    const double* pn = ws + ws_phin(B, S, F, M) + (base + f) * (M * M * 2);
-    cd A[M][M + 1];
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-#pragma unroll
-      for (int j = 0; j < M; ++j) A[i][j] = {pn[(i * M + j) * 2], pn[(i * M + j) * 2 + 1]};
-      A[i][i].re += epsi;                                 // tester.py:1086-1088,1221
-      A[i][M] = {s_d[(f * M + i) * 2], s_d[(f * M + i) * 2 + 1]};
-    }
-    // Gaussian elimination with partial pivoting (fully unrolled so A stays in registers)
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-      int piv = k;
-      double best = cabs2(A[k][k]);
-#pragma unroll
-      for (int i = k + 1; i < M; ++i) {
-        const double v = cabs2(A[i][k]);
-        if (v > best) { best = v; piv = i; }
-      }
-#pragma unroll
-      for (int i = k + 1; i < M; ++i) {
-        if (piv == i) {
-#pragma unroll
-          for (int j = 0; j <= M; ++j) { const cd tmp = A[k][j]; A[k][j] = A[i][j]; A[i][j] = tmp; }
-        }
-      }
-      const cd pk = A[k][k];
-#pragma unroll
-      for (int i = k + 1; i < M; ++i) {
-        const cd fac = cdiv(A[i][k], pk);
-#pragma unroll
-        for (int j = k; j <= M; ++j) A[i][j] = csub(A[i][j], cmul(fac, A[k][j]));
+  cd w[M];
+  double lam = 0.0;
+  if constexpr (KIND == BF_SOUDEN) {
+    if (tid < M) {                                         // G = L^-H X, column tid, in place
+      const int j = tid;
+      for (int i = M - 1; i >= 0; --i) {
+        cd acc = {s_A[i][j][0], s_A[i][j][1]};
+        for (int k = i + 1; k < M; ++k)                    // (L^H)[i][k] = conj(L[k][i])
+          acc = csub(acc, cmul(cconj(cd{s_L[k][i][0], s_L[k][i][1]}), cd{s_A[k][j][0], s_A[k][j][1]}));
+        const double lii = s_L[i][i][0];
+        s_A[i][j][0] = acc.re / lii; s_A[i][j][1] = acc.im / lii;
       }
     }
-    cd x[M];
-#pragma unroll
-    for (int i = M - 1; i >= 0; --i) {
-      cd acc = A[i][M];
-#pragma unroll
-      for (int j = i + 1; j < M; ++j) acc = csub(acc, cmul(A[i][j], x[j]));
-      x[i] = cdiv(acc, A[i][i]);
+    __syncthreads();
+    if (tid != 0) return;
+    cd tr = {0.0, 0.0};
+    for (int i = 0; i < M; ++i) tr = cadd(tr, cd{s_A[i][i][0], s_A[i][i][1]});
+    const bool zero = tr.re == 0.0 && tr.im == 0.0;
+    for (int i = 0; i < M; ++i) w[i] = zero ? cd{0.0, 0.0} : cdiv(cd{s_A[i][ref][0], s_A[i][ref][1]}, tr);
+  } else {
+    if (tid < M) {                                         // row tid of C: solve L c = conj(X[tid, :])^T, C[tid][i] = conj(c_i)
+      const int r = tid;
+      cd c[M];
+      for (int i = 0; i < M; ++i) {
+        cd acc = {s_A[r][i][0], -s_A[r][i][1]};
+        for (int k = 0; k < i; ++k) acc = csub(acc, cmul(cd{s_L[i][k][0], s_L[i][k][1]}, c[k]));
+        const double lii = s_L[i][i][0];
+        c[i] = {acc.re / lii, acc.im / lii};
+        s_C[r][i][0] = c[i].re; s_C[r][i][1] = -c[i].im;
+      }
     }
-    cd den = {0.0, 0.0};                                  // d^H x (tester.py:1223)
-#pragma unroll
+    __syncthreads();
+    for (int e = tid; e < M * M; e += 64) {                // Hermitian part of C (it is Hermitian up to rounding)
+      const int i = e / M, j = e - i * M;
+      s_A[i][j][0] = 0.5 * (s_C[i][j][0] + s_C[j][i][0]);
+      s_A[i][j][1] = (i == j) ? 0.0 : 0.5 * (s_C[i][j][1] - s_C[j][i][1]);
+    }
+    __syncthreads();
+    jacobi_hermitian<M>(s_A, s_V, tid);
+    if (tid != 0) return;
+    int best = 0;                                          // largest eigenvalue, first on ties
+    for (int i = 1; i < M; ++i)
+      if (s_A[i][i][0] > s_A[best][best][0]) best = i;
+    lam = s_A[best][best][0];
+    for (int i = M - 1; i >= 0; --i) {                     // w = L^-H u
+      cd acc = {s_V[i][best][0], s_V[i][best][1]};
+      for (int k = i + 1; k < M; ++k) acc = csub(acc, cmul(cconj(cd{s_L[k][i][0], s_L[k][i][1]}), w[k]));
+      const double lii = s_L[i][i][0];
+      w[i] = {acc.re / lii, acc.im / lii};
+    }
+    cd nref = {0.0, 0.0};                                  // (N w)[ref], and q = w^H N w
+    double q = 0.0;
     for (int i = 0; i < M; ++i) {
-      const cd di = {s_d[(f * M + i) * 2], s_d[(f * M + i) * 2 + 1]};
-      den = cadd(den, cmul(cconj(di), x[i]));
+      cd v = {0.0, 0.0};
+      for (int j = 0; j < M; ++j) v = cadd(v, cmul(cd{s_N[i][j][0], s_N[i][j][1]}, w[j]));
+      q += w[i].re * v.re + w[i].im * v.im;
+      if (i == ref) nref = v;
     }
-    double* wo = ws + ws_w(B, S, F, M) + (base + f) * (M * 2);
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      const cd wi = cdiv(x[i], den);
-      wo[i * 2] = wi.re;
-      wo[i * 2 + 1] = wi.im;
-    }
+    const double sc = 1.0 / sqrt(q);
+    const double az = sqrt(cabs2(nref));
+    cd rot = {sc, 0.0};                                    // scale, and the rotation that makes (N w)[ref] real and >= 0
+    if (az > 0.0) rot = {sc * nref.re / az, -sc * nref.im / az};
+    for (int i = 0; i < M; ++i) w[i] = cmul(w[i], rot);
   }
+  if (ban) ban_scale<M>(w, [&](int i, int j) { return cd{s_N[i][j][0], s_N[i][j][1]}; });
+  double* wo = ws + ws_w(B, S, F, M) + idx * (M * 2);
+  for (int i = 0; i < M; ++i) {
+    wo[i * 2] = w[i].re;
+    wo[i * 2 + 1] = w[i].im;
+  }
+  if (KIND == BF_GEV) ws[ws_lam(B, S, F, M) + idx] = lam;
 }
 
 template <int M>
@@ -373,8 +396,37 @@ __global__ __launch_bounds__(256) void mvdr_apply(const MvdrArgs a, const COut o
   }
 }
 
+template <int M, bool MIX>
+static hipError_t bf_run(const MvdrArgs& a, const COut& out, double* ws, hipStream_t s) {
+  dim3 g(a.F, a.B, a.S);
+  const bool ext = a.condition != 0.0 || a.trace_norm || a.ban;
+  if (a.kind == BF_MVDR) {
+    if (MIX) hipLaunchKernelGGL(bf_scm<M>, g, dim3(64), 0, s, a, ws);
+    else hipLaunchKernelGGL(mvdr_scm_eig<M>, g, dim3(64), 0, s, a, ws);
+    const size_t lds = (size_t)a.F * M * 2 * sizeof(double);
+    if (ext)
+      hipLaunchKernelGGL(mvdr_solve_ext<M>, dim3(a.B, a.S), dim3(256), lds, s, a.B, a.S, a.F, (double)a.epsi, ws,
+                         a.condition, a.trace_norm, a.ban);
+    else
+      hipLaunchKernelGGL(mvdr_solve<M>, dim3(a.B, a.S), dim3(256), lds, s, a.B, a.S, a.F, (double)a.epsi, ws);
+  } else {
+    if (MIX) hipLaunchKernelGGL(bf_scm<M>, g, dim3(64), 0, s, a, ws);
+    else hipLaunchKernelGGL(mvdr_scm_eig<M>, g, dim3(64), 0, s, a, ws);
+    if (a.kind == BF_SOUDEN)
+      hipLaunchKernelGGL((bf_solve<M, BF_SOUDEN>), g, dim3(64), 0, s, a.B, a.S, a.F, (double)a.epsi, a.condition,
+                         a.trace_norm, a.ban, a.bf_ref, ws);
+    else
+      hipLaunchKernelGGL((bf_solve<M, BF_GEV>), g, dim3(64), 0, s, a.B, a.S, a.F, (double)a.epsi, a.condition,
+                         a.trace_norm, a.ban, a.bf_ref, ws);
+  }
+  hipLaunchKernelGGL(mvdr_apply<M>, g, dim3(256), 0, s, a, out, (const double*)ws);
+  return hipGetLastError();
+}
+
 template <int M>
 static hipError_t mvdr_run(const MvdrArgs& a, const COut& out, double* ws, hipStream_t s) {
+  if (a.kind != BF_MVDR || a.noise_mix || a.condition != 0.0 || a.trace_norm || a.ban)
+    return a.noise_mix ? bf_run<M, true>(a, out, ws, s) : bf_run<M, false>(a, out, ws, s);
   dim3 g(a.F, a.B, a.S);
   // one wave per (b, f, spk): the 6x6 Jacobi runs on one lane (~100 us of dependent float64 work), so what matters is
   // how many of them are in flight per CU -- 8 single-wave workgroups instead of 2 four-wave ones
@@ -397,6 +449,15 @@ hipError_t launch_mvdr(const MvdrArgs& a, const COut& out, void* ws, hipStream_t
     case 8: return mvdr_run<8>(a, out, w, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+hipError_t launch_bf_debug(const void* ws, int B, int S, int F, int M, double* w, double* lam, hipStream_t s) {
+  const double* p = reinterpret_cast<const double*>(ws);
+  hipError_t e = hipSuccess;
+  if (w) e = hipMemcpyAsync(w, p + ws_w(B, S, F, M), (size_t)B * S * F * M * 2 * sizeof(double), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && lam)
+    e = hipMemcpyAsync(lam, p + ws_lam(B, S, F, M), (size_t)B * S * F * sizeof(double), hipMemcpyDeviceToDevice, s);
+  return e;
 }
 
 hipError_t launch_mvdr_debug(const void* ws, int B, int S, int F, int M, double* steer, double* w, hipStream_t s) {

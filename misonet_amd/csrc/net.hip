@@ -657,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 500; }   // 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 510; }   // 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1012,6 +1012,69 @@ int misonet_mvdr_debug(const void* ws, int B, int F, int M, void* steer, void* w
   if (!ws) return fail(MISONET_EINVAL, "null argument");
   HIPCHK(launch_mvdr_debug(ws, B, 1, F, M, reinterpret_cast<double*>(steer), reinterpret_cast<double*>(w),
                            reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- selectable beamformers (ABI 510) ------------------------------------------------------------------------------
+int misonet_bf_opts_default(misonet_bf_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->kind = BF_MVDR; o->noise = 0; o->condition = 0.0; o->trace_normalize = 0; o->epsi = 1e-6f; o->ban = 0; o->ref_ch = 0;
+  return MISONET_OK;
+}
+
+// host-side check of every field; M = the number of microphones ref_ch is counted in
+static int bf_opts_check(const misonet_bf_opts* o, int M) {
+  if (!o) return fail(MISONET_EINVAL, "null beamformer options");
+  if (o->kind != BF_MVDR && o->kind != BF_SOUDEN && o->kind != BF_GEV)
+    return fail(MISONET_EINVAL, "beamformer kind %d: 0 mvdr, 1 souden, 2 gev", o->kind);
+  if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "beamformer noise %d: 0 residual, 1 mix", o->noise);
+  if (!(o->condition >= 0.0) || !std::isfinite(o->condition))
+    return fail(MISONET_EINVAL, "beamformer condition (gamma) must be finite and >= 0 (got %g)", o->condition);
+  if (!(o->epsi >= 0.f) || !std::isfinite(o->epsi))
+    return fail(MISONET_EINVAL, "beamformer epsi must be finite and >= 0 (got %g)", (double)o->epsi);
+  if (o->ref_ch < 0 || o->ref_ch >= M)
+    return fail(MISONET_EINVAL, "beamformer ref_ch %d outside [0, %d)", o->ref_ch, M);
+  return MISONET_OK;
+}
+
+static void bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a) {
+  a.epsi = o.epsi; a.kind = o.kind; a.noise_mix = o.noise; a.trace_norm = o.trace_normalize != 0; a.ban = o.ban != 0;
+  a.bf_ref = o.ref_ch; a.condition = o.condition;
+}
+
+long long misonet_beamform_workspace_bytes(int B, int F, int M, const misonet_bf_opts* opts) {
+  if (B <= 0 || F <= 0 || M < 2 || M > 8 || bf_opts_check(opts, M)) return -1;
+  return bf_ws_bytes(B, 1, F, M, opts->kind);
+}
+
+int misonet_beamform(const void* src, const void* mix, int B, int F, int M, int T, const misonet_bf_opts* opts, void* out,
+                     void* ws, long long ws_bytes, misonet_stream stream) {
+  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F, T must be positive");
+  { int r = bf_opts_check(opts, M); if (r) return r; }
+  if (ws_bytes < bf_ws_bytes(B, 1, F, M, opts->kind)) return fail(MISONET_ENOMEM, "workspace too small");
+  MvdrArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  const float* x = reinterpret_cast<const float*>(src);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.src = {x, x + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
+  a.S = 1; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
+  bf_opts_apply(*opts, a);
+  float* o = reinterpret_cast<float*>(out);
+  COut co = {o, o + 1, 2LL * T * F, 0, 2LL * F, 2};      // [B,T,F] complex64 (tester.py:1134)
+  HIPCHK(launch_mvdr(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_beamform_debug(const void* ws, int B, int F, int M, const misonet_bf_opts* opts, void* w, double* lam,
+                           misonet_stream stream) {
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  if (B <= 0 || F <= 0 || M < 2 || M > 8) return fail(MISONET_EINVAL, "B, F must be positive and M in [2, 8]");
+  { int r = bf_opts_check(opts, M); if (r) return r; }
+  if (lam && opts->kind != BF_GEV) return fail(MISONET_EINVAL, "lambda_max exists for kind gev only");
+  HIPCHK(launch_bf_debug(ws, B, 1, F, M, reinterpret_cast<double*>(w), lam, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 
@@ -1378,6 +1441,7 @@ struct misonet_pipeline {
   misonet_net* n3;
   int M, S, ref_ch;
   float epsi;
+  misonet_bf_opts bf;      // the beamformer of step 5 (misonet_pipeline_set_beamformer); create: the defaults with epsi
 };
 
 struct PipeLayout {
@@ -1399,7 +1463,7 @@ static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
   // PIT distances [B*M + B][S][S] followed by their per-bin partials [B*M + B][F][S][S] (mvdr.hip pit_dist_k)
   P.off_dist = o;  o += align_up((long long)(B * p->M + B) * p->S * p->S * (F + 1) * 8, 256);
   P.off_sel = o;   o += align_up((long long)(B * p->M * p->S * 2 + B * p->S) * 4, 256);
-  P.off_mvdr = o;  o += align_up(mvdr_ws_bytes(B, p->S, F, p->M), 256);
+  P.off_mvdr = o;  o += align_up(bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
   P.clean_bstride = (long long)2 * p->S * F * Tp;
   P.off_clean = o; o += align_up(P.clean_bstride * B * 4, 256);
   P.L3.in_ext_bstride = p->n3 ? (long long)p->n3->cfg.in_ch * F * Tp : 0;
@@ -1426,7 +1490,16 @@ int misonet_pipeline_create(misonet_net* n1, misonet_net* n3, int num_mic, int n
     return fail(MISONET_EINVAL, "MISO_3 geometry must be in_ch = 2*(num_mic+2), out_ch = 2");
   { int rf = frontend_init(); if (rf) return rf; }
   misonet_pipeline* p = new misonet_pipeline{n1, n3, num_mic, num_spk, ref_ch, epsi};
+  misonet_bf_opts_default(&p->bf);
+  p->bf.epsi = epsi;
   *out = p;
+  return MISONET_OK;
+}
+
+int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* opts) {
+  if (!p) return fail(MISONET_EINVAL, "null argument");
+  { int r = bf_opts_check(opts, p->M); if (r) return r; }
+  p->bf = *opts;
   return MISONET_OK;
 }
 int misonet_pipeline_destroy(misonet_pipeline* p) { delete p; return MISONET_OK; }
@@ -1513,7 +1586,8 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
       a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};   // shift-0 sample = un-rolled mixture
       a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;
       a.src = {nullptr, nullptr, 0, 0, 0, 1};
-      a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp; a.epsi = p->epsi;
+      a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
+      bf_opts_apply(p->bf, a);
       COut co = {in3 + (long long)M * plane, in3 + (long long)(2 * M + 2) * plane, (long long)S * in3_bs, in3_bs, 1, Tp};
       ProfScope ps(s, PK_MVDR);
       HIPCHK(launch_mvdr(a, co, base + P.off_mvdr, s));

@@ -14,6 +14,7 @@ path; ``gather_outputs`` is the optional all_gather of the results (RCCL on GPUs
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import weakref
 from typing import Callable, Dict, List, Optional, Tuple
 
@@ -22,6 +23,7 @@ import torch
 
 from . import _lib
 from . import stft as S
+from .beamform import Beamformer
 from .model import MISO_1, MISO_3
 from .weights import N_FREQ
 
@@ -204,11 +206,14 @@ class _Overlapped:
 
 
 class Enhancer:
-    """Fused on-device MISO1 -> (alignment) -> MVDR -> MISO3 for batches of 4 s chunks."""
+    """Fused on-device MISO1 -> (alignment) -> beamformer (MVDR unless another is set) -> MISO3 for batches of 4 s chunks."""
 
-    def __init__(self, model_sep: MISO_1, model: Optional[MISO_3], num_spks: int = 2, ref_ch: int = 0, epsi: float = 1e-6):
+    def __init__(self, model_sep: MISO_1, model: Optional[MISO_3], num_spks: int = 2, ref_ch: int = 0, epsi: float = 1e-6,
+                 beamformer=None):
         """``model = None``: a separation-only Enhancer (:meth:`separate`, :meth:`beamform_utterance`,
-        :meth:`beamform_chunks` -- what the reference's ``Tester_Beamforming`` needs: it has no MISO_3, tester.py:259-262)."""
+        :meth:`beamform_chunks` -- what the reference's ``Tester_Beamforming`` needs: it has no MISO_3, tester.py:259-262).
+        ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields; it
+        reaches the fused pass and every ``beamform_*`` method (:meth:`set_beamformer`)."""
         if not isinstance(model_sep, MISO_1) or not (model is None or isinstance(model, MISO_3)):
             raise TypeError("Enhancer needs misonet_amd.MISO_1 and misonet_amd.MISO_3 (or None) instances")
         self.model_sep, self.model = model_sep, model
@@ -228,6 +233,33 @@ class Enhancer:
                                                       self.num_spks, self.ref_ch, float(epsi), C.byref(self._pipe)))
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._captured = weakref.WeakSet()     # live CapturedPass objects: check(B, T) must not silently look elsewhere
+        self._epsi = float(epsi)
+        self.beamformer = Beamformer()
+        if beamformer is not None:
+            self.set_beamformer(beamformer)
+
+    def set_beamformer(self, beamformer=None):
+        """Select the beamformer of the fused pass (:meth:`enhance` and everything built on it) and of
+        :meth:`beamform_chunks` / :meth:`beamform_utterance`: None (back to the reference's MVDR), a Beamformer or a dict of
+        its fields.  ``epsi`` left unset keeps each call's own default (the constructor's ``epsi`` in the fused pass).  Legal
+        between passes; ValueError for a bad field.  A captured pass keeps the options it was captured with, so the change is
+        refused while one is alive."""
+        bf = Beamformer.of(beamformer).validate(self.num_ch)
+        if bf == self.beamformer:
+            return
+        if len(self._captured):
+            raise RuntimeError("set_beamformer: a captured pass of this Enhancer is alive and would go on replaying the old "
+                               "beamformer; drop it and capture again after the change")
+        opts = bf.c_opts(self._epsi)
+        _lib.check(_lib.lib().misonet_pipeline_set_beamformer(self._pipe, C.byref(opts)))
+        self.beamformer = bf
+        self._ws.clear()                       # the workspace size depends on the kind
+
+    def _bf(self, beamformer, epsi):
+        """the options of one beamform_* call: its own ``beamformer`` (None: the Enhancer's) and ``epsi`` (None: the
+        options', else the reference's 1e-6)"""
+        bf = self.beamformer if beamformer is None else Beamformer.of(beamformer).validate(self.num_ch)
+        return bf if epsi is None else dataclasses.replace(bf, epsi=float(epsi))
 
     def __del__(self):
         try:
@@ -264,7 +296,7 @@ class Enhancer:
         # the layout depends on the arithmetic modes and on whether buffers may share memory
         m3 = self.model
         return (B, T, self.model_sep.precision, m3.precision if m3 is not None else None, self.model_sep._keep,
-                m3._keep if m3 is not None else None)
+                m3._keep if m3 is not None else None, self.beamformer.kind)
 
     def workspace(self, B, T):
         key = self._ws_key(B, T)
@@ -634,14 +666,15 @@ class Enhancer:
         return m1
 
     def beamform_utterance(self, obs_splits: List[torch.Tensor], clean_splits: List[torch.Tensor], gap: int,
-                           epsi: float = 1e-6, max_batch: int = 16, to_host: bool = True):
+                           epsi: Optional[float] = None, max_batch: int = 16, to_host: bool = True, beamformer=None):
         """Utterance-wise MVDR of the reference's Tester_Beamforming (tester.py:340-449, ``utterance_flag``) for ONE
         recording: its splits are separated as ONE batch (:meth:`separate`; the reference runs them one by one), all
         (speaker, mic) estimates and the observation go back to the time domain with one batched iSTFT, the splits are
         stitched (last one trimmed by ``gap``), the whole recording is re-analysed by the HIP STFT front-end and ONE MVDR per
         speaker is solved over all its frames (spatial covariances accumulated over the full utterance instead of per 4 s
         chunk).  obs_splits: list of complex [M,T,F]; clean_splits: list of complex [S,T,F].  Returns int16 [S, n] (an ndarray;
-        ``to_host=False``: the device tensor, nothing synchronises)."""
+        ``to_host=False``: the device tensor, nothing synchronises).  ``beamformer``: None = the Enhancer's
+        (:meth:`set_beamformer`); ``epsi``: None = the options' own, 1e-6 where they leave it unset."""
         K = len(obs_splits)
         if K < 1 or len(clean_splits) != K:
             raise ValueError("obs_splits / clean_splits must be non-empty lists of equal length")
@@ -649,14 +682,16 @@ class Enhancer:
         cl = torch.stack([torch.as_tensor(c) for c in clean_splits]).to(self.device, non_blocking=True)  # [K,S,T,F]
         est = torch.cat([self.separate(obs[lo:lo + max_batch], cl[lo:lo + max_batch])          # [K,S,M,T,F], in groups of
                          for lo in range(0, K, max_batch)])                                   # <= max_batch splits (workspace)
-        pcm = self._utterance_tail(est, obs, gap, epsi)
+        pcm = self._utterance_tail(est, obs, gap, epsi, beamformer)
         return pcm.cpu().numpy() if to_host else pcm
 
-    def _utterance_tail(self, est: torch.Tensor, obs: torch.Tensor, gap: int, epsi: float = 1e-6) -> torch.Tensor:
+    def _utterance_tail(self, est: torch.Tensor, obs: torch.Tensor, gap: int, epsi: Optional[float] = None,
+                        beamformer=None) -> torch.Tensor:
         """The per-recording tail of :meth:`beamform_utterance` (and of the coalesced utterance-wise Tester_Beamforming):
         est complex [K,S,M,T,F] = the separated splits, obs complex [K,M,T,F] (device) -> int16 [S, n] (device): one
         batched iSTFT, the splits stitched (last one trimmed by ``gap``), one long STFT, one MVDR per speaker, int16."""
         from .beamform import Apply_Beamforming
+        bf_opts = self._bf(beamformer, epsi)
         K = est.shape[0]
         e = S.istft(est)                                                                      # [K,S,M,chunk]
         o = S.istft(obs)                                                                      # [K,M,chunk]
@@ -670,20 +705,21 @@ class Enhancer:
         sig = torch.nn.functional.pad(sig, (0, pad)).permute(0, 2, 1).contiguous()      # [1+S, Lp, M]
         spec = S.stft_hip(sig)                                                # [1+S, M, Tt, F]
         mix_bf = spec[0].permute(2, 0, 1)[None]                               # [1,F,M,Tt]
-        bf = torch.stack([Apply_Beamforming(spec[1 + s].permute(2, 0, 1)[None], mix_bf, epsi)[0]
+        bf = torch.stack([Apply_Beamforming(spec[1 + s].permute(2, 0, 1)[None], mix_bf, beamformer=bf_opts)[0]
                           for s in range(self.num_spks)])                     # [S,Tt,F]
         return S.istft_int16(bf)
 
-    def beamform_chunks(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, epsi: float = 1e-6,
-                        check_nan: bool = True) -> torch.Tensor:
+    def beamform_chunks(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, epsi: Optional[float] = None,
+                        check_nan: bool = True, beamformer=None) -> torch.Tensor:
         """Chunk-wise MVDR (BASELINE configs[2]: MISO1 -> MVDR; the ``utterance_flag = False`` branch of the reference's
         Tester_Beamforming, tester.py:452-535): separation of a batch of 4 s chunks, then one MVDR per (chunk, speaker) over
         the chunk's own frames.  mix complex [B,M,T,F], clean complex [B,S,T,F] or None -> beamformer outputs complex64
         [B,S,T,F].  (With MISO_3 attached, ``enhance(..., want_bf=True)`` returns the same tensor from the fused pass.)"""
         from .beamform import Apply_Beamforming
+        bf_opts = self._bf(beamformer, epsi)
         est = self.separate(mix, clean, check_nan=check_nan)                                  # [B,S,M,T,F]
         mix_bf = self._check_c64(mix, "mix").permute(0, 3, 1, 2)                              # [B,F,M,T]
-        return torch.stack([Apply_Beamforming(est[:, s].permute(0, 3, 1, 2), mix_bf, epsi)
+        return torch.stack([Apply_Beamforming(est[:, s].permute(0, 3, 1, 2), mix_bf, beamformer=bf_opts)
                             for s in range(self.num_spks)], dim=1)                            # [B,S,T,F]
 
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,

@@ -47,6 +47,8 @@ class Tester_Enhance(object):
             model.cuda(device)
         self._enh = Enhancer(model_sep.eval(), model.eval(), num_spks=self.num_spks, ref_ch=self.ref_ch)
         self.score = False           # True: inference() also writes <saveDir>/scores.json (Enhancer.inference, score=True)
+        self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts.
+        #                              MISO_3 was trained on the reference's MVDR output: another beamformer is an experiment here
 
     def test(self):
         """tester.py:827-844: development set into ``cv_dev93``, test set into ``test_eval92``."""
@@ -59,6 +61,7 @@ class Tester_Enhance(object):
 
     def inference(self, data_loader, saveDir):
         """tester.py:846-975; returns {wav_name: int16 [num_spks, n_samples]} besides writing the files."""
+        self._enh.set_beamformer(self.beamformer)
         return self._enh.inference(data_loader, saveDir, fs=self.fs, score=bool(self.score))
 
 
@@ -99,6 +102,8 @@ class Tester_Beamforming(object):
             model.cuda(device)
         self._enh = Enhancer(model.eval(), None, num_spks=self.num_spks, ref_ch=self.ref_ch)
         self.score = False           # True: inference() also writes <saveDir>/scores.json for the beamformer output
+        self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts:
+        #                              the beamformed wav is this class's product, so this is its product setting
 
     def test(self):
         """tester.py:289-325: the training set into ``train_si284`` when ``tr_inference_flag``, else the development set into
@@ -127,6 +132,7 @@ class Tester_Beamforming(object):
         beamformer output that goes into the files (:func:`misonet_amd.score.score_waves`; the reference waves are the
         device iSTFT of the clean spectrograms at ``ref_ch``, stitched as the output is; no spectral criterion: the
         beamformer has none)."""
+        self._enh.set_beamformer(self.beamformer)
         if self.score:
             from . import score as SC
             refs, scores = {}, {}
