@@ -174,6 +174,40 @@ int misonet_beamform(const void* src_dev, const void* mix_dev, int B, int F, int
 int misonet_beamform_debug(const void* ws_dev, int B, int F, int M, const misonet_bf_opts* opts, void* w_c128_dev,
                            double* lambda_dev, misonet_stream stream);
 
+/* ---- WPE dereverberation (ABI 520) ---------------------------------------------------------------------------------
+ * Weighted prediction error (Nakatani et al. 2010; Yoshioka & Nakatani 2012), per (item b, bin f), independent of every other;
+ * Y = mix[b, :, :, f] is [M, T]:
+ *   Z[(k M + m), t] = Y[m, t - delay - k]   (k = 0 .. taps - 1; zero for t - delay - k < 0), order N = M taps
+ *   X <- Y; repeat `iterations` times:
+ *     p[t] = mean_m |X[m, t]|^2                  (first iteration: power_dev[b, t, f] when given -- "DNN-WPE")
+ *     w[t] = 1 / max(p[t], power_floor max_t p[t])
+ *     R = sum_t w[t] Z[:, t] Z[:, t]^H,  P = sum_t w[t] Z[:, t] Y[:, t]^H,  R += diag_load tr(R) / N I
+ *     G = R^-1 P  (Cholesky R = L L^H, two triangular solves),  X = Y - G^H Z
+ * With the defaults this is nara_wpe's wpe_v8 with psd_context = 0.  Everything after the complex64 loads is float64 (the
+ * correlations on the float64 matrix pipe); X is rounded to complex64 once, on the final store.  Every sum runs in a fixed
+ * order, without atomics: the bits of an item depend neither on B nor on its position in the batch.
+ * A bin in which a Cholesky pivot is not finite or not > 0 (the all-zero bin) is passed through unchanged -- X = Y, the
+ * remaining iterations skipped, fail[b, f] = 1, G = 0 -- and nothing is clamped.
+ * mix_dev and out_dev are complex64 [B, M, T, F], the output layout of misonet_stft and the input layout of misonet_istft;
+ * they must not be the same buffer.  Any T >= 2 (a whole recording is one call), 1 <= M <= 8, M taps <= 80, delay >= 1,
+ * 1 <= iterations <= 10, diag_load and power_floor finite and >= 0: anything else is refused on the host with MISONET_EINVAL
+ * and a message (the size function: -1), before any launch; a short workspace is MISONET_ENOMEM. */
+typedef struct {
+  int taps;
+  int delay;
+  int iterations;
+  double diag_load;
+  double power_floor;
+} misonet_wpe_opts;
+int misonet_wpe_opts_default(misonet_wpe_opts* opts);    /* 10, 3, 3, 0.0, 1e-10 */
+long long misonet_wpe_workspace_bytes(int B, int M, int T, int F, const misonet_wpe_opts* opts);
+int misonet_wpe(const void* mix_dev, const float* power_dev, int B, int M, int T, int F, const misonet_wpe_opts* opts,
+                void* out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_wpe, copy the filter G of the last iteration, complex128 [B, F, M taps, M], and fail int32 [B, F]
+ * to device buffers (either may be NULL) */
+int misonet_wpe_debug(const void* ws_dev, int B, int M, int F, const misonet_wpe_opts* opts, void* g_c128_dev, int* fail_dev,
+                      misonet_stream stream);
+
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
  * dist_dev (required: it is the call's only scratch, so the call allocates nothing and stays asynchronous): float64,

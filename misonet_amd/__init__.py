@@ -4,12 +4,14 @@ Host-side mirror of the reference call surface:
   MISO_1, MISO_3            (reference model.py:8-111, 282-395)
   Apply_Beamforming         (reference tester.py:1071-1136)
   Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN)
+  dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
 library raises -- there is no CPU fallback.
 """
-__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Enhancer", "weights"]
+__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Dereverb", "dereverb", "dereverb_wav", "Enhancer",
+           "weights"]
 
 
 def __getattr__(name):
@@ -22,6 +24,9 @@ def __getattr__(name):
     if name == "Beamformer":
         from .beamform import Beamformer
         return Beamformer
+    if name in ("Dereverb", "dereverb", "dereverb_wav"):
+        import importlib
+        return getattr(importlib.import_module(".dereverb", __name__), name)
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

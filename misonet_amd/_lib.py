@@ -32,6 +32,12 @@ class BfOpts(C.Structure):
                 ("epsi", C.c_float), ("ban", C.c_int), ("ref_ch", C.c_int)]
 
 
+class WpeOpts(C.Structure):
+    """misonet_wpe_opts (ABI 520)"""
+    _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("iterations", C.c_int), ("diag_load", C.c_double),
+                ("power_floor", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -67,6 +73,12 @@ SIGNATURES = {
     "misonet_beamform_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(BfOpts), C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "misonet_pipeline_set_beamformer": (C.c_int, [C.c_void_p, C.POINTER(BfOpts)]),
+    "misonet_wpe_opts_default": (C.c_int, [C.POINTER(WpeOpts)]),
+    "misonet_wpe_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WpeOpts)]),
+    "misonet_wpe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WpeOpts), C.c_void_p,
+                              C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_wpe_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpeOpts), C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

@@ -270,4 +270,12 @@ hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long
 hipError_t launch_stoi_measure(const double* x10, const int* len10 /*[B] or nullptr*/, int B, int NS, int R, long long n10,
                                const double* table, double* out, int* meta, double* scratch, hipStream_t s);
 
+// WPE dereverberation (wpe.hip).  mix / out complex64 [B][M][T][F], power float32 [B][T][F] or nullptr; the
+// workspace starts with fail int [B F] and G complex128 [B F][M taps][M], which launch_wpe_debug copies out.
+// 1 <= M <= 8, M taps <= 80, T >= 2.
+long long wpe_ws_bytes(int B, int M, int T, int F, int taps);
+hipError_t launch_wpe(const void* mix, const float* power, int B, int M, int T, int F, int taps, int delay, int iters,
+                      double diag_load, double power_floor, void* out, void* ws, hipStream_t s);
+hipError_t launch_wpe_debug(const void* ws, int B, int M, int F, int taps, void* g, int* fail, hipStream_t s);
+
 }  // namespace mn

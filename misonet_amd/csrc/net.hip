@@ -657,7 +657,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 510; }   // 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 520; }   // 520: misonet_wpe_opts, misonet_wpe, misonet_wpe_debug (WPE dereverberation); 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -1075,6 +1075,54 @@ int misonet_beamform_debug(const void* ws, int B, int F, int M, const misonet_bf
   { int r = bf_opts_check(opts, M); if (r) return r; }
   if (lam && opts->kind != BF_GEV) return fail(MISONET_EINVAL, "lambda_max exists for kind gev only");
   HIPCHK(launch_bf_debug(ws, B, 1, F, M, reinterpret_cast<double*>(w), lam, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- WPE dereverberation (ABI 520) ---------------------------------------------------------------------------------
+int misonet_wpe_opts_default(misonet_wpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->taps = 10; o->delay = 3; o->iterations = 3; o->diag_load = 0.0; o->power_floor = 1e-10;
+  return MISONET_OK;
+}
+
+// host-side check of every field and of the geometry they are used with
+static int wpe_check(int B, int M, int T, int F, const misonet_wpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null dereverberation options");
+  if (B < 1 || F < 1) return fail(MISONET_EINVAL, "B and F must be positive (got %d, %d)", B, F);
+  if (T < 2) return fail(MISONET_EINVAL, "T must be >= 2 (got %d)", T);
+  if (M < 1 || M > 8) return fail(MISONET_EINVAL, "M must be in [1, 8] (got %d)", M);
+  if (o->taps < 1 || (long long)M * o->taps > 80)
+    return fail(MISONET_EINVAL, "taps must be >= 1 and M * taps <= 80 (got taps %d, M %d)", o->taps, M);
+  if (o->delay < 1) return fail(MISONET_EINVAL, "delay must be >= 1 (got %d)", o->delay);
+  if (o->iterations < 1 || o->iterations > 10) return fail(MISONET_EINVAL, "iterations must be in [1, 10] (got %d)", o->iterations);
+  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
+    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!(o->power_floor >= 0.0) || !std::isfinite(o->power_floor))
+    return fail(MISONET_EINVAL, "power_floor must be finite and >= 0 (got %g)", o->power_floor);
+  return MISONET_OK;
+}
+
+long long misonet_wpe_workspace_bytes(int B, int M, int T, int F, const misonet_wpe_opts* opts) {
+  if (wpe_check(B, M, T, F, opts)) return -1;
+  return wpe_ws_bytes(B, M, T, F, opts->taps);
+}
+
+int misonet_wpe(const void* mix, const float* power, int B, int M, int T, int F, const misonet_wpe_opts* opts, void* out,
+                void* ws, long long ws_bytes, misonet_stream stream) {
+  if (!mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (out == mix) return fail(MISONET_EINVAL, "out_dev must not be mix_dev");
+  { int r = wpe_check(B, M, T, F, opts); if (r) return r; }
+  if (ws_bytes < wpe_ws_bytes(B, M, T, F, opts->taps)) return fail(MISONET_ENOMEM, "workspace too small");
+  HIPCHK(launch_wpe(mix, power, B, M, T, F, opts->taps, opts->delay, opts->iterations, opts->diag_load, opts->power_floor, out,
+                    ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_wpe_debug(const void* ws, int B, int M, int F, const misonet_wpe_opts* opts, void* g, int* fail_dev,
+                      misonet_stream stream) {
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  { int r = wpe_check(B, M, 2, F, opts); if (r) return r; }
+  HIPCHK(launch_wpe_debug(ws, B, M, F, opts->taps, g, fail_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -1,0 +1,167 @@
+"""WPE dereverberation on the device (csrc/wpe.hip, C ABI ``misonet_wpe`` in include/misonet.h).
+
+``dereverb(mix)``        complex [B, M, T, F] -> complex64 of the same shape: multichannel linear prediction per bin
+                         (Nakatani et al. 2010; with the defaults nara_wpe's ``wpe_v8``), float64 on the matrix cores
+``dereverb_wav(wav)``    float32 [L, M] -> float32 [L, M]: STFT of the whole recording -> WPE -> iSTFT, on the device
+``Dereverb``             the options as one plain-data object, used by every layer (``Enhancer(dereverb=...)``)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .beamform import _dev_c64
+
+HOP = 64
+
+
+@dataclasses.dataclass(frozen=True)
+class Dereverb:
+    """One plain-data description of the dereverberation (``misonet_wpe_opts`` of include/misonet.h).
+
+    taps         prediction filter length per microphone (M taps <= 80)
+    delay        prediction delay in frames (>= 1): the direct sound and the early reflections are left alone
+    iterations   alternations of power estimate and filter (1 .. 10)
+    diag_load    R <- R + diag_load tr(R) / (M taps) I
+    power_floor  w[t] = 1 / max(p[t], power_floor max_t p[t])
+    """
+    taps: int = 10
+    delay: int = 3
+    iterations: int = 3
+    diag_load: float = 0.0
+    power_floor: float = 1e-10
+
+    @classmethod
+    def of(cls, spec) -> "Dereverb":
+        """None or True (the defaults), a Dereverb, or a dict of the fields above"""
+        if spec is None or spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown dereverb field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("dereverb must be None, True, a Dereverb or a dict of its fields")
+
+    def validate(self, num_mic: Optional[int] = None) -> "Dereverb":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        for name in ("taps", "delay", "iterations"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"dereverb {name} must be an integer, got {v!r}")
+        if num_mic is not None and not 1 <= num_mic <= 8:
+            raise ValueError(f"dereverb takes 1 .. 8 microphones, got {num_mic}")
+        if self.taps < 1 or self.taps * (num_mic if num_mic is not None else 1) > 80:
+            raise ValueError(f"dereverb taps must be >= 1 with M * taps <= 80, got taps {self.taps}"
+                             + (f" at M = {num_mic}" if num_mic is not None else ""))
+        if self.delay < 1:
+            raise ValueError(f"dereverb delay must be >= 1, got {self.delay}")
+        if not 1 <= self.iterations <= 10:
+            raise ValueError(f"dereverb iterations must be in [1, 10], got {self.iterations}")
+        for name in ("diag_load", "power_floor"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"dereverb {name} must be finite and >= 0, got {v!r}")
+        return self
+
+    def c_opts(self) -> "_lib.WpeOpts":
+        return _lib.WpeOpts(int(self.taps), int(self.delay), int(self.iterations), float(self.diag_load),
+                            float(self.power_floor))
+
+
+def _wpe_device(mix: torch.Tensor, power: Optional[torch.Tensor], opts: "_lib.WpeOpts", return_debug: bool):
+    """mix complex64 [B, M, T, F] contiguous on the device (power float32 [B, T, F] or None) -> out (and the debug dict)"""
+    B, M, T, F = mix.shape
+    L = _lib.lib()
+    nws = L.misonet_wpe_workspace_bytes(B, M, T, F, C.byref(opts))
+    if nws < 0:
+        _lib.check(_lib.EINVAL)
+    ws = torch.empty(int(nws), dtype=torch.uint8, device=mix.device)
+    out = torch.empty_like(mix)
+    dbg = None
+    with torch.cuda.device(mix.device):
+        st = _lib.stream_ptr(mix.device)
+        _lib.check(L.misonet_wpe(mix.data_ptr(), power.data_ptr() if power is not None else None, B, M, T, F, C.byref(opts),
+                                 out.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        if return_debug:
+            g = torch.empty((B, F, M * opts.taps, M), dtype=torch.complex128, device=mix.device)
+            bad = torch.empty((B, F), dtype=torch.int32, device=mix.device)
+            _lib.check(L.misonet_wpe_debug(ws.data_ptr(), B, M, F, C.byref(opts), g.data_ptr(), bad.data_ptr(), st))
+            dbg = dict(G=g, fail=bad)
+    return out, dbg
+
+
+def dereverb(mix, power=None, *, taps=10, delay=3, iterations=3, diag_load=0.0, power_floor=1e-10, return_debug=False,
+             device=None):
+    """WPE dereverberation of a batch of spectrograms.
+
+    mix: complex [B, M, T, F] (np.ndarray or torch tensor): the layout of ``stft_hip`` and of the networks' input.  Returns
+    complex64 of the same shape: on the CPU for ndarray input, on the device for device input.  ``power`` float [B, T, F]
+    replaces the power estimate of the FIRST iteration (DNN-WPE: e.g. ``sum_s |MISO1 estimate|^2`` averaged over the
+    microphones, with ``iterations=1``).  A bin whose correlation matrix cannot be factored (an all-zero bin) comes back
+    unchanged.  ``return_debug`` adds, on the device, ``G`` complex128 [B, F, M taps, M] (the filter of the last
+    iteration) and ``fail`` int32 [B, F]."""
+    shape = np.shape(mix)
+    opts = Dereverb(taps, delay, iterations, diag_load, power_floor).validate(shape[1] if len(shape) == 4 else None)
+    if len(shape) != 4:
+        raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F]")
+    if shape[2] < 2 or shape[0] < 1 or shape[3] < 1:
+        raise ValueError(f"mix {tuple(shape)}: B and F must be positive and T >= 2")
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    x, np_in = _dev_c64(mix, device)
+    pw = None
+    if power is not None:
+        pw = torch.as_tensor(power)
+        if tuple(pw.shape) != (shape[0], shape[2], shape[3]) or pw.is_complex():
+            raise ValueError(f"power {tuple(pw.shape)} must be real [B, T, F] = {(shape[0], shape[2], shape[3])}")
+        pw = pw.to(x.device).to(torch.float32).contiguous()
+    out, dbg = _wpe_device(x, pw, opts.c_opts(), return_debug)
+    if np_in:
+        out = out.cpu()
+    return (out, dbg) if return_debug else out
+
+
+def dereverb_wav(wav, fs=16000, *, device=None, **opts):
+    """Recording-wise dereverberation: wav float32 [L, M] (ndarray or tensor) -> float32 [L, M] of the same kind.
+
+    The recording is zero-padded to whole hops, transformed in one piece (``misonet_stft``), dereverberated
+    (``misonet_wpe``: the filters are estimated over the whole recording), transformed back (``misonet_istft``, float32)
+    and trimmed to L: all on the device.  ``fs`` is accepted for symmetry with the other recording calls; the frame
+    geometry is the networks' (256 / 64 samples).  ``opts``: the fields of :class:`Dereverb`."""
+    from . import stft as S
+    d = Dereverb(**opts)
+    np_in = not isinstance(wav, torch.Tensor)
+    w = torch.as_tensor(wav)
+    if w.dim() != 2 or w.shape[0] <= w.shape[1]:
+        raise ValueError("wav must be [n_samples, n_mics] with n_samples > n_mics")
+    d.validate(int(w.shape[1]))
+    if device is None:
+        device = w.device if w.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    L, M = w.shape
+    Lp = max(2 * HOP, -(-L // HOP) * HOP)
+    padded = torch.zeros((1, Lp, M), dtype=torch.float32, device=device)
+    padded[0, :L] = w.to(device=device, dtype=torch.float32)
+    spec = S.stft_hip(padded)                                          # [1, M, Lp / 64 + 1, 129]
+    out, _ = _wpe_device(spec, None, d.c_opts(), False)
+    y = S._istft_hip(out, False)[0, :, :L].transpose(0, 1).contiguous()    # [L, M]
+    return y.cpu().numpy() if np_in else y
+
+
+# ``misonet_amd.dereverb`` names both this module and the function above: once the module is imported the package attribute is
+# the module, so the module itself is made callable -- ``misonet_amd.dereverb(mix)`` works either way.
+class _CallableModule(type(np)):
+    def __call__(self, *args, **kwargs):
+        return dereverb(*args, **kwargs)
+
+
+import sys as _sys
+_sys.modules[__name__].__class__ = _CallableModule

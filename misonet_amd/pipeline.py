@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from . import stft as S
 from .beamform import Beamformer
+from .dereverb import Dereverb, dereverb_wav
 from .model import MISO_1, MISO_3
 from .weights import N_FREQ
 
@@ -209,11 +210,13 @@ class Enhancer:
     """Fused on-device MISO1 -> (alignment) -> beamformer (MVDR unless another is set) -> MISO3 for batches of 4 s chunks."""
 
     def __init__(self, model_sep: MISO_1, model: Optional[MISO_3], num_spks: int = 2, ref_ch: int = 0, epsi: float = 1e-6,
-                 beamformer=None):
+                 beamformer=None, dereverb=None):
         """``model = None``: a separation-only Enhancer (:meth:`separate`, :meth:`beamform_utterance`,
         :meth:`beamform_chunks` -- what the reference's ``Tester_Beamforming`` needs: it has no MISO_3, tester.py:259-262).
         ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields; it
-        reaches the fused pass and every ``beamform_*`` method (:meth:`set_beamformer`)."""
+        reaches the fused pass and every ``beamform_*`` method (:meth:`set_beamformer`).
+        ``dereverb``: None (no dereverberation), True, a :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields:
+        the recording paths dereverberate the observation first (:meth:`set_dereverb`)."""
         if not isinstance(model_sep, MISO_1) or not (model is None or isinstance(model, MISO_3)):
             raise TypeError("Enhancer needs misonet_amd.MISO_1 and misonet_amd.MISO_3 (or None) instances")
         self.model_sep, self.model = model_sep, model
@@ -237,6 +240,26 @@ class Enhancer:
         self.beamformer = Beamformer()
         if beamformer is not None:
             self.set_beamformer(beamformer)
+        self.dereverb = None
+        if dereverb is not None:
+            self.set_dereverb(dereverb)
+
+    def set_dereverb(self, dereverb=None):
+        """WPE dereverberation in front of the recording paths (:meth:`enhance_recording`, :meth:`enhance_recordings`,
+        :meth:`enhance_continuous`): None (off, the default: the existing path, no extra launch), True (the defaults), a
+        :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields.  When set, the selected microphones of the whole
+        recording go through :func:`misonet_amd.dereverb.dereverb_wav` on the device before they are cut into chunks or
+        windows; everything downstream is untouched, and with ``score=True`` the mixture baseline (SI-SDRi, BSS-eval, STOI)
+        stays the ORIGINAL observation at ``ref_ch``.  :meth:`enhance`, the ``beamform_*`` methods and the loader-driven
+        :meth:`inference` receive ready spectrograms and are not changed: put ``dereverb(mix)`` in front of them.  Legal
+        between passes; ValueError for a bad field."""
+        self.dereverb = None if dereverb is None or dereverb is False else Dereverb.of(dereverb).validate(self.num_ch)
+
+    def _observe(self, obs):
+        """the selected microphones of one recording, float32 [L, M], as the networks will see them"""
+        if self.dereverb is None:
+            return obs
+        return dereverb_wav(np.ascontiguousarray(obs), device=self.device, **dataclasses.asdict(self.dereverb))
 
     def set_beamformer(self, beamformer=None):
         """Select the beamformer of the fused pass (:meth:`enhance` and everything built on it) and of
@@ -458,7 +481,8 @@ class Enhancer:
         """HOST-resident batches in, int16 waves out, copies overlapped with compute.
 
         ``score=True``: ``batches`` yields ``(wav, clean_wav, n_valid)`` (n_valid: B ints, the samples of each chunk that
-        count; None = all) and the generator yields ``(pcm, (stats float64 [B, S, S, 5], stats_mix float64 [B, S, 5]))``: the
+        count; None = all; a fourth element, float32 [B, n_samples, 1], replaces the observation at ``ref_ch`` as the
+        mixture of the baseline) and the generator yields ``(pcm, (stats float64 [B, S, S, 5], stats_mix float64 [B, S, 5]))``: the
         sums of :func:`score.wave_stats` of the int16 result (and of the observation at ``ref_ch``) against ``clean_wav``,
         launched on the compute stream right behind the iSTFT; the block travels with the result's D2H.
 
@@ -496,11 +520,12 @@ class Enhancer:
                 while len(pending) >= depth:                  # slot i % depth still belongs to batch i - depth
                     yield finish(pending.popleft())
                 if score:
-                    wav_h, clean_h, nv = item
+                    wav_h, clean_h, nv, *mix_ref = item          # mix_ref: the observation the baseline is taken from
                     if clean_h is None:
                         raise ValueError("score=True needs the clean sources of every batch")
                     nv = [wav_h.shape[1]] * wav_h.shape[0] if nv is None else nv
-                    pending.append(ov.submit(i, (wav_h, clean_h, self._nv_bits(nv, torch.float32)), self._wav_pass_score))
+                    pending.append(ov.submit(i, (wav_h, clean_h, self._nv_bits(nv, torch.float32), *mix_ref),
+                                             self._wav_pass_score))
                     continue
                 wav_h, clean_h = item if isinstance(item, (tuple, list)) else (item, None)
                 pending.append(ov.submit(i, (wav_h, clean_h), self._wav_pass))
@@ -542,16 +567,18 @@ class Enhancer:
         o = a + b
         return st, sm, ex[o:o + c].reshape(N, Sp, Sp), ex[o + c:o + 2 * c].reshape(N, Sp, Sp), ex[o + 2 * c:o + 2 * c + N]
 
-    def _wav_pass_score(self, wav, clean_wav, nv):
+    def _wav_pass_score(self, wav, clean_wav, nv, mix_ref=None):
         """:meth:`_wav_pass` and, right behind its iSTFT on the same stream, the sums of the int16 waves and of the
-        observation at ref_ch against the clean waves (read in place from the time-major inputs)"""
+        observation at ref_ch against the clean waves (read in place from the time-major inputs).  ``mix_ref`` [B, n, 1]:
+        the observation at ref_ch when ``wav`` is not it (a dereverberated recording)"""
         from . import score as SC
         pcm, flag = self._wav_pass(wav, clean_wav)
         n = pcm.shape[2]
         nvd = self._nv_dev(nv)
         ref = clean_wav.transpose(1, 2)[:, :, :n]
         st = SC.wave_stats(pcm, ref, nvd)
-        sm = SC.wave_stats(wav[:, :n, self.ref_ch:self.ref_ch + 1].transpose(1, 2), ref, nvd)
+        mix = wav[:, :n, self.ref_ch:self.ref_ch + 1] if mix_ref is None else mix_ref[:, :n]
+        sm = SC.wave_stats(mix.transpose(1, 2), ref, nvd)
         return pcm, flag, torch.cat((st.reshape(-1), sm.reshape(-1)))
 
     def _spec_pass_score(self, mix, clean, nv):
@@ -771,15 +798,16 @@ class Enhancer:
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
-        pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
+        pieces, cpieces, gap, mpieces = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
         K = len(pieces)
         if score:
             nv = [pieces[0].shape[0]] * (K - 1) + [pieces[0].shape[0] - gap]
 
             def scored_batches():
                 for lo in range(0, K, max_batch):
-                    yield (torch.from_numpy(np.stack(pieces[lo:lo + max_batch])),
-                           torch.from_numpy(np.stack(cpieces[lo:lo + max_batch])), nv[lo:lo + max_batch])
+                    b = (torch.from_numpy(np.stack(pieces[lo:lo + max_batch])),
+                         torch.from_numpy(np.stack(cpieces[lo:lo + max_batch])), nv[lo:lo + max_batch])
+                    yield b if mpieces is None else b + (torch.from_numpy(np.stack(mpieces[lo:lo + max_batch])),)
 
             got = list(self.stream_wav(scored_batches(), score=True))
             pcm = np.concatenate([g[0] for g in got], axis=0)
@@ -826,13 +854,17 @@ class Enhancer:
         return mics, obs
 
     def _recording_chunks(self, wav_observe, wav_clean, num_ch_utilize, chunk_size):
-        """enhance_recording's loader side: microphone sub-sampling, the clean sources at ref_ch, 4 s chunks ->
-        (list of float32 [chunk, M], list of float32 [chunk, S] or None, gap)"""
+        """enhance_recording's loader side: microphone sub-sampling, the dereverberation when one is set, the clean sources at
+        ref_ch, 4 s chunks -> (list of float32 [chunk, M], list of float32 [chunk, S] or None, gap, None or -- with a
+        dereverberation -- the chunks of the original observation at ref_ch, float32 [chunk, 1])"""
         mics, obs = self._select_mics(wav_observe, num_ch_utilize)
         L, M_all = obs.shape
         if int(chunk_size) < 2 * S.HOP or int(chunk_size) % S.HOP:
             raise ValueError(f"chunk_size must be a multiple of the hop ({S.HOP}) and at least two hops")
         obs = obs[:, mics]
+        raw = None
+        if self.dereverb is not None:
+            raw, obs = obs[:, self.ref_ch:self.ref_ch + 1], self._observe(obs)
         cl = None
         if wav_clean is not None:
             if len(wav_clean) != self.num_spks:
@@ -846,7 +878,8 @@ class Enhancer:
             cl = np.stack(srcs, axis=1)                                    # [L, S]
         pieces, gap = S.split_chunks(obs, int(chunk_size))
         cpieces = S.split_chunks(cl, int(chunk_size))[0] if cl is not None else None
-        return pieces, cpieces, gap
+        mpieces = S.split_chunks(raw, int(chunk_size))[0] if raw is not None else None
+        return pieces, cpieces, gap, mpieces
 
     def _finish_recording(self, pcm_chunks, gap, save_path, fs):
         """the K int16 chunks [S, chunk] of one recording -> stitched int16 [S, L]; ``save_path``: the PCM-24 files"""
@@ -894,7 +927,7 @@ class Enhancer:
         nb_max = max(1, int(max_batch))
         M, Sp, T, F = self.num_ch, self.num_spks, W // S.HOP + 1, N_FREQ
         padded = np.zeros((Lp, M), dtype=np.float32)
-        padded[:L] = obs[:, mics]
+        padded[:L] = self._observe(obs[:, mics])
         dev, lib = self.device, _lib.lib()
         out = np.empty((Sp, L), dtype=np.int16)
         with torch.cuda.device(dev):
@@ -996,22 +1029,26 @@ class Enhancer:
             for i, (wav_observe, wav_clean, name) in enumerate(recordings):
                 if score and wav_clean is None:
                     raise ValueError(f"score=True needs the clean sources (wav_clean) of every recording ({name} has none)")
-                pieces, cpieces, gap = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
+                pieces, cpieces, gap, mpieces = self._recording_chunks(wav_observe, wav_clean, num_ch_utilize, chunk_size)
                 key = (pieces[0].shape, cpieces[0].shape if cpieces is not None else None)
                 if score:
                     key = key + ((1,),)                              # the chunk's valid count rides as a third input
+                    if mpieces is not None:
+                        key = key + (mpieces[0].shape,)              # and the original observation at ref_ch as a fourth
                 if bss or stoi:
                     side_refs[i] = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
-                yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name))
+                yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name, mpieces))
 
         def fill(c, rows):
-            pieces, cpieces, gap, _ = c.item.payload
+            pieces, cpieces, gap, _, mpieces = c.item.payload
             rows[0].copy_(torch.from_numpy(pieces[c.split]))
             if rows[1] is not None:
                 rows[1].copy_(torch.from_numpy(cpieces[c.split]))
             if score:
                 n = pieces[0].shape[0]
                 rows[2].copy_(self._nv_bits([n - gap if c.split == len(pieces) - 1 else n], torch.float32)[0])
+                if mpieces is not None:
+                    rows[3].copy_(torch.from_numpy(mpieces[c.split]))
 
         results = {}
         side_refs, side_wait, side_done = {}, [], []
@@ -1028,7 +1065,7 @@ class Enhancer:
         for it in self._coalesced(items(), fill, self._wav_pass_score if score else self._wav_pass, torch.float32, max_batch,
                                   depth, lambda c: str(c.item.payload[3]),
                                   extra_rows=(lambda ex, n: self._score_rows(ex, n, False)) if score else None):
-            pieces, _, gap, name = it.payload
+            pieces, _, gap, name, _ = it.payload
             path = os.path.join(save_path, str(name)) if save_path is not None else None
             if score:
                 n = pieces[0].shape[0]

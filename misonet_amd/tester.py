@@ -49,6 +49,9 @@ class Tester_Enhance(object):
         self.score = False           # True: inference() also writes <saveDir>/scores.json (Enhancer.inference, score=True)
         self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts.
         #                              MISO_3 was trained on the reference's MVDR output: another beamformer is an experiment here
+        self.dereverb = None         # None / True / a Dereverb / dict of its fields (Enhancer.set_dereverb), read when inference()
+        #                              starts: it reaches the Enhancer's RECORDING paths (self._enh.enhance_recording(s) /
+        #                              enhance_continuous); the loader's ready STFT chunks are not dereverberated
 
     def test(self):
         """tester.py:827-844: development set into ``cv_dev93``, test set into ``test_eval92``."""
@@ -62,6 +65,7 @@ class Tester_Enhance(object):
     def inference(self, data_loader, saveDir):
         """tester.py:846-975; returns {wav_name: int16 [num_spks, n_samples]} besides writing the files."""
         self._enh.set_beamformer(self.beamformer)
+        self._enh.set_dereverb(self.dereverb)
         return self._enh.inference(data_loader, saveDir, fs=self.fs, score=bool(self.score))
 
 
@@ -104,6 +108,7 @@ class Tester_Beamforming(object):
         self.score = False           # True: inference() also writes <saveDir>/scores.json for the beamformer output
         self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts:
         #                              the beamformed wav is this class's product, so this is its product setting
+        self.dereverb = None         # as Tester_Enhance.dereverb: reaches the Enhancer (set_dereverb), whose recording paths use it
 
     def test(self):
         """tester.py:289-325: the training set into ``train_si284`` when ``tr_inference_flag``, else the development set into
@@ -133,6 +138,7 @@ class Tester_Beamforming(object):
         device iSTFT of the clean spectrograms at ``ref_ch``, stitched as the output is; no spectral criterion: the
         beamformer has none)."""
         self._enh.set_beamformer(self.beamformer)
+        self._enh.set_dereverb(self.dereverb)
         if self.score:
             from . import score as SC
             refs, scores = {}, {}
