@@ -1,0 +1,230 @@
+// C ABI of the array processing (include/misonet.h): the drop-in beamformers misonet_mvdr* / misonet_bf_* / misonet_beamform*
+// (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// misonet_css_* (css.hip).  Host code only.
+#include "api_common.hpp"
+
+#include <cmath>
+
+using namespace mn;
+
+// host-side check of every field; M = the number of microphones ref_ch is counted in
+int mn::bf_opts_check(const misonet_bf_opts* o, int M) {
+  if (!o) return fail(MISONET_EINVAL, "null beamformer options");
+  if (o->kind != BF_MVDR && o->kind != BF_SOUDEN && o->kind != BF_GEV)
+    return fail(MISONET_EINVAL, "beamformer kind %d: 0 mvdr, 1 souden, 2 gev", o->kind);
+  if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "beamformer noise %d: 0 residual, 1 mix", o->noise);
+  if (!(o->condition >= 0.0) || !std::isfinite(o->condition))
+    return fail(MISONET_EINVAL, "beamformer condition (gamma) must be finite and >= 0 (got %g)", o->condition);
+  if (!(o->epsi >= 0.f) || !std::isfinite(o->epsi))
+    return fail(MISONET_EINVAL, "beamformer epsi must be finite and >= 0 (got %g)", (double)o->epsi);
+  if (o->ref_ch < 0 || o->ref_ch >= M)
+    return fail(MISONET_EINVAL, "beamformer ref_ch %d outside [0, %d)", o->ref_ch, M);
+  return MISONET_OK;
+}
+
+void mn::bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a) {
+  a.epsi = o.epsi; a.kind = o.kind; a.noise_mix = o.noise; a.trace_norm = o.trace_normalize != 0; a.ban = o.ban != 0;
+  a.bf_ref = o.ref_ch; a.condition = o.condition;
+}
+
+// The drop-in beamformer call: src / mix complex64 [B,F,M,T], one source per item.  misonet_beamform passes the caller's options
+// (checked here, the workspace sized by their kind); misonet_mvdr passes the defaults with its epsi as trusted: that entry point
+// has never validated epsi, and its workspace is misonet_mvdr_workspace_bytes.
+static int beamform_dropin(const void* src, const void* mix, int B, int F, int M, int T, const misonet_bf_opts* opts,
+                           bool trusted, void* out, void* ws, long long ws_bytes, misonet_stream stream) {
+  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F, T must be positive");
+  if (!trusted) { int r = bf_opts_check(opts, M); if (r) return r; }
+  if (ws_bytes < (trusted ? mvdr_ws_bytes(B, 1, F, M) : bf_ws_bytes(B, 1, F, M, opts->kind)))
+    return fail(MISONET_ENOMEM, "workspace too small");
+  MvdrArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  const float* x = reinterpret_cast<const float*>(src);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.src = {x, x + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
+  a.S = 1; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
+  bf_opts_apply(*opts, a);
+  float* o = reinterpret_cast<float*>(out);
+  COut co = {o, o + 1, 2LL * T * F, 0, 2LL * F, 2};      // [B,T,F] complex64 (tester.py:1134)
+  HIPCHK(launch_mvdr(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+extern "C" {
+
+// ---- MVDR / PIT drop-in entry points ---------------------------------------------------------------------------
+long long misonet_mvdr_workspace_bytes(int B, int F, int M) { return mvdr_ws_bytes(B, 1, F, M); }
+
+int misonet_mvdr(const void* src, const void* mix, int B, int F, int M, int T, float epsi, void* out, void* ws,
+                 long long ws_bytes, misonet_stream stream) {
+  misonet_bf_opts o;
+  misonet_bf_opts_default(&o);
+  o.epsi = epsi;
+  return beamform_dropin(src, mix, B, F, M, T, &o, true, out, ws, ws_bytes, stream);
+}
+
+int misonet_mvdr_debug(const void* ws, int B, int F, int M, void* steer, void* w, misonet_stream stream) {
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_mvdr_debug(ws, B, 1, F, M, reinterpret_cast<double*>(steer), reinterpret_cast<double*>(w),
+                           reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- selectable beamformers (ABI 510) ------------------------------------------------------------------------------
+int misonet_bf_opts_default(misonet_bf_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->kind = BF_MVDR; o->noise = 0; o->condition = 0.0; o->trace_normalize = 0; o->epsi = 1e-6f; o->ban = 0; o->ref_ch = 0;
+  return MISONET_OK;
+}
+
+long long misonet_beamform_workspace_bytes(int B, int F, int M, const misonet_bf_opts* opts) {
+  if (B <= 0 || F <= 0 || M < 2 || M > 8 || bf_opts_check(opts, M)) return -1;
+  return bf_ws_bytes(B, 1, F, M, opts->kind);
+}
+
+int misonet_beamform(const void* src, const void* mix, int B, int F, int M, int T, const misonet_bf_opts* opts, void* out,
+                     void* ws, long long ws_bytes, misonet_stream stream) {
+  return beamform_dropin(src, mix, B, F, M, T, opts, false, out, ws, ws_bytes, stream);
+}
+
+int misonet_beamform_debug(const void* ws, int B, int F, int M, const misonet_bf_opts* opts, void* w, double* lam,
+                           misonet_stream stream) {
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  if (B <= 0 || F <= 0 || M < 2 || M > 8) return fail(MISONET_EINVAL, "B, F must be positive and M in [2, 8]");
+  { int r = bf_opts_check(opts, M); if (r) return r; }
+  if (lam && opts->kind != BF_GEV) return fail(MISONET_EINVAL, "lambda_max exists for kind gev only");
+  HIPCHK(launch_bf_debug(ws, B, 1, F, M, reinterpret_cast<double*>(w), lam, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- WPE dereverberation (ABI 520) ---------------------------------------------------------------------------------
+int misonet_wpe_opts_default(misonet_wpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->taps = 10; o->delay = 3; o->iterations = 3; o->diag_load = 0.0; o->power_floor = 1e-10;
+  return MISONET_OK;
+}
+
+// host-side check of every field and of the geometry they are used with
+static int wpe_check(int B, int M, int T, int F, const misonet_wpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null dereverberation options");
+  if (B < 1 || F < 1) return fail(MISONET_EINVAL, "B and F must be positive (got %d, %d)", B, F);
+  if (T < 2) return fail(MISONET_EINVAL, "T must be >= 2 (got %d)", T);
+  if (M < 1 || M > 8) return fail(MISONET_EINVAL, "M must be in [1, 8] (got %d)", M);
+  if (o->taps < 1 || (long long)M * o->taps > 80)
+    return fail(MISONET_EINVAL, "taps must be >= 1 and M * taps <= 80 (got taps %d, M %d)", o->taps, M);
+  if (o->delay < 1) return fail(MISONET_EINVAL, "delay must be >= 1 (got %d)", o->delay);
+  if (o->iterations < 1 || o->iterations > 10) return fail(MISONET_EINVAL, "iterations must be in [1, 10] (got %d)", o->iterations);
+  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
+    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!(o->power_floor >= 0.0) || !std::isfinite(o->power_floor))
+    return fail(MISONET_EINVAL, "power_floor must be finite and >= 0 (got %g)", o->power_floor);
+  return MISONET_OK;
+}
+
+long long misonet_wpe_workspace_bytes(int B, int M, int T, int F, const misonet_wpe_opts* opts) {
+  if (wpe_check(B, M, T, F, opts)) return -1;
+  return wpe_ws_bytes(B, M, T, F, opts->taps);
+}
+
+int misonet_wpe(const void* mix, const float* power, int B, int M, int T, int F, const misonet_wpe_opts* opts, void* out,
+                void* ws, long long ws_bytes, misonet_stream stream) {
+  if (!mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (out == mix) return fail(MISONET_EINVAL, "out_dev must not be mix_dev");
+  { int r = wpe_check(B, M, T, F, opts); if (r) return r; }
+  if (ws_bytes < wpe_ws_bytes(B, M, T, F, opts->taps)) return fail(MISONET_ENOMEM, "workspace too small");
+  HIPCHK(launch_wpe(mix, power, B, M, T, F, opts->taps, opts->delay, opts->iterations, opts->diag_load, opts->power_floor, out,
+                    ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_wpe_debug(const void* ws, int B, int M, int F, const misonet_wpe_opts* opts, void* g, int* fail_dev,
+                      misonet_stream stream) {
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  { int r = wpe_check(B, M, 2, F, opts); if (r) return r; }
+  HIPCHK(launch_wpe_debug(ws, B, M, F, opts->taps, g, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+long long misonet_pit_scratch_bytes(int B, int S, int F) {
+  if (B <= 0 || S <= 0 || F <= 0) return -1;
+  return (long long)B * S * S * (F + 1) * (long long)sizeof(double);
+}
+
+int misonet_pit_select(const void* anchor, const void* cand, int B, int S, int T, int F, int* sel, double* dist,
+                       long long dist_bytes, misonet_stream stream) {
+  if (!anchor || !cand || !sel || !dist) return fail(MISONET_EINVAL, "null argument (dist is required: B*S*S*(F+1) doubles)");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "PIT alignment enumerates S! permutations: 1 <= num_spks <= 4 (got %d)", S);
+  if (B <= 0 || T <= 0 || F <= 0) return fail(MISONET_EINVAL, "B, T, F must be positive");
+  if (dist_bytes < misonet_pit_scratch_bytes(B, S, F))
+    return fail(MISONET_ENOMEM, "dist scratch %lld < %lld bytes (B*S*S*(F+1) doubles)", dist_bytes, misonet_pit_scratch_bytes(B, S, F));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float* a = reinterpret_cast<const float*>(anchor);
+  const float* c = reinterpret_cast<const float*>(cand);
+  PitArgs p;
+  // [B,S,T,F] complex64: element (b, f, spk, t) at ((b*S + spk)*T + t)*F + f
+  p.a = {a, a + 1, 2LL * S * T * F, 2, 2LL * T * F, 2 * F};
+  p.b = {c, c + 1, 2LL * S * T * F, 2, 2LL * T * F, 2 * F};
+  p.B = B; p.F = F; p.T = T;
+  double* part = dist + (long long)B * S * S;          // per-bin partials [B][F][S][S] behind the result
+  HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
+  HIPCHK(launch_pit_pick(part, F, S, B, dist, sel, s));
+  return MISONET_OK;
+}
+
+// ---- continuous separation: speaker tracking across overlapping windows + cross-fade stitch (css.hip) -------------
+long long misonet_css_scratch_bytes(int K, int S, int F) {
+  if (K <= 0 || S <= 0 || F <= 0) return -1;
+  return (long long)(K - 1) * S * S * (F + 1) * (long long)sizeof(double);
+}
+
+int misonet_css_align(const void* est, int K, int S, int T, int F, int hop_frames, const int* perm0, int* perm,
+                      double* dist, long long dist_bytes, misonet_stream stream) {
+  if (!est || !perm) return fail(MISONET_EINVAL, "null argument");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "the alignment enumerates S! permutations: 1 <= S <= 4 (got %d)", S);
+  if (F != 129) return fail(MISONET_EINVAL, "F must be 129 (got %d)", F);
+  if (K < 1 || K - 1 > 65535) return fail(MISONET_EINVAL, "K must be in [1, 65536] (got %d)", K);
+  if (hop_frames <= 0 || T - hop_frames < 5)
+    return fail(MISONET_EINVAL, "hop_frames must be positive and leave an overlap of at least 5 frames (T %d, hop %d)", T,
+                hop_frames);
+  if (K > 1 && !dist) return fail(MISONET_EINVAL, "null argument (dist is required for K > 1: (K-1)*S*S*(F+1) doubles)");
+  if (dist_bytes < misonet_css_scratch_bytes(K, S, F))
+    return fail(MISONET_ENOMEM, "dist scratch %lld < %lld bytes ((K-1)*S*S*(F+1) doubles)", dist_bytes,
+                misonet_css_scratch_bytes(K, S, F));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (K > 1) {
+    // est complex64 [K,S,T,F]: element (k, f, spk, t) at ((k*S + spk)*T + t)*F + f.  Item b = k - 1 of the distance launch:
+    // anchor = window k - 1 from frame hop_frames on, candidate = window k from frame 0, over the T - hop_frames shared frames
+    const float* e = reinterpret_cast<const float*>(est);
+    const long long win = 2LL * S * T * F;
+    const float* a = e + 2LL * hop_frames * F;
+    const float* c = e + win;
+    PitArgs p;
+    p.a = {a, a + 1, win, 2, 2LL * T * F, 2 * F};
+    p.b = {c, c + 1, win, 2, 2LL * T * F, 2 * F};
+    p.B = K - 1; p.F = F; p.T = T - hop_frames;
+    double* part = dist + (long long)(K - 1) * S * S;                // per-bin partials [K-1][F][S][S] behind D
+    HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
+    HIPCHK(launch_pit_pick(part, F, S, K - 1, dist, perm + S, s));   // L_k -> row k of perm, composed in place below
+  }
+  HIPCHK(launch_css_chain(perm0, perm, K, S, s));
+  return MISONET_OK;
+}
+
+int misonet_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, int first, long long n_out,
+                       short* out_i16, float* out_f32, misonet_stream stream) {
+  if (!y || !perm || (!out_i16 && !out_f32)) return fail(MISONET_EINVAL, "null argument");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "S must be in [1, 4] (got %d)", S);
+  if (K < 1) return fail(MISONET_EINVAL, "K must be positive (got %d)", K);
+  if (W <= 0 || hop <= 0 || 2LL * hop < W || hop > W - 256)
+    return fail(MISONET_EINVAL, "hop %d outside [W/2, W-256] for W = %d", hop, W);
+  const long long base = first ? 0 : hop;
+  const long long cap = (long long)(K - 1) * hop + W - base;
+  if (n_out < 0 || n_out > cap) return fail(MISONET_EINVAL, "n_out %lld outside [0, %lld]", n_out, cap);
+  if (n_out == 0) return MISONET_OK;
+  HIPCHK(launch_css_stitch(y, perm, K, S, W, hop, base, n_out, out_i16, out_f32, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,199 @@
+// C ABI of the scoring against clean references (include/misonet.h): misonet_score_* (score.hip), BSS-eval misonet_bss_*
+// (bss.hip), STOI / ESTOI misonet_stoi_* (stoi.hip) and the STOI table of every device that uses it.  Host code only.
+#include "api_common.hpp"
+
+using namespace mn;
+
+// ---- checks the scorers share --------------------------------------------------------------------------------------------
+// the strided views of estimates and references: (item, source, sample) strides, or frame strides for the spectral score (`unit`)
+static int view_strides(long long est_sb, long long est_ss, long long est_st, long long ref_sb, long long ref_ss,
+                        long long ref_st, const char* unit, bool mix_bad = false) {
+  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1 || mix_bad)
+    return fail(MISONET_EINVAL, "strides must not be negative and the %s strides must be positive", unit);
+  return MISONET_OK;
+}
+// `sizing`: the call that gives `need`, as the message names it
+static int scratch_fits(long long scratch_bytes, long long need, const char* sizing) {
+  if (scratch_bytes < need) return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (%s)", scratch_bytes, need, sizing);
+  return MISONET_OK;
+}
+// estimates, references and items of BSS-eval and STOI (misonet_score_* take the mixture as a fifth estimate: score_ranges)
+static int erb_ranges(int B, int E, int R) {
+  if (E < 1 || E > 4) return fail(MISONET_EINVAL, "E must be in [1, 4] (got %d)", E);
+  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
+  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
+  return MISONET_OK;
+}
+
+extern "C" {
+
+// ---- scores against clean references (score.hip) --------------------------------------------------------------------
+// One size serves both entry points: the wave partials [B][ceil(n / 4096)][2E + 2R + E R] and the per-bin partials
+// [B][F][E][R] (F <= 1024), whichever is larger for the value given.
+long long misonet_score_scratch_bytes(int B, int E, int R, long long n_or_F) {
+  if (B <= 0 || E <= 0 || R <= 0 || n_or_F <= 0) return -1;
+  const long long wave = score_wave_segments(n_or_F) * (2LL * E + 2LL * R + (long long)E * R);
+  const long long spec = (n_or_F < 1024 ? n_or_F : 1024) * (long long)E * R;
+  return (long long)B * (wave > spec ? wave : spec) * (long long)sizeof(double);
+}
+
+static int score_ranges(int B, int E, int R) {
+  if (E < 1 || E > 5) return fail(MISONET_EINVAL, "E must be in [1, 5] (got %d): up to 4 speakers and the mixture", E);
+  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
+  if (B < 1 || B > 65535) return fail(MISONET_EINVAL, "B must be in [1, 65535] (got %d)", B);
+  return MISONET_OK;
+}
+
+int misonet_score_wave(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                       const float* ref, long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R,
+                       long long n, const int* n_valid, double* stats, void* scratch, long long scratch_bytes,
+                       misonet_stream stream) {
+  if (!est || !ref || !stats || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = score_ranges(B, E, R)) return rc;
+  if (n < 1 || n > (1LL << 40)) return fail(MISONET_EINVAL, "n must be in [1, 2^40] (got %lld)", n);
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample")) return rc;
+  if (const int rc = scratch_fits(scratch_bytes, misonet_score_scratch_bytes(B, E, R, n), "misonet_score_scratch_bytes(B, E, R, n)"))
+    return rc;
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
+  HIPCHK(launch_score_wave(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, reinterpret_cast<double*>(scratch), stats,
+                           reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_score_spec(const void* est, long long est_sb, long long est_ss, long long est_st, const void* ref,
+                       long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, int T, int F,
+                       double* pair, int* perm, double* upit, void* scratch, long long scratch_bytes,
+                       misonet_stream stream) {
+  if (!est || !ref || !pair || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = score_ranges(B, E, R)) return rc;
+  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
+  if (F < 1 || F > 1024) return fail(MISONET_EINVAL, "F must be in [1, 1024] (got %d)", F);
+  if ((perm || upit) && E != R)
+    return fail(MISONET_EINVAL, "the permutation pick needs as many estimates as references (E %d, R %d)", E, R);
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "frame")) return rc;
+  if (const int rc = scratch_fits(scratch_bytes, misonet_score_scratch_bytes(B, E, R, F), "misonet_score_scratch_bytes(B, E, R, F)"))
+    return rc;
+  // complex64 views, strides in complex elements, bins contiguous: element (b, f, source, t) at 2 (b sb + source ss + t st + f)
+  const float* a = reinterpret_cast<const float*>(est);
+  const float* c = reinterpret_cast<const float*>(ref);
+  PitArgs p;
+  p.a = {a, a + 1, 2 * est_sb, 2, 2 * est_ss, (int)(2 * est_st)};
+  p.b = {c, c + 1, 2 * ref_sb, 2, 2 * ref_ss, (int)(2 * ref_st)};
+  p.B = B; p.F = F; p.T = T;
+  HIPCHK(launch_score_spec(p, E, R, reinterpret_cast<double*>(scratch), pair, perm, upit,
+                           reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- BSS-eval energies (bss.hip) -----------------------------------------------------------------------------------------
+static int bss_ranges(int B, int E, int R, int Q) {
+  if (const int rc = erb_ranges(B, E, R)) return rc;
+  if (Q < 16 || Q > 1024 || Q % 16) return fail(MISONET_EINVAL, "Q must be a multiple of 16 in [16, 1024] (got %d)", Q);
+  return MISONET_OK;
+}
+
+// One size serves both calls: the correlation partials [B][ceil((n + 15) / 4096)][R R + R E + E][Q] and the systems of an item,
+// (R Q + 4) R Q + R (Q + 4) Q doubles, whichever is larger.
+long long misonet_bss_scratch_bytes(int B, int E, int R, long long n, int Q) {
+  if (B < 1 || B > 4096 || E < 1 || E > 4 || R < 1 || R > 4 || Q < 16 || Q > 1024 || Q % 16 || n < 1 || n > (1LL << 24)) return -1;
+  const long long corr = bss_corr_segments(n) * ((long long)R * R + (long long)R * E + E) * Q;
+  const long long sys = bss_solve_doubles(R, Q);
+  return (long long)B * (corr > sys ? corr : sys) * (long long)sizeof(double);
+}
+
+int misonet_bss_corr(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st, const float* ref,
+                     long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, long long n,
+                     const int* n_valid, int Q, double* Rrr, double* Rre, double* Eee, void* scratch,
+                     long long scratch_bytes, misonet_stream stream) {
+  if (!est || !ref || !Rrr || !Rre || !Eee || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample")) return rc;
+  if (const int rc = scratch_fits(scratch_bytes, misonet_bss_scratch_bytes(B, E, R, n, Q), "misonet_bss_scratch_bytes(B, E, R, n, Q)"))
+    return rc;
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
+  HIPCHK(launch_bss_corr(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, Q, reinterpret_cast<double*>(scratch), Rrr, Rre,
+                         Eee, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_bss_solve(const double* Rrr, const double* Rre, const double* Eee, int B, int E, int R, int Q, double* T, double* A,
+                      int* info, void* scratch, long long scratch_bytes, misonet_stream stream) {
+  if (!Rrr || !Rre || !Eee || !T || !A || !info || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
+  if (const int rc = scratch_fits(scratch_bytes, misonet_bss_scratch_bytes(B, E, R, 1, Q), "misonet_bss_scratch_bytes(B, E, R, 1, Q)"))
+    return rc;
+  HIPCHK(launch_bss_solve(Rrr, Rre, B, E, R, Q, T, A, info, reinterpret_cast<double*>(scratch),
+                          reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- STOI / ESTOI (stoi.hip) ------------------------------------------------------------------------------------------------
+// the table of the current device (window, twiddles, polyphase taps), built on first use: that one call allocates and copies
+// synchronously; every later call only queues kernels
+static DevTable<double> g_stoi_tab;
+static int get_stoi_table(const double** out) {
+  return g_stoi_tab.get(out, [](double** p) {
+    std::vector<double> t((size_t)stoi_table_count());
+    stoi_build_table(t.data());
+    return dev_upload(t, p);
+  });
+}
+
+long long misonet_stoi_resampled_len(long long n, int fs) { return stoi_resampled_len(n, fs); }
+
+int misonet_stoi_taps(int fs, double* taps_host) {
+  const int nt = stoi_taps(fs);
+  if (nt < 0) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
+  if (taps_host) {
+    std::vector<double> t((size_t)stoi_table_count());
+    stoi_build_table(t.data());
+    const int off = stoi_tap_offset(fs);
+    for (int i = 0; i < nt; ++i) taps_host[i] = t[(size_t)off + i];
+  }
+  return nt;
+}
+
+static bool stoi_ranges_ok(int B, int NS, int R, long long n10) {
+  return B >= 1 && B <= 4096 && R >= 1 && R <= 4 && NS - R >= 1 && NS - R <= 5 && n10 >= 1 && n10 <= 5 * (1LL << 22);
+}
+
+long long misonet_stoi_scratch_bytes(int B, int NS, int R, long long n10) {
+  if (!stoi_ranges_ok(B, NS, R, n10)) return -1;
+  return (long long)B * stoi_item_doubles(NS, R, n10) * (long long)sizeof(double);
+}
+
+int misonet_stoi_resample(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                          const float* ref, long long ref_sb, long long ref_ss, long long ref_st, const float* mix,
+                          long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid, int fs,
+                          double* x10, int* len10, misonet_stream stream) {
+  if (!est || !ref || !x10 || !len10) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = erb_ranges(B, E, R)) return rc;
+  if (fs != 8000 && fs != 10000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample", mix && (mix_sb < 0 || mix_st < 1)))
+    return rc;
+  const double* tab;
+  if (const int rc = get_stoi_table(&tab)) return rc;
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
+  HIPCHK(launch_stoi_resample(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, x10, len10,
+                              reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_stoi_measure(const double* x10, const int* len10, int B, int NS, int R, long long n10, double* out, int* frames,
+                         void* scratch, long long scratch_bytes, misonet_stream stream) {
+  if (!x10 || !out || !frames || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (!stoi_ranges_ok(B, NS, R, n10))
+    return fail(MISONET_EINVAL, "1 <= B <= 4096, 1 <= R <= 4, 1 <= NS - R <= 5, 1 <= n10 <= 5 * 2^22 (got %d, %d, %d, %lld)", B,
+                R, NS - R, n10);
+  if (const int rc = scratch_fits(scratch_bytes, misonet_stoi_scratch_bytes(B, NS, R, n10), "misonet_stoi_scratch_bytes(B, NS, R, n10)"))
+    return rc;
+  const double* tab;
+  if (const int rc = get_stoi_table(&tab)) return rc;
+  HIPCHK(launch_stoi_measure(x10, len10, B, NS, R, n10, tab, out, frames, reinterpret_cast<double*>(scratch),
+                             reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+}  // extern "C"

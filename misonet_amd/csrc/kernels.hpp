@@ -181,6 +181,28 @@ hipError_t launch_export(const float* src, long long src_bstride, int c0, int C,
                          const dstat_t* stats, int sstride, int ident_c, float* dst, int n_samples, hipStream_t s,
                          int oct = 0);   // oct: bf16 parts of a source in the oct layout (0 planar, 2, 3; sstride = channels
                                          // of the whole buffer)
+// what the fused pipeline adds: launch_unpack's general form (layout.hip: real / imaginary planes from channel c_re0 / c_im0 on,
+// sources picked through sel); the shift and clean alignments composed into one sel, and the MISO3 input [mixture | beamformer
+// planes, written by launch_mvdr | MISO1 estimate at ref_ch] (both mvdr.hip)
+hipError_t launch_unpack_ex(const float* src, long long src_bstride, int Tp, int S, int T, int F, int c_re0, int c_im0, int mode,
+                            int M, const int* sel, float2* dst, int n_out, int* nan_flag, hipStream_t s);
+hipError_t launch_compose_sel(const int* shift_sel, const int* clean_sel, int B, int M, int S, int* out, hipStream_t s);
+hipError_t launch_assemble3(const float* in1, long long in1_bstride, const float* out1, long long out1_bstride,
+                            const int* sel, int B, int M, int S, int ref_ch, int F, int Tp, float* in3,
+                            long long in3_bstride, hipStream_t s);
+
+// ---- STFT front-end (stft.hip) --------------------------------------------------------------------------------------
+// waveform -> planar network input, and complex64 spectrum -> waveform; each reads a twiddle table built on the host
+// (*_twiddle_count() floats) and needs its *_init() once per device (kernel attributes)
+hipError_t launch_stft_pack(const float* wav, int B, int L, int Mw, int T, const float* twid, float* dst,
+                            long long dst_bstride, int Tp, int F, int c_re, int c_im, int nshift, hipStream_t s);
+hipError_t stft_init();
+void stft_build_twiddles(float* tw);
+int stft_twiddle_count();
+hipError_t launch_istft(const void* spec, int N, int T, const float* itw, short* out_i16, float* out_f32, hipStream_t s);
+hipError_t istft_init();
+void istft_build_twiddles(float* tw);
+int istft_twiddle_count();
 
 // ---- MVDR + PIT -------------------------------------------------------------------------------------------------
 // Accessor for a multichannel complex STFT with frames contiguous: element (b, f, m, t) =
@@ -226,6 +248,11 @@ struct PitArgs {
 // K candidates per anchor: grid row bk = b*K + k uses anchor b and candidate bk
 hipError_t launch_pit_dist_k(const PitArgs& p, int S, int K, double* part /*[B*K][F][S][S]*/, hipStream_t s);
 hipError_t launch_pit_pick(const double* part, int F, int S, int n, double* dist /*[n][S][S]*/, int* sel /*[n][S]*/, hipStream_t s);
+
+// Continuous separation (css.hip): the window-to-window permutations composed along the recording, and the cross-fade stitch
+hipError_t launch_css_chain(const int* perm0, int* perm, int K, int S, hipStream_t s);
+hipError_t launch_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, long long base, long long n_out,
+                             short* out_i16, float* out_f32, hipStream_t s);
 
 // Scores of separated output against clean references (score.hip).  Wave statistics: est int16 or float32, ref float32, each
 // a strided view (item, source, sample) in elements (es / rs = the three strides); per-segment partials

@@ -1,7 +1,9 @@
-// Host runtime of libmisonet_hip.so: layer plan of a MISO trunk (reference model.py:8-111 / 282-395), the weight arena (the
-// images themselves: conv_weights.hip), workspace layout, forward scheduling, and the C ABI of include/misonet.h.
-#include "conv_select.hpp"
-#include "../../include/misonet.h"
+// The network of libmisonet_hip.so: layer plan of a MISO trunk (reference model.py:8-111 / 282-395), the weight arena (the
+// images themselves: conv_weights.hip), workspace layout and forward scheduling, behind the misonet_net_* entry points of
+// include/misonet.h.  Also the library's runtime: the error report, per-launch profiling and events.  The rest of the C ABI lies in
+// one host file per domain: api_frontend.hip (STFT / iSTFT), api_array.hip (beamformers, WPE, PIT, continuous separation),
+// api_score.hip (scores, BSS-eval, STOI) and api_pipeline.hip (the fused pipeline); what they share: api_common.hpp, net.hpp.
+#include "net.hpp"
 
 #include <math.h>
 #include <cmath>
@@ -10,160 +12,22 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
-#include <mutex>
-#include <string>
-#include <vector>
-
-namespace mn {
-hipError_t launch_unpack_ex(const float* src, long long src_bstride, int Tp, int S, int T, int F, int c_re0, int c_im0, int mode,
-                            int M, const int* sel, float2* dst, int n_out, int* nan_flag, hipStream_t s);
-hipError_t launch_compose_sel(const int* shift_sel, const int* clean_sel, int B, int M, int S, int* out, hipStream_t s);
-hipError_t launch_assemble3(const float* in1, long long in1_bstride, const float* out1, long long out1_bstride,
-                            const int* sel, int B, int M, int S, int ref_ch, int F, int Tp, float* in3,
-                            long long in3_bstride, hipStream_t s);
-hipError_t launch_stft_pack(const float* wav, int B, int L, int Mw, int T, const float* twid, float* dst,
-                            long long dst_bstride, int Tp, int F, int c_re, int c_im, int nshift, hipStream_t s);
-hipError_t stft_init();
-hipError_t launch_istft(const void* spec, int N, int T, const float* itw, short* out_i16, float* out_f32, hipStream_t s);
-hipError_t istft_init();
-void istft_build_twiddles(float* tw);
-int istft_twiddle_count();
-void stft_build_twiddles(float* tw);
-int stft_twiddle_count();
-hipError_t launch_css_chain(const int* perm0, int* perm, int K, int S, hipStream_t s);
-hipError_t launch_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, long long base, long long n_out,
-                             short* out_i16, float* out_f32, hipStream_t s);
-}  // namespace mn
 
 using namespace mn;
 
-static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+static thread_local char g_err[512] = "";       // the one message buffer: only fail() writes it, only misonet_last_error reads it
+int mn::fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-#define HIPCHK(expr)                                                                                    \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return fail(MISONET_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
-// ---- optional per-launch timing with HIP events on the caller's stream (bench.py roofline leg) ------------------
-enum { PK_CONV = 0, PK_TCN, PK_MVDR, PK_OTHER, PK_N };
-struct ProfRec { int kind; hipEvent_t e0, e1; };
-struct Prof {
-  bool on = false;
-  std::vector<hipEvent_t> pool;
-  size_t used = 0;
-  std::vector<ProfRec> recs;
-  bool overflow = false;
-};
-// one state per device (events belong to the device that was current when they were created); a process that drives
-// several GPUs profiles each of them independently
-constexpr int MAX_DEV = 64;
-static Prof g_profs[MAX_DEV];
-static std::atomic<int> g_prof_any{0};          // fast path: no hipGetDevice per launch while nobody profiles
-static int cur_dev() {
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= MAX_DEV) d = 0;
-  return d;
-}
-struct ProfScope {
-  hipStream_t s; int kind; hipEvent_t e0 = nullptr, e1 = nullptr; bool active = false; Prof* pr = nullptr;
-  ProfScope(hipStream_t s_, int kind_) : s(s_), kind(kind_) {
-    if (!g_prof_any.load(std::memory_order_relaxed)) return;
-    pr = &g_profs[cur_dev()];
-    if (!pr->on) return;
-    if (pr->used + 2 > pr->pool.size()) { pr->overflow = true; return; }
-    e0 = pr->pool[pr->used++];
-    e1 = pr->pool[pr->used++];
-    active = (hipEventRecord(e0, s) == hipSuccess);
-  }
-  ~ProfScope() {
-    if (!active) return;
-    if (hipEventRecord(e1, s) == hipSuccess) pr->recs.push_back({kind, e0, e1});
-  }
-};
-
-static int frontend_init();   // STFT / iSTFT tables of the current device (below, with the front-end entry points)
+Prof mn::g_profs[MAX_DEV];
+std::atomic<int> mn::g_prof_any{0};
 
 // ---------------------------------------------------------------------------------------------------------------
-struct Tensor {
-  std::string name;
-  long long numel;
-  std::vector<float> host;
-  bool set = false;
-};
-
-enum { B_IN = 0, B_E0, B_E1, B_E2, B_E3, B_E4, B_D0, B_D1, B_D2, B_D3, B_D4, B_D5, B_D6, B_X2, B_X3, B_X4, B_X5, B_X6,
-       B_OUT, B_TXA, B_TXB, B_TD, B_TP, NBUF };
-
-struct BufSpec { int C = 0, F = 0; };
-
-struct ConvL {
-  int in_buf, in_c0, Cin, ident_c;
-  int out_buf, out_c0, Cout;
-  int sf, padf, tr2, act;
-  bool transposed;
-  int wt, bt;                   // tensor indices
-  int cop, ncg;
-  ConvKind kind[CONV_NMODES];       // the layer's kernel per precision mode of the build (conv_select.hpp), filled by build_plan
-  long long img_off[CONV_NKIND];    // commit: offset (floats) into the device weight arena of the image of each kind that occurs in
-                                    // kind[] (and of DIRECT, always); -1: not packed
-  long long b_off = 0;              // ... and of the bias [ncg * cop]
-  float wscale = 1.f;               // f16x3: power of two that brings max |W| of the layer to [32, 64)
-  const float* img(const float* w_dev, ConvKind k) const { return w_dev + img_off[(int)k]; }
-};
-
-struct TcnHalf {
-  int dw, prelu, gamma, beta, pw; long long o_dw, o_prelu, o_gamma, o_beta, o_pw;
-  // the OUTER norm in front of this half (model.py:530,535; cfg.tcn_norm): tensors (gLN / cLN: gamma, beta; BatchNorm1d:
-  // weight, bias, running_mean, running_var) and the per-channel (scale, shift) pair the kernels read
-  int on[4] = {-1, -1, -1, -1};
-  long long o_nsc = 0, o_nsh = 0;
-};
-struct TcnBlock { int dilation; TcnHalf h[2]; };
-
-struct Tap { std::string name; int buf, c0, C; bool normalised; };
-
-struct Layout {
-  int N, T, Tp;
-  long long data_off[NBUF];      // floats: activation buffers (b < B_TXA): offset INSIDE a sample's block of the arena (sample n
-                                 // at + n * sample_stride); TCN buffers: offset of the whole [N][128][Tp] block
-  long long sample_stride;       // floats per sample of the activation arena
-  long long in_ext_off = -1;     // >= 0: the network input lives OUTSIDE this workspace, at ws + in_ext_off bytes, with
-  long long in_ext_bstride = 0;  // in_ext_bstride floats between samples (the pipeline's MISO3 input, see pipe_layout)
-  long long stats_off[NBUF];     // 8-byte words (dstat_t): [N][C][2][DS_NL] per buffer
-  long long tcn_xs, tcn_ps, tcn_gln;   // words (2 per double2 partial): [15][N*128*slots], [14][N*128*slots], [28][N*32]
-  long long stats_doubles;       // words in all
-  long long data_base;           // bytes from ws start to the float arena
-  long long wps_base, wps_nstride;   // bytes: per-sample folded weights of the layer in flight (DMA dataflow)
-  long long btab_base, btab_nstride; // bytes / floats: per-sample border-aware shift table
-  long long fstat_base;              // bytes: [N][Tp] float2 per-frame (mean, rstd) of the cLN outer norm (cfg.tcn_norm == 2)
-  long long total_bytes;
-};
-
-struct misonet_net {
-  misonet_cfg cfg;
-  int S;                         // speakers out = out_ch / 2
-  BufSpec bufs[NBUF];
-  std::vector<Tensor> tensors;
-  std::vector<ConvL> enc, dec;
-  std::vector<TcnBlock> tcn;
-  std::vector<Tap> taps;
-  float* w_dev = nullptr;
-  bool committed = false;
-  bool keep_taps = false;        // true: no buffer shares memory with another (every tap stays readable after a forward)
-  int precision = 3;             // 0: exact f32 MFMA, 1: bf16x3 planar, 2: bf16x3 DMA dataflow, 3: bf16x6 DMA dataflow (the
-                                 // default: fp32-faithful, what bench.py reports), 4: f16x3 DMA dataflow, 5: f32 MFMA with the
-                                 // dense-block convs in Winograd F(2x2, 3x3) form ("f32w": planar float32 layout like mode 0)
-};
-// (the modes of this build, product 0 / 3 / 5 or all seven: conv_select.hpp conv_mode_built)
-
 static int find_tensor(const misonet_net* n, const std::string& name) {
   for (size_t i = 0; i < n->tensors.size(); ++i)
     if (n->tensors[i].name == name) return (int)i;
@@ -361,16 +225,12 @@ static int build_plan(misonet_net* n) {
   return MISONET_OK;
 }
 
-static long long align_up(long long x, long long a) { return (x + a - 1) / a * a; }
-
 // floats one sample occupies in buffer b (an oct3 buffer holds 1.5 floats per element; C is a multiple of 8 there)
 static inline long long buf_floats(const misonet_net* n, int Tp, int b) {
   const long long e = (long long)n->bufs[b].C * n->bufs[b].F * Tp;
   return buf_oct(n, b) == 3 ? e + e / 2 : e;
 }
-// floats between consecutive samples of buffer b: the activation arena is SAMPLE-major (all buffers of a sample in one
-// block, so that buffers whose lifetimes do not overlap can share memory: make_layout), the TCN buffers are buffer-major
-static inline long long bstride(const misonet_net* n, const Layout& L, int b) {
+long long mn::bstride(const misonet_net* n, const Layout& L, int b) {
   if (b == B_IN && L.in_ext_off >= 0) return L.in_ext_bstride;
   return b >= B_TXA ? buf_floats(n, L.Tp, b) : L.sample_stride;
 }
@@ -388,7 +248,7 @@ static void buf_lifetime(int b, int& t0, int& t1) {
   else { t0 = 15; t1 = 16; }                                     // B_OUT
 }
 
-static Layout make_layout(const misonet_net* n, int N, int T, bool ext_in = false) {
+Layout mn::make_layout(const misonet_net* n, int N, int T, bool ext_in) {
   Layout L;
   L.N = N; L.T = T; L.Tp = frames_pitch(T);
   long long so = 0;
@@ -463,10 +323,6 @@ static Layout make_layout(const misonet_net* n, int N, int T, bool ext_in = fals
   return L;
 }
 
-static inline float* buf_ptr(const Layout& L, void* ws, int b) {
-  if (b == B_IN && L.in_ext_off >= 0) return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.in_ext_off);
-  return reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.data_base) + L.data_off[b];
-}
 static inline dstat_t* stats_base(void* ws) { return reinterpret_cast<dstat_t*>(reinterpret_cast<char*>(ws) + 256); }
 static inline dstat_t* stats_ptr(const Layout& L, void* ws, int b) { return stats_base(ws) + L.stats_off[b]; }
 
@@ -565,8 +421,7 @@ static unsigned layout_stamp(const misonet_net* n, const Layout& L) {
   return h | 1u;                                  // never 0 (= "no forward has run here")
 }
 
-// IN buffer already filled (planar).  Leaves the result (raw) in B_OUT.
-static int forward_planar(misonet_net* n, const Layout& L, void* ws, hipStream_t s) {
+int mn::forward_planar(misonet_net* n, const Layout& L, void* ws, hipStream_t s) {
   // the nan flag + the conv statistics (integer limbs are ACCUMULATED); the TCN partial arrays behind them are plainly written
   HIPCHK(hipMemsetAsync(ws, 0, (size_t)(256 + L.tcn_xs * 8), s));
   HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<char*>(ws) + 8), (int)layout_stamp(n, L), 1, s));
@@ -861,7 +716,7 @@ int misonet_net_commit(misonet_net* n) {
   HIPCHK(conv_bf16_dma_init());
 #endif
   HIPCHK(conv_bf16x6_init());
-  { int rf = frontend_init(); if (rf) return rf; }     // STFT / iSTFT tables: never allocated inside an asynchronous call
+  { int rf = misonet_frontend_init(); if (rf) return rf; }     // STFT / iSTFT tables: never allocated inside an asynchronous call
   n->committed = true;
   return MISONET_OK;
 }
@@ -984,701 +839,6 @@ int misonet_net_tap(misonet_net* n, const char* name, const void* ws, int B, int
       return MISONET_OK;
     }
   return fail(MISONET_EINVAL, "unknown tap '%s'", name);
-}
-
-// ---- MVDR / PIT drop-in entry points ---------------------------------------------------------------------------
-long long misonet_mvdr_workspace_bytes(int B, int F, int M) { return mvdr_ws_bytes(B, 1, F, M); }
-
-int misonet_mvdr(const void* src, const void* mix, int B, int F, int M, int T, float epsi, void* out, void* ws,
-                 long long ws_bytes, misonet_stream stream) {
-  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
-  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
-  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F, T must be positive");
-  if (ws_bytes < mvdr_ws_bytes(B, 1, F, M)) return fail(MISONET_ENOMEM, "workspace too small");
-  MvdrArgs a;
-  const float* y = reinterpret_cast<const float*>(mix);
-  const float* x = reinterpret_cast<const float*>(src);
-  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
-  a.src = {x, x + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
-  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
-  a.S = 1; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T; a.epsi = epsi;
-  float* o = reinterpret_cast<float*>(out);
-  COut co = {o, o + 1, 2LL * T * F, 0, 2LL * F, 2};      // [B,T,F] complex64 (tester.py:1134)
-  HIPCHK(launch_mvdr(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_mvdr_debug(const void* ws, int B, int F, int M, void* steer, void* w, misonet_stream stream) {
-  if (!ws) return fail(MISONET_EINVAL, "null argument");
-  HIPCHK(launch_mvdr_debug(ws, B, 1, F, M, reinterpret_cast<double*>(steer), reinterpret_cast<double*>(w),
-                           reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- selectable beamformers (ABI 510) ------------------------------------------------------------------------------
-int misonet_bf_opts_default(misonet_bf_opts* o) {
-  if (!o) return fail(MISONET_EINVAL, "null argument");
-  o->kind = BF_MVDR; o->noise = 0; o->condition = 0.0; o->trace_normalize = 0; o->epsi = 1e-6f; o->ban = 0; o->ref_ch = 0;
-  return MISONET_OK;
-}
-
-// host-side check of every field; M = the number of microphones ref_ch is counted in
-static int bf_opts_check(const misonet_bf_opts* o, int M) {
-  if (!o) return fail(MISONET_EINVAL, "null beamformer options");
-  if (o->kind != BF_MVDR && o->kind != BF_SOUDEN && o->kind != BF_GEV)
-    return fail(MISONET_EINVAL, "beamformer kind %d: 0 mvdr, 1 souden, 2 gev", o->kind);
-  if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "beamformer noise %d: 0 residual, 1 mix", o->noise);
-  if (!(o->condition >= 0.0) || !std::isfinite(o->condition))
-    return fail(MISONET_EINVAL, "beamformer condition (gamma) must be finite and >= 0 (got %g)", o->condition);
-  if (!(o->epsi >= 0.f) || !std::isfinite(o->epsi))
-    return fail(MISONET_EINVAL, "beamformer epsi must be finite and >= 0 (got %g)", (double)o->epsi);
-  if (o->ref_ch < 0 || o->ref_ch >= M)
-    return fail(MISONET_EINVAL, "beamformer ref_ch %d outside [0, %d)", o->ref_ch, M);
-  return MISONET_OK;
-}
-
-static void bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a) {
-  a.epsi = o.epsi; a.kind = o.kind; a.noise_mix = o.noise; a.trace_norm = o.trace_normalize != 0; a.ban = o.ban != 0;
-  a.bf_ref = o.ref_ch; a.condition = o.condition;
-}
-
-long long misonet_beamform_workspace_bytes(int B, int F, int M, const misonet_bf_opts* opts) {
-  if (B <= 0 || F <= 0 || M < 2 || M > 8 || bf_opts_check(opts, M)) return -1;
-  return bf_ws_bytes(B, 1, F, M, opts->kind);
-}
-
-int misonet_beamform(const void* src, const void* mix, int B, int F, int M, int T, const misonet_bf_opts* opts, void* out,
-                     void* ws, long long ws_bytes, misonet_stream stream) {
-  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
-  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
-  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F, T must be positive");
-  { int r = bf_opts_check(opts, M); if (r) return r; }
-  if (ws_bytes < bf_ws_bytes(B, 1, F, M, opts->kind)) return fail(MISONET_ENOMEM, "workspace too small");
-  MvdrArgs a;
-  const float* y = reinterpret_cast<const float*>(mix);
-  const float* x = reinterpret_cast<const float*>(src);
-  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
-  a.src = {x, x + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
-  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
-  a.S = 1; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
-  bf_opts_apply(*opts, a);
-  float* o = reinterpret_cast<float*>(out);
-  COut co = {o, o + 1, 2LL * T * F, 0, 2LL * F, 2};      // [B,T,F] complex64 (tester.py:1134)
-  HIPCHK(launch_mvdr(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_beamform_debug(const void* ws, int B, int F, int M, const misonet_bf_opts* opts, void* w, double* lam,
-                           misonet_stream stream) {
-  if (!ws) return fail(MISONET_EINVAL, "null argument");
-  if (B <= 0 || F <= 0 || M < 2 || M > 8) return fail(MISONET_EINVAL, "B, F must be positive and M in [2, 8]");
-  { int r = bf_opts_check(opts, M); if (r) return r; }
-  if (lam && opts->kind != BF_GEV) return fail(MISONET_EINVAL, "lambda_max exists for kind gev only");
-  HIPCHK(launch_bf_debug(ws, B, 1, F, M, reinterpret_cast<double*>(w), lam, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- WPE dereverberation (ABI 520) ---------------------------------------------------------------------------------
-int misonet_wpe_opts_default(misonet_wpe_opts* o) {
-  if (!o) return fail(MISONET_EINVAL, "null argument");
-  o->taps = 10; o->delay = 3; o->iterations = 3; o->diag_load = 0.0; o->power_floor = 1e-10;
-  return MISONET_OK;
-}
-
-// host-side check of every field and of the geometry they are used with
-static int wpe_check(int B, int M, int T, int F, const misonet_wpe_opts* o) {
-  if (!o) return fail(MISONET_EINVAL, "null dereverberation options");
-  if (B < 1 || F < 1) return fail(MISONET_EINVAL, "B and F must be positive (got %d, %d)", B, F);
-  if (T < 2) return fail(MISONET_EINVAL, "T must be >= 2 (got %d)", T);
-  if (M < 1 || M > 8) return fail(MISONET_EINVAL, "M must be in [1, 8] (got %d)", M);
-  if (o->taps < 1 || (long long)M * o->taps > 80)
-    return fail(MISONET_EINVAL, "taps must be >= 1 and M * taps <= 80 (got taps %d, M %d)", o->taps, M);
-  if (o->delay < 1) return fail(MISONET_EINVAL, "delay must be >= 1 (got %d)", o->delay);
-  if (o->iterations < 1 || o->iterations > 10) return fail(MISONET_EINVAL, "iterations must be in [1, 10] (got %d)", o->iterations);
-  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
-    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
-  if (!(o->power_floor >= 0.0) || !std::isfinite(o->power_floor))
-    return fail(MISONET_EINVAL, "power_floor must be finite and >= 0 (got %g)", o->power_floor);
-  return MISONET_OK;
-}
-
-long long misonet_wpe_workspace_bytes(int B, int M, int T, int F, const misonet_wpe_opts* opts) {
-  if (wpe_check(B, M, T, F, opts)) return -1;
-  return wpe_ws_bytes(B, M, T, F, opts->taps);
-}
-
-int misonet_wpe(const void* mix, const float* power, int B, int M, int T, int F, const misonet_wpe_opts* opts, void* out,
-                void* ws, long long ws_bytes, misonet_stream stream) {
-  if (!mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
-  if (out == mix) return fail(MISONET_EINVAL, "out_dev must not be mix_dev");
-  { int r = wpe_check(B, M, T, F, opts); if (r) return r; }
-  if (ws_bytes < wpe_ws_bytes(B, M, T, F, opts->taps)) return fail(MISONET_ENOMEM, "workspace too small");
-  HIPCHK(launch_wpe(mix, power, B, M, T, F, opts->taps, opts->delay, opts->iterations, opts->diag_load, opts->power_floor, out,
-                    ws, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_wpe_debug(const void* ws, int B, int M, int F, const misonet_wpe_opts* opts, void* g, int* fail_dev,
-                      misonet_stream stream) {
-  if (!ws) return fail(MISONET_EINVAL, "null argument");
-  { int r = wpe_check(B, M, 2, F, opts); if (r) return r; }
-  HIPCHK(launch_wpe_debug(ws, B, M, F, opts->taps, g, fail_dev, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-long long misonet_pit_scratch_bytes(int B, int S, int F) {
-  if (B <= 0 || S <= 0 || F <= 0) return -1;
-  return (long long)B * S * S * (F + 1) * (long long)sizeof(double);
-}
-
-int misonet_pit_select(const void* anchor, const void* cand, int B, int S, int T, int F, int* sel, double* dist,
-                       long long dist_bytes, misonet_stream stream) {
-  if (!anchor || !cand || !sel || !dist) return fail(MISONET_EINVAL, "null argument (dist is required: B*S*S*(F+1) doubles)");
-  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "PIT alignment enumerates S! permutations: 1 <= num_spks <= 4 (got %d)", S);
-  if (B <= 0 || T <= 0 || F <= 0) return fail(MISONET_EINVAL, "B, T, F must be positive");
-  if (dist_bytes < misonet_pit_scratch_bytes(B, S, F))
-    return fail(MISONET_ENOMEM, "dist scratch %lld < %lld bytes (B*S*S*(F+1) doubles)", dist_bytes, misonet_pit_scratch_bytes(B, S, F));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const float* a = reinterpret_cast<const float*>(anchor);
-  const float* c = reinterpret_cast<const float*>(cand);
-  PitArgs p;
-  // [B,S,T,F] complex64: element (b, f, spk, t) at ((b*S + spk)*T + t)*F + f
-  p.a = {a, a + 1, 2LL * S * T * F, 2, 2LL * T * F, 2 * F};
-  p.b = {c, c + 1, 2LL * S * T * F, 2, 2LL * T * F, 2 * F};
-  p.B = B; p.F = F; p.T = T;
-  double* part = dist + (long long)B * S * S;          // per-bin partials [B][F][S][S] behind the result
-  HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
-  HIPCHK(launch_pit_pick(part, F, S, B, dist, sel, s));
-  return MISONET_OK;
-}
-
-// ---- continuous separation: speaker tracking across overlapping windows + cross-fade stitch (css.hip) -------------
-long long misonet_css_scratch_bytes(int K, int S, int F) {
-  if (K <= 0 || S <= 0 || F <= 0) return -1;
-  return (long long)(K - 1) * S * S * (F + 1) * (long long)sizeof(double);
-}
-
-int misonet_css_align(const void* est, int K, int S, int T, int F, int hop_frames, const int* perm0, int* perm,
-                      double* dist, long long dist_bytes, misonet_stream stream) {
-  if (!est || !perm) return fail(MISONET_EINVAL, "null argument");
-  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "the alignment enumerates S! permutations: 1 <= S <= 4 (got %d)", S);
-  if (F != 129) return fail(MISONET_EINVAL, "F must be 129 (got %d)", F);
-  if (K < 1 || K - 1 > 65535) return fail(MISONET_EINVAL, "K must be in [1, 65536] (got %d)", K);
-  if (hop_frames <= 0 || T - hop_frames < 5)
-    return fail(MISONET_EINVAL, "hop_frames must be positive and leave an overlap of at least 5 frames (T %d, hop %d)", T,
-                hop_frames);
-  if (K > 1 && !dist) return fail(MISONET_EINVAL, "null argument (dist is required for K > 1: (K-1)*S*S*(F+1) doubles)");
-  if (dist_bytes < misonet_css_scratch_bytes(K, S, F))
-    return fail(MISONET_ENOMEM, "dist scratch %lld < %lld bytes ((K-1)*S*S*(F+1) doubles)", dist_bytes,
-                misonet_css_scratch_bytes(K, S, F));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (K > 1) {
-    // est complex64 [K,S,T,F]: element (k, f, spk, t) at ((k*S + spk)*T + t)*F + f.  Item b = k - 1 of the distance launch:
-    // anchor = window k - 1 from frame hop_frames on, candidate = window k from frame 0, over the T - hop_frames shared frames
-    const float* e = reinterpret_cast<const float*>(est);
-    const long long win = 2LL * S * T * F;
-    const float* a = e + 2LL * hop_frames * F;
-    const float* c = e + win;
-    PitArgs p;
-    p.a = {a, a + 1, win, 2, 2LL * T * F, 2 * F};
-    p.b = {c, c + 1, win, 2, 2LL * T * F, 2 * F};
-    p.B = K - 1; p.F = F; p.T = T - hop_frames;
-    double* part = dist + (long long)(K - 1) * S * S;                // per-bin partials [K-1][F][S][S] behind D
-    HIPCHK(launch_pit_dist_k(p, S, 1, part, s));
-    HIPCHK(launch_pit_pick(part, F, S, K - 1, dist, perm + S, s));   // L_k -> row k of perm, composed in place below
-  }
-  HIPCHK(launch_css_chain(perm0, perm, K, S, s));
-  return MISONET_OK;
-}
-
-int misonet_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, int first, long long n_out,
-                       short* out_i16, float* out_f32, misonet_stream stream) {
-  if (!y || !perm || (!out_i16 && !out_f32)) return fail(MISONET_EINVAL, "null argument");
-  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "S must be in [1, 4] (got %d)", S);
-  if (K < 1) return fail(MISONET_EINVAL, "K must be positive (got %d)", K);
-  if (W <= 0 || hop <= 0 || 2LL * hop < W || hop > W - 256)
-    return fail(MISONET_EINVAL, "hop %d outside [W/2, W-256] for W = %d", hop, W);
-  const long long base = first ? 0 : hop;
-  const long long cap = (long long)(K - 1) * hop + W - base;
-  if (n_out < 0 || n_out > cap) return fail(MISONET_EINVAL, "n_out %lld outside [0, %lld]", n_out, cap);
-  if (n_out == 0) return MISONET_OK;
-  HIPCHK(launch_css_stitch(y, perm, K, S, W, hop, base, n_out, out_i16, out_f32, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- scores against clean references (score.hip) --------------------------------------------------------------------
-// One size serves both entry points: the wave partials [B][ceil(n / 4096)][2E + 2R + E R] and the per-bin partials
-// [B][F][E][R] (F <= 1024), whichever is larger for the value given.
-long long misonet_score_scratch_bytes(int B, int E, int R, long long n_or_F) {
-  if (B <= 0 || E <= 0 || R <= 0 || n_or_F <= 0) return -1;
-  const long long wave = score_wave_segments(n_or_F) * (2LL * E + 2LL * R + (long long)E * R);
-  const long long spec = (n_or_F < 1024 ? n_or_F : 1024) * (long long)E * R;
-  return (long long)B * (wave > spec ? wave : spec) * (long long)sizeof(double);
-}
-
-static int score_ranges(int B, int E, int R) {
-  if (E < 1 || E > 5) return fail(MISONET_EINVAL, "E must be in [1, 5] (got %d): up to 4 speakers and the mixture", E);
-  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
-  if (B < 1 || B > 65535) return fail(MISONET_EINVAL, "B must be in [1, 65535] (got %d)", B);
-  return MISONET_OK;
-}
-
-int misonet_score_wave(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
-                       const float* ref, long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R,
-                       long long n, const int* n_valid, double* stats, void* scratch, long long scratch_bytes,
-                       misonet_stream stream) {
-  if (!est || !ref || !stats || !scratch) return fail(MISONET_EINVAL, "null argument");
-  if (const int rc = score_ranges(B, E, R)) return rc;
-  if (n < 1 || n > (1LL << 40)) return fail(MISONET_EINVAL, "n must be in [1, 2^40] (got %lld)", n);
-  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
-    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
-  const long long need = misonet_score_scratch_bytes(B, E, R, n);
-  if (scratch_bytes < need)
-    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_score_scratch_bytes(B, E, R, n))", scratch_bytes, need);
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
-  HIPCHK(launch_score_wave(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, reinterpret_cast<double*>(scratch), stats,
-                           reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_score_spec(const void* est, long long est_sb, long long est_ss, long long est_st, const void* ref,
-                       long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, int T, int F,
-                       double* pair, int* perm, double* upit, void* scratch, long long scratch_bytes,
-                       misonet_stream stream) {
-  if (!est || !ref || !pair || !scratch) return fail(MISONET_EINVAL, "null argument");
-  if (const int rc = score_ranges(B, E, R)) return rc;
-  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
-  if (F < 1 || F > 1024) return fail(MISONET_EINVAL, "F must be in [1, 1024] (got %d)", F);
-  if ((perm || upit) && E != R)
-    return fail(MISONET_EINVAL, "the permutation pick needs as many estimates as references (E %d, R %d)", E, R);
-  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
-    return fail(MISONET_EINVAL, "strides must not be negative and the frame strides must be positive");
-  const long long need = misonet_score_scratch_bytes(B, E, R, F);
-  if (scratch_bytes < need)
-    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_score_scratch_bytes(B, E, R, F))", scratch_bytes, need);
-  // complex64 views, strides in complex elements, bins contiguous: element (b, f, source, t) at 2 (b sb + source ss + t st + f)
-  const float* a = reinterpret_cast<const float*>(est);
-  const float* c = reinterpret_cast<const float*>(ref);
-  PitArgs p;
-  p.a = {a, a + 1, 2 * est_sb, 2, 2 * est_ss, (int)(2 * est_st)};
-  p.b = {c, c + 1, 2 * ref_sb, 2, 2 * ref_ss, (int)(2 * ref_st)};
-  p.B = B; p.F = F; p.T = T;
-  HIPCHK(launch_score_spec(p, E, R, reinterpret_cast<double*>(scratch), pair, perm, upit,
-                           reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- BSS-eval energies (bss.hip) -----------------------------------------------------------------------------------------
-static int bss_ranges(int B, int E, int R, int Q) {
-  if (E < 1 || E > 4) return fail(MISONET_EINVAL, "E must be in [1, 4] (got %d)", E);
-  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
-  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
-  if (Q < 16 || Q > 1024 || Q % 16) return fail(MISONET_EINVAL, "Q must be a multiple of 16 in [16, 1024] (got %d)", Q);
-  return MISONET_OK;
-}
-
-// One size serves both calls: the correlation partials [B][ceil((n + 15) / 4096)][R R + R E + E][Q] and the systems of an item,
-// (R Q + 4) R Q + R (Q + 4) Q doubles, whichever is larger.
-long long misonet_bss_scratch_bytes(int B, int E, int R, long long n, int Q) {
-  if (B < 1 || B > 4096 || E < 1 || E > 4 || R < 1 || R > 4 || Q < 16 || Q > 1024 || Q % 16 || n < 1 || n > (1LL << 24)) return -1;
-  const long long corr = bss_corr_segments(n) * ((long long)R * R + (long long)R * E + E) * Q;
-  const long long sys = bss_solve_doubles(R, Q);
-  return (long long)B * (corr > sys ? corr : sys) * (long long)sizeof(double);
-}
-
-int misonet_bss_corr(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st, const float* ref,
-                     long long ref_sb, long long ref_ss, long long ref_st, int B, int E, int R, long long n,
-                     const int* n_valid, int Q, double* Rrr, double* Rre, double* Eee, void* scratch,
-                     long long scratch_bytes, misonet_stream stream) {
-  if (!est || !ref || !Rrr || !Rre || !Eee || !scratch) return fail(MISONET_EINVAL, "null argument");
-  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
-  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1)
-    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
-  const long long need = misonet_bss_scratch_bytes(B, E, R, n, Q);
-  if (scratch_bytes < need)
-    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_bss_scratch_bytes(B, E, R, n, Q))", scratch_bytes, need);
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
-  HIPCHK(launch_bss_corr(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, Q, reinterpret_cast<double*>(scratch), Rrr, Rre,
-                         Eee, reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_bss_solve(const double* Rrr, const double* Rre, const double* Eee, int B, int E, int R, int Q, double* T, double* A,
-                      int* info, void* scratch, long long scratch_bytes, misonet_stream stream) {
-  if (!Rrr || !Rre || !Eee || !T || !A || !info || !scratch) return fail(MISONET_EINVAL, "null argument");
-  if (const int rc = bss_ranges(B, E, R, Q)) return rc;
-  const long long need = misonet_bss_scratch_bytes(B, E, R, 1, Q);
-  if (scratch_bytes < need)
-    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_bss_scratch_bytes(B, E, R, 1, Q))", scratch_bytes, need);
-  HIPCHK(launch_bss_solve(Rrr, Rre, B, E, R, Q, T, A, info, reinterpret_cast<double*>(scratch),
-                          reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- STOI / ESTOI (stoi.hip) ------------------------------------------------------------------------------------------------
-// the table of the current device (window, twiddles, polyphase taps), built on first use: that one call allocates and copies
-// synchronously; every later call only queues kernels
-static std::atomic<double*> g_stoi_tab[MAX_DEV] = {};
-static std::mutex g_stoi_mu;
-static int get_stoi_table(const double** out) {
-  const int d = cur_dev();
-  if (!g_stoi_tab[d].load(std::memory_order_acquire)) {
-    std::lock_guard<std::mutex> lk(g_stoi_mu);
-    if (!g_stoi_tab[d].load(std::memory_order_acquire)) {
-      std::vector<double> t((size_t)stoi_table_count());
-      stoi_build_table(t.data());
-      double* p = nullptr;
-      HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), t.size() * sizeof(double)));
-      HIPCHK(hipMemcpy(p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice));
-      g_stoi_tab[d].store(p, std::memory_order_release);
-    }
-  }
-  *out = g_stoi_tab[d].load(std::memory_order_acquire);
-  return MISONET_OK;
-}
-
-long long misonet_stoi_resampled_len(long long n, int fs) { return stoi_resampled_len(n, fs); }
-
-int misonet_stoi_taps(int fs, double* taps_host) {
-  const int nt = stoi_taps(fs);
-  if (nt < 0) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
-  if (taps_host) {
-    std::vector<double> t((size_t)stoi_table_count());
-    stoi_build_table(t.data());
-    const int off = stoi_tap_offset(fs);
-    for (int i = 0; i < nt; ++i) taps_host[i] = t[(size_t)off + i];
-  }
-  return nt;
-}
-
-static bool stoi_ranges_ok(int B, int NS, int R, long long n10) {
-  return B >= 1 && B <= 4096 && R >= 1 && R <= 4 && NS - R >= 1 && NS - R <= 5 && n10 >= 1 && n10 <= 5 * (1LL << 22);
-}
-
-long long misonet_stoi_scratch_bytes(int B, int NS, int R, long long n10) {
-  if (!stoi_ranges_ok(B, NS, R, n10)) return -1;
-  return (long long)B * stoi_item_doubles(NS, R, n10) * (long long)sizeof(double);
-}
-
-int misonet_stoi_resample(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
-                          const float* ref, long long ref_sb, long long ref_ss, long long ref_st, const float* mix,
-                          long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid, int fs,
-                          double* x10, int* len10, misonet_stream stream) {
-  if (!est || !ref || !x10 || !len10) return fail(MISONET_EINVAL, "null argument");
-  if (E < 1 || E > 4) return fail(MISONET_EINVAL, "E must be in [1, 4] (got %d)", E);
-  if (R < 1 || R > 4) return fail(MISONET_EINVAL, "R must be in [1, 4] (got %d)", R);
-  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
-  if (fs != 8000 && fs != 10000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
-  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (est_sb < 0 || est_ss < 0 || est_st < 1 || ref_sb < 0 || ref_ss < 0 || ref_st < 1 || (mix && (mix_sb < 0 || mix_st < 1)))
-    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
-  const double* tab;
-  if (const int rc = get_stoi_table(&tab)) return rc;
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
-  HIPCHK(launch_stoi_resample(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, x10, len10,
-                              reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_stoi_measure(const double* x10, const int* len10, int B, int NS, int R, long long n10, double* out, int* frames,
-                         void* scratch, long long scratch_bytes, misonet_stream stream) {
-  if (!x10 || !out || !frames || !scratch) return fail(MISONET_EINVAL, "null argument");
-  if (!stoi_ranges_ok(B, NS, R, n10))
-    return fail(MISONET_EINVAL, "1 <= B <= 4096, 1 <= R <= 4, 1 <= NS - R <= 5, 1 <= n10 <= 5 * 2^22 (got %d, %d, %d, %lld)", B,
-                R, NS - R, n10);
-  const long long need = misonet_stoi_scratch_bytes(B, NS, R, n10);
-  if (scratch_bytes < need)
-    return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (misonet_stoi_scratch_bytes(B, NS, R, n10))", scratch_bytes, need);
-  const double* tab;
-  if (const int rc = get_stoi_table(&tab)) return rc;
-  HIPCHK(launch_stoi_measure(x10, len10, B, NS, R, n10, tab, out, frames, reinterpret_cast<double*>(scratch),
-                             reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-// ---- STFT front-end ------------------------------------------------------------------------------------------------
-// twiddle table + the > 64 KB dynamic-LDS attribute of stft_pack_k, per device (the table lives in the memory of the
-// device that was current when it was first needed)
-// (atomic: the getters read them outside the mutex -- acquire / release, a reader sees the table fully built or not at all)
-static std::atomic<float*> g_twid[MAX_DEV] = {};
-static std::atomic<float*> g_itwid[MAX_DEV] = {};
-static std::mutex g_front_mu;
-// Builds both tables on the CURRENT device (hipMalloc + synchronous copy + kernel attributes).  misonet_net_commit and
-// misonet_pipeline_create call it, so every path that runs a network has them before its first asynchronous call -- a HIP
-// graph may capture misonet_pipeline_run_wav / misonet_istft as the first call of a process.  Idempotent, thread-safe.
-static int frontend_init() {
-  const int d = cur_dev();
-  std::lock_guard<std::mutex> lk(g_front_mu);
-  if (!g_twid[d].load(std::memory_order_acquire)) {
-    std::vector<float> tw((size_t)stft_twiddle_count());
-    stft_build_twiddles(tw.data());
-    float* p = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), tw.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(stft_init());
-    g_twid[d].store(p, std::memory_order_release);
-  }
-  if (!g_itwid[d].load(std::memory_order_acquire)) {
-    std::vector<float> tw((size_t)istft_twiddle_count());
-    istft_build_twiddles(tw.data());
-    float* p = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), tw.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(p, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(istft_init());
-    g_itwid[d].store(p, std::memory_order_release);
-  }
-  return MISONET_OK;
-}
-int misonet_frontend_init(void) { return frontend_init(); }
-
-// the table of the current device; a stand-alone misonet_stft / misonet_istft without any committed network on this device
-// builds it on first use (that one call allocates and synchronises: not inside a stream capture; include/misonet.h)
-static int get_twiddles(const float** out) {
-  const int d = cur_dev();
-  if (!g_twid[d].load(std::memory_order_acquire)) { int r = frontend_init(); if (r) return r; }
-  *out = g_twid[d].load(std::memory_order_acquire);
-  return MISONET_OK;
-}
-static int get_itwiddles(const float** out) {
-  const int d = cur_dev();
-  if (!g_itwid[d].load(std::memory_order_acquire)) { int r = frontend_init(); if (r) return r; }
-  *out = g_itwid[d].load(std::memory_order_acquire);
-  return MISONET_OK;
-}
-
-int misonet_istft(const void* spec_dev, int N, int T, void* out_i16_dev, float* out_f32_dev, misonet_stream stream) {
-  if (!spec_dev || (!out_i16_dev && !out_f32_dev)) return fail(MISONET_EINVAL, "null argument");
-  if (N <= 0 || T < 2) return fail(MISONET_EINVAL, "N must be positive and T >= 2 (got %d, %d)", N, T);
-  const float* tw;
-  int r = get_itwiddles(&tw);
-  if (r) return r;
-  HIPCHK(launch_istft(spec_dev, N, T, tw, reinterpret_cast<short*>(out_i16_dev), out_f32_dev,
-                      reinterpret_cast<hipStream_t>(stream)));
-  return MISONET_OK;
-}
-
-int misonet_stft_frames(int n_samples) { return n_samples > 0 ? n_samples / 64 + 1 : -1; }
-
-long long misonet_stft_workspace_bytes(int B, int M, int n_samples) {
-  const int T = misonet_stft_frames(n_samples);
-  if (B <= 0 || M <= 0 || T <= 0) return -1;
-  return (long long)B * 2 * M * 129 * frames_pitch(T) * 4;
-}
-
-int misonet_stft(const float* wav_dev, int B, int n_samples, int M, void* out_c64, void* ws, long long ws_bytes,
-                 misonet_stream stream) {
-  if (!wav_dev || !out_c64 || !ws) return fail(MISONET_EINVAL, "null argument");
-  if (B <= 0 || M <= 0 || M > 64 || n_samples <= 0) return fail(MISONET_EINVAL, "bad B / M / n_samples");
-  if (ws_bytes < misonet_stft_workspace_bytes(B, M, n_samples)) return fail(MISONET_ENOMEM, "workspace too small");
-  const int T = misonet_stft_frames(n_samples), Tp = frames_pitch(T), F = 129;
-  const float* tw;
-  int r = get_twiddles(&tw);
-  if (r) return r;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* planar = reinterpret_cast<float*>(ws);
-  const long long bs = 2LL * M * F * Tp;
-  HIPCHK(launch_stft_pack(wav_dev, B, n_samples, M, T, tw, planar, bs, Tp, F, 0, M, 1, s));
-  HIPCHK(launch_unpack(planar, bs, Tp, M, T, F, reinterpret_cast<float2*>(out_c64), B, nullptr, s));
-  return MISONET_OK;
-}
-
-// ---- fused pipeline ----------------------------------------------------------------------------------------------
-struct misonet_pipeline {
-  misonet_net* n1;
-  misonet_net* n3;
-  int M, S, ref_ch;
-  float epsi;
-  misonet_bf_opts bf;      // the beamformer of step 5 (misonet_pipeline_set_beamformer); create: the defaults with epsi
-};
-
-struct PipeLayout {
-  Layout L1, L3;
-  long long off_ws1, off_ws3, off_clean, off_dist, off_sel, off_mvdr, total;
-  long long clean_bstride;
-};
-
-static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
-  PipeLayout P;
-  // MISO3 runs in MISO1's workspace (MISO1 is finished when MISO3 starts; what the steps in between read of it -- its input
-  // and output planes -- is consumed before the MISO3 forward writes anything): only the MISO3 INPUT, which those steps
-  // build while MISO1's planes are still being read, has its own memory
-  P.L1 = make_layout(p->n1, B * p->M, T);
-  if (p->n3) P.L3 = make_layout(p->n3, B * p->S, T, true);
-  else { P.L3 = Layout(); P.L3.total_bytes = 0; }       // separation-only pipeline: no MISO3 workspace, no MISO3 input
-  const int F = p->n1->cfg.n_freq, Tp = P.L1.Tp;
-  long long o = 256;                                   // [0]: nan flag
-  // PIT distances [B*M + B][S][S] followed by their per-bin partials [B*M + B][F][S][S] (mvdr.hip pit_dist_k)
-  P.off_dist = o;  o += align_up((long long)(B * p->M + B) * p->S * p->S * (F + 1) * 8, 256);
-  P.off_sel = o;   o += align_up((long long)(B * p->M * p->S * 2 + B * p->S) * 4, 256);
-  P.off_mvdr = o;  o += align_up(bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
-  P.clean_bstride = (long long)2 * p->S * F * Tp;
-  P.off_clean = o; o += align_up(P.clean_bstride * B * 4, 256);
-  P.L3.in_ext_bstride = p->n3 ? (long long)p->n3->cfg.in_ch * F * Tp : 0;
-  const long long in3_bytes = align_up(P.L3.in_ext_bstride * B * p->S * 4, 256);
-  P.off_ws1 = o;   o += align_up(std::max(P.L1.total_bytes, P.L3.total_bytes), 256);
-  P.off_ws3 = P.off_ws1;
-  P.L3.in_ext_off = o - P.off_ws3;                     // relative to the (shared) workspace base
-  o += in3_bytes;
-  P.total = o;
-  return P;
-}
-
-int misonet_pipeline_create(misonet_net* n1, misonet_net* n3, int num_mic, int num_spk, int ref_ch, float epsi,
-                            misonet_pipeline** out) {
-  // n3 == NULL: a separation-only pipeline (MISO1_Inference + alignments: the body shared by the reference's
-  // Tester_Beamforming, tester.py:340-449) -- misonet_pipeline_run then only accepts out == NULL, bf_out == NULL
-  if (!n1 || !out) return fail(MISONET_EINVAL, "null argument");
-  if (num_spk < 1 || num_spk > 4) return fail(MISONET_EINVAL, "num_spk must be in [1, 4] (PIT enumerates num_spk! permutations)");
-  if (num_mic < 2 || num_mic > 8) return fail(MISONET_EINVAL, "num_mic must be in [2, 8]");
-  if (ref_ch < 0 || ref_ch >= num_mic) return fail(MISONET_EINVAL, "ref_ch out of range");
-  if (n1->cfg.in_ch != 2 * num_mic || n1->cfg.out_ch != 2 * num_spk)
-    return fail(MISONET_EINVAL, "MISO_1 geometry does not match num_mic/num_spk");
-  if (n3 && (n3->cfg.in_ch != 2 * (num_mic + 2) || n3->cfg.out_ch != 2))
-    return fail(MISONET_EINVAL, "MISO_3 geometry must be in_ch = 2*(num_mic+2), out_ch = 2");
-  { int rf = frontend_init(); if (rf) return rf; }
-  misonet_pipeline* p = new misonet_pipeline{n1, n3, num_mic, num_spk, ref_ch, epsi};
-  misonet_bf_opts_default(&p->bf);
-  p->bf.epsi = epsi;
-  *out = p;
-  return MISONET_OK;
-}
-
-int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* opts) {
-  if (!p) return fail(MISONET_EINVAL, "null argument");
-  { int r = bf_opts_check(opts, p->M); if (r) return r; }
-  p->bf = *opts;
-  return MISONET_OK;
-}
-int misonet_pipeline_destroy(misonet_pipeline* p) { delete p; return MISONET_OK; }
-
-long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T) {
-  if (!p || B <= 0 || T <= 0) return -1;
-  return pipe_layout(p, B, T).total;
-}
-
-static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* clean, const float* wav,
-                             const float* clean_wav, int n_samples, int B, int T, void* out, void* bf_out,
-                             void* miso1_out, void* ws, long long ws_bytes, misonet_stream stream) {
-  if (!p || (!mix && !wav) || (!out && !miso1_out) || !ws) return fail(MISONET_EINVAL, "null argument");
-  if (!p->n1->committed || (p->n3 && !p->n3->committed)) return fail(MISONET_ESTATE, "networks not committed");
-  if (!p->n3 && (out || bf_out))
-    return fail(MISONET_ESTATE, "this pipeline was created without MISO_3 (separation only): out and bf_out must be NULL");
-  if (B <= 0 || T <= 0) return fail(MISONET_EINVAL, "B and T must be positive");
-  const PipeLayout P = pipe_layout(p, B, T);
-  if (ws_bytes < P.total) return fail(MISONET_ENOMEM, "workspace %lld < %lld bytes", ws_bytes, P.total);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  char* base = reinterpret_cast<char*>(ws);
-  void* ws1 = base + P.off_ws1;
-  void* ws3 = base + P.off_ws3;
-  const int M = p->M, S = p->S, F = p->n1->cfg.n_freq, Tp = P.L1.Tp;
-  misonet_net *n1 = p->n1, *n3 = p->n3;
-  double* dist_shift = reinterpret_cast<double*>(base + P.off_dist);          // [B*M][S][S]
-  double* dist_clean = dist_shift + (long long)B * M * S * S;                  // [B][S][S]
-  double* part_shift = dist_clean + (long long)B * S * S;                      // [B*M][F][S][S]
-  double* part_clean = part_shift + (long long)B * M * F * S * S;              // [B][F][S][S]
-  int* sel_shift = reinterpret_cast<int*>(base + P.off_sel);                   // [B*M][S]
-  int* sel_final = sel_shift + (long long)B * M * S;                           // [B*M][S]
-  int* sel_clean = sel_final + (long long)B * M * S;                           // [B][S]
-  HIPCHK(hipMemsetAsync(base, 0, 256, s));                                     // nan flag
-
-  // 1. MISO1_Inference: the M circular shifts as one batch of B*M samples (tester.py:1033-1051)
-  float* in1 = buf_ptr(P.L1, ws1, B_IN);
-  const long long in1_bs = bstride(n1, P.L1, B_IN);
-  const float* tw = nullptr;
-  if (wav) { int rt = get_twiddles(&tw); if (rt) return rt; }
-  if (wav) HIPCHK(launch_stft_pack(wav, B, n_samples, M, T, tw, in1, in1_bs, Tp, F, 0, M, M, s));
-  else HIPCHK(launch_pack(reinterpret_cast<const float2*>(mix), B, M, T, F, in1, in1_bs, Tp, 0, M, M, s));
-  int r = forward_planar(n1, P.L1, ws1, s);
-  if (r) return r;
-  float* out1 = buf_ptr(P.L1, ws1, B_OUT);
-  const long long out1_bs = bstride(n1, P.L1, B_OUT);
-  const long long plane = (long long)F * Tp;
-
-  // 2. align the speakers of every shift to the reference-mic forward (tester.py:1043-1065)
-  {
-    PitArgs q;
-    const float* anc = out1 + (long long)p->ref_ch * out1_bs;
-    q.a = {anc, anc + S * plane, (long long)M * out1_bs, Tp, plane, 1};
-    q.b = {out1, out1 + S * plane, out1_bs, Tp, plane, 1};
-    q.B = B; q.F = F; q.T = T;
-    HIPCHK(launch_pit_dist_k(q, S, M, part_shift, s));
-    HIPCHK(launch_pit_pick(part_shift, F, S, B * M, dist_shift, sel_shift, s));
-  }
-  // 3. align to the clean references at ref_ch (tester.py:889-915), optional
-  if (clean || clean_wav) {
-    float* cl = reinterpret_cast<float*>(base + P.off_clean);
-    if (clean_wav) HIPCHK(launch_stft_pack(clean_wav, B, n_samples, S, T, tw, cl, P.clean_bstride, Tp, F, 0, S, 1, s));
-    else HIPCHK(launch_pack(reinterpret_cast<const float2*>(clean), B, S, T, F, cl, P.clean_bstride, Tp, 0, S, 1, s));
-    // anchors = clean sources; candidates = shift-aligned ref-mic estimates.  The ref-mic forward is never
-    // permuted by step 2 (its distance matrix has a zero diagonal), so the raw OUT1 planes are the candidates.
-    PitArgs q;
-    const float* cand = out1 + (long long)p->ref_ch * out1_bs;
-    q.a = {cl, cl + S * plane, P.clean_bstride, Tp, plane, 1};
-    q.b = {cand, cand + S * plane, (long long)M * out1_bs, Tp, plane, 1};
-    q.B = B; q.F = F; q.T = T;
-    HIPCHK(launch_pit_dist_k(q, S, 1, part_clean, s));
-    HIPCHK(launch_pit_pick(part_clean, F, S, B, dist_clean, sel_clean, s));
-  }
-  HIPCHK(launch_compose_sel(sel_shift, (clean || clean_wav) ? sel_clean : nullptr, B, M, S, sel_final, s));
-
-  if (out) {   // out == NULL: separation only (MISO1_Inference + alignments), e.g. for the utterance-wise beamformer
-    // 4. MISO3 input = [mixture | beamformer | MISO1 estimate at ref_ch] (tester.py:936-939), B*S samples
-    float* in3 = buf_ptr(P.L3, ws3, B_IN);
-    const long long in3_bs = bstride(n3, P.L3, B_IN);
-    HIPCHK(launch_assemble3(in1, in1_bs, out1, out1_bs, sel_final, B, M, S, p->ref_ch, F, Tp, in3, in3_bs, s));
-
-    // 5. MVDR per aligned speaker (tester.py:917-924, 1071-1136); writes the beamformer planes of the MISO3 input
-    {
-      MvdrArgs a;
-      a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};   // shift-0 sample = un-rolled mixture
-      a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;
-      a.src = {nullptr, nullptr, 0, 0, 0, 1};
-      a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
-      bf_opts_apply(p->bf, a);
-      COut co = {in3 + (long long)M * plane, in3 + (long long)(2 * M + 2) * plane, (long long)S * in3_bs, in3_bs, 1, Tp};
-      ProfScope ps(s, PK_MVDR);
-      HIPCHK(launch_mvdr(a, co, base + P.off_mvdr, s));
-    }
-    // (the aligned MISO1 estimates leave the shared workspace before MISO3 overwrites it)
-    if (miso1_out)
-      HIPCHK(launch_unpack_ex(out1, out1_bs, Tp, S, T, F, 0, S, 1, M, sel_final, reinterpret_cast<float2*>(miso1_out),
-                              B * S * M, reinterpret_cast<int*>(base), s));
-    // 6. MISO3 per speaker (tester.py:1231-1244), in MISO1's workspace
-    r = forward_planar(n3, P.L3, ws3, s);
-    if (r) return r;
-    HIPCHK(launch_unpack(buf_ptr(P.L3, ws3, B_OUT), bstride(n3, P.L3, B_OUT), Tp, 1, T, F, reinterpret_cast<float2*>(out),
-                         B * S, reinterpret_cast<int*>(base), s));
-    if (bf_out)
-      HIPCHK(launch_unpack_ex(in3, in3_bs, Tp, 1, T, F, M, 2 * M + 2, 0, 1, nullptr,
-                              reinterpret_cast<float2*>(bf_out), B * S, reinterpret_cast<int*>(base), s));
-  } else if (miso1_out) {
-    HIPCHK(launch_unpack_ex(out1, out1_bs, Tp, S, T, F, 0, S, 1, M, sel_final, reinterpret_cast<float2*>(miso1_out),
-                            B * S * M, reinterpret_cast<int*>(base), s));
-  }
-  return MISONET_OK;
-}
-
-int misonet_pipeline_run(misonet_pipeline* p, const void* mix, const void* clean, int B, int T, void* out, void* bf_out,
-                         void* miso1_out, void* ws, long long ws_bytes, misonet_stream stream) {
-  return pipeline_run_impl(p, mix, clean, nullptr, nullptr, 0, B, T, out, bf_out, miso1_out, ws, ws_bytes, stream);
-}
-
-int misonet_pipeline_run_wav(misonet_pipeline* p, const float* wav, const float* clean_wav, int B, int n_samples,
-                             void* out, void* bf_out, void* miso1_out, void* ws, long long ws_bytes,
-                             misonet_stream stream) {
-  if (n_samples <= 0) return fail(MISONET_EINVAL, "n_samples must be positive");
-  return pipeline_run_impl(p, nullptr, nullptr, wav, clean_wav, n_samples, B, misonet_stft_frames(n_samples), out, bf_out,
-                           miso1_out, ws, ws_bytes, stream);
-}
-
-int misonet_pipeline_check(misonet_pipeline* p, const void* ws, misonet_stream stream) {
-  if (!p || !ws) return fail(MISONET_EINVAL, "null argument");
-  int flag = 0;
-  HIPCHK(hipMemcpyAsync(&flag, ws, sizeof(int), hipMemcpyDeviceToHost, reinterpret_cast<hipStream_t>(stream)));
-  HIPCHK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)));
-  if (flag) return fail(MISONET_ENAN, "NaN in pipeline output");
-  return MISONET_OK;
 }
 
 // ---- per-launch profiling -----------------------------------------------------------------------------------------
