@@ -129,23 +129,48 @@ def tcn_forward(x, sd, taps: Optional[Dict] = None, norm_type: str = "IN"):
     return x
 
 
+def enc0_conv(x, sd):
+    """init_Conv2d_ (model.py:401-406): the first conv alone, no activation / norm.  [B, Cin, T, 129] -> [B, C0, T, 127]"""
+    return F.conv2d(x, _t(sd, "encoders.0.0.conv2d.weight"), _t(sd, "encoders.0.0.conv2d.bias"), stride=(1, 1), padding=(1, 0))
+
+
+def encoder_level(b, x, sd, taps: Optional[Dict] = None, from_conv: bool = False):
+    """Encoder level b = 0..6 on its input x (the previous level's output; level 0: the network input, or with ``from_conv`` the
+    output of enc0_conv) -> the level's output = the tap ``enc{b}``."""
+    if b == 0:
+        if not from_conv:
+            x = enc0_conv(x, sd)
+            if taps is not None:
+                taps["enc0_conv"] = x
+        return _dense_block(x, sd, "encoders.0.1")
+    stride = (1, 1) if b == 6 else (1, 2)      # model.py:49-52
+    x = _conv_elu_in(x, _t(sd, f"encoders.{b}.0.net.0.weight"), _t(sd, f"encoders.{b}.0.net.0.bias"), stride, (1, 0))
+    if b < 5:
+        x = _dense_block(x, sd, f"encoders.{b}.1")
+    return x
+
+
+def decoder_level(b, de_prev, skip, sd):
+    """Decoder level b = 0..6 on the previous decoder output (level 0: the TCN output [B, 128, T, 1]) and the skip connection
+    ``enc{6 - b}`` -> the level's output = the tap ``dec{b}``."""
+    de = torch.cat((de_prev, skip), dim=1)          # model.py:99
+    if b >= 2:
+        de = _dense_block(de, sd, f"decoders.{b}.0")
+        if b == 6:
+            return F.conv_transpose2d(de, _t(sd, "decoders.6.1.deconv2d.weight"), _t(sd, "decoders.6.1.deconv2d.bias"),
+                                      stride=(1, 1), padding=(1, 0))   # last_Deconv2d_: no act / norm
+        return _conv_elu_in(de, _t(sd, f"decoders.{b}.1.net.0.weight"), _t(sd, f"decoders.{b}.1.net.0.bias"),
+                            (1, 2), (1, 0), transposed=True)
+    stride = (1, 1) if b == 0 else (1, 2)        # model.py:68-71
+    return _conv_elu_in(de, _t(sd, f"decoders.{b}.0.net.0.weight"), _t(sd, f"decoders.{b}.0.net.0.bias"),
+                        stride, (1, 0), transposed=True)
+
+
 def trunk_forward(x, sd, taps: Optional[Dict] = None, norm_type: str = "IN"):
     """x: float [B, Cin, T, 129] (real||imag channels) -> float [B, Cout, T, 129]."""
     xs = []
     for b in range(7):
-        if b == 0:
-            # init_Conv2d_: no activation / norm, model.py:401-406
-            x = F.conv2d(x, _t(sd, "encoders.0.0.conv2d.weight"), _t(sd, "encoders.0.0.conv2d.bias"),
-                         stride=(1, 1), padding=(1, 0))
-            if taps is not None:
-                taps["enc0_conv"] = x
-            x = _dense_block(x, sd, "encoders.0.1")
-        else:
-            stride = (1, 1) if b == 6 else (1, 2)      # model.py:49-52
-            x = _conv_elu_in(x, _t(sd, f"encoders.{b}.0.net.0.weight"), _t(sd, f"encoders.{b}.0.net.0.bias"),
-                             stride, (1, 0))
-            if b < 5:
-                x = _dense_block(x, sd, f"encoders.{b}.1")
+        x = encoder_level(b, x, sd, taps)
         xs.append(x)
         if taps is not None:
             taps[f"enc{b}"] = x
@@ -157,19 +182,7 @@ def trunk_forward(x, sd, taps: Optional[Dict] = None, norm_type: str = "IN"):
         taps["tcn_out"] = x
     de = x.unsqueeze(-1)
     for b in range(7):
-        de = torch.cat((de, xs[6 - b]), dim=1)          # model.py:99
-        if b >= 2:
-            de = _dense_block(de, sd, f"decoders.{b}.0")
-            if b == 6:
-                de = F.conv_transpose2d(de, _t(sd, "decoders.6.1.deconv2d.weight"), _t(sd, "decoders.6.1.deconv2d.bias"),
-                                        stride=(1, 1), padding=(1, 0))   # last_Deconv2d_: no act / norm
-            else:
-                de = _conv_elu_in(de, _t(sd, f"decoders.{b}.1.net.0.weight"), _t(sd, f"decoders.{b}.1.net.0.bias"),
-                                  (1, 2), (1, 0), transposed=True)
-        else:
-            stride = (1, 1) if b == 0 else (1, 2)        # model.py:68-71
-            de = _conv_elu_in(de, _t(sd, f"decoders.{b}.0.net.0.weight"), _t(sd, f"decoders.{b}.0.net.0.bias"),
-                              stride, (1, 0), transposed=True)
+        de = decoder_level(b, de, xs[6 - b], sd)
         if taps is not None:
             taps[f"dec{b}"] = de
     return de
