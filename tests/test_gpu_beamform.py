@@ -7,7 +7,8 @@ the same CPU experiment (beamform_parts with the covariances accumulated in comp
 order) moves out and w by <= 6.1e-6 over the four small shapes and by 1.1e-5 at (3, 129, 6, 1001), for every kind and option
 set below, so the bar of the existing MVDR test, rel-L2 < 1e-4, sits an order of magnitude over the floor of the number
 format and is not taken from what the kernels give.  T >= 2 M everywhere: with T < M the
-result is set by eps."""
+result is set by eps.
+Stage by stage (eig, phase, solve, apply at K = 4 float32 yardsticks), odd M and the frame-loop seams: tests/test_gpu_beamform_stages.py."""
 import ctypes as C
 import os
 
