@@ -118,25 +118,48 @@ def test_conv_levels_on_their_own_input_vs_float64(net, mode, T):
     _check_levels(sd, _planar(x), taps, conv_ref.LEVELS, (0, 1) if T == 65 else (1,), "MISO_1", mode, T)
 
 
-@pytest.mark.parametrize("mode", MODES)
-def test_miso3_first_layer_on_its_own_input_vs_float64(mode):
-    """16 input channels: the other first-layer shape of DIRECT, W1D and X6_FIRST"""
+def _first_layer(model, M, mode):
+    """the first conv and the first encoder level of MISO_1 (2 M input channels) / MISO_3 (2 (M + 2)) with M microphones on their own
+    input, T = 65, B = 2, both samples"""
     _need_gpu()
     import misonet_amd as mz
     from misonet_amd import weights as W
     T = 65
-    sd3 = W.make_state_dict(W.miso3_spec(), seed=4)
-    r = np.random.default_rng(6400 + T)
-    x, a, b = [(r.standard_normal((2, c, T, 129)) + 1j * r.standard_normal((2, c, T, 129))).astype(np.complex64) for c in (6, 1, 1)]
-    for v in (x, a, b):
+    segs = (M,) if model == "MISO_1" else (M, 1, 1)
+    spec = W.miso1_spec(num_ch=M) if model == "MISO_1" else W.miso3_spec(num_ch=M)
+    sd = W.make_state_dict(spec, seed=4)
+    r = np.random.default_rng(6400 + T + (0 if (model, M) == ("MISO_3", 6) else 100 * M + (1000 if model == "MISO_1" else 0)))
+    xs = [(r.standard_normal((2, c, T, 129)) + 1j * r.standard_normal((2, c, T, 129))).astype(np.complex64) for c in segs]
+    for v in xs:
         v[1] *= 3.0
-    m3 = mz.MISO_3(1, 6, 7, list(W.DEFAULT_EN_CH), list(W.DEFAULT_DE_CH), "IN").cuda(0)
-    m3.load_state_dict(sd3)
-    m3.eval().keep_activations(True).set_precision(mode)
-    y = m3(torch.from_numpy(x).cuda(), torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
-    assert tuple(y.shape) == (2, 1, T, 129)
-    taps = _taps(m3, 2, T, ("enc0_conv", "enc0"))
-    _check_levels(sd3, _planar(x, a, b), taps, ("enc0_conv", "enc0"), (0, 1), "MISO_3", mode, T)
+    cls = mz.MISO_1 if model == "MISO_1" else mz.MISO_3
+    m = cls(2 if model == "MISO_1" else 1, M, 7, list(W.DEFAULT_EN_CH), list(W.DEFAULT_DE_CH), "IN").cuda(0)
+    m.load_state_dict(sd)
+    m.eval().keep_activations(True).set_precision(mode)
+    y = m(*[torch.from_numpy(v).cuda() for v in xs])
+    assert tuple(y.shape) == (2, m.num_spks, T, 129)
+    assert sd["encoders.0.0.conv2d.weight"].shape[1] == 2 * sum(segs)
+    taps = _taps(m, 2, T, ("enc0_conv", "enc0"))
+    _check_levels(sd, _planar(*xs), taps, ("enc0_conv", "enc0"), (0, 1), f"{model} M={M} Cin={2 * sum(segs)}", mode, T)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_miso3_first_layer_on_its_own_input_vs_float64(mode):
+    """16 input channels: the other first-layer shape of DIRECT, W1D and X6_FIRST"""
+    _first_layer("MISO_3", 6, mode)
+
+
+# the first-layer input channels the fused pipeline can create besides 12 and 16 (misonet_pipeline_create admits 2-8 microphones):
+# 4, 10, 14 are no multiples of the 8-channel chunk; 18 and 20 are past conv3x3_x6_first (Cin <= 16), so in bf16x6 the first layer
+# is the exact-f32 kernel writing the oct3 layout
+FIRST_SHAPES = [("MISO_1", 2), ("MISO_1", 5), ("MISO_1", 7), ("MISO_3", 2), ("MISO_3", 5), ("MISO_3", 7), ("MISO_3", 8)]
+
+
+@pytest.mark.parametrize("model,M", FIRST_SHAPES, ids=[f"{n}-M{M}" for n, M in FIRST_SHAPES])
+@pytest.mark.parametrize("mode", MODES)
+def test_first_layer_at_every_admitted_microphone_count_vs_float64(mode, model, M):
+    """Cin = 4, 10, 14 (MISO_1) and 8, 14, 18, 20 (MISO_3): same taps, same bound as the 12 and 16 channels above"""
+    _first_layer(model, M, mode)
 
 
 # ---- b. the workspace's previous contents ---------------------------------------------------------------------------------------

@@ -276,6 +276,23 @@ def test_conv_plan_kernel_per_layer(in_ch, out_ch, mode):
     lib.misonet_net_destroy(h)
 
 
+@pytest.mark.parametrize("in_ch", [4, 8, 10, 12, 14, 16, 18, 20])
+def test_first_layer_kernel_at_every_admitted_microphone_count(in_ch):
+    """misonet_pipeline_create admits 2-8 microphones: first layers of 4 ... 16 (MISO_1) and 8 ... 20 (MISO_3) input channels.  f32 runs
+    them on the direct kernel, f32w in its 1-D Winograd form (Cin < 24), bf16x6 on conv3x3_x6_first up to 16 channels and on the
+    direct kernel writing the oct3 layout above (18, 20); every other layer of bf16x6 reads oct3 and is X6 either way."""
+    L, rc, h = _make(in_ch=in_ch, out_ch=2)
+    assert rc == 0
+    lib = L.lib()
+    kind = (C.c_int * 64)()
+    for mode, first in ((0, DIRECT), (5, W1D), (3, X6_FIRST if in_ch <= 16 else DIRECT)):
+        assert lib.misonet_net_conv_plan(h, mode, 64, kind) == 64
+        assert kind[0] == first, (in_ch, mode, kind[0])
+        if mode == 3:
+            assert all(k == X6 for k in kind[1:64])
+    lib.misonet_net_destroy(h)
+
+
 def test_conv_plan_rejects_modes_not_in_build():
     L, rc, h = _make()
     lib = L.lib()
