@@ -1,6 +1,7 @@
 """GPU tests of the on-device STFT front-end (csrc/stft.hip) against the reference's SciPy contract
 (dataloader/data.py:505-522,540-544, restated in oracle/pipeline_oracle.stft_chunk) and of the waveform entry of the
 pipeline."""
+# The float64 bounds of stft_pack_k / istft_k at every tile edge, per frame, bin and hop, are in tests/test_gpu_stft.py.
 import numpy as np
 import pytest
 import torch
