@@ -208,6 +208,45 @@ int misonet_wpe(const void* mix_dev, const float* power_dev, int B, int M, int T
 int misonet_wpe_debug(const void* ws_dev, int B, int M, int F, const misonet_wpe_opts* opts, void* g_c128_dev, int* fail_dev,
                       misonet_stream stream);
 
+/* ---- WPD (ABI 530) ---------------------------------------------------------------------------------------------------
+ * The weighted power minimisation distortionless response convolutional beamformer (Nakatani & Kinoshita 2019) in the
+ * mask-based form of Zhang, Boeddeker et al. 2020 (ESPnet's "wpd"): one filter per (item b, bin f) that dereverberates and
+ * beamforms in one solve, driven by the power of the SOURCE estimate.  Y = mix[b, f] and S = src[b, f] are [M, T]:
+ *   Z[(k M + m), t] = Y[m, t - delay - k]   (k = 0 .. taps - 1; zero before the start: WPE's Z)
+ *   ybar[t] = [Y[:, t]; Z[:, t]], order K = M (taps + 1)
+ *   p[t] = mean_m |S[m, t]|^2,  w[t] = 1 / max(p[t], power_floor max_t p[t])
+ *   R = sum_t w[t] ybar[t] ybar[t]^H,  R += diag_load tr(R) / K I
+ *   Phi_s = S S^H / T (Hermitian, as misonet_beamform makes it), Phibar = Phi_s in the top-left block of a K x K zero matrix
+ *   A = R^-1 Phibar (Cholesky R = L L^H, two triangular solves),  wbar = A[:, ref_ch] / tr(A)  (the complex trace, as "souden")
+ *   out[t] = wbar^H ybar[t]
+ * One pass: p is not re-estimated from the output, and there is no steering-vector form.  Everything after the complex64 loads is
+ * float64 (the correlations on the float64 matrix pipe); out is rounded to complex64 once, on the store.  Every sum runs in a
+ * fixed order, without atomics: the bits of a bin depend neither on B nor on its position in the batch (nor, in the fused
+ * pipeline, on the number of speakers).
+ * A (b, f) FAILS if a Cholesky pivot is not finite or not > 0 (the all-zero bin or source: w infinite, R not finite) or if tr(A) is
+ * not finite or is 0: then wbar = 0, out = 0 and fail[b, f] = 1.  Nothing is clamped.
+ * src_dev, mix_dev, out_dev: the layouts of misonet_beamform (complex64 [B, F, M, T] and [B, T, F]).  2 <= M <= 8, taps >= 1,
+ * delay >= 1, K = M (taps + 1) <= 88 (the order the Gram scheme reaches; its K x K factor, right-hand sides and frame windows take
+ * 156 KB of the 160 KB of LDS at M = 8, taps = 10), T > delay + taps - 1, 0 <= ref_ch < M, diag_load and power_floor finite and
+ * >= 0: anything else is refused on the host with MISONET_EINVAL and a message (the size function: -1), before any launch and
+ * before any pointer is looked at; a short workspace is MISONET_ENOMEM.  The call allocates nothing and does not synchronise (its
+ * first use on a device sets one kernel attribute). */
+typedef struct {
+  int taps;
+  int delay;
+  double diag_load;
+  double power_floor;
+  int ref_ch;
+} misonet_wpd_opts;
+int misonet_wpd_opts_default(misonet_wpd_opts* opts);    /* 5, 3, 0.0, 1e-10, 0 */
+long long misonet_wpd_workspace_bytes(int B, int F, int M, const misonet_wpd_opts* opts);
+int misonet_wpd(const void* src_dev, const void* mix_dev, int B, int F, int M, int T, const misonet_wpd_opts* opts,
+                void* out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_wpd, copy wbar complex128 [B, F, K] (order [y; z]: the M weights on the current frame first) and
+ * fail int32 [B, F] to device buffers (either may be NULL) */
+int misonet_wpd_debug(const void* ws_dev, int B, int F, int M, const misonet_wpd_opts* opts, void* wbar_c128_dev, int* fail_dev,
+                      misonet_stream stream);
+
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
  * dist_dev (required: it is the call's only scratch, so the call allocates nothing and stays asynchronous): float64,
@@ -363,6 +402,11 @@ int misonet_pipeline_destroy(misonet_pipeline* p);
  * make this return MISONET_ESTATE; the owner of a captured graph captures again (misonet_amd.Enhancer refuses the change
  * while one of its captured passes is alive). */
 int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* opts);
+/* ABI 530: WPD as that step, per aligned speaker, on the same views and into the same beamformer planes (M = num_mic; the source
+ * estimate is MISO1's at every microphone).  opts == NULL: back to the misonet_bf_opts that are set.  Legal between runs; the
+ * workspace size depends on it (ask misonet_pipeline_workspace_bytes again); a run with T <= delay + taps - 1 frames is refused
+ * with MISONET_EINVAL.  MISONET_EINVAL for bad fields (as misonet_wpd).  With WPD not set every bit of every path is unchanged. */
+int misonet_pipeline_set_wpd(misonet_pipeline* p, const misonet_wpd_opts* opts);
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T);
 /* mix_dev complex64 [B,M,T,F]; clean_dev complex64 [B,S,T,F] or NULL; out_dev complex64 [B,S,T,F] (MISO3);
  * optional outputs (may be NULL): bf_dev complex64 [B,S,T,F] (MVDR), miso1_dev complex64 [B,S,M,T,F] (aligned).

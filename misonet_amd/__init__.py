@@ -3,7 +3,8 @@
 Host-side mirror of the reference call surface:
   MISO_1, MISO_3            (reference model.py:8-111, 282-395)
   Apply_Beamforming         (reference tester.py:1071-1136)
-  Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN)
+  Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN; and
+                             of the WPD convolutional beamformer, kind "wpd")
   dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)

@@ -38,6 +38,12 @@ class WpeOpts(C.Structure):
                 ("power_floor", C.c_double)]
 
 
+class WpdOpts(C.Structure):
+    """misonet_wpd_opts (ABI 530)"""
+    _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("diag_load", C.c_double), ("power_floor", C.c_double),
+                ("ref_ch", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -79,6 +85,13 @@ SIGNATURES = {
                               C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_wpe_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpeOpts), C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "misonet_wpd_opts_default": (C.c_int, [C.POINTER(WpdOpts)]),
+    "misonet_wpd_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts)]),
+    "misonet_wpd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts), C.c_void_p,
+                              C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_wpd_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts), C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "misonet_pipeline_set_wpd": (C.c_int, [C.c_void_p, C.POINTER(WpdOpts)]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

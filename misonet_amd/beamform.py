@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's array-processing calls on the inference path.
 
 ``Apply_Beamforming(source_stft, mix_stft, epsi)``  -- reference tester.py:1071-1136 (MVDR per frequency bin); keywords
-                                                       select the other beamformers (:class:`Beamformer`)
+                                                       select the other beamformers (:class:`Beamformer`), among them the
+                                                       WPD convolutional beamformer (``beamformer="wpd"``: misonet_wpd)
 ``pit_select(anchor, cand)``                        -- reference tester.py:1043-1065 / 889-915 (PIT over all S! permutations)
 
 Both run as HIP kernels through the C ABI (misonet_beamform / misonet_pit_select in include/misonet.h).
@@ -29,7 +30,9 @@ def _dev_c64(x, device):
     return t.to(torch.complex64).contiguous(), was_numpy
 
 
-KINDS = ("mvdr", "souden", "gev")
+KINDS = ("mvdr", "souden", "gev")            # the kinds of misonet_bf_opts, in its numbering
+WPD = "wpd"                                  # the convolutional beamformer has options and entry points of its own (ABI 530)
+WPD_KMAX = 88                                # the largest order M (taps + 1) the kernel takes (include/misonet.h, "WPD")
 NOISES = ("residual", "mix")
 
 
@@ -45,7 +48,16 @@ class Beamformer:
     trace_normalize  Phi_n <- Phi_n / tr(Phi_n) (tester.py:1099), after the conditioning
     epsi             Phi_n' = Phi_n + epsi I, last (tester.py:1221); None = the default of the call that uses the options
     ban              blind analytic normalisation of w (tester.py:1186-1208)
-    ref_ch           reference microphone of "souden" and "gev"
+    ref_ch           reference microphone of "souden", "gev" and "wpd"
+
+    kind "wpd" (``misonet_wpd_opts``): the WPD convolutional beamformer, one filter of order M (taps + 1) per bin over the
+    current frame and ``taps`` frames that lie ``delay`` and more back, R weighted by the power of the source estimate, the
+    Souden solve against the zero-padded Phi_s.  Its fields -- ignored by the other kinds:
+    taps, delay      frames of the prediction part and its distance (>= 1 each; M (taps + 1) <= 88)
+    diag_load        R += diag_load tr(R) / K I
+    power_floor      w[t] = 1 / max(p[t], power_floor max_t p[t])
+    It has no noise covariance: ``noise``, ``condition``, ``trace_normalize`` and ``ban`` must keep their defaults; ``epsi`` is
+    ignored.
     """
     kind: str = "mvdr"
     noise: str = "residual"
@@ -54,6 +66,10 @@ class Beamformer:
     epsi: Optional[float] = None
     ban: bool = False
     ref_ch: int = 0
+    taps: int = 5
+    delay: int = 3
+    diag_load: float = 0.0
+    power_floor: float = 1e-10
 
     @classmethod
     def of(cls, spec) -> "Beamformer":
@@ -76,8 +92,8 @@ class Beamformer:
 
     def validate(self, num_mic: Optional[int] = None) -> "Beamformer":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
-        if self.kind not in KINDS:
-            raise ValueError(f"beamformer kind {self.kind!r}: one of {KINDS}")
+        if self.kind not in KINDS + (WPD,):
+            raise ValueError(f"beamformer kind {self.kind!r}: one of {KINDS + (WPD,)}")
         if self.noise not in NOISES:
             raise ValueError(f"beamformer noise {self.noise!r}: one of {NOISES}")
         if not (isinstance(self.condition, (int, float)) and math.isfinite(self.condition) and self.condition >= 0):
@@ -86,16 +102,65 @@ class Beamformer:
             raise ValueError(f"beamformer epsi must be finite and >= 0, got {self.epsi!r}")
         if int(self.ref_ch) != self.ref_ch or self.ref_ch < 0 or (num_mic is not None and self.ref_ch >= num_mic):
             raise ValueError(f"beamformer ref_ch {self.ref_ch!r} outside [0, {num_mic if num_mic is not None else 'M'})")
+        if self.kind == WPD:
+            if self.noise != "residual" or self.condition != 0 or self.trace_normalize or self.ban:
+                raise ValueError('beamformer kind "wpd" has no noise covariance: noise, condition, trace_normalize and ban '
+                                 "must keep their defaults")
+            for name in ("taps", "delay"):
+                v = getattr(self, name)
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                    raise ValueError(f"wpd {name} must be an integer >= 1, got {v!r}")
+            if num_mic is not None and not 2 <= num_mic <= 8:
+                raise ValueError(f"wpd needs 2 <= M <= 8 microphones, got {num_mic}")
+            if (num_mic if num_mic is not None else 2) * (self.taps + 1) > WPD_KMAX:
+                raise ValueError(f"wpd order M (taps + 1) must be <= {WPD_KMAX}, got taps {self.taps}"
+                                 + (f" with M {num_mic}" if num_mic is not None else ""))
+            for name in ("diag_load", "power_floor"):
+                v = getattr(self, name)
+                if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+                    raise ValueError(f"wpd {name} must be finite and >= 0, got {v!r}")
         return self
 
     def c_opts(self, epsi_default: float = 1e-6) -> "_lib.BfOpts":
+        if self.kind == WPD:
+            raise ValueError('kind "wpd" is not a misonet_bf_opts kind: use wpd_opts()')
         return _lib.BfOpts(KINDS.index(self.kind), NOISES.index(self.noise), float(self.condition),
                            int(bool(self.trace_normalize)), float(self.epsi if self.epsi is not None else epsi_default),
                            int(bool(self.ban)), int(self.ref_ch))
 
+    def wpd_opts(self) -> "_lib.WpdOpts":
+        """the fields of kind "wpd" as ``misonet_wpd_opts``"""
+        return _lib.WpdOpts(int(self.taps), int(self.delay), float(self.diag_load), float(self.power_floor), int(self.ref_ch))
+
+
+def _wpd_device(src, mix, bf, return_debug):
+    """misonet_wpd on device tensors [B, F, M, T]: (out [B, T, F], None or dict(w [B, F, K], fail [B, F]))"""
+    B, F, M, T = src.shape
+    if T <= bf.delay + bf.taps - 1:
+        raise ValueError(f"wpd needs T > delay + taps - 1 = {bf.delay + bf.taps - 1} frames, got {T}")
+    opts = bf.wpd_opts()
+    L = _lib.lib()
+    nws = L.misonet_wpd_workspace_bytes(B, F, M, C.byref(opts))
+    if nws < 0:
+        _lib.check(_lib.EINVAL)
+    ws = torch.empty(max(int(nws), 8), dtype=torch.uint8, device=src.device)
+    out = torch.empty((B, T, F), dtype=torch.complex64, device=src.device)
+    dbg = None
+    with torch.cuda.device(src.device):
+        st = _lib.stream_ptr(src.device)
+        _lib.check(L.misonet_wpd(src.data_ptr(), mix.data_ptr(), B, F, M, T, C.byref(opts), out.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), st))
+        if return_debug:
+            w = torch.empty((B, F, M * (bf.taps + 1)), dtype=torch.complex128, device=src.device)
+            bad = torch.empty((B, F), dtype=torch.int32, device=src.device)
+            _lib.check(L.misonet_wpd_debug(ws.data_ptr(), B, F, M, C.byref(opts), w.data_ptr(), bad.data_ptr(), st))
+            dbg = dict(w=w, fail=bad)
+    return out, dbg
+
 
 def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debug=False, *, beamformer="mvdr",
-                      noise="residual", condition=0.0, trace_normalize=False, ban=False, ref_ch=0):
+                      noise="residual", condition=0.0, trace_normalize=False, ban=False, ref_ch=0, taps=5, delay=3,
+                      diag_load=0.0, power_floor=1e-10):
     """Beamforming, same arguments and (with the keyword defaults) same result as Tester_Enhance.Apply_Beamforming
     (tester.py:1071-1136: residual-noise MVDR).
 
@@ -105,11 +170,14 @@ def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debu
 
     The keywords are the fields of :class:`Beamformer` (``beamformer`` = its ``kind``, or a whole Beamformer / dict, whose
     ``epsi``, when set, wins over the positional one).  ``return_debug`` adds what the kind has, complex128 / float64 on
-    the device: "mvdr" ``steer1`` and ``w`` [B, F, Ch]; "souden" ``w``; "gev" ``w`` and ``lam`` [B, F] (lambda_max).
+    the device: "mvdr" ``steer1`` and ``w`` [B, F, Ch]; "souden" ``w``; "gev" ``w`` and ``lam`` [B, F] (lambda_max);
+    "wpd" ``w`` [B, F, Ch (taps + 1)] (the weights on the current frame first) and ``fail`` int32 [B, F].
+    ``beamformer="wpd"`` (``taps``, ``delay``, ``diag_load``, ``power_floor``, ``ref_ch``) is the WPD convolutional
+    beamformer (``misonet_wpd``); it needs T > delay + taps - 1 frames.
     """
     if isinstance(beamformer, str):
         bf = Beamformer(kind=beamformer, noise=noise, condition=condition, trace_normalize=trace_normalize, epsi=epsi,
-                        ban=ban, ref_ch=ref_ch)
+                        ban=ban, ref_ch=ref_ch, taps=taps, delay=delay, diag_load=diag_load, power_floor=power_floor)
     else:
         bf = Beamformer.of(beamformer).with_epsi(epsi)
     bf.validate(np.shape(source_stft)[2] if np.ndim(source_stft) == 4 else None)     # before any copy or launch
@@ -120,6 +188,11 @@ def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debu
     if src.shape != mix.shape or src.dim() != 4:
         raise ValueError(f"source_stft {tuple(src.shape)} and mix_stft {tuple(mix.shape)} must both be [B, F, Ch, T]")
     B, F, M, T = src.shape
+    if bf.kind == WPD:
+        out, dbg = _wpd_device(src, mix, bf, return_debug)
+        if np_in:
+            out = out.cpu()
+        return (out, dbg) if return_debug else out
     opts = bf.c_opts()
     L = _lib.lib()
     nws = L.misonet_beamform_workspace_bytes(B, F, M, C.byref(opts))

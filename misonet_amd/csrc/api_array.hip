@@ -27,6 +27,44 @@ void mn::bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a) {
   a.bf_ref = o.ref_ch; a.condition = o.condition;
 }
 
+// WPD: every field, against M microphones and (T >= 0) against T frames.  The order K = M (taps + 1) is bounded by WPD_KMAX, the
+// order the Gram scheme of wpd.hip reaches; the LDS of every such K fits (wpd_lds_bytes is checked all the same).
+int mn::wpd_opts_check(const misonet_wpd_opts* o, int M, int T) {
+  if (!o) return fail(MISONET_EINVAL, "null WPD options");
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (o->taps < 1 || (long long)M * ((long long)o->taps + 1) > WPD_KMAX)
+    return fail(MISONET_EINVAL, "taps must be >= 1 and M * (taps + 1) <= %d (got taps %d, M %d)", WPD_KMAX, o->taps, M);
+  if (wpd_lds_bytes(M, o->taps) > 160 * 1024)
+    return fail(MISONET_EINVAL, "taps %d with M %d does not fit the 160 KB of LDS", o->taps, M);
+  if (o->delay < 1) return fail(MISONET_EINVAL, "delay must be >= 1 (got %d)", o->delay);
+  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
+    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!(o->power_floor >= 0.0) || !std::isfinite(o->power_floor))
+    return fail(MISONET_EINVAL, "power_floor must be finite and >= 0 (got %g)", o->power_floor);
+  if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "WPD ref_ch %d outside [0, %d)", o->ref_ch, M);
+  if (T >= 0 && (long long)T <= (long long)o->delay + o->taps - 1)
+    return fail(MISONET_EINVAL, "T must be > delay + taps - 1 = %lld (got %d)", (long long)o->delay + o->taps - 1, T);
+  return MISONET_OK;
+}
+
+void mn::wpd_opts_apply(const misonet_wpd_opts& o, WpdArgs& a) {
+  a.taps = o.taps; a.delay = o.delay; a.ref = o.ref_ch; a.diag_load = o.diag_load; a.power_floor = o.power_floor;
+}
+
+// the dynamic-LDS attribute of wpd_bin_k: once per device, never inside an asynchronous call after that
+int mn::wpd_ready() {
+  static std::atomic<bool> done[MAX_DEV];
+  static std::mutex mu;
+  const int d = cur_dev();
+  if (done[d].load(std::memory_order_acquire)) return MISONET_OK;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!done[d].load(std::memory_order_acquire)) {
+    HIPCHK(wpd_init());
+    done[d].store(true, std::memory_order_release);
+  }
+  return MISONET_OK;
+}
+
 // The drop-in beamformer call: src / mix complex64 [B,F,M,T], one source per item.  misonet_beamform passes the caller's options
 // (checked here, the workspace sized by their kind); misonet_mvdr passes the defaults with its epsi as trusted: that entry point
 // has never validated epsi, and its workspace is misonet_mvdr_workspace_bytes.
@@ -144,6 +182,49 @@ int misonet_wpe_debug(const void* ws, int B, int M, int F, const misonet_wpe_opt
   if (!ws) return fail(MISONET_EINVAL, "null argument");
   { int r = wpe_check(B, M, 2, F, opts); if (r) return r; }
   HIPCHK(launch_wpe_debug(ws, B, M, F, opts->taps, g, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- WPD convolutional beamformer (ABI 530) --------------------------------------------------------------------------
+int misonet_wpd_opts_default(misonet_wpd_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->taps = 5; o->delay = 3; o->diag_load = 0.0; o->power_floor = 1e-10; o->ref_ch = 0;
+  return MISONET_OK;
+}
+
+long long misonet_wpd_workspace_bytes(int B, int F, int M, const misonet_wpd_opts* opts) {
+  if (B <= 0 || F <= 0) { fail(MISONET_EINVAL, "B and F must be positive (got %d, %d)", B, F); return -1; }
+  if (wpd_opts_check(opts, M, -1)) return -1;
+  return wpd_ws_bytes(B, 1, F, M, opts->taps);
+}
+
+int misonet_wpd(const void* src, const void* mix, int B, int F, int M, int T, const misonet_wpd_opts* opts, void* out, void* ws,
+                long long ws_bytes, misonet_stream stream) {
+  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F, T must be positive");
+  { int r = wpd_opts_check(opts, M, T); if (r) return r; }
+  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (ws_bytes < wpd_ws_bytes(B, 1, F, M, opts->taps)) return fail(MISONET_ENOMEM, "workspace too small");
+  { int r = wpd_ready(); if (r) return r; }
+  WpdArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  const float* x = reinterpret_cast<const float*>(src);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.src = {x, x + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
+  a.S = 1; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
+  wpd_opts_apply(*opts, a);
+  float* o = reinterpret_cast<float*>(out);
+  COut co = {o, o + 1, 2LL * T * F, 0, 2LL * F, 2};      // [B,T,F] complex64, as misonet_beamform
+  HIPCHK(launch_wpd(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_wpd_debug(const void* ws, int B, int F, int M, const misonet_wpd_opts* opts, void* wbar, int* fail_dev,
+                      misonet_stream stream) {
+  if (B <= 0 || F <= 0) return fail(MISONET_EINVAL, "B and F must be positive (got %d, %d)", B, F);
+  { int r = wpd_opts_check(opts, M, -1); if (r) return r; }
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_wpd_debug(ws, B, 1, F, M, opts->taps, wbar, fail_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -94,5 +94,10 @@ int get_twiddles(const float** out);
 // api_array.hip: host-side check of every field (M = the number of microphones ref_ch is counted in), and the options as MvdrArgs
 int bf_opts_check(const misonet_bf_opts* o, int M);
 void bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a);
+// api_array.hip: host-side check of every WPD field against M microphones (and against T frames when T >= 0); the options as
+// WpdArgs; the kernel's attributes on the current device, set at the first call there
+int wpd_opts_check(const misonet_wpd_opts* o, int M, int T);
+void wpd_opts_apply(const misonet_wpd_opts& o, WpdArgs& a);
+int wpd_ready();
 
 }  // namespace mn

@@ -12,6 +12,8 @@ struct misonet_pipeline {
   int M, S, ref_ch;
   float epsi;
   misonet_bf_opts bf;      // the beamformer of step 5 (misonet_pipeline_set_beamformer); create: the defaults with epsi
+  bool use_wpd;            // step 5 is WPD (misonet_pipeline_set_wpd) with the options below, bf is kept for the way back
+  misonet_wpd_opts wpd;
 };
 
 struct PipeLayout {
@@ -33,7 +35,8 @@ static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
   // PIT distances [B*M + B][S][S] followed by their per-bin partials [B*M + B][F][S][S] (mvdr.hip pit_dist_k)
   P.off_dist = o;  o += align_up((long long)(B * p->M + B) * p->S * p->S * (F + 1) * 8, 256);
   P.off_sel = o;   o += align_up((long long)(B * p->M * p->S * 2 + B * p->S) * 4, 256);
-  P.off_mvdr = o;  o += align_up(bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
+  P.off_mvdr = o;  o += align_up(p->use_wpd ? wpd_ws_bytes(B, p->S, F, p->M, p->wpd.taps)
+                                            : bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
   P.clean_bstride = (long long)2 * p->S * F * Tp;
   P.off_clean = o; o += align_up(P.clean_bstride * B * 4, 256);
   P.L3.in_ext_bstride = p->n3 ? (long long)p->n3->cfg.in_ch * F * Tp : 0;
@@ -74,6 +77,14 @@ int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* 
   p->bf = *opts;
   return MISONET_OK;
 }
+int misonet_pipeline_set_wpd(misonet_pipeline* p, const misonet_wpd_opts* opts) {
+  if (!p) return fail(MISONET_EINVAL, "null argument");
+  if (!opts) { p->use_wpd = false; return MISONET_OK; }
+  { int r = wpd_opts_check(opts, p->M, -1); if (r) return r; }
+  p->wpd = *opts;
+  p->use_wpd = true;
+  return MISONET_OK;
+}
 int misonet_pipeline_destroy(misonet_pipeline* p) { delete p; return MISONET_OK; }
 
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T) {
@@ -89,6 +100,11 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
   if (!p->n3 && (out || bf_out))
     return fail(MISONET_ESTATE, "this pipeline was created without MISO_3 (separation only): out and bf_out must be NULL");
   if (B <= 0 || T <= 0) return fail(MISONET_EINVAL, "B and T must be positive");
+  if (p->use_wpd && out) {
+    int rw = wpd_opts_check(&p->wpd, p->M, T);
+    if (!rw) rw = wpd_ready();
+    if (rw) return rw;
+  }
   const PipeLayout P = pipe_layout(p, B, T);
   if (ws_bytes < P.total) return fail(MISONET_ENOMEM, "workspace %lld < %lld bytes", ws_bytes, P.total);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -153,7 +169,17 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
     HIPCHK(launch_assemble3(in1, in1_bs, out1, out1_bs, sel_final, B, M, S, p->ref_ch, F, Tp, in3, in3_bs, s));
 
     // 5. MVDR per aligned speaker (tester.py:917-924, 1071-1136); writes the beamformer planes of the MISO3 input
-    {
+    if (p->use_wpd) {   // ... or WPD on the same views and the same planes
+      WpdArgs a;
+      a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};
+      a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;
+      a.src = {nullptr, nullptr, 0, 0, 0, 1};
+      a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
+      wpd_opts_apply(p->wpd, a);
+      COut co = {in3 + (long long)M * plane, in3 + (long long)(2 * M + 2) * plane, (long long)S * in3_bs, in3_bs, 1, Tp};
+      ProfScope ps(s, PK_MVDR);
+      HIPCHK(launch_wpd(a, co, base + P.off_mvdr, s));
+    } else {
       MvdrArgs a;
       a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};   // shift-0 sample = un-rolled mixture
       a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;

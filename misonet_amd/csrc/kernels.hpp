@@ -305,4 +305,27 @@ hipError_t launch_wpe(const void* mix, const float* power, int B, int M, int T, 
                       double diag_load, double power_floor, void* out, void* ws, hipStream_t s);
 hipError_t launch_wpe_debug(const void* ws, int B, int M, int F, int taps, void* g, int* fail, hipStream_t s);
 
+// WPD convolutional beamformer (wpd.hip): one filter of order K = M (taps + 1) per (b, speaker, bin) from the
+// observation and the source estimate, both read as launch_mvdr reads them (mix through a CView; the source through est /
+// est_bstride / sel in pipeline mode or through src when est == nullptr), applied to the stacked observation and written through
+// a COut.  The workspace holds fail int [B S F] and wbar complex128 [B S F][K] (order [y; z]), which launch_wpd_debug copies out.
+// 2 <= M <= 8, taps >= 1, delay >= 1, K <= WPD_KMAX and wpd_lds_bytes(M, taps) <= 160 KB (true for every K <= WPD_KMAX),
+// T > delay + taps - 1: the caller checks them.  wpd_init() once per device (the kernel's dynamic-LDS attribute).
+constexpr int WPD_KMAX = 88;
+struct WpdArgs {
+  CView mix;
+  const float* est;
+  long long est_bstride;
+  const int* sel;
+  CView src;
+  int S, B, F, M, T, Tp;
+  int taps, delay, ref;
+  double diag_load, power_floor;
+};
+long long wpd_ws_bytes(int B, int S, int F, int M, int taps);
+int wpd_lds_bytes(int M, int taps);
+hipError_t wpd_init();
+hipError_t launch_wpd(const WpdArgs& a, const COut& out, void* ws, hipStream_t s);
+hipError_t launch_wpd_debug(const void* ws, int B, int S, int F, int M, int taps, void* wbar, int* fail, hipStream_t s);
+
 }  // namespace mn

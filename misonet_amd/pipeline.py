@@ -273,8 +273,14 @@ class Enhancer:
         if len(self._captured):
             raise RuntimeError("set_beamformer: a captured pass of this Enhancer is alive and would go on replaying the old "
                                "beamformer; drop it and capture again after the change")
-        opts = bf.c_opts(self._epsi)
-        _lib.check(_lib.lib().misonet_pipeline_set_beamformer(self._pipe, C.byref(opts)))
+        L = _lib.lib()
+        if bf.kind == "wpd":                   # the convolutional beamformer has options and an entry point of its own
+            wopts = bf.wpd_opts()
+            _lib.check(L.misonet_pipeline_set_wpd(self._pipe, C.byref(wopts)))
+        else:
+            opts = bf.c_opts(self._epsi)
+            _lib.check(L.misonet_pipeline_set_beamformer(self._pipe, C.byref(opts)))
+            _lib.check(L.misonet_pipeline_set_wpd(self._pipe, None))
         self.beamformer = bf
         self._ws.clear()                       # the workspace size depends on the kind
 
