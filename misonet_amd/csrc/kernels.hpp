@@ -328,4 +328,25 @@ hipError_t wpd_init();
 hipError_t launch_wpd(const WpdArgs& a, const COut& out, void* ws, hipStream_t s);
 hipError_t launch_wpd_debug(const void* ws, int B, int S, int F, int M, int taps, void* wbar, int* fail, hipStream_t s);
 
+// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs or WpdArgs
+// (est / est_bstride / sel in pipeline mode, src when est == nullptr)
+template <typename Args>
+__device__ __forceinline__ void src_row(const Args& a, int b, int f, int m, int spk, const float*& re, const float*& im,
+                                        int& st) {
+  if (a.est) {
+    const int n = b * a.M + m;
+    const int q = a.sel ? a.sel[n * a.S + spk] : spk;
+    const long long plane = (long long)a.F * a.Tp;
+    const float* base = a.est + (long long)n * a.est_bstride + (long long)f * a.Tp;
+    re = base + (long long)q * plane;
+    im = base + (long long)(a.S + q) * plane;
+    st = 1;
+  } else {
+    const long long off = (long long)b * a.src.sb + (long long)f * a.src.sf + (long long)m * a.src.sm;
+    re = a.src.re + off;
+    im = a.src.im + off;
+    st = a.src.st;
+  }
+}
+
 }  // namespace mn

@@ -55,25 +55,6 @@ long long bf_ws_bytes(int B, int S, int F, int M, int kind) {
   return (ws_lam(B, S, F, M) + (long long)B * S * F) * (long long)sizeof(double);
 }
 
-// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f
-__device__ inline void src_row(const MvdrArgs& a, int b, int f, int m, int spk, const float*& re, const float*& im,
-                               int& st) {
-  if (a.est) {
-    const int n = b * a.M + m;
-    const int q = a.sel ? a.sel[n * a.S + spk] : spk;
-    const long long plane = (long long)a.F * a.Tp;
-    const float* base = a.est + (long long)n * a.est_bstride + (long long)f * a.Tp;
-    re = base + (long long)q * plane;
-    im = base + (long long)(a.S + q) * plane;
-    st = 1;
-  } else {
-    const long long off = (long long)b * a.src.sb + (long long)f * a.src.sf + (long long)m * a.src.sm;
-    re = a.src.re + off;
-    im = a.src.im + off;
-    st = a.src.st;
-  }
-}
-
 // Complex Jacobi on the Hermitian s_A with a PARALLEL (round-robin) ordering; eigenvectors accumulate in the columns of
 // s_V.  A sweep is ME - 1 rounds of M / 2 DISJOINT pivot pairs; disjoint rotations commute, so a round applies
 // A <- R^H A R with R = R_1 R_2 .. in three phases separated by barriers: (0) every lane of pair j computes that

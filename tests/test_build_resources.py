@@ -135,3 +135,12 @@ def test_wino_kernel_register_files(table):
     assert total == own and total >= 896, (total, own)          # per body: epilogue reads (256 / 128) + 256 prologue zeroing writes
     assert dma >= 2 * 6 * 10, dma                               # two instantiations x six chunk bodies x (4 U-image + 6 raw-input pieces)
     assert not any("flat_load" in ln or "flat_store" in ln or "scratch_" in ln for ln in asm)
+
+
+def test_stacked_gram_kernels_fit_two_workgroups(table):
+    """wpe_bin_k and wpd_bin_k (the bin solver of csrc/stacked_gram.hpp): a 512-thread workgroup and an LDS budget written for
+    two workgroups per CU = 2 waves per SIMD, nine float64 accumulator tiles per wave held in registers over the frame loop"""
+    for k in ("mn::wpe_bin_k", "mn::wpd_bin_k"):
+        r = table[k]
+        assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (k, r)
+        assert r["vgprs"] <= 256 and r["occupancy"] >= 2, (k, r)
