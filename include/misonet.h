@@ -383,6 +383,40 @@ int misonet_stoi_resample(const void* est_dev, int est_is_i16, long long est_sb,
 int misonet_stoi_measure(const double* x10_dev, const int* len10_dev, int B, int NS, int R, long long n10, double* out_dev,
                          int* frames_dev, void* scratch_dev, long long scratch_bytes, misonet_stream stream);
 
+/* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
+/* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
+ * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so
+ * the figures have not been compared against them): frames of N = fs / 40 samples (25 ms) every H = fs / 100 (10 ms) under
+ * MATLAB's hanning(N), a transform of NFFT = 256 (8 kHz) or 512 (16 kHz) points, and per frame of every signal 25 real cepstral
+ * coefficients (floor 1e-15 on the magnitudes), 23 mel band sums of the magnitudes, the autocorrelation at lags 0..12 and the
+ * LPC of order 12 by Levinson-Durbin.  Per pair: the frames whose reference has r[0] > 0 are used (K of them); CD is the
+ * mean-normalised cepstral distance in dB capped at 10, LLR = ln(a_y' R_x a_y / a_x' R_x a_x) clipped to [0, 2] over the
+ * K_llr used frames where neither recursion failed and both forms are positive, fwSegSNR the mean over the bands, weighted by
+ * (g_x X_b)^0.2, of 10 log10(X_b^2 / (X_b - Y_b)^2) clipped to [-10, 35] after both signals are scaled to unit power.  All
+ * arithmetic after the loads is float64, without floating-point atomics and in a fixed order: bit-reproducible, independent of
+ * B, of the item's position in the batch and of the layout; samples past n_valid are not read.
+ * misonet_reverb_frames: the frames of n samples, (n - N) / H + 1 or 0 for n < N (host only); -1 for fs other than 8000, 16000
+ *   or n outside 1..2^24.
+ * misonet_reverb_measure: the views, n_valid_dev and the int16 rule of misonet_score_wave; mix_dev (may be NULL) as in
+ *   misonet_stoi_resample: the mixture is measured as one more estimate, the last.  out_dev double [B][E (+ 1)][R][6] = (CD
+ *   mean, CD median, LLR mean, LLR median, fwSegSNR mean, fwSegSNR median) over the counted frames of estimate i against
+ *   reference j, all NaN where K = 0 or the reference is silent, the LLR pair NaN where K_llr = 0; the median of an even count
+ *   is the mean of the two middle values.  count_dev int32 [B][E (+ 1)][R][3] = (frames of n_valid, K, K_llr).  frame_dev (may
+ *   be NULL) double [B][E (+ 1)][R][3][misonet_reverb_frames(n, fs)]: the CD, LLR and fwSegSNR of every frame, NaN where the
+ *   frame is not counted; entries past the frames of the item's n_valid are not written.
+ * scratch_dev: misonet_reverb_scratch_bytes(B, NS, R, n, fs) bytes (host only), NS = R + E (+ 1) = the signals of an item, =
+ *   8 B (NS + 75 NS f + 3 (NS - R) R f) with f = max(frames of n, 1); less returns MISONET_ENOMEM.  MISONET_EINVAL (the size
+ *   functions: -1): a null argument, E or R outside 1..4, NS - R outside 1..5, B outside 1..4096, n outside 1..2^24, another
+ *   rate, a negative stride.  The first call on a device builds a table of 10082 doubles (twiddles, windows, mel triangles:
+ *   one allocation and one synchronous copy); after that the call is asynchronous on the stream and allocates nothing. */
+long long misonet_reverb_frames(long long n, int fs);
+long long misonet_reverb_scratch_bytes(int B, int NS, int R, long long n, int fs);
+int misonet_reverb_measure(const void* est_dev, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                           const float* ref_dev, long long ref_sb, long long ref_ss, long long ref_st, const float* mix_dev,
+                           long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid_dev, int fs,
+                           double* out_dev, int* count_dev, double* frame_dev, void* scratch_dev, long long scratch_bytes,
+                           misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

@@ -1,5 +1,6 @@
 // C ABI of the scoring against clean references (include/misonet.h): misonet_score_* (score.hip), BSS-eval misonet_bss_*
-// (bss.hip), STOI / ESTOI misonet_stoi_* (stoi.hip) and the STOI table of every device that uses it.  Host code only.
+// (bss.hip), STOI / ESTOI misonet_stoi_* (stoi.hip), cepstral distance / LLR / fwSegSNR misonet_reverb_* (reverb.hip) and the
+// STOI and reverb tables of every device that uses them.  Host code only.
 #include "api_common.hpp"
 
 using namespace mn;
@@ -193,6 +194,49 @@ int misonet_stoi_measure(const double* x10, const int* len10, int B, int NS, int
   if (const int rc = get_stoi_table(&tab)) return rc;
   HIPCHK(launch_stoi_measure(x10, len10, B, NS, R, n10, tab, out, frames, reinterpret_cast<double*>(scratch),
                              reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- cepstral distance, LLR, fwSegSNR (reverb.hip) -----------------------------------------------------------------------
+// the table of the current device (twiddles and, per rate, window, mel triangles, their bin ranges), built on first use as
+// the STOI table is
+static DevTable<double> g_reverb_tab;
+static int get_reverb_table(const double** out) {
+  return g_reverb_tab.get(out, [](double** p) {
+    std::vector<double> t((size_t)reverb_table_count());
+    reverb_build_table(t.data());
+    return dev_upload(t, p);
+  });
+}
+
+long long misonet_reverb_frames(long long n, int fs) { return reverb_frames(n, fs); }
+
+long long misonet_reverb_scratch_bytes(int B, int NS, int R, long long n, int fs) {
+  if (B < 1 || B > 4096 || R < 1 || R > 4 || NS - R < 1 || NS - R > 5) return -1;
+  const long long item = reverb_item_doubles(NS, R, n, fs);
+  return item < 0 ? -1 : (long long)B * item * (long long)sizeof(double);
+}
+
+int misonet_reverb_measure(const void* est, int est_is_i16, long long est_sb, long long est_ss, long long est_st,
+                           const float* ref, long long ref_sb, long long ref_ss, long long ref_st, const float* mix,
+                           long long mix_sb, long long mix_st, int B, int E, int R, long long n, const int* n_valid, int fs,
+                           double* out, int* count, double* frame, void* scratch, long long scratch_bytes,
+                           misonet_stream stream) {
+  if (!est || !ref || !out || !count || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (const int rc = erb_ranges(B, E, R)) return rc;
+  if (fs != 8000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000 or 16000 (got %d)", fs);
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample", mix && (mix_sb < 0 || mix_st < 1)))
+    return rc;
+  const int NS = R + E + (mix ? 1 : 0);
+  if (const int rc = scratch_fits(scratch_bytes, misonet_reverb_scratch_bytes(B, NS, R, n, fs),
+                                  "misonet_reverb_scratch_bytes(B, R + E (+ 1), R, n, fs)"))
+    return rc;
+  const double* tab;
+  if (const int rc = get_reverb_table(&tab)) return rc;
+  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
+  HIPCHK(launch_reverb_measure(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, out, count, frame,
+                               reinterpret_cast<double*>(scratch), reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -297,6 +297,20 @@ hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long
 hipError_t launch_stoi_measure(const double* x10, const int* len10 /*[B] or nullptr*/, int B, int NS, int R, long long n10,
                                const double* table, double* out, int* meta, double* scratch, hipStream_t s);
 
+// Cepstral distance, LLR and fwSegSNR (reverb.hip).  The table (reverb_table_count() doubles, built on the
+// host): the twiddles of the 512-point transform and, per rate, the window, the 23 mel triangles and their bin ranges.  One call
+// reads the strided views of launch_score_wave (ms as for launch_stoi_resample) and writes out [B][E (+ 1)][R][6], count
+// [B][E (+ 1)][R][3] and, where frame_out is not nullptr, the values of every frame [B][E (+ 1)][R][3][frames of n]; per item
+// reverb_item_doubles(NS, R, n, fs) doubles of scratch, NS = R + E (+ 1).
+int reverb_table_count();
+void reverb_build_table(double* t);
+long long reverb_frames(long long n, int fs);      // -1 for a rate that is not served or n outside 1 .. 2^24
+long long reverb_item_doubles(int NS, int R, long long n, int fs);
+hipError_t launch_reverb_measure(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
+                                 const float* mix, const long long* ms, int B, int E, int R, long long n,
+                                 const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out, int* count,
+                                 double* frame_out /*or nullptr*/, double* scratch, hipStream_t s);
+
 // WPE dereverberation (wpe.hip).  mix / out complex64 [B][M][T][F], power float32 [B][T][F] or nullptr; the
 // workspace starts with fail int [B F] and G complex128 [B F][M taps][M], which launch_wpe_debug copies out.
 // 1 <= M <= 8, M taps <= 80, T >= 2.

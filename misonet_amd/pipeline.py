@@ -757,7 +757,7 @@ class Enhancer:
 
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                           max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000, score: bool = False,
-                          bss: bool = False, bss_filt_len: int = 512, stoi: bool = False):
+                          bss: bool = False, bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False):
         """Recording in -> enhanced int16 waves out: the reference's loader item AND its tester body as one device-side
         object (``AudioDataset_Test.__getitem__``, dataloader/data.py:524-597, + ``Tester_Enhance.inference``,
         tester.py:846-975), without host STFT dicts.
@@ -791,16 +791,28 @@ class Enhancer:
         ``(pcm, Score, Stoi)`` or ``(pcm, Score, BssEval, Stoi)``; everything before it keeps its bits.  It holds STOI and
         ESTOI of the stitched int16 result against the clean sources at ``ref_ch`` at rate ``fs`` (8000,
         10000 or 16000), the observation at ``ref_ch`` as the mixture: what
-        ``score.stoi_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns."""
+        ``score.stoi_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns.
+
+        ``reverb=True`` (needs ``score=True``): a :class:`score.Reverb` is appended as the last element of the returned
+        tuple, after ``BssEval`` and ``Stoi`` where those are asked for; everything before it keeps its bits.  It holds the
+        cepstral distance, the log-likelihood ratio and the frequency-weighted segmental SNR, the figures
+        dereverberation is judged by, of the stitched int16 result against the clean sources at ``ref_ch`` at rate ``fs``
+        (8000 or 16000), the original observation at ``ref_ch`` as the mixture (also with ``dereverb=`` set): what
+        ``score.reverb_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns."""
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
         if stoi and not score:
             raise ValueError("stoi=True needs score=True (and the clean sources)")
+        if reverb and not score:
+            raise ValueError("reverb=True needs score=True (and the clean sources)")
         if score and wav_clean is None:
             raise ValueError("score=True needs the clean sources (wav_clean)")
         if stoi:
             from . import score as SC
             SC.check_stoi_fs(fs)
+        if reverb:
+            from . import score as SC
+            SC.check_reverb_fs(fs)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -819,7 +831,7 @@ class Enhancer:
             pcm = np.concatenate([g[0] for g in got], axis=0)
             rows = [(g[1][0][b], g[1][1][b]) for g in got for b in range(g[0].shape[0])]
             out, sc = self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs), self._recording_score(rows, nv)
-            if not bss and not stoi:
+            if not bss and not stoi and not reverb:
                 return out, sc
             from . import score as SC
             clean, mix = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
@@ -828,6 +840,8 @@ class Enhancer:
                 res = res + (SC.bss_eval_waves(out, clean, mix, filt_len=bss_filt_len, device=self.device),)
             if stoi:
                 res = res + (SC.stoi_waves(out, clean, mix, fs=fs, device=self.device),)
+            if reverb:
+                res = res + (SC.reverb_waves(out, clean, mix, fs=fs, device=self.device),)
             return res
 
         def batches():
@@ -839,7 +853,7 @@ class Enhancer:
         return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
 
     def _wave_refs(self, wav_observe, wav_clean, num_ch_utilize):
-        """the references of BSS-eval and STOI for one recording: (the clean sources at ref_ch of the sub-sampled array, float32
+        """the references of BSS-eval, STOI and the reverb figures for one recording: (the clean sources at ref_ch of the sub-sampled array, float32
         [S, L]; the observation there, float32 [L])"""
         mics, obs = self._select_mics(wav_observe, num_ch_utilize)
         m = mics[self.ref_ch]
@@ -1000,7 +1014,7 @@ class Enhancer:
     def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
                            depth: int = 2, score: bool = False, bss: bool = False,
-                           bss_filt_len: int = 512, stoi: bool = False) -> Dict[str, np.ndarray]:
+                           bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False) -> Dict[str, np.ndarray]:
         """:meth:`enhance_recording` over many recordings, with every launch filled across them.
 
         ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
@@ -1017,16 +1031,23 @@ class Enhancer:
         one batch per group: a recording's figures do not depend on the group) and nothing waits for them until every
         recording has gone through: the pass is not stalled.  ``stoi=True`` (needs ``score=True``): a :class:`score.Stoi`
         (STOI and ESTOI at rate ``fs``, csrc/stoi.hip) is appended as the last element of every tuple, queued in the same
-        groups on the same side stream; everything before it keeps its bits."""
+        groups on the same side stream; everything before it keeps its bits.  ``reverb=True`` (needs ``score=True``): a
+        :class:`score.Reverb` (cepstral distance, LLR and fwSegSNR at rate ``fs``, csrc/reverb.hip) is appended after those,
+        from the same padded, pinned batch on the same side stream."""
         import os
         from .coalesce import Item
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
         if stoi and not score:
             raise ValueError("stoi=True needs score=True (and the clean sources)")
+        if reverb and not score:
+            raise ValueError("reverb=True needs score=True (and the clean sources)")
         if stoi:
             from . import score as SC
             SC.check_stoi_fs(fs)
+        if reverb:
+            from . import score as SC
+            SC.check_reverb_fs(fs)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -1041,7 +1062,7 @@ class Enhancer:
                     key = key + ((1,),)                              # the chunk's valid count rides as a third input
                     if mpieces is not None:
                         key = key + (mpieces[0].shape,)              # and the original observation at ref_ch as a fourth
-                if bss or stoi:
+                if bss or stoi or reverb:
                     side_refs[i] = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
                 yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name, mpieces))
 
@@ -1058,15 +1079,16 @@ class Enhancer:
 
         results = {}
         side_refs, side_wait, side_done = {}, [], []
-        if bss or stoi:
+        if bss or stoi or reverb:
             from . import score as SC
             side = torch.cuda.Stream(self.device)
 
             def side_flush():
                 with torch.cuda.stream(side):
-                    side_done.append(([w[0] for w in side_wait],) + SC.side_queue(
+                    blocks = SC.side_queue(
                         [w[1:] for w in side_wait], self.device, pinned=True, bss_filt_len=bss_filt_len if bss else None,
-                        stoi_fs=fs if stoi else None))                 # one padded, pinned batch serves both
+                        stoi_fs=fs if stoi else None, reverb_fs=fs if reverb else None)   # one padded, pinned batch serves all
+                    side_done.append(([w[0] for w in side_wait],) + tuple(blocks[:2]) + (blocks[2] if reverb else None,))
                 side_wait.clear()
         for it in self._coalesced(items(), fill, self._wav_pass_score if score else self._wav_pass, torch.float32, max_batch,
                                   depth, lambda c: str(c.item.payload[3]),
@@ -1077,17 +1099,17 @@ class Enhancer:
                 n = pieces[0].shape[0]
                 pcm = self._finish_recording([o[0][0] for o in it.outputs], gap, path, fs)
                 results[name] = (pcm, self._recording_score([o[0][1:] for o in it.outputs], [n] * (len(pieces) - 1) + [n - gap]))
-                if bss or stoi:
+                if bss or stoi or reverb:
                     side_wait.append((name, pcm) + side_refs.pop(it.index))
                     if len(side_wait) >= self.BSS_GROUP:
                         side_flush()
             else:
                 results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
-        if bss or stoi:
+        if bss or stoi or reverb:
             if side_wait:
                 side_flush()
             side.synchronize()
-            for names, block, sblock in side_done:
+            for names, block, sblock, rblock in side_done:
                 if bss:
                     for name, row in zip(names, block.cpu().numpy()):
                         pcm, sc = results[name]
@@ -1095,6 +1117,9 @@ class Enhancer:
                 if stoi:
                     for name, row in zip(names, sblock.cpu().numpy()):
                         results[name] = results[name] + (SC.stoi_unpack(row, self.num_spks, int(fs), results[name][0].shape[1]),)
+                if reverb:
+                    for name, row in zip(names, rblock.cpu().numpy()):
+                        results[name] = results[name] + (SC.reverb_unpack(row, self.num_spks, int(fs), results[name][0].shape[1]),)
         return results
 
     def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2, score=False):

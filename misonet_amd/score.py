@@ -5,7 +5,9 @@ into dB on the host.  tests/score_ref.py restates every definition in NumPy.  BS
 the figures SMS-WSJ tabulates) come from the energies of two projections (csrc/bss.hip, C ABI ``misonet_bss_corr`` /
 ``misonet_bss_solve``; :class:`BssEval`, INTEGRATION.md 4e, restated in tests/bss_ref.py).  STOI and ESTOI, the intelligibility
 figures, are computed whole on the device (csrc/stoi.hip, C ABI ``misonet_stoi_resample`` / ``misonet_stoi_measure``;
-:class:`Stoi`, INTEGRATION.md 4f, restated in tests/stoi_ref.py).
+:class:`Stoi`, INTEGRATION.md 4f, restated in tests/stoi_ref.py).  Cepstral distance, log-likelihood ratio and
+frequency-weighted segmental SNR, the figures dereverberation is judged by, likewise (csrc/reverb.hip, C ABI
+``misonet_reverb_measure``; :class:`Reverb`, INTEGRATION.md 4j, restated in tests/reverb_ref.py).
 
 Definitions:
   * stats[i][j] = (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j) over the valid samples; additive over the chunks of a recording;
@@ -541,27 +543,35 @@ def _wave_batch(items, dev, pinned, limits):
     return (padded(0, S, recs[0][0].dtype), padded(1, S, torch.float32), padded(2, 1, torch.float32) if with_mix else None, nv)
 
 
-def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = None, stoi_fs: Optional[int] = None):
+def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = None, stoi_fs: Optional[int] = None,
+               reverb_fs: Optional[int] = None):
     """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
     same S and all or none with a mixture; any lengths) -> (the device block [len(items), W] of :func:`bss_energies` for
     filters of ``bss_filt_len`` taps, that of :func:`stoi_block` at rate ``stoi_fs``), either None where its argument is
     None, queued on the current stream of ``dev``.  Several recordings go as one batch, zero-padded to the longest with
     ``n_valid`` set, and the batch is built and copied once for both: a row is bit for bit what the recording gives
-    alone.  ``pinned``: host inputs go through pinned memory and asynchronous copies, so that the caller is not held up."""
+    alone.  ``pinned``: host inputs go through pinned memory and asynchronous copies, so that the caller is not held up.
+    ``reverb_fs`` (not None): a third entry, the block of :func:`reverb_block` at that rate, from the same batch; without it
+    the pair is returned as it always was."""
     import torch
     if stoi_fs is not None:
         stoi_fs = check_stoi_fs(stoi_fs)
+    if reverb_fs is not None:
+        reverb_fs = check_reverb_fs(reverb_fs)
 
     def limits(S, L):
         if bss_filt_len is not None:
             _bss_limits(S, S, int(bss_filt_len), L)
         if stoi_fs is not None:
             _stoi_limits(S, L)
+        if reverb_fs is not None:
+            _reverb_limits(S, L)
 
     with torch.cuda.device(dev):
         est, clean, mix, nv = _wave_batch(items, dev, pinned, limits)
-        return (bss_energies(est, clean, mix, nv, int(bss_filt_len)) if bss_filt_len is not None else None,
-                stoi_block(est, clean, mix, nv, stoi_fs) if stoi_fs is not None else None)
+        res = (bss_energies(est, clean, mix, nv, int(bss_filt_len)) if bss_filt_len is not None else None,
+               stoi_block(est, clean, mix, nv, stoi_fs) if stoi_fs is not None else None)
+        return res if reverb_fs is None else res + (reverb_block(est, clean, mix, nv, reverb_fs),)
 
 
 def bss_queue(items, filt_len: int, dev, pinned: bool = False):
@@ -831,3 +841,229 @@ def stoi_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Stoi:
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     row = stoi_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
     return stoi_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))
+
+
+# ---- cepstral distance, LLR and fwSegSNR -------------------------------------------------------------
+# x the clean reference, y the estimate, float64 throughout: frames of 25 ms every 10 ms under MATLAB's hanning, per frame the
+# real cepstrum (25 coefficients), 23 mel band sums, the autocorrelation and the LPC of order 12; CD = the mean-normalised
+# cepstral distance in dB (cap 10), LLR = ln(a_y' R_x a_y / a_x' R_x a_x) in [0, 2], fwSegSNR = the band-weighted segmental SNR
+# in [-10, 35] dB of the signals at unit power; mean and median over the frames whose reference is not digital silence.  The
+# parameters are the REVERB challenge's as published; the figures have not been compared against its MATLAB tools.
+REVERB_RATES = (8000, 16000)
+REVERB_SCRATCH_CAP = 1 << 30    # bytes of device scratch per group of reverb_block: larger batches go in groups
+REVERB_FIGURES = ("cd", "cd_median", "llr", "llr_median", "fwsegsnr", "fwsegsnr_median")
+
+
+@dataclasses.dataclass
+class Reverb:
+    """Cepstral distance (dB), log-likelihood ratio (nats) and frequency-weighted segmental SNR (dB) of one recording, speaker
+    j = reference j: the mean and the median over the counted frames.  Smaller is better for CD and LLR, larger for fwSegSNR,
+    so an improvement ``*_i`` (best assignment minus mixture, a plain difference) is good when NEGATIVE for CD and LLR and when
+    POSITIVE for fwSegSNR.  ``valid[j] = False``: reference j has no frame that is not digital silence; every figure is NaN."""
+    cd: np.ndarray                        # [S] mean CD(e_j, r_j)
+    cd_median: np.ndarray
+    llr: np.ndarray
+    llr_median: np.ndarray
+    fwsegsnr: np.ndarray
+    fwsegsnr_median: np.ndarray
+    perm_best: List[int]                  # p[j] = the estimate of reference j in the assignment with the least summed mean CD
+    cd_best: np.ndarray                   # [S] the figures of (e_p[j], r_j)
+    cd_median_best: np.ndarray
+    llr_best: np.ndarray
+    llr_median_best: np.ndarray
+    fwsegsnr_best: np.ndarray
+    fwsegsnr_median_best: np.ndarray
+    cd_mix: Optional[np.ndarray]          # [S] the figures of (mixture, r_j), or None without a mixture
+    cd_median_mix: Optional[np.ndarray]
+    llr_mix: Optional[np.ndarray]
+    llr_median_mix: Optional[np.ndarray]
+    fwsegsnr_mix: Optional[np.ndarray]
+    fwsegsnr_median_mix: Optional[np.ndarray]
+    cd_i: Optional[np.ndarray]            # [S] cd_best - cd_mix (negative is better), ...
+    cd_median_i: Optional[np.ndarray]
+    llr_i: Optional[np.ndarray]
+    llr_median_i: Optional[np.ndarray]
+    fwsegsnr_i: Optional[np.ndarray]      # ... fwsegsnr_best - fwsegsnr_mix (positive is better)
+    fwsegsnr_median_i: Optional[np.ndarray]
+    frames: np.ndarray                    # [S] int: frames of the recording
+    frames_used: np.ndarray               # [S] int: K, those where reference j is not digital silence
+    frames_llr: np.ndarray                # [S] int: K_llr of (e_j, r_j)
+    valid: np.ndarray                     # [S] bool
+    fs: int
+    n_samples: int
+
+    def as_dict(self) -> dict:
+        def lst(x):
+            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
+        out = {}
+        for key in REVERB_FIGURES:
+            for suffix in ("", "_best", "_mix", "_i"):
+                out[key + suffix] = lst(getattr(self, key + suffix))
+        out.update(perm_best=[int(p) for p in self.perm_best], frames=[int(v) for v in self.frames],
+                   frames_used=[int(v) for v in self.frames_used], frames_llr=[int(v) for v in self.frames_llr],
+                   valid=[bool(v) for v in self.valid], fs=int(self.fs), n_samples=int(self.n_samples))
+        return out
+
+
+def reverb_from_matrices(figures, counts, fs: int = 16000, n_samples: int = 0) -> Reverb:
+    """figures float64 [S (+ 1) estimates, S references, 6] and counts int [S (+ 1), S, 3] = (frames, K, K_llr) as the device
+    leaves them (the mixture as the last estimate, where there is one) -> :class:`Reverb`.  Host, no GPU."""
+    fig = np.array(figures, dtype=np.float64)
+    cnt = np.asarray(counts, dtype=np.int64)
+    if fig.ndim != 3 or fig.shape[2] != 6 or fig.shape[0] not in (fig.shape[1], fig.shape[1] + 1) \
+            or cnt.shape != fig.shape[:2] + (3,):
+        raise ValueError("figures must be [S (+ 1), S, 6] (estimates x references) and counts [S (+ 1), S, 3]")
+    S = fig.shape[1]
+    idx = np.arange(S)
+    p = best_perm(-fig[:S, :, 0])
+    f = {}
+    for k, key in enumerate(REVERB_FIGURES):
+        f[key] = fig[idx, idx, k]
+        f[key + "_best"] = np.array([fig[p[j], j, k] for j in range(S)])
+        f[key + "_mix"] = fig[S, :, k].copy() if fig.shape[0] > S else None
+        f[key + "_i"] = f[key + "_best"] - f[key + "_mix"] if fig.shape[0] > S else None
+    return Reverb(perm_best=p, frames=cnt[idx, idx, 0], frames_used=cnt[idx, idx, 1], frames_llr=cnt[idx, idx, 2],
+                  valid=cnt[idx, idx, 1] >= 1, fs=int(fs), n_samples=int(n_samples), **f)
+
+
+def reverb_mean_of(items: Sequence[Reverb]) -> dict:
+    """The ``"reverb"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers"""
+    out = {}
+    for key in REVERB_FIGURES:
+        for suffix in ("", "_best", "_mix", "_i"):
+            vals = [float(getattr(e, key + suffix)[j]) for e in items if getattr(e, key + suffix) is not None
+                    for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key + suffix)[j])]
+            out[key + suffix] = float(np.mean(vals)) if vals else None
+    out["n_recordings"] = len(items)
+    out["n_speakers_valid"] = int(sum(int(np.sum(e.valid)) for e in items))
+    return out
+
+
+def check_reverb_fs(fs):
+    if int(fs) != fs or int(fs) not in REVERB_RATES:
+        raise ValueError(f"CD, LLR and fwSegSNR are defined here for fs = 8000 or 16000 Hz (got {fs})")
+    return int(fs)
+
+
+def reverb_frames(n: int, fs: int) -> int:
+    """(n - N) // H + 1 frames of N = fs / 40 samples every H = fs / 100, 0 for n < N; negative outside the limits (n <= 2^24,
+    the two rates)"""
+    return int(_lib.lib().misonet_reverb_frames(int(n), int(fs)))
+
+
+def reverb_scratch_bytes(B: int, NS: int, R: int, n: int, fs: int) -> int:
+    """bytes of scratch for :func:`reverb_measure` over NS signals per item (R references, the estimates, the mixture) of n
+    samples: 8 B (NS + 75 NS f + 3 (NS - R) R f), f = max(frames, 1); negative outside the limits"""
+    return int(_lib.lib().misonet_reverb_scratch_bytes(int(B), int(NS), int(R), int(n), int(fs)))
+
+
+def _reverb_limits(S, L):
+    if not (1 <= S <= 4):
+        raise ValueError(f"1 <= S <= 4 speakers (got {S})")
+    if not (1 <= L <= 1 << 24):
+        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
+
+
+def reverb_measure(est, ref, mix=None, n_valid=None, fs: int = 16000, frame_values: bool = False):
+    """est int16 or float32 [B, E, n], ref float32 [B, R, n] (device views as :func:`wave_stats` takes them), mix float32
+    [B, 1, n] or None (measured as one more estimate, the last), n_valid int32 [B] (device) or None.  Returns (out float64
+    [B, E (+ 1), R, 6] = (CD mean, CD median, LLR mean, LLR median, fwSegSNR mean, fwSegSNR median), count int32
+    [B, E (+ 1), R, 3] = (frames, K, K_llr), frame float64 [B, E (+ 1), R, 3, frames of n] or None: the CD, LLR and fwSegSNR of
+    every frame, NaN where it is not counted).  Asynchronous on the current stream; an item's rows do not depend on the batch."""
+    import torch
+    fs = check_reverb_fs(fs)
+    est = _wave_view(est, "est", (torch.int16, torch.float32))
+    ref = _wave_view(ref, "ref", (torch.float32,))
+    B, E, n = est.shape
+    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
+        raise ValueError("est and ref must agree in B, n and device")
+    R = ref.shape[1]
+    if not (1 <= E <= 4 and 1 <= R <= 4):
+        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+    if not (1 <= n <= 1 << 24):
+        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
+    if B < 1 or B > 4096:
+        raise ValueError("1 <= B <= 4096 items")
+    dev = est.device
+    if mix is not None:
+        mix = _wave_view(mix, "mix", (torch.float32,))
+        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
+            raise ValueError("mix must be [B, 1, n] on the device of est")
+    if n_valid is not None:
+        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
+                or n_valid.numel() != B or not n_valid.is_contiguous():
+            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    L = _lib.lib()
+    NE = E + (1 if mix is not None else 0)
+    nb = int(L.misonet_reverb_scratch_bytes(B, R + NE, R, n, fs))
+    out = torch.empty((B, NE, R, 6), dtype=torch.float64, device=dev)
+    count = torch.empty((B, NE, R, 3), dtype=torch.int32, device=dev)
+    frame = None
+    if frame_values:
+        frame = torch.full((B, NE, R, 3, int(L.misonet_reverb_frames(n, fs))), float("nan"), dtype=torch.float64, device=dev)
+    scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.misonet_reverb_measure(est.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
+                                            est.stride(2), ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
+                                            mix.data_ptr() if mix is not None else None,
+                                            mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
+                                            B, E, R, n, n_valid.data_ptr() if n_valid is not None else None, fs,
+                                            out.data_ptr(), count.data_ptr(),
+                                            frame.data_ptr() if frame is not None and frame.numel() else None,
+                                            scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    return out, count, frame
+
+
+def reverb_frame_values(est, ref, fs: int = 16000, mix=None, n_valid=None):
+    """the values of every frame behind the figures, for tests and plots: est / ref / mix / n_valid as :func:`reverb_measure`
+    takes them -> float64 [B, E (+ 1), R, 3, frames of n] = the CD, LLR and fwSegSNR of frame t of estimate i against reference
+    j, NaN where the frame is not counted"""
+    return reverb_measure(est, ref, mix, n_valid, fs, frame_values=True)[2]
+
+
+def reverb_block(est, ref, mix=None, n_valid=None, fs: int = 16000):
+    """est int16 / float32 [B, S, n], ref float32 [B, S, n], mix float32 [B, 1, n] or None (device views), n_valid int32 [B] or
+    None -> a device float64 block [B, W]: per item the six figures of every (estimate, reference) pair ([S (+ 1), S, 6], the
+    mixture as the last estimate) and (frames, K, K_llr) per pair ([S (+ 1), S, 3]): what :func:`reverb_unpack` reads.
+    Everything is queued on the current stream; nothing synchronises.  Batches beyond 1 GiB of scratch run in groups."""
+    import torch
+    B, E, n = est.shape
+    R = ref.shape[1]
+    NS = R + E + (1 if mix is not None else 0)
+    per = max(reverb_scratch_bytes(1, NS, R, max(n, 1), check_reverb_fs(fs)), 1)
+    g = max(1, min(B, REVERB_SCRATCH_CAP // per))
+    rows = []
+    for lo in range(0, B, g):
+        hi = min(B, lo + g)
+        out, count, _ = reverb_measure(est[lo:hi], ref[lo:hi], mix[lo:hi] if mix is not None else None,
+                                       n_valid[lo:hi] if n_valid is not None else None, fs)
+        rows.append(torch.cat([out.reshape(hi - lo, -1), count.to(torch.float64).reshape(hi - lo, -1)], dim=1))
+    return rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+
+
+def reverb_unpack(row, S: int, fs: int, n_samples: int) -> Reverb:
+    """one host row of :func:`reverb_block` -> :class:`Reverb`"""
+    row = np.asarray(row, dtype=np.float64)
+    E = row.shape[0] // (9 * S)
+    if E not in (S, S + 1) or row.shape[0] != 9 * S * E:
+        raise ValueError("not a row of reverb_block for this number of speakers")
+    return reverb_from_matrices(row[:6 * S * E].reshape(E, S, 6), row[6 * S * E:].reshape(E, S, 3), fs=fs, n_samples=n_samples)
+
+
+def reverb_queue(items, fs: int, dev, pinned: bool = False):
+    """:func:`side_queue` for CD / LLR / fwSegSNR alone: the device block [len(items), W] of :func:`reverb_block`"""
+    return side_queue(items, dev, pinned, reverb_fs=fs)[2]
+
+
+def reverb_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Reverb:
+    """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
+    :class:`Reverb` (1 <= S <= 4, L <= 2^24, fs 8000 or 16000): the counterpart of :func:`score_waves` for cepstral distance,
+    LLR and fwSegSNR, for the output of ``enhance_continuous`` and for files read back from disk."""
+    import torch
+    fs = check_reverb_fs(fs)
+    est = torch.as_tensor(est)
+    if est.dim() == 2:
+        _reverb_limits(int(est.shape[0]), int(est.shape[1]))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    row = reverb_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
+    return reverb_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Scores a directory of separated wav files against a directory of clean ones, on the device.
 
-    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]] [--stoi]
+    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]] [--stoi] [--reverb]
 
 EST_DIR holds ``<name>_{s}.wav`` (what ``enhance_recording(save_path=...)`` / ``inference`` write: 24-bit or 16-bit PCM, mono);
 REF_DIR holds the clean sources under the same names (``<name>_{s}.wav``, any channel count: channel ``--ref-ch`` is used)
@@ -9,7 +9,9 @@ and, there or in ``--mix-dir``, the observation as ``<name>.wav`` (optional: wit
 Prints (or writes) the JSON ``Enhancer.inference(..., score=True)`` writes: ``{name: Score.as_dict()}`` plus ``"mean"``.
 ``--bss`` adds BSS-eval SDR, SIR and SAR (``BssEval.as_dict()``, INTEGRATION.md 4e, filters of ``--filt-len`` taps) as a
 ``"bss"`` entry of every recording and of ``"mean"``; ``--stoi`` adds STOI and ESTOI (``Stoi.as_dict()``, INTEGRATION.md 4f, at
-the rate the files carry: 8, 10 or 16 kHz) as a ``"stoi"`` entry likewise; without the flags the output is what it always was.
+the rate the files carry: 8, 10 or 16 kHz) as a ``"stoi"`` entry likewise; ``--reverb`` adds the cepstral distance, the
+log-likelihood ratio and the frequency-weighted segmental SNR (``Reverb.as_dict()``, INTEGRATION.md 4j, at the rate the files
+carry: 8 or 16 kHz) as a ``"reverb"`` entry; without the flags the output is what it always was.
 Definitions: INTEGRATION.md 4d.  Lengths may differ by the padding of the last hop: the common length is scored.
 """
 import argparse
@@ -53,13 +55,14 @@ def main(argv=None):
     ap.add_argument("--bss", action="store_true", help="also BSS-eval SDR / SIR / SAR")
     ap.add_argument("--filt-len", type=int, default=512, help="taps of the BSS-eval projection filters")
     ap.add_argument("--stoi", action="store_true", help="also STOI and ESTOI (the rate comes from the files)")
+    ap.add_argument("--reverb", action="store_true", help="also cepstral distance, LLR and fwSegSNR (the rate comes from the files)")
     a = ap.parse_args(argv)
     from misonet_amd import score
     pat = re.compile(r"^(.*)_0\.wav$")
     names = sorted(m.group(1) for m in map(pat.match, os.listdir(a.est_dir)) if m)
     if not names:
         raise SystemExit(f"no <name>_0.wav in {a.est_dir}")
-    scores, evals, stois = {}, {}, {}
+    scores, evals, stois, reverbs = {}, {}, {}, {}
     for name in names:
         est, ref, rates = [], [], set()
         for s in range(a.num_spks):
@@ -81,7 +84,12 @@ def main(argv=None):
             if len(rates) != 1:
                 raise SystemExit(f"{name}: the estimates disagree about the rate ({sorted(rates)})")
             stois[name] = score.stoi_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
-                                           mix[:n] if mix is not None else None, fs=rates.pop())
+                                           mix[:n] if mix is not None else None, fs=min(rates))
+        if a.reverb:
+            if len(rates) != 1:
+                raise SystemExit(f"{name}: the estimates disagree about the rate ({sorted(rates)})")
+            reverbs[name] = score.reverb_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
+                                               mix[:n] if mix is not None else None, fs=min(rates))
     doc = {name: sc.as_dict() for name, sc in scores.items()}
     doc["mean"] = score.mean_of(list(scores.values()))
     if a.bss:
@@ -92,6 +100,10 @@ def main(argv=None):
         for name, st in stois.items():
             doc[name]["stoi"] = st.as_dict()
         doc["mean"]["stoi"] = score.stoi_mean_of(list(stois.values()))
+    if a.reverb:
+        for name, rv in reverbs.items():
+            doc[name]["reverb"] = rv.as_dict()
+        doc["mean"]["reverb"] = score.reverb_mean_of(list(reverbs.values()))
     text = json.dumps(doc, indent=1)
     if a.out:
         with open(a.out, "w") as fh:
