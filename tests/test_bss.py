@@ -1,6 +1,13 @@
 """BSS-eval on the CPU: the two NumPy / SciPy forms of tests/bss_ref.py against each other (the explicit mir_eval form is the
 oracle of tests/test_gpu_bss.py), the host function ``score.bss_from_energies`` against the restated rules, and the host
-side of the C ABI (version 490, the size function and its limits).  No device is needed."""
+side of the C ABI (version 490, the size function and its limits).  No device is needed.
+
+The solver on its own input (``bss_ref.SOLVE_SHAPES``: every panel width, the short systems that end early, R = 4, Q = 1024):
+the two forms on those inputs, the reference by Cholesky against the one by LU within ``bss_ref.solve_bound``, and
+``bss_ref.blocked`` -- the panel scheme of the device restated in NumPy -- within the same bound when it is clean and outside
+it by a factor of 100 or more with every planted fault.  The full-size case (N = 4096) runs through all of it but the planted
+faults: Q = 1024 is whole panels, the one fault it reaches is reached at (2, 2, 1024) already."""
+import functools
 import itertools
 import os
 import re
@@ -33,6 +40,93 @@ def test_the_two_forms_agree(kind, S):
             assert d <= FORMS_TOL, (kind, S, L, Q, d)
             worst = max(worst, d)
     print(f"[bss] {kind} S={S}: largest gap between the forms {worst:.2e} dB")
+
+
+@functools.lru_cache(maxsize=None)
+def _solve_ref(kind, R, E, Q, L):
+    """one SOLVE_SHAPES case: the signals, their float64 correlations and the Cholesky reference, computed once"""
+    est, refs = bss_ref.long_case(kind, R, E, Q, L)
+    Rrr, Rre, Eee = bss_ref.correlations(est, refs, Q)
+    T, A, info, cond = bss_ref.solve_energies(Rrr, Rre)
+    for x in (est, refs, Rrr, Rre, Eee, T, A):
+        x.setflags(write=False)
+    return dict(est=est, refs=refs, Rrr=Rrr, Rre=Rre, Eee=Eee, T=T, A=A, info=info, cond=cond)
+
+
+def _miss(T, A, c, R, Q):
+    """the largest error / solve_bound over T and A against the reference of case c"""
+    bT = np.array([bss_ref.solve_bound(Q, k) for k in c["cond"][1:]])
+    return max(float(np.max(np.abs(A - c["A"]) / (np.abs(c["A"]) * bss_ref.solve_bound(R * Q, c["cond"][0])))),
+               float(np.max(np.abs(T - c["T"]) / (np.abs(c["T"]) * bT))))
+
+
+_CASES = bss_ref.solve_cases()
+_ids = lambda c: "-".join(str(v) for v in c)     # noqa: E731
+
+
+@pytest.mark.parametrize("case", _CASES, ids=_ids)
+def test_the_two_forms_agree_on_the_solver_inputs(case):
+    kind, R, E, Q, L = case
+    c = _solve_ref(*case)
+    sdr, sir, sar = bss_ref.explicit(c["est"], c["refs"], Q)
+    T, A, Eee, valid, info = bss_ref.energies(c["est"], c["refs"], Q)
+    assert info == -1 and valid.all()
+    assert np.array_equal(T, c["T"]) and np.array_equal(A, c["A"])          # solve_energies is the same form
+    d = max(np.abs(10 * np.log10(T / (Eee[:, None] - T)) - sdr).max(), np.abs(10 * np.log10(A / (Eee - A)) - sar).max())
+    if R > 1:
+        d = max(d, np.abs(10 * np.log10(T / (A[:, None] - T)) - sir).max())
+    print(f"[bss] solver input {case}: cond {c['cond'][0]:.2e}; forms differ by {d:.2e} dB")
+    assert d <= FORMS_TOL, (case, d)
+
+
+@pytest.mark.parametrize("case", _CASES, ids=_ids)
+def test_the_reference_stays_inside_the_bound(case):
+    kind, R, E, Q, L = case
+    c = _solve_ref(*case)
+    assert c["info"] == -1 and np.isfinite(c["cond"]).all()
+    T, A, info, _ = bss_ref.solve_energies(c["Rrr"], c["Rre"], solver="lu", cond=False)
+    m = _miss(T, A, c, R, Q)
+    print(f"[bss] solver input {case}: cond {[f'{k:.2e}' for k in c['cond']]}; LU - Cholesky = {m:.2e} of the bound")
+    assert info == -1 and m <= 1.0, (case, m)
+
+
+_fault_miss = {}
+
+
+@pytest.mark.parametrize("case", _CASES, ids=_ids)
+def test_the_restatement_is_clean_and_every_fault_is_caught(case):
+    kind, R, E, Q, L = case
+    c = _solve_ref(*case)
+    T, A, info = bss_ref.blocked(c["Rrr"], c["Rre"])
+    m = _miss(T, A, c, R, Q)
+    print(f"[bss] solver input {case}: blocked - reference = {m:.2e} of the bound")
+    assert info == -1 and m <= 1.0, (case, m)
+    for fault in bss_ref.FAULTS if case[1:] != bss_ref.FULL_SIZE else ():
+        hit = []
+        T, A, info = bss_ref.blocked(c["Rrr"], c["Rre"], fault=fault, hit=hit)
+        if not hit:
+            continue                                                # the shape does not reach the place
+        f = np.inf if info != -1 else _miss(T, A, c, R, Q)
+        print(f"[bss] solver input {case}: fault {fault}: info {info}, {f:.2e} of the bound")
+        _fault_miss[fault] = min(_fault_miss.get(fault, np.inf), f)
+        assert f >= 100.0, (case, fault, f)
+
+
+def test_every_fault_is_reached_by_a_shape():
+    """a fault no shape exposes is a gap in SOLVE_SHAPES (the shapes up to N = 320 reach all five); after the table above
+    this prints the smallest miss factor per fault over all shapes"""
+    reached = set()
+    for case in _CASES:
+        kind, R, E, Q, L = case
+        if kind == "white" and R * Q <= 320:
+            c = _solve_ref(*case)
+            for fault in bss_ref.FAULTS:
+                hit = []
+                bss_ref.blocked(c["Rrr"], c["Rre"], fault=fault, hit=hit)
+                reached.update(hit)
+    assert sorted(reached) == sorted(bss_ref.FAULTS)
+    for fault, f in sorted(_fault_miss.items()):
+        print(f"[bss] fault {fault}: smallest miss over the shapes {f:.2e} of the bound")
 
 
 def _same(ev, want):
@@ -105,6 +199,25 @@ def test_identical_references_trip_the_pivot_rule_at_row_q():
         np.linalg.cholesky(bss_ref.gram(bss_ref.correlations(est, refs, Q)[0]))
 
 
+def test_the_pivot_rule_inside_a_narrow_panel():
+    """three references, the third a copy of the first, Q = 16: the only panel is 48 wide and fails at row 32; two identical
+    references at Q = 48 and 80 fail at row Q, in panel 0 (row 48 of 64) and in column 16 of panel 1.  The restatement of
+    the device's scheme reports the same rows."""
+    est, refs = bss_ref.long_case("ar2", 3, 3, 16, 2000)
+    refs[2] = refs[0]
+    T, A, Eee, valid, info = bss_ref.energies(est, refs, 16)
+    assert info == 32 and np.isnan(T).all() and np.isnan(A).all() and valid.all()
+    Rrr, Rre, _ = bss_ref.correlations(est, refs, 16)
+    Tb, Ab, ib = bss_ref.blocked(Rrr, Rre)
+    assert ib == 32 and np.isnan(Tb).all() and np.isnan(Ab).all()
+    for Q in (48, 80):
+        est, refs = bss_ref.long_case("ar2", 2, 2, Q, 4000)
+        refs[1] = refs[0]
+        assert bss_ref.energies(est, refs, Q)[4] == Q
+        Rrr, Rre, _ = bss_ref.correlations(est, refs, Q)
+        assert bss_ref.solve_energies(Rrr, Rre, cond=False)[2] == Q and bss_ref.blocked(Rrr, Rre)[2] == Q
+
+
 def test_silent_reference_leaves_the_span():
     est, refs = bss_ref.case("white", 3, 5000)
     refs[1] = 0
@@ -131,7 +244,8 @@ def test_abi_490_header_exports_and_signatures():
 
 def test_scratch_bytes_value_and_limits():
     from misonet_amd import score
-    for B, E, R, n, Q in itertools.product((1, 16), (1, 2, 4), (1, 2, 4), (1, 5000, 192000, 1 << 24), (16, 64, 512, 1024)):
+    for B, E, R, n, Q in itertools.product((1, 16), (1, 2, 4), (1, 2, 4), (1, 5000, 192000, 1 << 24),
+                                         (16, 48, 64, 80, 272, 512, 1008, 1024)):
         corr = -(-(n + 15) // 4096) * (R * R + R * E + E) * Q
         systems = (R * Q + 4) * R * Q + R * (Q + 4) * Q
         assert score.bss_scratch_bytes(B, E, R, n, Q) == 8 * B * max(corr, systems), (B, E, R, n, Q)

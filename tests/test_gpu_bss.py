@@ -5,7 +5,15 @@ permutation, and the recording paths with ``bss=True``.
 
 Measured on one MI355X: correlations within 2.7e-3 of their bound; largest deviation from the oracle over all 72 inputs
 6.3e-8 dB (quarter-band sources; 3.9e-11 dB on white and AR(2) ones) against the ceiling of 1e-6 dB.  The
-module prints both (``[bss] correlations ...``, ``[bss] all inputs ...``)."""
+module prints both (``[bss] correlations ...``, ``[bss] all inputs ...``).
+
+The solver on its own input (``bss_ref.SOLVE_SHAPES``, 21 inputs: every panel width from 16 to 64, order-Q systems that end
+narrow while system 0 goes on, R = 4, E != R, Q = 1024, N = 4096; estimates whose filters span all Q lags): T and A against
+``bss_ref.solve_energies`` on the device's own correlations within ``bss_ref.solve_bound`` = 4 N u cond, relative.  Measured
+on one MI355X: largest error / bound 1.7e-2 (white, R = 3, E = 2, Q = 16), 3.4e-4 at N = 4096; largest deviation of the figures
+from the explicit oracle on those inputs 1.1e-12 dB (``[bss] solver ...``).  Correlations at Q = 16 ... 1008 and
+n = 15 ... 9000 within 4.7e-3 of their bound.  The same bits from a scratch of all ones and of all zero."""
+import functools
 import json
 import os
 
@@ -53,11 +61,36 @@ def _check_corr(got, est, refs, nv, Q, tag):
 def test_correlations_against_numpy(Q, i16):
     """float32 and int16 estimates, contiguous and time-major views, B = 3 with different n_valid, lengths that are no
     multiple of 4096 and one shorter than Q"""
+    _corr_sweep(Q, i16, ((300, 2, 2), (4096, 1, 1), (5000, 4, 4), (20001, 2, 3), (70000, 1, 2)))
+
+
+@pytest.mark.parametrize("i16", [True, False], ids=["int16", "float32"])
+@pytest.mark.parametrize("Q", [16, 48, 240, 256, 272, 768, 1008])
+def test_correlations_at_the_other_lag_tilings(Q, i16):
+    """a last wave with fewer than 256 lags (16, 48, 240, 272, 1008), exactly one and two waves (256, 272), three waves of
+    four (768); n = 15 (one staging round, every lag past n), 4081 / 4082 (the last length of one segment and the first of
+    two: row v of A reads x[k - v], so segment 1 starts with x[4081]), 4097 and 9000 (three segments)"""
+    _corr_sweep(Q, i16, [(n, E, R) for n in (15, 4081, 4082, 4097, 9000) for E, R in ((1, 1), (2, 3))])
+
+
+def test_segment_count_steps_at_4082():
+    """ceil((n + 15) / 4096) segments.  The size function returns the larger of the correlation partials and the systems, and
+    at every admitted shape the systems outweigh two segments, so the step shows where the partials lead: E = 4, R = 1,
+    Q = 16 (9 pairs of 16 lags per segment against 640 doubles of systems) from five segments on, at n = 4 * 4096 + 4081
+    and + 4082.  At 4081 and 4082 themselves the size is that of the systems."""
+    from misonet_amd import score
+    per_seg = 8 * (1 + 4 + 4) * 16
+    assert score.bss_scratch_bytes(1, 4, 1, 4 * 4096 + 4081, 16) == 5 * per_seg
+    assert score.bss_scratch_bytes(1, 4, 1, 4 * 4096 + 4082, 16) == 6 * per_seg
+    assert score.bss_scratch_bytes(1, 4, 1, 4081, 16) == score.bss_scratch_bytes(1, 4, 1, 4082, 16) == 8 * 640
+
+
+def _corr_sweep(Q, i16, shapes):
     _need_gpu()
     from misonet_amd import score
     rng = np.random.default_rng(Q + int(i16))
     worst = 0.0
-    for n, E, R in ((300, 2, 2), (4096, 1, 1), (5000, 4, 4), (20001, 2, 3), (70000, 1, 2)):
+    for n, E, R in shapes:
         refs = (0.1 * rng.standard_normal((3, R, n))).astype(np.float32)
         est = (0.1 * rng.standard_normal((3, E, n))).astype(np.float32)
         est[:, :min(E, R)] += np.float32(0.5) * refs[:, :min(E, R)]
@@ -88,6 +121,137 @@ def _device_figures(est, refs, Q):
     T, A, info = score.bss_solve(Rrr, Rre, Eee)
     assert int(info[0]) == -1
     return bss_ref.figures(T[0].cpu().numpy(), A[0].cpu().numpy(), Eee[0].cpu().numpy())
+
+
+@functools.lru_cache(maxsize=None)
+def _solver_run(case):
+    """one SOLVE_SHAPES case through bss_corr and bss_solve, and the float64 reference on the DEVICE's correlations: the
+    error of the correlations is not part of what is measured.  Computed once, shared by the tests below."""
+    from misonet_amd import score
+    kind, R, E, Q, L = case
+    est, refs = bss_ref.long_case(kind, R, E, Q, L)
+    Rrr, Rre, Eee = score.bss_corr(_dev(est)[None], _dev(refs)[None], None, Q)
+    T, A, info = score.bss_solve(Rrr, Rre, Eee)
+    out = dict(est=est, refs=refs, Rrr=Rrr[0].cpu().numpy(), Rre=Rre[0].cpu().numpy(), Eee=Eee[0].cpu().numpy(),
+               T=T[0].cpu().numpy(), A=A[0].cpu().numpy(), info=int(info[0]))
+    out["T_ref"], out["A_ref"], out["info_ref"], out["cond"] = bss_ref.solve_energies(out["Rrr"], out["Rre"])
+    for x in out.values():
+        if isinstance(x, np.ndarray):
+            x.setflags(write=False)
+    return out
+
+
+_CASES = bss_ref.solve_cases()
+_ids = lambda c: "-".join(str(v) for v in c)     # noqa: E731
+_ratios, _devs = {}, {}
+
+
+@pytest.mark.parametrize("case", _CASES, ids=_ids)
+def test_solver_on_its_own_input(case):
+    """every T[i, j] and A[i] within ``bss_ref.solve_bound`` (4 N u cond, relative) of the float64 reference on the device's
+    own correlations, at every panel width the solver admits (bss_ref.SOLVE_SHAPES)"""
+    _need_gpu()
+    kind, R, E, Q, L = case
+    c = _solver_run(case)
+    assert c["T"].shape == (E, R) and c["A"].shape == (E,)
+    bA = bss_ref.solve_bound(R * Q, c["cond"][0])
+    bT = np.array([bss_ref.solve_bound(Q, k) for k in c["cond"][1:]])
+    rA = np.abs(c["A"] - c["A_ref"]) / (np.abs(c["A_ref"]) * bA)
+    rT = np.abs(c["T"] - c["T_ref"]) / (np.abs(c["T_ref"]) * bT)
+    worst = float(max(rA.max(), rT.max()))                           # NaN where the device gave one: fails below
+    _ratios[case] = worst
+    print(f"[bss] solver {case}: info {c['info']} cond(G) {c['cond'][0]:.2e}; error / bound: A {rA.max():.3e} T {rT.max():.3e}")
+    print(f"[bss] solver: worst error / bound so far {max(_ratios.values()):.3e} over {len(_ratios)} of {len(_CASES)} inputs")
+    assert c["info"] == -1 and c["info_ref"] == -1
+    assert np.all(rA <= 1.0) and np.all(rT <= 1.0), (case, rA, rT)
+
+
+@pytest.mark.parametrize("case", _CASES, ids=_ids)
+def test_solver_inputs_against_the_explicit_oracle(case):
+    _need_gpu()
+    kind, R, E, Q, L = case
+    c = _solver_run(case)
+    sdr, sir, sar = bss_ref.explicit(c["est"], c["refs"], Q)
+    assert c["info"] == -1
+    T, A, Eee = c["T"], c["A"], c["Eee"]
+    # bss_ref.figures wants as many estimates as references: the three figures straight from their definitions
+    d = max(np.abs(10 * np.log10(T / (Eee[:, None] - T)) - sdr).max(), np.abs(10 * np.log10(A / (Eee - A)) - sar).max())
+    if R > 1:
+        d = max(d, np.abs(10 * np.log10(T / (A[:, None] - T)) - sir).max())
+    _devs[case] = float(d)
+    print(f"[bss] solver input {case}: device - oracle {d:.3e} dB")
+    print(f"[bss] solver inputs: largest deviation from the oracle so far {max(_devs.values()):.3e} dB (ceiling {DB_CEIL:.0e})")
+    assert d <= DB_CEIL, (case, d)
+
+
+def test_pivot_rule_inside_narrow_panels():
+    """the first failing row lies inside a narrow panel: row 32 of the only panel (48 wide) with three references of which
+    the third repeats the first at Q = 16; row Q with two identical references at Q = 48 (panel 0, 64 wide in system 0) and
+    80 (column 16 of panel 1).  The item beside the failed one keeps the bits it has alone."""
+    _need_gpu()
+    from misonet_amd import score
+    for R, Q, L, row in ((3, 16, 2000, 32), (2, 48, 4000, 48), (2, 80, 4000, 80)):
+        est, refs = bss_ref.long_case("ar2", R, R, Q, L)
+        refs[R - 1] = refs[0]
+        Rrr, Rre, Eee = score.bss_corr(_dev(est)[None], _dev(refs)[None], None, Q)
+        T, A, info = score.bss_solve(Rrr, Rre, Eee)
+        assert int(info[0]) == row, (R, Q, int(info[0]))
+        assert torch.isnan(T).all() and torch.isnan(A).all()
+        e2, r2 = bss_ref.long_case("ar2", R, R, Q, L, seed=9)
+        both = _block(np.stack([est, e2]), np.stack([refs, r2]), None, None, Q)
+        alone = _block(e2[None], r2[None], None, None, Q)[0]
+        assert np.array_equal(both[1], alone) and np.isfinite(alone).all() and alone[R * R + 3 * R] == -1.0
+        assert both[0][R * R + 3 * R] == float(row) and np.isnan(both[0][:R * R + R]).all()
+
+
+def test_silent_middle_reference_at_a_narrow_panel():
+    """R = 3, Q = 48: N = 144 = two panels and one of 16; the identity block of the silent reference spans the seam of
+    panels 0 and 1"""
+    _need_gpu()
+    from misonet_amd import score
+    Q = 48
+    est, refs = bss_ref.long_case("white", 3, 3, Q, 4000)
+    refs[1] = 0
+    Rrr, Rre, Eee = score.bss_corr(_dev(est)[None], _dev(refs)[None], None, Q)
+    T, A, info = score.bss_solve(Rrr, Rre, Eee)
+    assert int(info[0]) == -1 and torch.equal(T[0, :, 1], torch.zeros(3, dtype=torch.float64, device="cuda"))
+    ev = score.bss_eval_waves(est, refs, filt_len=Q)
+    assert ev.ok and list(ev.valid) == [True, False, True]
+    assert np.isnan(ev.sdr[1]) and np.isnan(ev.sir[1]) and np.isfinite(ev.sar).all()
+    sdr, sir, sar = bss_ref.explicit(est, refs[[0, 2]], Q)           # the oracle run without that reference
+    for j, c in ((0, 0), (2, 1)):
+        assert abs(ev.sdr[j] - sdr[j, c]) <= DB_CEIL and abs(ev.sir[j] - sir[j, c]) <= DB_CEIL
+    assert np.abs(ev.sar - sar).max() <= DB_CEIL
+
+
+@pytest.mark.parametrize("R,E,Q,L", [(2, 2, 48, 4000), (3, 3, 272, 16000)])
+def test_result_does_not_depend_on_what_the_scratch_held(R, E, Q, L):
+    """bss_assemble_k writes the lower triangle only and bss_update_k reads, adds to and stores the upper half of every
+    diagonal tile: a caller-owned scratch of exactly misonet_bss_scratch_bytes bytes, all ones (NaN as float64) and all zero,
+    must give the same bits"""
+    _need_gpu()
+    from misonet_amd import _lib, score
+    est, refs = bss_ref.long_case("ar2", R, E, Q, L)
+    Rrr, Rre, Eee = score.bss_corr(_dev(est)[None], _dev(refs)[None], None, Q)
+    lib = _lib.lib()
+    nbytes = int(lib.misonet_bss_scratch_bytes(1, E, R, 1, Q))
+    assert nbytes == 8 * ((R * Q + 4) * R * Q + R * (Q + 4) * Q)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    got = []
+    for fill in (0xFF, 0x00):
+        scratch.fill_(fill)
+        T = torch.full((1, E, R), -7.0, dtype=torch.float64, device="cuda")
+        A = torch.full((1, E), -7.0, dtype=torch.float64, device="cuda")
+        info = torch.full((1,), 99, dtype=torch.int32, device="cuda")
+        _lib.check(lib.misonet_bss_solve(Rrr.data_ptr(), Rre.data_ptr(), Eee.data_ptr(), 1, E, R, Q, T.data_ptr(), A.data_ptr(),
+                                         info.data_ptr(), scratch.data_ptr(), nbytes, _lib.stream_ptr(scratch.device)))
+        torch.cuda.synchronize()
+        got.append((T.cpu().numpy(), A.cpu().numpy(), info.cpu().numpy()))
+    for a, b in zip(*got):
+        assert np.array_equal(a, b) and np.isfinite(a).all()
+    assert int(got[0][2][0]) == -1
+    T, A, info = score.bss_solve(Rrr, Rre, Eee)                      # and those of the call that allocates its own
+    assert np.array_equal(T.cpu().numpy(), got[0][0]) and np.array_equal(A.cpu().numpy(), got[0][1])
 
 
 _seen = {}
@@ -121,7 +285,7 @@ def _block(est, refs, mix, nv, Q):
     return score.bss_energies(_dev(est), _dev(refs), _dev(mix) if mix is not None else None, nv_dev, Q).cpu().numpy()
 
 
-@pytest.mark.parametrize("Q", [64, 512])
+@pytest.mark.parametrize("Q", [48, 64, 512])
 def test_reproducible_and_independent_of_the_batch(Q):
     _need_gpu()
     lens = (20000, 64000, 33333)
