@@ -417,6 +417,38 @@ int misonet_reverb_measure(const void* est_dev, int est_is_i16, long long est_sb
                            double* out_dev, int* count_dev, double* frame_dev, void* scratch_dev, long long scratch_bytes,
                            misonet_stream stream);
 
+/* ---- SRMR: the figure that needs no clean reference (ABI 550) ------------------------------------------------------------- */
+/* The speech-to-reverberation modulation energy ratio (Falk, Zheng & Chan 2010) of a signal, as INTEGRATION.md 4k defines it in
+ * full (tests/srmr_ref.py restates it; no SRMR toolbox was available, so the figure has not been compared against one): a
+ * 23-channel gammatone bank (Slaney's ERB filters, 125 Hz .. fs / 2), per channel the magnitude of the analytic signal over the
+ * whole recording (a transform of P = the smallest power of two >= n points), eight second-order modulation filters (4 .. 128 Hz,
+ * Q = 2) at the full rate, the energy of every 256 ms frame (64 ms hop, symmetric Hamming window) averaged over the frames, and
+ * the ratio of the energy in the four lowest modulation bands to that in bands 4 .. K* - 1, K* in 5..8 following the bandwidth
+ * of the channel that completes 90 % of the energy from the top.  All arithmetic after the loads is float64, without
+ * floating-point atomics and in a fixed order: bit-reproducible, independent of B, of the item's position in the batch and of the
+ * layout; samples past n_valid are not read, and P, the chunks and the frames of an item follow its own n_valid.
+ * misonet_srmr_frames: the frames of n samples, 1 + (n - N_w) / H_w or 0 for n < N_w, N_w = ceil(0.256 fs), H_w = ceil(0.064 fs)
+ *   (host only); -1 for fs other than 8000, 16000 or n outside 0..2^24.
+ * misonet_srmr_chunk: the samples C of a chunk of the scan that runs the recurrences in parallel along time (host only).
+ * misonet_srmr_measure: sig_dev, its strides, n_valid_dev and the int16 rule as the estimates of misonet_score_wave, S signals
+ *   per item; mix_dev (may be NULL) as in misonet_stoi_resample: the mixture is measured as one more signal, the last.  out_dev
+ *   double [B][S (+ 1)][3] = (SRMR, K*, BW in Hz); (NaN, 0, NaN) for a signal shorter than one frame or without energy.
+ *   count_dev int32 [B][S (+ 1)] = the frames of n_valid.  energy_dev (may be NULL) double [B][S (+ 1)][23][8]: the mean
+ *   modulation energies, channels ascending; NaN for a signal shorter than one frame.
+ * scratch_dev: misonet_srmr_scratch_bytes(B, NS, n, fs) bytes (host only), NS = S (+ 1): the 184 means of every signal and as
+ *   many slots of one (signal, channel) as fit 1 GiB (at least one; a slot is 8 (n + 2 P [P > 4096] + 24 chunks + 32 hops)
+ *   bytes), so the size is bounded whatever B; less returns MISONET_ENOMEM.  MISONET_EINVAL (the size functions: -1): a null
+ *   argument, S outside 1..4, NS outside 1..5, B outside 1..4096, n outside 1..2^24, another rate, a negative stride.  The first
+ *   call on a device builds a table of 28080 doubles (twiddles, windows, coefficients, transitions: one allocation and one
+ *   synchronous copy); after that the call is asynchronous on the stream, allocates nothing and can be captured. */
+long long misonet_srmr_frames(long long n, int fs);
+long long misonet_srmr_scratch_bytes(int B, int NS, long long n, int fs);
+int misonet_srmr_chunk(void);
+int misonet_srmr_measure(const void* sig_dev, int sig_is_i16, long long sig_sb, long long sig_ss, long long sig_st,
+                         const float* mix_dev, long long mix_sb, long long mix_st, int B, int S, long long n,
+                         const int* n_valid_dev, int fs, double* out_dev, int* count_dev, double* energy_dev, void* scratch_dev,
+                         long long scratch_bytes, misonet_stream stream);
+
 /* ---- fused on-device pipeline: the body of Tester_Enhance.inference (tester.py:865-939) -------------------- */
 /* MISO1_Inference (6 circular shifts batched as 6B forwards, tester.py:1014-1068) -> clean-reference
  * alignment (tester.py:889-915; skipped when clean_dev == NULL) -> MVDR per speaker (tester.py:917-924) ->

@@ -128,6 +128,12 @@ SIGNATURES = {
                                          C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong,
                                          C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_srmr_frames": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "misonet_srmr_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_longlong, C.c_int]),
+    "misonet_srmr_chunk": (C.c_int, []),
+    "misonet_srmr_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong,
+                                       C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_pipeline_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.POINTER(C.c_void_p)]),
     "misonet_pipeline_destroy": (C.c_int, [C.c_void_p]),

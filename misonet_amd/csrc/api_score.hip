@@ -1,6 +1,6 @@
 // C ABI of the scoring against clean references (include/misonet.h): misonet_score_* (score.hip), BSS-eval misonet_bss_*
-// (bss.hip), STOI / ESTOI misonet_stoi_* (stoi.hip), cepstral distance / LLR / fwSegSNR misonet_reverb_* (reverb.hip) and the
-// STOI and reverb tables of every device that uses them.  Host code only.
+// (bss.hip), STOI / ESTOI misonet_stoi_* (stoi.hip), cepstral distance / LLR / fwSegSNR misonet_reverb_* (reverb.hip), SRMR misonet_srmr_* (srmr.hip) and the
+// STOI, reverb and SRMR tables of every device that uses them.  Host code only.
 #include "api_common.hpp"
 
 using namespace mn;
@@ -237,6 +237,47 @@ int misonet_reverb_measure(const void* est, int est_is_i16, long long est_sb, lo
   const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
   HIPCHK(launch_reverb_measure(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, out, count, frame,
                                reinterpret_cast<double*>(scratch), reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- SRMR (srmr.hip) ---------------------------------------------------------------------------------------------------------
+// the table of the current device (twiddles and, per rate, window, filter coefficients, transitions, ERB, cutoffs), built on first
+// use as the STOI table is
+static DevTable<double> g_srmr_tab;
+static int get_srmr_table(const double** out) {
+  return g_srmr_tab.get(out, [](double** p) {
+    std::vector<double> t((size_t)srmr_table_count());
+    srmr_build_table(t.data());
+    return dev_upload(t, p);
+  });
+}
+
+long long misonet_srmr_frames(long long n, int fs) { return srmr_frames(n, fs); }
+int misonet_srmr_chunk(void) { return srmr_chunk(); }
+
+long long misonet_srmr_scratch_bytes(int B, int NS, long long n, int fs) {
+  const long long d = srmr_scratch_doubles(B, NS, n, fs);
+  return d < 0 ? -1 : d * (long long)sizeof(double);
+}
+
+int misonet_srmr_measure(const void* sig, int sig_is_i16, long long sig_sb, long long sig_ss, long long sig_st, const float* mix,
+                         long long mix_sb, long long mix_st, int B, int S, long long n, const int* n_valid, int fs, double* out,
+                         int* count, double* energy, void* scratch, long long scratch_bytes, misonet_stream stream) {
+  if (!sig || !out || !count || !scratch) return fail(MISONET_EINVAL, "null argument");
+  if (S < 1 || S > 4) return fail(MISONET_EINVAL, "S must be in [1, 4] (got %d)", S);
+  if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
+  if (fs != 8000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000 or 16000 (got %d)", fs);
+  if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
+  if (sig_sb < 0 || sig_ss < 0 || sig_st < 1 || (mix && (mix_sb < 0 || mix_st < 1)))
+    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
+  const int NS = S + (mix ? 1 : 0);
+  if (const int rc = scratch_fits(scratch_bytes, misonet_srmr_scratch_bytes(B, NS, n, fs), "misonet_srmr_scratch_bytes(B, S (+ 1), n, fs)"))
+    return rc;
+  const double* tab;
+  if (const int rc = get_srmr_table(&tab)) return rc;
+  const long long ss[3] = {sig_sb, sig_ss, sig_st}, ms[2] = {mix_sb, mix_st};
+  HIPCHK(launch_srmr_measure(sig, sig_is_i16 != 0, ss, mix, ms, B, S, n, n_valid, fs, tab, out, count, energy,
+                             reinterpret_cast<double*>(scratch), reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

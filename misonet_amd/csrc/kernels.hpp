@@ -311,6 +311,21 @@ hipError_t launch_reverb_measure(const void* est, int est_is_i16, const long lon
                                  const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out, int* count,
                                  double* frame_out /*or nullptr*/, double* scratch, hipStream_t s);
 
+// SRMR, the speech-to-reverberation modulation energy ratio (srmr.hip).  The table (srmr_table_count() doubles,
+// built on the host): the twiddles of the transforms and, per rate, the window, the gammatone and modulation coefficients, their
+// chunk-to-chunk transitions A^C, ERB(cf_j) and the lower cutoffs ll_k.  One call reads S signals through the strided view of
+// launch_score_wave's estimates (ss) and, where mix is not nullptr, the mixture as one more signal, the last (ms as for
+// launch_stoi_resample), and writes out [B][S (+ 1)][3] = (SRMR, K*, BW), count [B][S (+ 1)] = the frames and, where energy is
+// not nullptr, the mean modulation energies [B][S (+ 1)][23][8]; srmr_scratch_doubles(B, S (+ 1), n, fs) doubles of scratch.
+int srmr_table_count();
+void srmr_build_table(double* t);
+int srmr_chunk();                                  // C of the chunked scan
+long long srmr_frames(long long n, int fs);        // -1 for a rate that is not served or n outside 0 .. 2^24
+long long srmr_scratch_doubles(int B, int NS, long long n, int fs);   // -1 outside the limits
+hipError_t launch_srmr_measure(const void* sig, int sig_is_i16, const long long* ss, const float* mix, const long long* ms, int B,
+                               int S, long long n, const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out,
+                               int* count, double* energy /*or nullptr*/, double* scratch, hipStream_t s);
+
 // WPE dereverberation (wpe.hip).  mix / out complex64 [B][M][T][F], power float32 [B][T][F] or nullptr; the
 // workspace starts with fail int [B F] and G complex128 [B F][M taps][M], which launch_wpe_debug copies out.
 // 1 <= M <= 8, M taps <= 80, T >= 2.

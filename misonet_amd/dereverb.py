@@ -130,14 +130,22 @@ def dereverb(mix, power=None, *, taps=10, delay=3, iterations=3, diag_load=0.0, 
     return (out, dbg) if return_debug else out
 
 
-def dereverb_wav(wav, fs=16000, *, device=None, **opts):
+def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, **opts):
     """Recording-wise dereverberation: wav float32 [L, M] (ndarray or tensor) -> float32 [L, M] of the same kind.
 
     The recording is zero-padded to whole hops, transformed in one piece (``misonet_stft``), dereverberated
     (``misonet_wpe``: the filters are estimated over the whole recording), transformed back (``misonet_istft``, float32)
     and trimmed to L: all on the device.  ``fs`` is accepted for symmetry with the other recording calls; the frame
-    geometry is the networks' (256 / 64 samples).  ``opts``: the fields of :class:`Dereverb`."""
+    geometry is the networks' (256 / 64 samples).  ``opts``: the fields of :class:`Dereverb`.
+
+    ``srmr=True``: returns ``(wav, Srmr)``: the speech-to-reverberation modulation energy ratio (the figure
+    that needs no clean reference) of output channel ``ref_ch`` at rate ``fs`` (8000 or 16000), with input channel ``ref_ch``
+    as the mixture, so that ``srmr_i`` is what the dereverberation gained.  Both are read on the device, in place, as
+    time-major views; the waves are bit for bit those of ``srmr=False``."""
     from . import stft as S
+    if srmr:
+        from . import score as SC
+        SC.check_srmr_fs(fs)
     d = Dereverb(**opts)
     np_in = not isinstance(wav, torch.Tensor)
     w = torch.as_tensor(wav)
@@ -153,6 +161,13 @@ def dereverb_wav(wav, fs=16000, *, device=None, **opts):
     spec = S.stft_hip(padded)                                          # [1, M, Lp / 64 + 1, 129]
     out, _ = _wpe_device(spec, None, d.c_opts(), False)
     y = S._istft_hip(out, False)[0, :, :L].transpose(0, 1).contiguous()    # [L, M]
+    if srmr:
+        if not 0 <= int(ref_ch) < M:
+            raise ValueError(f"ref_ch must be in [0, {M}) (got {ref_ch})")
+        r = int(ref_ch)
+        block = SC.srmr_block(y[:, r:r + 1].transpose(0, 1)[None], padded[:, :L, r:r + 1].transpose(1, 2), None, fs)
+        sr = SC.srmr_unpack(block[0].cpu().numpy(), 1, int(fs), int(L))
+        return (y.cpu().numpy() if np_in else y), sr
     return y.cpu().numpy() if np_in else y
 
 

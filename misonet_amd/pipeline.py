@@ -757,7 +757,8 @@ class Enhancer:
 
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                           max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000, score: bool = False,
-                          bss: bool = False, bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False):
+                          bss: bool = False, bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False,
+                          srmr: bool = False):
         """Recording in -> enhanced int16 waves out: the reference's loader item AND its tester body as one device-side
         object (``AudioDataset_Test.__getitem__``, dataloader/data.py:524-597, + ``Tester_Enhance.inference``,
         tester.py:846-975), without host STFT dicts.
@@ -798,7 +799,20 @@ class Enhancer:
         cepstral distance, the log-likelihood ratio and the frequency-weighted segmental SNR, the figures
         dereverberation is judged by, of the stitched int16 result against the clean sources at ``ref_ch`` at rate ``fs``
         (8000 or 16000), the original observation at ``ref_ch`` as the mixture (also with ``dereverb=`` set): what
-        ``score.reverb_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns."""
+        ``score.reverb_waves(pcm, clean[:, :, ref_ch], mix, fs)`` returns.
+
+        ``srmr=True`` (needs neither ``score=True`` nor the clean sources): a :class:`score.Srmr` is appended as the last
+        element, ``(pcm, Srmr)`` on its own or after ``Reverb`` and the others; everything before it keeps its bits.  It
+        holds the speech-to-reverberation modulation energy ratio, the one figure that takes no clean
+        reference, of the stitched int16 result at rate ``fs`` (8000 or 16000), the original observation at ``ref_ch`` as the
+        mixture: what ``score.srmr_waves(pcm, mix, fs)`` returns.  A recording shorter than one 256 ms frame gives an
+        invalid ``Srmr``, not an error."""
+        if srmr:
+            from . import score as SC
+            SC.check_srmr_fs(fs)
+            res = self.enhance_recording(wav_observe, wav_clean, num_ch_utilize, chunk_size, max_batch, save_path, fs, score,
+                                         bss, bss_filt_len, stoi, reverb)
+            return (res if isinstance(res, tuple) else (res,)) + (self._srmr_of(res, wav_observe, num_ch_utilize, fs),)
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
         if stoi and not score:
@@ -851,6 +865,14 @@ class Enhancer:
 
         pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
         return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
+
+    def _srmr_of(self, res, wav_observe, num_ch_utilize, fs):
+        """the :class:`score.Srmr` of a recording's result (int16 [S, L], or a tuple that starts with it) with the original
+        observation at ref_ch of the sub-sampled array as the mixture"""
+        from . import score as SC
+        mics, obs = self._select_mics(wav_observe, num_ch_utilize)
+        pcm = res[0] if isinstance(res, tuple) else res
+        return SC.srmr_waves(pcm, np.ascontiguousarray(obs[:, mics[self.ref_ch]]), fs=fs, device=self.device)
 
     def _wave_refs(self, wav_observe, wav_clean, num_ch_utilize):
         """the references of BSS-eval, STOI and the reverb figures for one recording: (the clean sources at ref_ch of the sub-sampled array, float32
@@ -917,7 +939,7 @@ class Enhancer:
 
     def enhance_continuous(self, wav_observe, num_ch_utilize: Optional[int] = None, window: int = 64000,
                            hop: Optional[int] = None, max_batch: int = 16, save_path: Optional[str] = None,
-                           fs: int = 16000, return_perms: bool = False):
+                           fs: int = 16000, return_perms: bool = False, srmr: bool = False):
         """A long recording WITHOUT clean references -> one speaker per output from start to end (continuous separation).
 
         wav_observe float32 [L, M_all] (as :meth:`enhance_recording` takes it; same microphone sub-sampling).  The recording
@@ -933,9 +955,19 @@ class Enhancer:
 
         Returns int16 [S, L] (ndarray) and, with ``return_perms``, P int32 [K, S] (output speaker s of window k = MISO3
         output P[k, s] of that window).  ``save_path`` also writes ``<save_path>_{s}.wav`` as 24-bit PCM.  A NaN raises
-        FloatingPointError naming the first window that produced it."""
+        FloatingPointError naming the first window that produced it.
+
+        ``srmr=True``: a :class:`score.Srmr` is appended, ``(pcm, Srmr)`` or ``(pcm, P, Srmr)``: the speech-to-reverberation
+        modulation energy ratio of the stitched int16 result at rate ``fs`` (8000 or 16000), the original
+        observation at ``ref_ch`` as the mixture -- the figure to read when choosing ``taps``, ``delay`` or ``iterations``
+        on recordings that have no references.  It is measured on the device from the int16 pieces the pass leaves there;
+        the waves and P are bit for bit those of ``srmr=False``, and the figure is what
+        ``score.srmr_waves(pcm, observation[:, ref_ch], fs)`` returns."""
         import collections
         from . import css
+        if srmr:
+            from . import score as SC
+            SC.check_srmr_fs(fs)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -957,6 +989,7 @@ class Enhancer:
             perm = torch.empty((nb_max + 1, Sp), dtype=torch.int32, device=dev)
             dist = torch.empty(max(8, css.scratch_bytes(nb_max + 1, Sp, F)), dtype=torch.uint8, device=dev)
             perms = torch.empty((K, Sp), dtype=torch.int32, device=dev)
+            kept = torch.empty((1, Sp, L), dtype=torch.int16, device=dev) if srmr else None
 
             def compute_for(lo, hi):
                 def compute(wav):
@@ -971,6 +1004,8 @@ class Enhancer:
                     _lib.check(lib.misonet_istft(est[c].data_ptr(), nb * Sp, T, None, y[c].data_ptr(), st))
                     pcm = css.stitch(y[:n], perm[:n], H, c == 0, (L if hi == K else hi * H) - lo * H)
                     perms[lo:hi].copy_(perm[c:n])
+                    if kept is not None:
+                        kept[0, :, lo * H: lo * H + pcm.shape[1]].copy_(pcm)
                     if hi < K and n > 1:
                         est[0].copy_(est[n - 1])
                         y[0].copy_(y[n - 1])
@@ -996,9 +1031,17 @@ class Enhancer:
             while pending:
                 finish(*pending.popleft())
             P = perms.cpu().numpy() if return_perms else None
+            sr = None
+            if srmr:
+                torch.cuda.synchronize(dev)                   # the pieces were left by the streams of the batches
+                mixd = torch.from_numpy(np.ascontiguousarray(obs[:, mics[self.ref_ch]])).to(dev)[None, None]
+                sr = SC.srmr_unpack(SC.srmr_block(kept, mixd, None, fs)[0].cpu().numpy(), Sp, int(fs), L)
         if save_path is not None:
             self._write_speakers(out, save_path, fs)
-        return (out, P) if return_perms else out
+        res = (out, P) if return_perms else out
+        if srmr:
+            return (res if return_perms else (res,)) + (sr,)
+        return res
 
     def _nan_window(self, padded, lo, hi, W, H):
         """the message of a NaN in the batch of windows lo..hi-1: those windows again, one at a time, to name the first"""
@@ -1014,7 +1057,8 @@ class Enhancer:
     def enhance_recordings(self, recordings, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
                            depth: int = 2, score: bool = False, bss: bool = False,
-                           bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False) -> Dict[str, np.ndarray]:
+                           bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False,
+                           srmr: bool = False) -> Dict[str, np.ndarray]:
         """:meth:`enhance_recording` over many recordings, with every launch filled across them.
 
         ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
@@ -1033,9 +1077,31 @@ class Enhancer:
         (STOI and ESTOI at rate ``fs``, csrc/stoi.hip) is appended as the last element of every tuple, queued in the same
         groups on the same side stream; everything before it keeps its bits.  ``reverb=True`` (needs ``score=True``): a
         :class:`score.Reverb` (cepstral distance, LLR and fwSegSNR at rate ``fs``, csrc/reverb.hip) is appended after those,
-        from the same padded, pinned batch on the same side stream."""
+        from the same padded, pinned batch on the same side stream.  ``srmr=True`` (needs neither ``score=True`` nor clean
+        sources): a :class:`score.Srmr` (csrc/srmr.hip) is appended as the last element of every entry,
+        ``(pcm, Srmr)`` on its own; the stitched recordings go in padded batches of ``BSS_GROUP`` with their observation at
+        ``ref_ch`` as the mixture, and each figure is what :meth:`enhance_recording` gives for the recording alone."""
         import os
         from .coalesce import Item
+        if srmr:
+            from . import score as SC
+            SC.check_srmr_fs(fs)
+            recordings = list(recordings)
+            res = self.enhance_recordings(recordings, num_ch_utilize, chunk_size, max_batch, save_path, fs, depth, score, bss,
+                                          bss_filt_len, stoi, reverb)
+            names = list(res)
+            mixes = {}
+            for wav_observe, _, name in recordings:
+                mics, obs = self._select_mics(wav_observe, num_ch_utilize)
+                mixes[name] = np.ascontiguousarray(obs[:, mics[self.ref_ch]])
+            for lo in range(0, len(names), self.BSS_GROUP):
+                grp = names[lo:lo + self.BSS_GROUP]
+                pcms = [res[k][0] if isinstance(res[k], tuple) else res[k] for k in grp]
+                block = SC.srmr_queue([(p, mixes[k]) for p, k in zip(pcms, grp)], fs, self.device).cpu().numpy()
+                for k, p, row in zip(grp, pcms, block):
+                    res[k] = (res[k] if isinstance(res[k], tuple) else (res[k],)) + \
+                        (SC.srmr_unpack(row, self.num_spks, int(fs), p.shape[1]),)
+            return res
         if bss and not score:
             raise ValueError("bss=True needs score=True (and the clean sources)")
         if stoi and not score:

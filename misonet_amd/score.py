@@ -7,7 +7,9 @@ the figures SMS-WSJ tabulates) come from the energies of two projections (csrc/b
 figures, are computed whole on the device (csrc/stoi.hip, C ABI ``misonet_stoi_resample`` / ``misonet_stoi_measure``;
 :class:`Stoi`, INTEGRATION.md 4f, restated in tests/stoi_ref.py).  Cepstral distance, log-likelihood ratio and
 frequency-weighted segmental SNR, the figures dereverberation is judged by, likewise (csrc/reverb.hip, C ABI
-``misonet_reverb_measure``; :class:`Reverb`, INTEGRATION.md 4j, restated in tests/reverb_ref.py).
+``misonet_reverb_measure``; :class:`Reverb`, INTEGRATION.md 4j, restated in tests/reverb_ref.py).  SRMR, the one figure that
+takes no clean reference, is at the end (csrc/srmr.hip, ``misonet_srmr_measure``; :class:`Srmr`, INTEGRATION.md 4k,
+tests/srmr_ref.py).
 
 Definitions:
   * stats[i][j] = (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j) over the valid samples; additive over the chunks of a recording;
@@ -519,32 +521,42 @@ def _wave_batch(items, dev, pinned, limits):
         limits(S, r[0].shape[1])
     if any(r[0].dtype != recs[0][0].dtype for r in recs):
         raise ValueError("int16 and float32 estimates cannot share a batch")
-    with_mix = recs[0][2] is not None
+    cols, nv = _pad_batch([(e, c, m.reshape(1, -1) if m is not None else None) for e, c, m in recs], dev, pinned)
+    return cols[0], cols[1], cols[2], nv
+
+
+def _pad_batch(recs, dev, pinned):
+    """recs: per recording a tuple of 2-D tensors [rows_k, L] (or None, alike in every recording) -> (per entry the device
+    tensor [G, rows_k, n], zero-padded to the longest recording, or None; n_valid int32 [G], or None for a single recording,
+    which goes up as it is)"""
+    import torch
 
     def up(x):
         if x.device.type == "cpu" and pinned:
             return x.contiguous().pin_memory().to(dev, non_blocking=True)
         return x.to(dev).contiguous()
 
+    G = len(recs)
     if G == 1:
-        est, clean, mix = recs[0]
-        return up(est)[None], up(clean)[None], up(mix)[None, None] if with_mix else None, None
+        return [up(x)[None] if x is not None else None for x in recs[0]], None
     lens = [int(r[0].shape[1]) for r in recs]
     n = max(lens)
-
-    def padded(k, rows, dtype):
-        buf = torch.zeros((G, rows, n), dtype=dtype, pin_memory=pinned)
-        for g, r in enumerate(recs):
-            buf[g, :, :lens[g]].copy_(r[k].reshape(rows, -1))
-        return buf.to(dev, non_blocking=pinned)
-
     nv = torch.tensor(lens, dtype=torch.int32)
     nv = (nv.pin_memory() if pinned else nv).to(dev, non_blocking=pinned)
-    return (padded(0, S, recs[0][0].dtype), padded(1, S, torch.float32), padded(2, 1, torch.float32) if with_mix else None, nv)
+    cols = []
+    for k, first in enumerate(recs[0]):
+        if first is None:
+            cols.append(None)
+            continue
+        buf = torch.zeros((G, first.shape[0], n), dtype=first.dtype, pin_memory=pinned)
+        for g, r in enumerate(recs):
+            buf[g, :, :lens[g]].copy_(r[k])
+        cols.append(buf.to(dev, non_blocking=pinned))
+    return cols, nv
 
 
 def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = None, stoi_fs: Optional[int] = None,
-               reverb_fs: Optional[int] = None):
+               reverb_fs: Optional[int] = None, srmr_fs: Optional[int] = None):
     """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
     same S and all or none with a mixture; any lengths) -> (the device block [len(items), W] of :func:`bss_energies` for
     filters of ``bss_filt_len`` taps, that of :func:`stoi_block` at rate ``stoi_fs``), either None where its argument is
@@ -552,8 +564,11 @@ def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = N
     ``n_valid`` set, and the batch is built and copied once for both: a row is bit for bit what the recording gives
     alone.  ``pinned``: host inputs go through pinned memory and asynchronous copies, so that the caller is not held up.
     ``reverb_fs`` (not None): a third entry, the block of :func:`reverb_block` at that rate, from the same batch; without it
-    the pair is returned as it always was."""
+    the pair is returned as it always was.  ``srmr_fs`` (not None): four entries, (bss, stoi, reverb or None, the block of
+    :func:`srmr_block` of the estimates and the mixture at that rate), again from the same batch."""
     import torch
+    if srmr_fs is not None:
+        srmr_fs = check_srmr_fs(srmr_fs)
     if stoi_fs is not None:
         stoi_fs = check_stoi_fs(stoi_fs)
     if reverb_fs is not None:
@@ -566,11 +581,16 @@ def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = N
             _stoi_limits(S, L)
         if reverb_fs is not None:
             _reverb_limits(S, L)
+        if srmr_fs is not None:
+            _srmr_limits(S, L)
 
     with torch.cuda.device(dev):
         est, clean, mix, nv = _wave_batch(items, dev, pinned, limits)
         res = (bss_energies(est, clean, mix, nv, int(bss_filt_len)) if bss_filt_len is not None else None,
                stoi_block(est, clean, mix, nv, stoi_fs) if stoi_fs is not None else None)
+        if srmr_fs is not None:
+            return res + (reverb_block(est, clean, mix, nv, reverb_fs) if reverb_fs is not None else None,
+                          srmr_block(est, mix, nv, srmr_fs))
         return res if reverb_fs is None else res + (reverb_block(est, clean, mix, nv, reverb_fs),)
 
 
@@ -1067,3 +1087,219 @@ def reverb_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Reverb:
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     row = reverb_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
     return reverb_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))
+
+
+# ---- SRMR: the figure that needs no clean reference ------------------------------------------------------------------------------
+# Definition (restated in tests/srmr_ref.py): 23 gammatone channels (Slaney's ERB filters, 125 Hz .. fs / 2),
+# the magnitude of the analytic signal of every channel over the whole recording, eight second-order modulation filters (4 .. 128
+# Hz, Q = 2), the energy of every 256 ms frame (64 ms hop, Hamming) averaged over the frames; SRMR = the energy in the four
+# lowest modulation bands over that in bands 4 .. K* - 1, K* following the bandwidth of the channel that completes 90 % of the
+# energy from the top.  The figure has not been compared against the SRMRToolbox or srmrpy: neither was available.
+SRMR_RATES = (8000, 16000)
+SRMR_CHANNELS, SRMR_MODULATIONS = 23, 8
+
+
+@dataclasses.dataclass
+class Srmr:
+    """The speech-to-reverberation modulation energy ratio of the S signals of one recording; larger is better, and nothing is
+    paired with anything, so there is no permutation.  ``srmr_i = srmr - srmr_mix`` is an improvement when POSITIVE.
+    ``valid[j] = False``: signal j is shorter than one 256 ms frame or has no energy; its figures are NaN and ``k_star`` 0."""
+    srmr: np.ndarray                      # [S]
+    k_star: np.ndarray                    # [S] int: modulation bands 4 .. k_star - 1 form the denominator (5 .. 8)
+    bw90: np.ndarray                      # [S] Hz: ERB of the channel that completes 90 % of the energy from the top
+    frames: np.ndarray                    # [S] int
+    valid: np.ndarray                     # [S] bool
+    srmr_mix: Optional[float]             # the figure of the mixture, or None without one
+    srmr_i: Optional[np.ndarray]          # [S] srmr - srmr_mix (positive is better)
+    energy: Optional[np.ndarray]          # [S, 23, 8] the mean modulation energies, channels ascending, or None
+    fs: int
+    n_samples: int
+
+    def as_dict(self) -> dict:
+        def lst(x):
+            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
+        return dict(srmr=lst(self.srmr), k_star=[int(v) for v in self.k_star], bw90=lst(self.bw90),
+                    frames=[int(v) for v in self.frames], valid=[bool(v) for v in self.valid],
+                    srmr_mix=None if self.srmr_mix is None else float(self.srmr_mix), srmr_i=lst(self.srmr_i),
+                    fs=int(self.fs), n_samples=int(self.n_samples))
+
+
+def check_srmr_fs(fs):
+    if int(fs) != fs or int(fs) not in SRMR_RATES:
+        raise ValueError(f"SRMR is defined here for fs = 8000 or 16000 Hz (got {fs})")
+    return int(fs)
+
+
+def srmr_frames(n: int, fs: int) -> int:
+    """1 + (n - N_w) // H_w frames of N_w = ceil(0.256 fs) samples every H_w = ceil(0.064 fs), 0 for n < N_w; negative outside
+    the limits (0 <= n <= 2^24, the two rates)"""
+    return int(_lib.lib().misonet_srmr_frames(int(n), int(fs)))
+
+
+def srmr_chunk() -> int:
+    """the samples of a chunk of the scan that runs the recurrences in parallel along time"""
+    return int(_lib.lib().misonet_srmr_chunk())
+
+
+def srmr_scratch_bytes(B: int, NS: int, n: int, fs: int) -> int:
+    """bytes of scratch for :func:`srmr_measure` over NS signals per item of n samples: the 184 means of every signal and as many
+    slots of one (signal, channel) as fit 1 GiB, at least one -- bounded whatever B; negative outside the limits"""
+    return int(_lib.lib().misonet_srmr_scratch_bytes(int(B), int(NS), int(n), int(fs)))
+
+
+def _srmr_limits(S, L):
+    if not (1 <= S <= 4):
+        raise ValueError(f"1 <= S <= 4 signals (got {S})")
+    if not (1 <= L <= 1 << 24):
+        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
+
+
+def srmr_measure(sig, mix=None, n_valid=None, fs: int = 16000, energy: bool = False, scratch=None):
+    """sig int16 or float32 [B, S, n] (a device view as :func:`wave_stats` takes its estimates), mix float32 [B, 1, n] or None
+    (measured as one more signal, the last), n_valid int32 [B] (device) or None.  Returns (out float64 [B, S (+ 1), 3] = (SRMR,
+    K*, BW), count int32 [B, S (+ 1)] = the frames, energy float64 [B, S (+ 1), 23, 8] or None).  Asynchronous on the current
+    stream; an item's rows do not depend on the batch.  ``scratch``: a uint8 device tensor of at least
+    :func:`srmr_scratch_bytes` bytes to work in (its contents do not matter); by default one is allocated."""
+    import torch
+    fs = check_srmr_fs(fs)
+    sig = _wave_view(sig, "sig", (torch.int16, torch.float32))
+    B, S, n = sig.shape
+    _srmr_limits(S, n)
+    if B < 1 or B > 4096:
+        raise ValueError("1 <= B <= 4096 items")
+    dev = sig.device
+    if mix is not None:
+        mix = _wave_view(mix, "mix", (torch.float32,))
+        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
+            raise ValueError("mix must be [B, 1, n] on the device of sig")
+    if n_valid is not None:
+        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
+                or n_valid.numel() != B or not n_valid.is_contiguous():
+            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    L = _lib.lib()
+    NS = S + (1 if mix is not None else 0)
+    nb = int(L.misonet_srmr_scratch_bytes(B, NS, n, fs))
+    out = torch.empty((B, NS, 3), dtype=torch.float64, device=dev)
+    count = torch.empty((B, NS), dtype=torch.int32, device=dev)
+    en = torch.empty((B, NS, SRMR_CHANNELS, SRMR_MODULATIONS), dtype=torch.float64, device=dev) if energy else None
+    if scratch is None:
+        scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+    elif not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != dev \
+            or not scratch.is_contiguous() or scratch.numel() < nb or scratch.data_ptr() % 16:
+        raise ValueError(f"scratch must be a contiguous uint8 device tensor of at least {nb} bytes, 16-byte aligned")
+    with torch.cuda.device(dev):
+        _lib.check(L.misonet_srmr_measure(sig.data_ptr(), 1 if sig.dtype == torch.int16 else 0, sig.stride(0), sig.stride(1),
+                                          sig.stride(2), mix.data_ptr() if mix is not None else None,
+                                          mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
+                                          B, S, n, n_valid.data_ptr() if n_valid is not None else None, fs, out.data_ptr(),
+                                          count.data_ptr(), en.data_ptr() if en is not None else None, scratch.data_ptr(),
+                                          scratch.numel(), _lib.stream_ptr(dev)))
+    return out, count, en
+
+
+def srmr_block(sig, mix=None, n_valid=None, fs: int = 16000):
+    """sig int16 / float32 [B, S, n], mix float32 [B, 1, n] or None (device views), n_valid int32 [B] or None -> a device float64
+    block [B, W]: per item (SRMR, K*, BW) of every signal ([S (+ 1), 3], the mixture last) and the frames ([S (+ 1)]): what
+    :func:`srmr_unpack` reads.  Everything is queued on the current stream; nothing synchronises.  The scratch is bounded by the
+    library itself (the channels run in groups), so a batch is one call."""
+    import torch
+    out, count, _ = srmr_measure(sig, mix, n_valid, fs)
+    B = out.shape[0]
+    return torch.cat([out.reshape(B, -1), count.to(torch.float64).reshape(B, -1)], dim=1)
+
+
+def srmr_from_rows(figures, frames, fs: int = 16000, n_samples: int = 0, S: Optional[int] = None, energy=None) -> Srmr:
+    """figures float64 [S (+ 1), 3] = (SRMR, K*, BW) and frames int [S (+ 1)] as the device leaves them (the mixture last, where
+    there is one: S tells) -> :class:`Srmr`.  Host, no GPU."""
+    fig = np.array(figures, dtype=np.float64)
+    fr = np.asarray(frames, dtype=np.int64)
+    if fig.ndim != 2 or fig.shape[1] != 3 or fr.shape != fig.shape[:1]:
+        raise ValueError("figures must be [S (+ 1), 3] and frames [S (+ 1)]")
+    S = fig.shape[0] if S is None else int(S)
+    if fig.shape[0] not in (S, S + 1) or S < 1:
+        raise ValueError("figures must hold S signals, or S and the mixture")
+    with_mix = fig.shape[0] == S + 1
+    srmr = fig[:S, 0].copy()
+    mixv = float(fig[S, 0]) if with_mix else None
+    return Srmr(srmr=srmr, k_star=fig[:S, 1].astype(np.int64), bw90=fig[:S, 2].copy(), frames=fr[:S].copy(),
+                valid=np.isfinite(srmr) & (fr[:S] >= 1), srmr_mix=mixv, srmr_i=srmr - mixv if with_mix else None,
+                energy=None if energy is None else np.array(energy, dtype=np.float64)[:S], fs=int(fs), n_samples=int(n_samples))
+
+
+def srmr_unpack(row, S: int, fs: int, n_samples: int) -> Srmr:
+    """one host row of :func:`srmr_block` -> :class:`Srmr`"""
+    row = np.asarray(row, dtype=np.float64)
+    NS = row.shape[0] // 4
+    if NS not in (S, S + 1) or row.shape[0] != 4 * NS:
+        raise ValueError("not a row of srmr_block for this number of signals")
+    return srmr_from_rows(row[:3 * NS].reshape(NS, 3), row[3 * NS:], fs=fs, n_samples=n_samples, S=S)
+
+
+def srmr_mean_of(items: Sequence[Srmr]) -> dict:
+    """The ``"srmr"`` part of the ``"mean"`` entry of scores.json: the figures averaged over the valid signals"""
+    out = {}
+    for key in ("srmr", "srmr_i"):
+        vals = [float(getattr(e, key)[j]) for e in items if getattr(e, key) is not None
+                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
+        out[key] = float(np.mean(vals)) if vals else None
+    mixes = [float(e.srmr_mix) for e in items if e.srmr_mix is not None and np.isfinite(e.srmr_mix)]
+    out["srmr_mix"] = float(np.mean(mixes)) if mixes else None
+    out["n_recordings"] = len(items)
+    out["n_signals_valid"] = int(sum(int(np.sum(e.valid)) for e in items))
+    return out
+
+
+def srmr_queue(items, fs: int, dev, pinned: bool = False):
+    """items: a list of (signals int16 or float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the same S and all or
+    none with a mixture; any lengths) -> the device block [len(items), W] of :func:`srmr_block`, queued on the current stream
+    of ``dev``: one padded batch with ``n_valid`` set, a row bit for bit what the recording gives alone"""
+    import torch
+    fs = check_srmr_fs(fs)
+    with torch.cuda.device(dev):
+        recs = [(torch.as_tensor(sig), torch.as_tensor(mix) if mix is not None else None) for sig, mix in items]
+        for sig, _ in recs:
+            if sig.dim() != 2:
+                raise ValueError("signals must be [S, L]")
+        sig, mix, nv = _srmr_batch(recs, dev, pinned)
+        return srmr_block(sig, mix, nv, fs)
+
+
+def _srmr_batch(recs, dev, pinned):
+    """recs: (signals [S, L], mix [L] or None) tensors -> (sig [G, S, n], mix [G, 1, n] or None, n_valid int32 [G] or None),
+    zero-padded to the longest by :func:`_pad_batch`, as :func:`_wave_batch` forms its batch"""
+    import torch
+    out = []
+    for sig, mix in recs:
+        if sig.dtype != torch.int16:
+            sig = sig.to(torch.float32)
+        if mix is not None:
+            mix = mix.to(torch.float32).reshape(-1)
+            if mix.numel() != sig.shape[1]:
+                raise ValueError("mix must hold L samples")
+        out.append((sig, mix))
+    if not out:
+        raise ValueError("at least one recording")
+    S, G = out[0][0].shape[0], len(out)
+    if any(r[0].shape[0] != S for r in out) or any((r[1] is None) != (out[0][1] is None) for r in out):
+        raise ValueError("every recording must have the same number of signals, and all or none a mixture")
+    for r in out:
+        _srmr_limits(S, r[0].shape[1])
+    if any(r[0].dtype != out[0][0].dtype for r in out):
+        raise ValueError("int16 and float32 signals cannot share a batch")
+    cols, nv = _pad_batch([(x, m.reshape(1, -1) if m is not None else None) for x, m in out], dev, pinned)
+    return cols[0], cols[1], nv
+
+
+def srmr_waves(waves, mix=None, fs: int = 16000, device=None) -> Srmr:
+    """waves int16 or float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) -> :class:`Srmr`
+    (1 <= S <= 4, L <= 2^24, fs 8000 or 16000): the figure for the output of ``enhance_continuous``, ``dereverb_wav`` and for
+    files read back from disk, none of which has a clean reference."""
+    import torch
+    fs = check_srmr_fs(fs)
+    waves = torch.as_tensor(waves)
+    if waves.dim() != 2:
+        raise ValueError("waves must be [S, L]")
+    _srmr_limits(int(waves.shape[0]), int(waves.shape[1]))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    row = srmr_queue([(waves, mix)], fs, dev)[0].cpu().numpy()
+    return srmr_unpack(row, int(waves.shape[0]), fs, int(waves.shape[1]))

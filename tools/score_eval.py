@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Scores a directory of separated wav files against a directory of clean ones, on the device.
 
-    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]] [--stoi] [--reverb]
+    python tools/score_eval.py EST_DIR REF_DIR [--num-spks 2] [--ref-ch 0] [--mix-dir DIR] [--out scores.json] [--bss [--filt-len 512]] [--stoi] [--reverb] [--srmr]
 
 EST_DIR holds ``<name>_{s}.wav`` (what ``enhance_recording(save_path=...)`` / ``inference`` write: 24-bit or 16-bit PCM, mono);
 REF_DIR holds the clean sources under the same names (``<name>_{s}.wav``, any channel count: channel ``--ref-ch`` is used)
@@ -11,7 +11,10 @@ Prints (or writes) the JSON ``Enhancer.inference(..., score=True)`` writes: ``{n
 ``"bss"`` entry of every recording and of ``"mean"``; ``--stoi`` adds STOI and ESTOI (``Stoi.as_dict()``, INTEGRATION.md 4f, at
 the rate the files carry: 8, 10 or 16 kHz) as a ``"stoi"`` entry likewise; ``--reverb`` adds the cepstral distance, the
 log-likelihood ratio and the frequency-weighted segmental SNR (``Reverb.as_dict()``, INTEGRATION.md 4j, at the rate the files
-carry: 8 or 16 kHz) as a ``"reverb"`` entry; without the flags the output is what it always was.
+carry: 8 or 16 kHz) as a ``"reverb"`` entry; ``--srmr`` adds the speech-to-reverberation modulation energy ratio of the
+estimates and of the observation (``Srmr.as_dict()``, INTEGRATION.md 4k, the figure that uses no reference; 8 or 16 kHz) as a
+``"srmr"`` entry; without the flags the output is what it always was.  For a directory that has no references at all use
+tools/srmr_eval.py.
 Definitions: INTEGRATION.md 4d.  Lengths may differ by the padding of the last hop: the common length is scored.
 """
 import argparse
@@ -56,13 +59,14 @@ def main(argv=None):
     ap.add_argument("--filt-len", type=int, default=512, help="taps of the BSS-eval projection filters")
     ap.add_argument("--stoi", action="store_true", help="also STOI and ESTOI (the rate comes from the files)")
     ap.add_argument("--reverb", action="store_true", help="also cepstral distance, LLR and fwSegSNR (the rate comes from the files)")
+    ap.add_argument("--srmr", action="store_true", help="also SRMR of the estimates and the observation (the rate comes from the files)")
     a = ap.parse_args(argv)
     from misonet_amd import score
     pat = re.compile(r"^(.*)_0\.wav$")
     names = sorted(m.group(1) for m in map(pat.match, os.listdir(a.est_dir)) if m)
     if not names:
         raise SystemExit(f"no <name>_0.wav in {a.est_dir}")
-    scores, evals, stois, reverbs = {}, {}, {}, {}
+    scores, evals, stois, reverbs, srmrs = {}, {}, {}, {}, {}
     for name in names:
         est, ref, rates = [], [], set()
         for s in range(a.num_spks):
@@ -90,6 +94,10 @@ def main(argv=None):
                 raise SystemExit(f"{name}: the estimates disagree about the rate ({sorted(rates)})")
             reverbs[name] = score.reverb_waves(np.stack([x[:n] for x in est]), np.stack([x[:n] for x in ref]),
                                                mix[:n] if mix is not None else None, fs=min(rates))
+        if a.srmr:
+            if len(rates) != 1:
+                raise SystemExit(f"{name}: the estimates disagree about the rate ({sorted(rates)})")
+            srmrs[name] = score.srmr_waves(np.stack([x[:n] for x in est]), mix[:n] if mix is not None else None, fs=min(rates))
     doc = {name: sc.as_dict() for name, sc in scores.items()}
     doc["mean"] = score.mean_of(list(scores.values()))
     if a.bss:
@@ -104,6 +112,10 @@ def main(argv=None):
         for name, rv in reverbs.items():
             doc[name]["reverb"] = rv.as_dict()
         doc["mean"]["reverb"] = score.reverb_mean_of(list(reverbs.values()))
+    if a.srmr:
+        for name, sv in srmrs.items():
+            doc[name]["srmr"] = sv.as_dict()
+        doc["mean"]["srmr"] = score.srmr_mean_of(list(srmrs.values()))
     text = json.dumps(doc, indent=1)
     if a.out:
         with open(a.out, "w") as fh:
