@@ -247,6 +247,50 @@ int misonet_wpd(const void* src_dev, const void* mix_dev, int B, int F, int M, i
 int misonet_wpd_debug(const void* ws_dev, int B, int F, int M, const misonet_wpd_opts* opts, void* wbar_c128_dev, int* fail_dev,
                       misonet_stream stream);
 
+/* ---- guided spatial clustering: cACGMM (ABI 560) ------------------------------------------------------------------------
+ * The complex angular central Gaussian mixture model (Ito, Araki & Nakatani 2016) that mask-based front ends put between a
+ * network and a beamformer ("guided source separation"): the time-frequency masks are re-estimated from the observation itself,
+ * started from -- and, with prior 1, held to -- the masks the caller brings.  This is the project's own definition in that
+ * family (INTEGRATION.md 4l has it in full; tests/cacgmm_ref.py restates it); nothing here was compared against pb_bss.
+ * Per (item b, bin f), K = S + 1 classes (k < S: speaker k; S: noise), Y = mix[b, f] [M, T], everything after the loads float64:
+ *   z[t] = y[t] / |y[t]|; a frame with |y[t]|^2 == 0 is EMPTY: it enters no sum, its output mask is its initial mask
+ *   sweep 0 (M-step only, gamma = the initial masks, q = 1):
+ *     n_k = sum_t gamma[k, t],  B_k = M / n_k sum_t gamma[k, t] / q[k, t] z[t] z[t]^H,  B_k += diag_load tr(B_k) / M I,
+ *     B_k = L_k L_k^H (Cholesky), logdet_k = 2 sum_i log L_k[i, i]
+ *     prior 0 "bin": pi[k] = n_k / sum_k n_k;  prior 1 "guided": pi[k, t] = max(initial mask[k, t], prior_floor), fixed
+ *   iteration 1 .. iterations (E-step, then the M-step above; the last one the E-step only):
+ *     q[k, t] = |L_k^-1 z[t]|^2,  l[k, t] = log pi - logdet_k - M log q[k, t],  gamma[., t] = softmax_k l[., t]
+ *   log-likelihood = sum_t logsumexp_k l[k, t] of the last E-step; iterations == 0 returns the initial masks
+ * A bin is UNSOLVED when an n_k is not > 0 or not finite, a Cholesky pivot is not finite or not > 0, or the log-likelihood of an
+ * E-step is not finite: it keeps its initial masks (and their images), fail[b, f] = 1.  Nothing is clamped.  Every sum runs in
+ * a fixed order, without atomics: the bits of a bin depend neither on B nor on its position in the batch.
+ * mix_dev complex64 [B, F, M, T] (the layout of misonet_beamform); init_masks_dev, masks_out_dev float32 [B, K, F, T] (two
+ * different buffers); images_out_dev NULL or complex64 [B, S, F, M, T] = gamma_s Y rounded once, speaker s in the layout
+ * misonet_beamform and misonet_wpd take as src_dev.  2 <= M <= 8, 2 <= K <= 5 (1 <= S <= 4), T >= 1, 0 <= iterations <= 1000,
+ * diag_load and prior_floor finite and >= 0, prior_floor > 0 with prior 1: anything else is MISONET_EINVAL with a message (the size
+ * function: -1) before any launch and before any pointer is looked at; a short workspace is MISONET_ENOMEM.  The workspace does
+ * not grow with T.  The calls allocate nothing and do not synchronise. */
+typedef struct {
+  int iterations;
+  int prior;               /* 0 "bin", 1 "guided" */
+  double diag_load;
+  double prior_floor;
+} misonet_cacgmm_opts;
+int misonet_cacgmm_opts_default(misonet_cacgmm_opts* opts);    /* 10, 0, 1e-8, 1e-6 */
+long long misonet_cacgmm_workspace_bytes(int B, int K, int F, int M);
+int misonet_cacgmm(const void* mix_dev, const float* init_masks_dev, int B, int K, int F, int M, int T,
+                   const misonet_cacgmm_opts* opts, float* masks_out_dev, void* images_out_dev, void* ws_dev, long long ws_bytes,
+                   misonet_stream stream);
+/* diagnostic: after misonet_cacgmm, copy B_k of the last M-step (as it was factored) complex128 [B, F, K, M, M], the bin prior
+ * n_k / sum n_k of that M-step float64 [B, F, K] (computed for either prior), the log-likelihood float64 [B, F] and fail int32
+ * [B, F] to device buffers (any may be NULL).  An unsolved bin and iterations == 0 report zeros for the first three. */
+int misonet_cacgmm_debug(const void* ws_dev, int B, int K, int F, int M, void* bk_c128_dev, double* pi_dev, double* ll_dev,
+                         int* fail_dev, misonet_stream stream);
+/* initial masks from S source estimates est_dev complex64 [B, S, F, M, T] and mix_dev [B, F, M, T]: P_s = sum_m |est_s|^2,
+ * P_n = sum_m |y - sum_s est_s|^2 (float64), masks_out_dev float32 [B, S + 1, F, T] = P_k / sum_k P_k, 1 / (S + 1) where that sum is 0 */
+int misonet_masks_from_estimates(const void* est_dev, const void* mix_dev, int B, int S, int F, int M, int T,
+                                 float* masks_out_dev, misonet_stream stream);
+
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
  * dist_dev (required: it is the call's only scratch, so the call allocates nothing and stays asynchronous): float64,
@@ -473,6 +517,12 @@ int misonet_pipeline_set_beamformer(misonet_pipeline* p, const misonet_bf_opts* 
  * workspace size depends on it (ask misonet_pipeline_workspace_bytes again); a run with T <= delay + taps - 1 frames is refused
  * with MISONET_EINVAL.  MISONET_EINVAL for bad fields (as misonet_wpd).  With WPD not set every bit of every path is unchanged. */
 int misonet_pipeline_set_wpd(misonet_pipeline* p, const misonet_wpd_opts* opts);
+/* ABI 560: a step between the alignments and the beamformer: initial masks from the aligned MISO1 estimates and the mixture
+ * (misonet_masks_from_estimates), misonet_cacgmm with these options, and the refined images gamma_s Y as the source estimate of
+ * whichever beamformer is set.  MISO3's third input and miso1_dev stay the raw MISO1 estimate.  opts == NULL: off again.  Legal
+ * between runs; the workspace grows only while it is set (ask misonet_pipeline_workspace_bytes again).  MISONET_EINVAL for bad
+ * fields (as misonet_cacgmm).  With it not set every bit of every path and the workspace size are unchanged. */
+int misonet_pipeline_set_refine(misonet_pipeline* p, const misonet_cacgmm_opts* opts);
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T);
 /* mix_dev complex64 [B,M,T,F]; clean_dev complex64 [B,S,T,F] or NULL; out_dev complex64 [B,S,T,F] (MISO3);
  * optional outputs (may be NULL): bf_dev complex64 [B,S,T,F] (MVDR), miso1_dev complex64 [B,S,M,T,F] (aligned).

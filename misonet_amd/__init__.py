@@ -6,13 +6,14 @@ Host-side mirror of the reference call surface:
   Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN; and
                              of the WPD convolutional beamformer, kind "wpd")
   dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
+  cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
 library raises -- there is no CPU fallback.
 """
-__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Dereverb", "dereverb", "dereverb_wav", "Enhancer",
-           "weights"]
+__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
+           "masks_from_estimates", "Enhancer", "weights"]
 
 
 def __getattr__(name):
@@ -28,6 +29,9 @@ def __getattr__(name):
     if name in ("Dereverb", "dereverb", "dereverb_wav"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)
+    if name in ("Refine", "cacgmm", "masks_from_estimates"):
+        import importlib
+        return getattr(importlib.import_module(".refine", __name__), name)
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

@@ -44,6 +44,11 @@ class WpdOpts(C.Structure):
                 ("ref_ch", C.c_int)]
 
 
+class CacgmmOpts(C.Structure):
+    """misonet_cacgmm_opts (ABI 560): prior 0 bin / 1 guided"""
+    _fields_ = [("iterations", C.c_int), ("prior", C.c_int), ("diag_load", C.c_double), ("prior_floor", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -92,6 +97,15 @@ SIGNATURES = {
     "misonet_wpd_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts), C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "misonet_pipeline_set_wpd": (C.c_int, [C.c_void_p, C.POINTER(WpdOpts)]),
+    "misonet_cacgmm_opts_default": (C.c_int, [C.POINTER(CacgmmOpts)]),
+    "misonet_cacgmm_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "misonet_cacgmm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CacgmmOpts),
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_cacgmm_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "misonet_masks_from_estimates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p]),
+    "misonet_pipeline_set_refine": (C.c_int, [C.c_void_p, C.POINTER(CacgmmOpts)]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

@@ -1,5 +1,6 @@
 // C ABI of the array processing (include/misonet.h): the drop-in beamformers misonet_mvdr* / misonet_bf_* / misonet_beamform*
-// (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), the WPD beamformer misonet_wpd* (wpd.hip), guided spatial clustering
+// misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
@@ -62,6 +63,26 @@ int mn::wpd_ready() {
     HIPCHK(wpd_init());
     done[d].store(true, std::memory_order_release);
   }
+  return MISONET_OK;
+}
+
+// cACGMM: every field (the geometry is checked by the calls)
+int mn::cacgmm_opts_check(const misonet_cacgmm_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null clustering options");
+  if (o->iterations < 0 || o->iterations > 1000)
+    return fail(MISONET_EINVAL, "iterations must be in [0, 1000] (got %d)", o->iterations);
+  if (o->prior != 0 && o->prior != 1) return fail(MISONET_EINVAL, "prior %d: 0 bin, 1 guided", o->prior);
+  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
+    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!(o->prior_floor >= 0.0) || !std::isfinite(o->prior_floor) || (o->prior == 1 && !(o->prior_floor > 0.0)))
+    return fail(MISONET_EINVAL, "prior_floor must be finite and >= 0, and > 0 for the guided prior (got %g)", o->prior_floor);
+  return MISONET_OK;
+}
+
+static int cacgmm_geometry(int B, int K, int F, int M) {
+  if (B <= 0 || B > 65535 || F <= 0) return fail(MISONET_EINVAL, "B must be in [1, 65535] and F positive (got %d, %d)", B, F);
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (K < 2 || K > 5) return fail(MISONET_EINVAL, "K = speakers + 1 must be in [2, 5] (got %d)", K);
   return MISONET_OK;
 }
 
@@ -225,6 +246,66 @@ int misonet_wpd_debug(const void* ws, int B, int F, int M, const misonet_wpd_opt
   { int r = wpd_opts_check(opts, M, -1); if (r) return r; }
   if (!ws) return fail(MISONET_EINVAL, "null argument");
   HIPCHK(launch_wpd_debug(ws, B, 1, F, M, opts->taps, wbar, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- guided spatial clustering, cACGMM (ABI 560) -----------------------------------------------------------------------
+int misonet_cacgmm_opts_default(misonet_cacgmm_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->iterations = 10; o->prior = 0; o->diag_load = 1e-8; o->prior_floor = 1e-6;
+  return MISONET_OK;
+}
+
+long long misonet_cacgmm_workspace_bytes(int B, int K, int F, int M) {
+  if (cacgmm_geometry(B, K, F, M)) return -1;
+  return cacgmm_ws_bytes(B, K, F, M);
+}
+
+int misonet_cacgmm(const void* mix, const float* init_masks, int B, int K, int F, int M, int T, const misonet_cacgmm_opts* opts,
+                   float* masks_out, void* images_out, void* ws, long long ws_bytes, misonet_stream stream) {
+  { int r = cacgmm_geometry(B, K, F, M); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
+  { int r = cacgmm_opts_check(opts); if (r) return r; }
+  if (!mix || !init_masks || !masks_out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (masks_out == init_masks) return fail(MISONET_EINVAL, "masks_out must not be init_masks (the initial masks are read in every sweep)");
+  if (ws_bytes < cacgmm_ws_bytes(B, K, F, M)) return fail(MISONET_ENOMEM, "workspace too small");
+  CacgmmArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.init = init_masks; a.masks = masks_out;
+  float* o = reinterpret_cast<float*>(images_out);
+  const int S = K - 1;
+  a.img = {o, o ? o + 1 : nullptr, 2LL * S * F * M * T, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2, T};   // [B,S,F,M,T] complex64
+  a.B = B; a.K = K; a.F = F; a.M = M; a.T = T;
+  a.iters = opts->iterations; a.guided = opts->prior; a.diag_load = opts->diag_load; a.prior_floor = opts->prior_floor;
+  HIPCHK(launch_cacgmm(a, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_cacgmm_debug(const void* ws, int B, int K, int F, int M, void* bk, double* pi, double* ll, int* fail_dev,
+                         misonet_stream stream) {
+  { int r = cacgmm_geometry(B, K, F, M); if (r) return r; }
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_cacgmm_debug(ws, B, K, F, M, bk, pi, ll, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_masks_from_estimates(const void* est, const void* mix, int B, int S, int F, int M, int T, float* masks_out,
+                                 misonet_stream stream) {
+  { int r = cacgmm_geometry(B, S + 1, F, M); if (r) return r; }
+  if (F > 65535) return fail(MISONET_EINVAL, "F must be <= 65535 (got %d)", F);
+  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
+  if (!est || !mix || !masks_out) return fail(MISONET_EINVAL, "null argument");
+  MaskArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  const float* x = reinterpret_cast<const float*>(est);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.src = {x, x + 1, 2LL * S * F * M * T, 2LL * M * T, 2LL * T, 2};                  // [B,S,F,M,T] complex64
+  a.src_ss = 2LL * F * M * T;
+  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
+  a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
+  a.masks = masks_out;
+  HIPCHK(launch_masks_from_est(a, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

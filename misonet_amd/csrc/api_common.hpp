@@ -99,5 +99,7 @@ void bf_opts_apply(const misonet_bf_opts& o, MvdrArgs& a);
 int wpd_opts_check(const misonet_wpd_opts* o, int M, int T);
 void wpd_opts_apply(const misonet_wpd_opts& o, WpdArgs& a);
 int wpd_ready();
+// api_array.hip: host-side check of every cACGMM field
+int cacgmm_opts_check(const misonet_cacgmm_opts* o);
 
 }  // namespace mn

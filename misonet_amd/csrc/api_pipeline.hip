@@ -14,12 +14,17 @@ struct misonet_pipeline {
   misonet_bf_opts bf;      // the beamformer of step 5 (misonet_pipeline_set_beamformer); create: the defaults with epsi
   bool use_wpd;            // step 5 is WPD (misonet_pipeline_set_wpd) with the options below, bf is kept for the way back
   misonet_wpd_opts wpd;
+  bool use_refine;         // step 4b: guided spatial clustering between the alignments and step 5 (misonet_pipeline_set_refine)
+  misonet_cacgmm_opts refine;
 };
 
 struct PipeLayout {
   Layout L1, L3;
   long long off_ws1, off_ws3, off_clean, off_dist, off_sel, off_mvdr, total;
   long long clean_bstride;
+  // step 4b, only with refine set: the initial and the refined masks [B][S + 1][F][T], the refined images in the planar estimate
+  // layout [B M][2 S][F][Tp], the workspace of launch_cacgmm
+  long long off_rmask0, off_rmask, off_rimg, off_rws, rimg_bstride;
 };
 
 static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
@@ -45,6 +50,15 @@ static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
   P.off_ws3 = P.off_ws1;
   P.L3.in_ext_off = o - P.off_ws3;                     // relative to the (shared) workspace base
   o += in3_bytes;
+  P.off_rmask0 = P.off_rmask = P.off_rimg = P.off_rws = 0;
+  P.rimg_bstride = (long long)2 * p->S * F * Tp;
+  if (p->use_refine) {                                 // behind everything else: nothing before it moves
+    const long long mask_bytes = align_up((long long)B * (p->S + 1) * F * T * 4, 256);
+    P.off_rmask0 = o; o += mask_bytes;
+    P.off_rmask = o;  o += mask_bytes;
+    P.off_rimg = o;   o += align_up(P.rimg_bstride * B * p->M * 4, 256);
+    P.off_rws = o;    o += align_up(cacgmm_ws_bytes(B, p->S + 1, F, p->M), 256);
+  }
   P.total = o;
   return P;
 }
@@ -83,6 +97,14 @@ int misonet_pipeline_set_wpd(misonet_pipeline* p, const misonet_wpd_opts* opts) 
   { int r = wpd_opts_check(opts, p->M, -1); if (r) return r; }
   p->wpd = *opts;
   p->use_wpd = true;
+  return MISONET_OK;
+}
+int misonet_pipeline_set_refine(misonet_pipeline* p, const misonet_cacgmm_opts* opts) {
+  if (!p) return fail(MISONET_EINVAL, "null argument");
+  if (!opts) { p->use_refine = false; return MISONET_OK; }
+  { int r = cacgmm_opts_check(opts); if (r) return r; }
+  p->refine = *opts;
+  p->use_refine = true;
   return MISONET_OK;
 }
 int misonet_pipeline_destroy(misonet_pipeline* p) { delete p; return MISONET_OK; }
@@ -168,11 +190,37 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
     const long long in3_bs = bstride(n3, P.L3, B_IN);
     HIPCHK(launch_assemble3(in1, in1_bs, out1, out1_bs, sel_final, B, M, S, p->ref_ch, F, Tp, in3, in3_bs, s));
 
+    // 4b. guided spatial clustering (optional): initial masks from the aligned MISO1 planes and the shift-0 mixture, the cACGMM,
+    // and its images gamma_s Y as the source estimate of step 5.  MISO3's third input (above) and miso1_out stay the raw estimate
+    const float* est5 = out1;
+    long long est5_bs = out1_bs;
+    const int* sel5 = sel_final;
+    if (p->use_refine) {
+      float* m0 = reinterpret_cast<float*>(base + P.off_rmask0);
+      float* rimg = reinterpret_cast<float*>(base + P.off_rimg);
+      MaskArgs ma;
+      ma.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};
+      ma.est = out1; ma.est_bstride = out1_bs; ma.sel = sel_final;
+      ma.src = {nullptr, nullptr, 0, 0, 0, 1}; ma.src_ss = 0;
+      ma.S = S; ma.B = B; ma.F = F; ma.M = M; ma.T = T; ma.Tp = Tp;
+      ma.masks = m0;
+      HIPCHK(launch_masks_from_est(ma, s));
+      CacgmmArgs ca;
+      ca.mix = ma.mix;
+      ca.init = m0; ca.masks = reinterpret_cast<float*>(base + P.off_rmask);
+      ca.img = {rimg, rimg + (long long)S * plane, (long long)M * P.rimg_bstride, plane, Tp, P.rimg_bstride, 1, Tp};
+      ca.B = B; ca.K = S + 1; ca.F = F; ca.M = M; ca.T = T;
+      ca.iters = p->refine.iterations; ca.guided = p->refine.prior; ca.diag_load = p->refine.diag_load;
+      ca.prior_floor = p->refine.prior_floor;
+      HIPCHK(launch_cacgmm(ca, base + P.off_rws, s));
+      est5 = rimg; est5_bs = P.rimg_bstride; sel5 = nullptr;
+    }
+
     // 5. MVDR per aligned speaker (tester.py:917-924, 1071-1136); writes the beamformer planes of the MISO3 input
     if (p->use_wpd) {   // ... or WPD on the same views and the same planes
       WpdArgs a;
       a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};
-      a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;
+      a.est = est5; a.est_bstride = est5_bs; a.sel = sel5;
       a.src = {nullptr, nullptr, 0, 0, 0, 1};
       a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
       wpd_opts_apply(p->wpd, a);
@@ -182,7 +230,7 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
     } else {
       MvdrArgs a;
       a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};   // shift-0 sample = un-rolled mixture
-      a.est = out1; a.est_bstride = out1_bs; a.sel = sel_final;
+      a.est = est5; a.est_bstride = est5_bs; a.sel = sel5;
       a.src = {nullptr, nullptr, 0, 0, 0, 1};
       a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
       bf_opts_apply(p->bf, a);

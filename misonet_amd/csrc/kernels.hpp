@@ -357,8 +357,43 @@ hipError_t wpd_init();
 hipError_t launch_wpd(const WpdArgs& a, const COut& out, void* ws, hipStream_t s);
 hipError_t launch_wpd_debug(const void* ws, int B, int S, int F, int M, int taps, void* wbar, int* fail, hipStream_t s);
 
-// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs or WpdArgs
-// (est / est_bstride / sel in pipeline mode, src when est == nullptr)
+// Guided spatial clustering (cacgmm.hip): the cACGMM of K = S + 1 classes per (b, bin), started from and
+// (prior "guided") held to the initial masks.  mix through a CView; init / masks float32 [B][K][F][T]; the refined source images
+// gamma_s Y of the S speaker classes through a CImg (re == nullptr: not wanted), frames [T, Tp) written as zeros.  The
+// workspace holds fail int [B F], the log-likelihood double [B F], pi double [B F][K] and B_k complex128 [B F][K][M][M], which
+// launch_cacgmm_debug copies out.  2 <= M <= 8, 2 <= K <= 5, iters >= 0: the caller checks them.
+// element (b, s, f, m, t) of the images at re[b*sb + s*ss + f*sf + m*sm + t*st], im likewise
+struct CImg { float* re; float* im; long long sb, ss, sf, sm; int st, Tp; };
+struct CacgmmArgs {
+  CView mix;
+  const float* init;
+  float* masks;
+  CImg img;
+  int B, K, F, M, T;
+  int iters, guided;
+  double diag_load, prior_floor;
+};
+long long cacgmm_ws_bytes(int B, int K, int F, int M);
+hipError_t launch_cacgmm(const CacgmmArgs& a, void* ws, hipStream_t s);
+hipError_t launch_cacgmm_debug(const void* ws, int B, int K, int F, int M, void* bk, double* pi, double* ll, int* fail,
+                               hipStream_t s);
+// the initial masks of launch_cacgmm from S source estimates and the mixture: P_s = sum_m |est_s|^2, P_n = sum_m |y - sum_s est_s|^2,
+// masks [B][S + 1][F][T] = P_k / sum_k P_k (1 / (S + 1) where that sum is 0).  The estimates as launch_mvdr reads them (est /
+// est_bstride / sel in pipeline mode; src with the speaker stride src_ss when est == nullptr)
+struct MaskArgs {
+  CView mix;
+  const float* est;
+  long long est_bstride;
+  const int* sel;
+  CView src;
+  long long src_ss;
+  int S, B, F, M, T, Tp;
+  float* masks;
+};
+hipError_t launch_masks_from_est(const MaskArgs& a, hipStream_t s);
+
+// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs or
+// MaskArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
 template <typename Args>
 __device__ __forceinline__ void src_row(const Args& a, int b, int f, int m, int spk, const float*& re, const float*& im,
                                         int& st) {

@@ -9,6 +9,8 @@
 //   sg_gram_tile    the real Gram matrix of [Re s; Im s] (2 K rows, 16 x 16 tiles, lower half) on v_mfma_f64_16x16x4_f64 with
 //                   the weight w[t] folded into the B operand; the tiles are dealt round-robin to the waves (SgTiles), up to
 //                   SG_SLOTS accumulators each, which reaches 2 K = 176
+//   sg_gram_tile1   the one-tile case (2 n <= 16 float64 rows staged frame-major, one wave; cacgmm_bin_k of cacgmm.hip, which also
+//                   uses sg_stage_rows, sg_diag_load and sg_cholesky) and sg_tile1_entry, the complex entry from such a tile
 //   sg_panel        its blocks give the complex panel sum_t w s s^H, lower triangle, the first `ncols` columns, in four
 //                   phases in which every component is written by one lane
 //   sg_diag_load    + diag_load tr / n on the leading n x n block
@@ -148,6 +150,25 @@ __device__ __forceinline__ void sg_gram_tile(SgTiles& g, const float* zwin, cons
       if (s < g.nslots)
         g.acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[s], (double)bv[s] * wv, g.acc[s], 0, 0, 0);
   }
+}
+
+// The one-tile case (2 n <= 16 rows, cacgmm_bin_k): rows = [Re v; Im v] as float64, staged frame-major, double [SG_TT][pitch]
+// with the rows past 2 n zero.  acc += sum_t w[t] r[t] r[t]^T over the SG_TT frames of the tile, in ascending t; called by one
+// whole wave
+__device__ __forceinline__ void sg_gram_tile1(d4& acc, const double* rows, int pitch, const double* wt) {
+  const int lane = threadIdx.x & 63, lr = lane & 15, lg = lane >> 4;
+#pragma unroll 4
+  for (int k4 = 0; k4 < SG_TT; k4 += 4) {
+    const double v = rows[(k4 + lg) * pitch + lr];                     // A[i = lr][k = lg], B[k = lg][j = lr]
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v * wt[k4 + lg], acc, 0, 0, 0);
+  }
+}
+
+// element (i, j), i >= j, of the complex n x n matrix sum w v v^H from that tile, g: double [16][16] as the accumulator left it
+// (row = (lane >> 4) + 4 reg, column = lane & 15): Re = G[i][j] + G[n + i][n + j], Im = G[n + i][j] - G[n + j][i], a real
+// diagonal
+__device__ __forceinline__ double2 sg_tile1_entry(const double* g, int n, int i, int j) {
+  return make_double2(g[i * 16 + j] + g[(n + i) * 16 + n + j], i == j ? 0.0 : g[(n + i) * 16 + j] - g[(n + j) * 16 + i]);
 }
 
 // the complex panel P [K][ncols] (lower triangle of its square block; ncols < K: the rows below it too) from the blocks of

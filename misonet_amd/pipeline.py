@@ -26,6 +26,7 @@ from . import stft as S
 from .beamform import Beamformer
 from .dereverb import Dereverb, dereverb_wav
 from .model import MISO_1, MISO_3
+from .refine import Refine, refined_images
 from .weights import N_FREQ
 
 
@@ -210,13 +211,15 @@ class Enhancer:
     """Fused on-device MISO1 -> (alignment) -> beamformer (MVDR unless another is set) -> MISO3 for batches of 4 s chunks."""
 
     def __init__(self, model_sep: MISO_1, model: Optional[MISO_3], num_spks: int = 2, ref_ch: int = 0, epsi: float = 1e-6,
-                 beamformer=None, dereverb=None):
+                 beamformer=None, dereverb=None, refine=None):
         """``model = None``: a separation-only Enhancer (:meth:`separate`, :meth:`beamform_utterance`,
         :meth:`beamform_chunks` -- what the reference's ``Tester_Beamforming`` needs: it has no MISO_3, tester.py:259-262).
         ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields; it
         reaches the fused pass and every ``beamform_*`` method (:meth:`set_beamformer`).
         ``dereverb``: None (no dereverberation), True, a :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields:
-        the recording paths dereverberate the observation first (:meth:`set_dereverb`)."""
+        the recording paths dereverberate the observation first (:meth:`set_dereverb`).
+        ``refine``: None (off), True, a :class:`misonet_amd.refine.Refine` or a dict of its fields: guided spatial clustering
+        between the separation and the beamformer (:meth:`set_refine`)."""
         if not isinstance(model_sep, MISO_1) or not (model is None or isinstance(model, MISO_3)):
             raise TypeError("Enhancer needs misonet_amd.MISO_1 and misonet_amd.MISO_3 (or None) instances")
         self.model_sep, self.model = model_sep, model
@@ -243,6 +246,9 @@ class Enhancer:
         self.dereverb = None
         if dereverb is not None:
             self.set_dereverb(dereverb)
+        self.refine = None
+        if refine is not None:
+            self.set_refine(refine)
 
     def set_dereverb(self, dereverb=None):
         """WPE dereverberation in front of the recording paths (:meth:`enhance_recording`, :meth:`enhance_recordings`,
@@ -283,6 +289,26 @@ class Enhancer:
             _lib.check(L.misonet_pipeline_set_wpd(self._pipe, None))
         self.beamformer = bf
         self._ws.clear()                       # the workspace size depends on the kind
+
+    def set_refine(self, refine=None):
+        """Guided spatial clustering (cACGMM, :mod:`misonet_amd.refine`) between the separation and the beamformer: None or
+        False (off, the default: every path and the workspace as without it), True (the defaults), a Refine or a dict of its
+        fields.  When set, the initial masks come from the aligned MISO1 estimates and the mixture, and the refined source
+        images ``gamma_s * Y`` are the source estimate of whichever beamformer is set -- in the fused pass (:meth:`enhance`
+        and everything built on it: the recording and continuous paths, captured graphs) and in :meth:`beamform_chunks` /
+        :meth:`beamform_utterance` (there one clustering over the whole recording's frames).  MISO3's third input and the
+        ``miso1`` output stay the raw MISO1 estimate.  Legal between passes; ValueError for a bad field; refused while a
+        captured pass is alive, as :meth:`set_beamformer`."""
+        rf = None if refine is None or refine is False else Refine.of(refine).validate(self.num_ch, self.num_spks)
+        if rf == self.refine:
+            return
+        if len(self._captured):
+            raise RuntimeError("set_refine: a captured pass of this Enhancer is alive and would go on replaying the old "
+                               "options; drop it and capture again after the change")
+        opts = rf.c_opts() if rf is not None else None
+        _lib.check(_lib.lib().misonet_pipeline_set_refine(self._pipe, C.byref(opts) if opts is not None else None))
+        self.refine = rf
+        self._ws.clear()                       # the workspace grows while it is set
 
     def _bf(self, beamformer, epsi):
         """the options of one beamform_* call: its own ``beamformer`` (None: the Enhancer's) and ``epsi`` (None: the
@@ -325,7 +351,7 @@ class Enhancer:
         # the layout depends on the arithmetic modes and on whether buffers may share memory
         m3 = self.model
         return (B, T, self.model_sep.precision, m3.precision if m3 is not None else None, self.model_sep._keep,
-                m3._keep if m3 is not None else None, self.beamformer.kind)
+                m3._keep if m3 is not None else None, self.beamformer.kind, self.refine is not None)
 
     def workspace(self, B, T):
         key = self._ws_key(B, T)
@@ -738,7 +764,10 @@ class Enhancer:
         sig = torch.nn.functional.pad(sig, (0, pad)).permute(0, 2, 1).contiguous()      # [1+S, Lp, M]
         spec = S.stft_hip(sig)                                                # [1+S, M, Tt, F]
         mix_bf = spec[0].permute(2, 0, 1)[None]                               # [1,F,M,Tt]
-        bf = torch.stack([Apply_Beamforming(spec[1 + s].permute(2, 0, 1)[None], mix_bf, beamformer=bf_opts)[0]
+        src = spec[1:].permute(0, 3, 1, 2)[None]                              # [1,S,F,M,Tt]
+        if self.refine is not None:                                           # one clustering over the recording's frames
+            src = refined_images(src, mix_bf, self.refine)
+        bf = torch.stack([Apply_Beamforming(src[:, s], mix_bf, beamformer=bf_opts)[0]
                           for s in range(self.num_spks)])                     # [S,Tt,F]
         return S.istft_int16(bf)
 
@@ -752,6 +781,8 @@ class Enhancer:
         bf_opts = self._bf(beamformer, epsi)
         est = self.separate(mix, clean, check_nan=check_nan)                                  # [B,S,M,T,F]
         mix_bf = self._check_c64(mix, "mix").permute(0, 3, 1, 2)                              # [B,F,M,T]
+        if self.refine is not None:
+            est = refined_images(est.permute(0, 1, 4, 2, 3), mix_bf, self.refine).permute(0, 1, 3, 4, 2)
         return torch.stack([Apply_Beamforming(est[:, s].permute(0, 3, 1, 2), mix_bf, beamformer=bf_opts)
                             for s in range(self.num_spks)], dim=1)                            # [B,S,T,F]
 

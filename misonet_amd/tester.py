@@ -52,6 +52,8 @@ class Tester_Enhance(object):
         self.dereverb = None         # None / True / a Dereverb / dict of its fields (Enhancer.set_dereverb), read when inference()
         #                              starts: it reaches the Enhancer's RECORDING paths (self._enh.enhance_recording(s) /
         #                              enhance_continuous); the loader's ready STFT chunks are not dereverberated
+        self.refine = None           # None / True / a Refine / dict of its fields (Enhancer.set_refine), read when inference()
+        #                              starts: guided spatial clustering between MISO1 and the beamformer
 
     def test(self):
         """tester.py:827-844: development set into ``cv_dev93``, test set into ``test_eval92``."""
@@ -66,6 +68,7 @@ class Tester_Enhance(object):
         """tester.py:846-975; returns {wav_name: int16 [num_spks, n_samples]} besides writing the files."""
         self._enh.set_beamformer(self.beamformer)
         self._enh.set_dereverb(self.dereverb)
+        self._enh.set_refine(self.refine)
         return self._enh.inference(data_loader, saveDir, fs=self.fs, score=bool(self.score))
 
 
@@ -109,6 +112,7 @@ class Tester_Beamforming(object):
         self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts:
         #                              the beamformed wav is this class's product, so this is its product setting
         self.dereverb = None         # as Tester_Enhance.dereverb: reaches the Enhancer (set_dereverb), whose recording paths use it
+        self.refine = None           # as Tester_Enhance.refine: reaches the Enhancer (set_refine) and its beamform_* methods
 
     def test(self):
         """tester.py:289-325: the training set into ``train_si284`` when ``tr_inference_flag``, else the development set into
@@ -139,6 +143,7 @@ class Tester_Beamforming(object):
         beamformer has none)."""
         self._enh.set_beamformer(self.beamformer)
         self._enh.set_dereverb(self.dereverb)
+        self._enh.set_refine(self.refine)
         if self.score:
             from . import score as SC
             refs, scores = {}, {}
