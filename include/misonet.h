@@ -291,6 +291,56 @@ int misonet_cacgmm_debug(const void* ws_dev, int B, int K, int F, int M, void* b
 int misonet_masks_from_estimates(const void* est_dev, const void* mix_dev, int B, int S, int F, int M, int T,
                                  float* masks_out_dev, misonet_stream stream);
 
+/* ---- joint multi-speaker beamformers: LCMV, SDW-MWF, rank-1 MWF (ABI 570) ----------------------------------------------------
+ * The beamformers above see one source estimate and the mixture; these own a whole bin, all S speakers at once: "lcmv" (unit
+ * gain on the target, a null on every other speaker), "mwf" / "sdw_mwf" and "r1mwf" of the mask-based family, with an explicit
+ * interference model.  This is the project's own definition in the ESPnet / pb_bss family (INTEGRATION.md 4m has it in full;
+ * tests/jbf_ref.py restates it in NumPy float64); nothing here was compared against those packages and no quality figure on real
+ * speech was measured.
+ * Per (item b, bin f): Y = mix[b, f] [M, T], X_s = src[b, s, f] [M, T], complex64 as loaded, float64 after the loads:
+ *   V = Y - sum_s X_s,  Phi_s = X_s X_s^H / T,  Phi_v = V V^H / T  (noise 1 "mix", lcmv only: Y Y^H / T, power minimisation, "LCMP")
+ *   (the lower triangle computed and mirrored, a real diagonal),  R = Phi_v + diag_load tr(Phi_v) / M I,  N_s = sum_{j != s} Phi_j + R
+ *   kind 0 "lcmv":  R = L L^H (Cholesky), once per bin;
+ *                   rtf 0 "cw" (covariance whitening): C_s = L^-1 Phi_s L^-H, q_s = its principal eigenvector (cyclic complex
+ *                   Jacobi), a_s = L q_s;  rtf 1 "eig": a_s = the principal eigenvector of Phi_s;
+ *                   d_s = a_s / a_s[ref_ch],  D = [d_0 .. d_{S-1}],  Z = L^-1 D,  G = Z^H Z = K K^H (Cholesky),
+ *                   W = L^-H Z G^-1,  w_s = column s of W, so that w_s^H d_j = delta_sj.  With S = 1 this is the MVDR
+ *                   w = R^-1 d / (d^H R^-1 d).  mu is ignored.
+ *   kind 1 "mwf":   w_s = (Phi_s + mu N_s)^-1 Phi_s e_ref  (Cholesky; mu > 0; mu = 1: the multichannel Wiener filter)
+ *   kind 2 "r1mwf": A_s = N_s^-1 Phi_s (Cholesky of N_s),  w_s = A_s e_ref / (mu + tr A_s)  (mu >= 0; the complex trace, as
+ *                   "souden").  mu = 0: the Souden MVDR on the sum-of-sources model; with S = 1 that is "souden" with noise
+ *                   "residual", condition = diag_load, epsi = 0.  For S > 1 it differs from "souden" by the cross terms X_j V^H
+ *                   that the residual (Y - X_s)(Y - X_s)^H carries and the sum-of-sources model leaves out.
+ *   out_s[t] = w_s^H y[t], rounded to complex64 once, on the store.
+ * Nothing is clamped.  "lcmv" FAILS as a whole bin -- a pivot of R or of G not finite or not > 0, a tr Phi_s that is 0 or not
+ * finite (an exactly-zero estimate has no direction), an a_s[ref_ch] that is 0 or not finite: w_s = 0, out_s = 0 and
+ * fail[b, s, f] = 1 for every s.  "mwf" / "r1mwf" fail per (b, s, f) -- a pivot, for "r1mwf" also mu + tr A_s 0 or not finite --
+ * and only that speaker is zeroed and flagged; a zero Phi_s under "mwf" is no failure (w_s = 0, fail = 0, as "souden").  Equal
+ * leading eigenvalues make d_s arbitrary: that case is NOT detected.  Every sum runs in a fixed order, without atomics: the bits
+ * of a bin depend neither on B nor on its position in the batch (on S they depend by definition).
+ * src_dev complex64 [B, S, F, M, T] (speaker s in the layout misonet_beamform takes), mix_dev complex64 [B, F, M, T], out_dev
+ * complex64 [B, S, T, F].  2 <= M <= 8, 1 <= S <= 4, S <= M, T >= 1, 0 <= ref_ch < M, diag_load finite and >= 0, mu finite and
+ * > 0 for "mwf", >= 0 for "r1mwf"; noise 1 and rtf 1 belong to "lcmv" and must be 0 elsewhere: anything else is MISONET_EINVAL
+ * with a message (the size function: -1) before any launch and before any pointer is looked at; a short workspace is
+ * MISONET_ENOMEM.  The workspace does not grow with T.  The calls allocate nothing and do not synchronise. */
+typedef struct {
+  int kind;                /* 0 "lcmv", 1 "mwf", 2 "r1mwf" */
+  int noise;               /* 0 "residual", 1 "mix" (lcmv only) */
+  int rtf;                 /* 0 "cw", 1 "eig" (lcmv only) */
+  double mu;
+  double diag_load;
+  int ref_ch;
+} misonet_jbf_opts;
+int misonet_jbf_opts_default(misonet_jbf_opts* opts);    /* 0, 0, 0, 1.0, 0.0, 0 */
+long long misonet_beamform_joint_workspace_bytes(int B, int S, int F, int M, const misonet_jbf_opts* opts);
+int misonet_beamform_joint(const void* src_dev, const void* mix_dev, int B, int S, int F, int M, int T,
+                           const misonet_jbf_opts* opts, void* out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_beamform_joint, copy the weights complex128 [B, S, F, M], the relative transfer functions d_s
+ * complex128 [B, S, F, M] ("lcmv" only: MISONET_EINVAL for another kind) and fail int32 [B, S, F] to device buffers (any may be
+ * NULL).  A failed speaker reports zeros for the first two. */
+int misonet_beamform_joint_debug(const void* ws_dev, int B, int S, int F, int M, const misonet_jbf_opts* opts, void* w_c128_dev,
+                                 void* rtf_c128_dev, int* fail_dev, misonet_stream stream);
+
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
  * dist_dev (required: it is the call's only scratch, so the call allocates nothing and stays asynchronous): float64,
@@ -523,6 +573,13 @@ int misonet_pipeline_set_wpd(misonet_pipeline* p, const misonet_wpd_opts* opts);
  * between runs; the workspace grows only while it is set (ask misonet_pipeline_workspace_bytes again).  MISONET_EINVAL for bad
  * fields (as misonet_cacgmm).  With it not set every bit of every path and the workspace size are unchanged. */
 int misonet_pipeline_set_refine(misonet_pipeline* p, const misonet_cacgmm_opts* opts);
+/* ABI 570: a joint beamformer (misonet_beamform_joint) as step 5: one launch for all num_spk aligned speakers, on the same views
+ * and into the same beamformer planes; with refine set it reads the refined images, so that V = Y - sum_s gamma_s Y is the noise
+ * class's image.  opts == NULL: back to the per-speaker step that is set (misonet_bf_opts or WPD).  Legal between runs; the
+ * workspace size depends on it (ask misonet_pipeline_workspace_bytes again).  MISONET_EINVAL for bad fields (as
+ * misonet_beamform_joint, M = num_mic, S = num_spk).  With it not set every bit of every path, every workspace offset and the
+ * workspace size are unchanged. */
+int misonet_pipeline_set_joint(misonet_pipeline* p, const misonet_jbf_opts* opts);
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T);
 /* mix_dev complex64 [B,M,T,F]; clean_dev complex64 [B,S,T,F] or NULL; out_dev complex64 [B,S,T,F] (MISO3);
  * optional outputs (may be NULL): bf_dev complex64 [B,S,T,F] (MVDR), miso1_dev complex64 [B,S,M,T,F] (aligned).

@@ -5,6 +5,7 @@ Host-side mirror of the reference call surface:
   Apply_Beamforming         (reference tester.py:1071-1136)
   Beamformer                (the options of the selectable beamformers: mvdr / souden / gev, MPDR, conditioning, BAN; and
                              of the WPD convolutional beamformer, kind "wpd")
+  Apply_Beamforming_Joint   (the joint multi-speaker beamformers: LCMV, SDW-MWF, rank-1 MWF; JointBeamformer: their options)
   dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
@@ -12,7 +13,7 @@ Host-side mirror of the reference call surface:
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
 library raises -- there is no CPU fallback.
 """
-__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
+__all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "masks_from_estimates", "Enhancer", "weights"]
 
 
@@ -26,6 +27,9 @@ def __getattr__(name):
     if name == "Beamformer":
         from .beamform import Beamformer
         return Beamformer
+    if name in ("Apply_Beamforming_Joint", "JointBeamformer"):
+        from . import beamform
+        return getattr(beamform, name)
     if name in ("Dereverb", "dereverb", "dereverb_wav"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)

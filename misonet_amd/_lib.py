@@ -49,6 +49,12 @@ class CacgmmOpts(C.Structure):
     _fields_ = [("iterations", C.c_int), ("prior", C.c_int), ("diag_load", C.c_double), ("prior_floor", C.c_double)]
 
 
+class JbfOpts(C.Structure):
+    """misonet_jbf_opts (ABI 570): kind 0 lcmv / 1 mwf / 2 r1mwf, noise 0 residual / 1 mix, rtf 0 cw / 1 eig"""
+    _fields_ = [("kind", C.c_int), ("noise", C.c_int), ("rtf", C.c_int), ("mu", C.c_double), ("diag_load", C.c_double),
+                ("ref_ch", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -106,6 +112,13 @@ SIGNATURES = {
     "misonet_masks_from_estimates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p]),
     "misonet_pipeline_set_refine": (C.c_int, [C.c_void_p, C.POINTER(CacgmmOpts)]),
+    "misonet_jbf_opts_default": (C.c_int, [C.POINTER(JbfOpts)]),
+    "misonet_beamform_joint_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JbfOpts)]),
+    "misonet_beamform_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JbfOpts),
+                                         C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_beamform_joint_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JbfOpts), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_pipeline_set_joint": (C.c_int, [C.c_void_p, C.POINTER(JbfOpts)]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

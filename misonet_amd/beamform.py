@@ -5,7 +5,10 @@
                                                        WPD convolutional beamformer (``beamformer="wpd"``: misonet_wpd)
 ``pit_select(anchor, cand)``                        -- reference tester.py:1043-1065 / 889-915 (PIT over all S! permutations)
 
-Both run as HIP kernels through the C ABI (misonet_beamform / misonet_pit_select in include/misonet.h).
+``Apply_Beamforming_Joint(sources_stft, mix_stft)``  -- the joint multi-speaker beamformers (:class:`JointBeamformer`: LCMV,
+                                                       SDW-MWF, rank-1 MWF): all speakers of a bin in one solve
+
+All run as HIP kernels through the C ABI (misonet_beamform / misonet_beamform_joint / misonet_pit_select in include/misonet.h).
 """
 from __future__ import annotations
 
@@ -34,6 +37,8 @@ KINDS = ("mvdr", "souden", "gev")            # the kinds of misonet_bf_opts, in 
 WPD = "wpd"                                  # the convolutional beamformer has options and entry points of its own (ABI 530)
 WPD_KMAX = 88                                # the largest order M (taps + 1) the kernel takes (include/misonet.h, "WPD")
 NOISES = ("residual", "mix")
+JOINT_KINDS = ("lcmv", "mwf", "r1mwf")       # the kinds of misonet_jbf_opts, in its numbering (ABI 570); "sdw_mwf" is "mwf"
+RTFS = ("cw", "eig")
 
 
 @dataclasses.dataclass(frozen=True)
@@ -93,7 +98,10 @@ class Beamformer:
     def validate(self, num_mic: Optional[int] = None) -> "Beamformer":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
         if self.kind not in KINDS + (WPD,):
-            raise ValueError(f"beamformer kind {self.kind!r}: one of {KINDS + (WPD,)}")
+            hint = ""
+            if self.kind in JOINT_KINDS + ("sdw_mwf",):
+                hint = " (a joint kind: JointBeamformer / Apply_Beamforming_Joint take it)"
+            raise ValueError(f"beamformer kind {self.kind!r}: one of {KINDS + (WPD,)}{hint}")
         if self.noise not in NOISES:
             raise ValueError(f"beamformer noise {self.noise!r}: one of {NOISES}")
         if not (isinstance(self.condition, (int, float)) and math.isfinite(self.condition) and self.condition >= 0):
@@ -218,6 +226,128 @@ def Apply_Beamforming(source_stft, mix_stft, epsi=1e-6, device=None, return_debu
                                                     lam.data_ptr() if lam is not None else None, st))
                 if lam is not None:
                     dbg["lam"] = lam
+    if np_in:
+        out = out.cpu()
+    return (out, dbg) if return_debug else out
+
+
+@dataclasses.dataclass(frozen=True)
+class JointBeamformer:
+    """The options of the joint multi-speaker beamformers (``misonet_jbf_opts`` of include/misonet.h): one
+    solve per bin for ALL speakers, from their estimates and the mixture.  Deliberately not a :class:`Beamformer` kind: a kind
+    name or a dict still means Beamformer everywhere; the joint kinds are selected with an instance of this class.
+
+    kind       "lcmv" (unit gain on the target's relative transfer function, a null on every other speaker's), "mwf" (the
+               speech-distortion-weighted multichannel Wiener filter; "sdw_mwf" is accepted as its name) or "r1mwf" (rank-1 MWF)
+    noise      "residual": Phi_v from Y - sum_s X_s; "mix": from Y (lcmv only: power minimisation, "LCMP")
+    rtf        "cw": relative transfer functions by covariance whitening; "eig": the principal eigenvector of Phi_s (lcmv only)
+    mu         the speech-distortion weight: > 0 for "mwf" (1 = the MWF), >= 0 for "r1mwf" (0 = Souden MVDR on the sum-of-sources
+               model); ignored by "lcmv"
+    diag_load  R = Phi_v + diag_load tr(Phi_v) / M I
+    ref_ch     reference microphone
+    """
+    kind: str = "lcmv"
+    noise: str = "residual"
+    rtf: str = "cw"
+    mu: float = 1.0
+    diag_load: float = 0.0
+    ref_ch: int = 0
+
+    def __post_init__(self):
+        if self.kind == "sdw_mwf":
+            object.__setattr__(self, "kind", "mwf")
+
+    @classmethod
+    def of(cls, spec) -> "JointBeamformer":
+        """None (the defaults), a JointBeamformer, a kind name, or a dict of the fields above"""
+        if spec is None:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            return cls(kind=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown joint beamformer field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("joint beamformer must be None, a JointBeamformer, a kind name or a dict of its fields")
+
+    def validate(self, num_mic: Optional[int] = None, num_spks: Optional[int] = None) -> "JointBeamformer":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        if self.kind not in JOINT_KINDS:
+            raise ValueError(f"joint beamformer kind {self.kind!r}: one of {JOINT_KINDS}")
+        if self.noise not in NOISES:
+            raise ValueError(f"joint beamformer noise {self.noise!r}: one of {NOISES}")
+        if self.rtf not in RTFS:
+            raise ValueError(f"joint beamformer rtf {self.rtf!r}: one of {RTFS}")
+        if self.kind != "lcmv" and (self.noise != "residual" or self.rtf != "cw"):
+            raise ValueError(f'noise "mix" and rtf belong to kind "lcmv": they must keep their defaults for kind {self.kind!r}')
+        for name in ("diag_load",) if self.kind == "lcmv" else ("mu", "diag_load"):      # mu is ignored by "lcmv"
+            v = getattr(self, name)
+            if isinstance(v, bool) or not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+                raise ValueError(f"joint beamformer {name} must be finite and >= 0, got {v!r}")
+        if self.kind == "mwf" and not self.mu > 0:
+            raise ValueError(f'joint beamformer mu must be > 0 for kind "mwf", got {self.mu!r}')
+        if int(self.ref_ch) != self.ref_ch or self.ref_ch < 0 or (num_mic is not None and self.ref_ch >= num_mic):
+            raise ValueError(f"joint beamformer ref_ch {self.ref_ch!r} outside [0, {num_mic if num_mic is not None else 'M'})")
+        if num_mic is not None and not 2 <= num_mic <= 8:
+            raise ValueError(f"the joint beamformers need 2 <= M <= 8 microphones, got {num_mic}")
+        if num_spks is not None and not 1 <= num_spks <= min(4, num_mic if num_mic is not None else 4):
+            raise ValueError(f"the joint beamformers need 1 <= S <= 4 speakers and S <= M, got S {num_spks}"
+                             + (f" with M {num_mic}" if num_mic is not None else ""))
+        return self
+
+    def c_opts(self) -> "_lib.JbfOpts":
+        return _lib.JbfOpts(JOINT_KINDS.index(self.kind), NOISES.index(self.noise), RTFS.index(self.rtf), float(self.mu),
+                            float(self.diag_load), int(self.ref_ch))
+
+
+def Apply_Beamforming_Joint(sources_stft, mix_stft, beamformer="lcmv", *, noise="residual", rtf="cw", mu=1.0, diag_load=0.0,
+                            ref_ch=0, device=None, return_debug=False):
+    """The joint multi-speaker beamformers (``misonet_beamform_joint``): every speaker's filter of a bin from ONE solve that
+    knows all of them.
+
+    sources_stft complex [B, S, F, Ch, T] (the S source estimates at every microphone), mix_stft complex [B, F, Ch, T];
+    np.ndarray or torch tensors, as :func:`Apply_Beamforming` takes them (permuted views are fine, nothing is modified).
+    Returns a torch complex64 tensor [B, S, T, F]: on the CPU when the inputs were ndarrays, on the device when they were
+    device tensors.  The keywords are the fields of :class:`JointBeamformer` (``beamformer`` = its ``kind``, or a whole
+    JointBeamformer / dict).  ``return_debug`` adds, on the device, ``w`` complex128 [B, S, F, Ch], ``fail`` int32 [B, S, F]
+    and, for "lcmv", ``rtf`` complex128 [B, S, F, Ch] (the relative transfer functions d_s)."""
+    if isinstance(beamformer, str):
+        bf = JointBeamformer(kind=beamformer, noise=noise, rtf=rtf, mu=mu, diag_load=diag_load, ref_ch=ref_ch)
+    else:
+        bf = JointBeamformer.of(beamformer)
+    five = np.ndim(sources_stft) == 5
+    bf.validate(np.shape(sources_stft)[3] if five else None, np.shape(sources_stft)[1] if five else None)   # before any copy
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    src, np_in = _dev_c64(sources_stft, device)
+    mix, _ = _dev_c64(mix_stft, device)
+    if src.dim() != 5 or mix.dim() != 4 or src.shape[:1] + src.shape[2:] != mix.shape:
+        raise ValueError(f"sources_stft {tuple(src.shape)} must be [B, S, F, Ch, T] and mix_stft {tuple(mix.shape)} [B, F, Ch, T]")
+    B, S, F, M, T = src.shape
+    opts = bf.c_opts()
+    L = _lib.lib()
+    nws = L.misonet_beamform_joint_workspace_bytes(B, S, F, M, C.byref(opts))
+    if nws < 0:
+        _lib.check(_lib.EINVAL)
+    ws = torch.empty(max(int(nws), 8), dtype=torch.uint8, device=src.device)
+    out = torch.empty((B, S, T, F), dtype=torch.complex64, device=src.device)
+    dbg = None
+    with torch.cuda.device(src.device):
+        st = _lib.stream_ptr(src.device)
+        _lib.check(L.misonet_beamform_joint(src.data_ptr(), mix.data_ptr(), B, S, F, M, T, C.byref(opts), out.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), st))
+        if return_debug:
+            w = torch.empty((B, S, F, M), dtype=torch.complex128, device=src.device)
+            bad = torch.empty((B, S, F), dtype=torch.int32, device=src.device)
+            d = torch.empty_like(w) if bf.kind == "lcmv" else None
+            _lib.check(L.misonet_beamform_joint_debug(ws.data_ptr(), B, S, F, M, C.byref(opts), w.data_ptr(),
+                                                      d.data_ptr() if d is not None else None, bad.data_ptr(), st))
+            dbg = dict(w=w, fail=bad)
+            if d is not None:
+                dbg["rtf"] = d
     if np_in:
         out = out.cpu()
     return (out, dbg) if return_debug else out

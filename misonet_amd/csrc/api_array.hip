@@ -1,6 +1,6 @@
 // C ABI of the array processing (include/misonet.h): the drop-in beamformers misonet_mvdr* / misonet_bf_* / misonet_beamform*
 // (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), the WPD beamformer misonet_wpd* (wpd.hip), guided spatial clustering
-// misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
@@ -83,6 +83,36 @@ static int cacgmm_geometry(int B, int K, int F, int M) {
   if (B <= 0 || B > 65535 || F <= 0) return fail(MISONET_EINVAL, "B must be in [1, 65535] and F positive (got %d, %d)", B, F);
   if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
   if (K < 2 || K > 5) return fail(MISONET_EINVAL, "K = speakers + 1 must be in [2, 5] (got %d)", K);
+  return MISONET_OK;
+}
+
+// joint beamformers: every field, against M microphones and S speakers
+int mn::jbf_opts_check(const misonet_jbf_opts* o, int M, int S) {
+  if (!o) return fail(MISONET_EINVAL, "null joint beamformer options");
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (S < 1 || S > 4 || S > M) return fail(MISONET_EINVAL, "S must be in [1, 4] and <= M (got S %d, M %d)", S, M);
+  if (o->kind != JBF_LCMV && o->kind != JBF_MWF && o->kind != JBF_R1MWF)
+    return fail(MISONET_EINVAL, "joint beamformer kind %d: 0 lcmv, 1 mwf, 2 r1mwf", o->kind);
+  if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "joint beamformer noise %d: 0 residual, 1 mix", o->noise);
+  if (o->rtf != 0 && o->rtf != 1) return fail(MISONET_EINVAL, "joint beamformer rtf %d: 0 cw, 1 eig", o->rtf);
+  if (o->kind != JBF_LCMV && (o->noise != 0 || o->rtf != 0))
+    return fail(MISONET_EINVAL, "noise \"mix\" and rtf belong to kind lcmv: they must keep their defaults for kind %d", o->kind);
+  if (!(o->diag_load >= 0.0) || !std::isfinite(o->diag_load))
+    return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (o->kind == JBF_MWF && (!(o->mu > 0.0) || !std::isfinite(o->mu)))
+    return fail(MISONET_EINVAL, "mu must be finite and > 0 for kind mwf (got %g)", o->mu);
+  if (o->kind == JBF_R1MWF && (!(o->mu >= 0.0) || !std::isfinite(o->mu)))
+    return fail(MISONET_EINVAL, "mu must be finite and >= 0 for kind r1mwf (got %g)", o->mu);
+  if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "joint beamformer ref_ch %d outside [0, %d)", o->ref_ch, M);
+  return MISONET_OK;
+}
+
+void mn::jbf_opts_apply(const misonet_jbf_opts& o, JbfArgs& a) {
+  a.kind = o.kind; a.noise_mix = o.noise; a.rtf_eig = o.rtf; a.ref = o.ref_ch; a.mu = o.mu; a.diag_load = o.diag_load;
+}
+
+static int jbf_geometry(int B, int F) {
+  if (B <= 0 || B > 65535 || F <= 0) return fail(MISONET_EINVAL, "B must be in [1, 65535] and F positive (got %d, %d)", B, F);
   return MISONET_OK;
 }
 
@@ -306,6 +336,50 @@ int misonet_masks_from_estimates(const void* est, const void* mix, int B, int S,
   a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
   a.masks = masks_out;
   HIPCHK(launch_masks_from_est(a, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- joint multi-speaker beamformers: LCMV, SDW-MWF, rank-1 MWF (ABI 570) ------------------------------------------------
+int misonet_jbf_opts_default(misonet_jbf_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->kind = JBF_LCMV; o->noise = 0; o->rtf = 0; o->mu = 1.0; o->diag_load = 0.0; o->ref_ch = 0;
+  return MISONET_OK;
+}
+
+long long misonet_beamform_joint_workspace_bytes(int B, int S, int F, int M, const misonet_jbf_opts* opts) {
+  if (jbf_geometry(B, F) || jbf_opts_check(opts, M, S)) return -1;
+  return jbf_ws_bytes(B, S, F, M, opts->kind);
+}
+
+int misonet_beamform_joint(const void* src, const void* mix, int B, int S, int F, int M, int T, const misonet_jbf_opts* opts,
+                           void* out, void* ws, long long ws_bytes, misonet_stream stream) {
+  { int r = jbf_geometry(B, F); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be positive (got %d)", T);
+  { int r = jbf_opts_check(opts, M, S); if (r) return r; }
+  if (!src || !mix || !out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (ws_bytes < jbf_ws_bytes(B, S, F, M, opts->kind)) return fail(MISONET_ENOMEM, "workspace too small");
+  JbfArgs a;
+  const float* y = reinterpret_cast<const float*>(mix);
+  const float* x = reinterpret_cast<const float*>(src);
+  a.mix = {y, y + 1, 2LL * F * M * T, 2LL * M * T, 2LL * T, 2};
+  a.src = {x, x + 1, 2LL * S * F * M * T, 2LL * M * T, 2LL * T, 2};                  // [B,S,F,M,T] complex64
+  a.src_ss = 2LL * F * M * T;
+  a.est = nullptr; a.est_bstride = 0; a.sel = nullptr;
+  a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = T;
+  jbf_opts_apply(*opts, a);
+  float* o = reinterpret_cast<float*>(out);
+  COut co = {o, o + 1, 2LL * S * T * F, 2LL * T * F, 2LL * F, 2};                    // [B,S,T,F] complex64
+  HIPCHK(launch_jbf(a, co, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_beamform_joint_debug(const void* ws, int B, int S, int F, int M, const misonet_jbf_opts* opts, void* w, void* rtf,
+                                 int* fail_dev, misonet_stream stream) {
+  { int r = jbf_geometry(B, F); if (r) return r; }
+  { int r = jbf_opts_check(opts, M, S); if (r) return r; }
+  if (rtf && opts->kind != JBF_LCMV) return fail(MISONET_EINVAL, "the relative transfer functions exist for kind lcmv only");
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_jbf_debug(ws, B, S, F, M, opts->kind, w, rtf, fail_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

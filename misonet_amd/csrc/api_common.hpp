@@ -101,5 +101,8 @@ void wpd_opts_apply(const misonet_wpd_opts& o, WpdArgs& a);
 int wpd_ready();
 // api_array.hip: host-side check of every cACGMM field
 int cacgmm_opts_check(const misonet_cacgmm_opts* o);
+// api_array.hip: host-side check of every field of the joint beamformers against M microphones and S speakers; the options as JbfArgs
+int jbf_opts_check(const misonet_jbf_opts* o, int M, int S);
+void jbf_opts_apply(const misonet_jbf_opts& o, JbfArgs& a);
 
 }  // namespace mn

@@ -16,6 +16,8 @@ struct misonet_pipeline {
   misonet_wpd_opts wpd;
   bool use_refine;         // step 4b: guided spatial clustering between the alignments and step 5 (misonet_pipeline_set_refine)
   misonet_cacgmm_opts refine;
+  bool use_joint;          // step 5 is one joint beamformer for all speakers (misonet_pipeline_set_joint); bf / wpd are kept
+  misonet_jbf_opts joint;
 };
 
 struct PipeLayout {
@@ -40,8 +42,9 @@ static PipeLayout pipe_layout(const misonet_pipeline* p, int B, int T) {
   // PIT distances [B*M + B][S][S] followed by their per-bin partials [B*M + B][F][S][S] (mvdr.hip pit_dist_k)
   P.off_dist = o;  o += align_up((long long)(B * p->M + B) * p->S * p->S * (F + 1) * 8, 256);
   P.off_sel = o;   o += align_up((long long)(B * p->M * p->S * 2 + B * p->S) * 4, 256);
-  P.off_mvdr = o;  o += align_up(p->use_wpd ? wpd_ws_bytes(B, p->S, F, p->M, p->wpd.taps)
-                                            : bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
+  P.off_mvdr = o;  o += align_up(p->use_joint ? jbf_ws_bytes(B, p->S, F, p->M, p->joint.kind)
+                                 : p->use_wpd ? wpd_ws_bytes(B, p->S, F, p->M, p->wpd.taps)
+                                              : bf_ws_bytes(B, p->S, F, p->M, p->bf.kind), 256);
   P.clean_bstride = (long long)2 * p->S * F * Tp;
   P.off_clean = o; o += align_up(P.clean_bstride * B * 4, 256);
   P.L3.in_ext_bstride = p->n3 ? (long long)p->n3->cfg.in_ch * F * Tp : 0;
@@ -107,6 +110,14 @@ int misonet_pipeline_set_refine(misonet_pipeline* p, const misonet_cacgmm_opts* 
   p->use_refine = true;
   return MISONET_OK;
 }
+int misonet_pipeline_set_joint(misonet_pipeline* p, const misonet_jbf_opts* opts) {
+  if (!p) return fail(MISONET_EINVAL, "null argument");
+  if (!opts) { p->use_joint = false; return MISONET_OK; }
+  { int r = jbf_opts_check(opts, p->M, p->S); if (r) return r; }
+  p->joint = *opts;
+  p->use_joint = true;
+  return MISONET_OK;
+}
 int misonet_pipeline_destroy(misonet_pipeline* p) { delete p; return MISONET_OK; }
 
 long long misonet_pipeline_workspace_bytes(const misonet_pipeline* p, int B, int T) {
@@ -122,7 +133,7 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
   if (!p->n3 && (out || bf_out))
     return fail(MISONET_ESTATE, "this pipeline was created without MISO_3 (separation only): out and bf_out must be NULL");
   if (B <= 0 || T <= 0) return fail(MISONET_EINVAL, "B and T must be positive");
-  if (p->use_wpd && out) {
+  if (p->use_wpd && !p->use_joint && out) {
     int rw = wpd_opts_check(&p->wpd, p->M, T);
     if (!rw) rw = wpd_ready();
     if (rw) return rw;
@@ -217,7 +228,17 @@ static int pipeline_run_impl(misonet_pipeline* p, const void* mix, const void* c
     }
 
     // 5. MVDR per aligned speaker (tester.py:917-924, 1071-1136); writes the beamformer planes of the MISO3 input
-    if (p->use_wpd) {   // ... or WPD on the same views and the same planes
+    if (p->use_joint) {   // ... or one joint beamformer for all speakers, on the same views and the same planes
+      JbfArgs a;
+      a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};
+      a.est = est5; a.est_bstride = est5_bs; a.sel = sel5;
+      a.src = {nullptr, nullptr, 0, 0, 0, 1}; a.src_ss = 0;
+      a.S = S; a.B = B; a.F = F; a.M = M; a.T = T; a.Tp = Tp;
+      jbf_opts_apply(p->joint, a);
+      COut co = {in3 + (long long)M * plane, in3 + (long long)(2 * M + 2) * plane, (long long)S * in3_bs, in3_bs, 1, Tp};
+      ProfScope ps(s, PK_MVDR);
+      HIPCHK(launch_jbf(a, co, base + P.off_mvdr, s));
+    } else if (p->use_wpd) {   // ... or WPD on the same views and the same planes
       WpdArgs a;
       a.mix = {in1, in1 + (long long)M * plane, (long long)M * in1_bs, Tp, plane, 1};
       a.est = est5; a.est_bstride = est5_bs; a.sel = sel5;

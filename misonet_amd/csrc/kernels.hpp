@@ -392,8 +392,33 @@ struct MaskArgs {
 };
 hipError_t launch_masks_from_est(const MaskArgs& a, hipStream_t s);
 
-// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs or
-// MaskArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
+// Joint multi-speaker beamformers (jbf.hip): LCMV, SDW-MWF and rank-1 MWF, one workgroup per (b, bin) that
+// owns all S speakers.  mix through a CView; the S estimates as launch_masks_from_est reads them (est / est_bstride / sel in
+// pipeline mode; src with the speaker stride src_ss when est == nullptr); out through a COut (os = the speaker stride), the
+// frames [T, Tp) of it untouched.  The workspace holds fail int [B][S][F], w complex128 [B][S][F][M] and, for lcmv, the relative
+// transfer functions d complex128 [B][S][F][M], which launch_jbf_debug copies out.  2 <= M <= 8, 1 <= S <= min(4, M), T >= 1,
+// 0 <= ref < M: the caller checks them.
+enum { JBF_LCMV = 0, JBF_MWF = 1, JBF_R1MWF = 2 };
+struct JbfArgs {
+  CView mix;
+  const float* est;
+  long long est_bstride;
+  const int* sel;
+  CView src;
+  long long src_ss;
+  int S, B, F, M, T, Tp;
+  int kind;               // JBF_LCMV / JBF_MWF / JBF_R1MWF
+  int noise_mix;          // lcmv: Phi_v from Y instead of Y - sum_s X_s ("LCMP")
+  int rtf_eig;            // lcmv: a_s = the principal eigenvector of Phi_s instead of covariance whitening
+  int ref;
+  double mu, diag_load;
+};
+long long jbf_ws_bytes(int B, int S, int F, int M, int kind);
+hipError_t launch_jbf(const JbfArgs& a, const COut& out, void* ws, hipStream_t s);
+hipError_t launch_jbf_debug(const void* ws, int B, int S, int F, int M, int kind, void* w, void* d, int* fail, hipStream_t s);
+
+// source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs,
+// MaskArgs or JbfArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
 template <typename Args>
 __device__ __forceinline__ void src_row(const Args& a, int b, int f, int m, int spk, const float*& re, const float*& im,
                                         int& st) {

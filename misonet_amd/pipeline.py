@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from . import stft as S
-from .beamform import Beamformer
+from .beamform import Beamformer, JointBeamformer
 from .dereverb import Dereverb, dereverb_wav
 from .model import MISO_1, MISO_3
 from .refine import Refine, refined_images
@@ -214,8 +214,9 @@ class Enhancer:
                  beamformer=None, dereverb=None, refine=None):
         """``model = None``: a separation-only Enhancer (:meth:`separate`, :meth:`beamform_utterance`,
         :meth:`beamform_chunks` -- what the reference's ``Tester_Beamforming`` needs: it has no MISO_3, tester.py:259-262).
-        ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields; it
-        reaches the fused pass and every ``beamform_*`` method (:meth:`set_beamformer`).
+        ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields, or a
+        :class:`misonet_amd.beamform.JointBeamformer` instance (one joint solve for all speakers); it reaches the fused pass and
+        every ``beamform_*`` method (:meth:`set_beamformer`).
         ``dereverb``: None (no dereverberation), True, a :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields:
         the recording paths dereverberate the observation first (:meth:`set_dereverb`).
         ``refine``: None (off), True, a :class:`misonet_amd.refine.Refine` or a dict of its fields: guided spatial clustering
@@ -272,14 +273,25 @@ class Enhancer:
         :meth:`beamform_chunks` / :meth:`beamform_utterance`: None (back to the reference's MVDR), a Beamformer or a dict of
         its fields.  ``epsi`` left unset keeps each call's own default (the constructor's ``epsi`` in the fused pass).  Legal
         between passes; ValueError for a bad field.  A captured pass keeps the options it was captured with, so the change is
-        refused while one is alive."""
-        bf = Beamformer.of(beamformer).validate(self.num_ch)
+        refused while one is alive.  A :class:`JointBeamformer` INSTANCE selects a joint multi-speaker beamformer (LCMV, SDW-MWF,
+        rank-1 MWF: one solve per bin for all speakers) as that step; a kind name or a dict always means Beamformer."""
+        if isinstance(beamformer, JointBeamformer):
+            bf = beamformer.validate(self.num_ch, self.num_spks)
+        else:
+            bf = Beamformer.of(beamformer).validate(self.num_ch)
         if bf == self.beamformer:
             return
         if len(self._captured):
             raise RuntimeError("set_beamformer: a captured pass of this Enhancer is alive and would go on replaying the old "
                                "beamformer; drop it and capture again after the change")
         L = _lib.lib()
+        if isinstance(bf, JointBeamformer):    # the per-speaker options that are set stay behind it, for the way back
+            jopts = bf.c_opts()
+            _lib.check(L.misonet_pipeline_set_joint(self._pipe, C.byref(jopts)))
+            self.beamformer = bf
+            self._ws.clear()
+            return
+        _lib.check(L.misonet_pipeline_set_joint(self._pipe, None))
         if bf.kind == "wpd":                   # the convolutional beamformer has options and an entry point of its own
             wopts = bf.wpd_opts()
             _lib.check(L.misonet_pipeline_set_wpd(self._pipe, C.byref(wopts)))
@@ -313,7 +325,11 @@ class Enhancer:
     def _bf(self, beamformer, epsi):
         """the options of one beamform_* call: its own ``beamformer`` (None: the Enhancer's) and ``epsi`` (None: the
         options', else the reference's 1e-6)"""
+        if isinstance(beamformer, JointBeamformer):
+            return beamformer.validate(self.num_ch, self.num_spks)
         bf = self.beamformer if beamformer is None else Beamformer.of(beamformer).validate(self.num_ch)
+        if isinstance(bf, JointBeamformer):    # the joint kinds have no epsi
+            return bf
         return bf if epsi is None else dataclasses.replace(bf, epsi=float(epsi))
 
     def __del__(self):
@@ -749,7 +765,7 @@ class Enhancer:
         """The per-recording tail of :meth:`beamform_utterance` (and of the coalesced utterance-wise Tester_Beamforming):
         est complex [K,S,M,T,F] = the separated splits, obs complex [K,M,T,F] (device) -> int16 [S, n] (device): one
         batched iSTFT, the splits stitched (last one trimmed by ``gap``), one long STFT, one MVDR per speaker, int16."""
-        from .beamform import Apply_Beamforming
+        from .beamform import Apply_Beamforming, Apply_Beamforming_Joint
         bf_opts = self._bf(beamformer, epsi)
         K = est.shape[0]
         e = S.istft(est)                                                                      # [K,S,M,chunk]
@@ -767,8 +783,11 @@ class Enhancer:
         src = spec[1:].permute(0, 3, 1, 2)[None]                              # [1,S,F,M,Tt]
         if self.refine is not None:                                           # one clustering over the recording's frames
             src = refined_images(src, mix_bf, self.refine)
-        bf = torch.stack([Apply_Beamforming(src[:, s], mix_bf, beamformer=bf_opts)[0]
-                          for s in range(self.num_spks)])                     # [S,Tt,F]
+        if isinstance(bf_opts, JointBeamformer):                              # one joint solve for all speakers
+            bf = Apply_Beamforming_Joint(src, mix_bf, bf_opts)[0]
+        else:
+            bf = torch.stack([Apply_Beamforming(src[:, s], mix_bf, beamformer=bf_opts)[0]
+                              for s in range(self.num_spks)])                 # [S,Tt,F]
         return S.istft_int16(bf)
 
     def beamform_chunks(self, mix: torch.Tensor, clean: Optional[torch.Tensor] = None, epsi: Optional[float] = None,
@@ -777,12 +796,14 @@ class Enhancer:
         Tester_Beamforming, tester.py:452-535): separation of a batch of 4 s chunks, then one MVDR per (chunk, speaker) over
         the chunk's own frames.  mix complex [B,M,T,F], clean complex [B,S,T,F] or None -> beamformer outputs complex64
         [B,S,T,F].  (With MISO_3 attached, ``enhance(..., want_bf=True)`` returns the same tensor from the fused pass.)"""
-        from .beamform import Apply_Beamforming
+        from .beamform import Apply_Beamforming, Apply_Beamforming_Joint
         bf_opts = self._bf(beamformer, epsi)
         est = self.separate(mix, clean, check_nan=check_nan)                                  # [B,S,M,T,F]
         mix_bf = self._check_c64(mix, "mix").permute(0, 3, 1, 2)                              # [B,F,M,T]
         if self.refine is not None:
             est = refined_images(est.permute(0, 1, 4, 2, 3), mix_bf, self.refine).permute(0, 1, 3, 4, 2)
+        if isinstance(bf_opts, JointBeamformer):                                              # one joint solve for all speakers
+            return Apply_Beamforming_Joint(est.permute(0, 1, 4, 2, 3), mix_bf, bf_opts)
         return torch.stack([Apply_Beamforming(est[:, s].permute(0, 3, 1, 2), mix_bf, beamformer=bf_opts)
                             for s in range(self.num_spks)], dim=1)                            # [B,S,T,F]
 

@@ -47,7 +47,8 @@ class Tester_Enhance(object):
             model.cuda(device)
         self._enh = Enhancer(model_sep.eval(), model.eval(), num_spks=self.num_spks, ref_ch=self.ref_ch)
         self.score = False           # True: inference() also writes <saveDir>/scores.json (Enhancer.inference, score=True)
-        self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts.
+        self.beamformer = None       # a Beamformer / dict of its fields, or a JointBeamformer instance (Enhancer.set_beamformer),
+        #                              read when inference() starts.
         #                              MISO_3 was trained on the reference's MVDR output: another beamformer is an experiment here
         self.dereverb = None         # None / True / a Dereverb / dict of its fields (Enhancer.set_dereverb), read when inference()
         #                              starts: it reaches the Enhancer's RECORDING paths (self._enh.enhance_recording(s) /
@@ -109,7 +110,8 @@ class Tester_Beamforming(object):
             model.cuda(device)
         self._enh = Enhancer(model.eval(), None, num_spks=self.num_spks, ref_ch=self.ref_ch)
         self.score = False           # True: inference() also writes <saveDir>/scores.json for the beamformer output
-        self.beamformer = None       # a Beamformer / dict of its fields (Enhancer.set_beamformer), read when inference() starts:
+        self.beamformer = None       # a Beamformer / dict of its fields, or a JointBeamformer instance (Enhancer.set_beamformer),
+        #                              read when inference() starts:
         #                              the beamformed wav is this class's product, so this is its product setting
         self.dereverb = None         # as Tester_Enhance.dereverb: reaches the Enhancer (set_dereverb), whose recording paths use it
         self.refine = None           # as Tester_Enhance.refine: reaches the Enhancer (set_refine) and its beamform_* methods
