@@ -85,6 +85,48 @@ def gather(raw, sel, M):
     return out
 
 
+# ---- the read path of steps 4b and 5 (csrc/kernels.hpp, src_row in pipeline mode) ---------------------------------------------------
+# The beamformers and masks_from_est_k do not read the exported miso1: they read the raw planar MISO_1 output [B*M][2 S][F][Tp]
+# through sel_final, with n = b*M + m, q = sel[n*S + spk], the real plane q and the imaginary plane S + q of sample n.
+
+READ_FAULTS = {
+    "mic0": "the sel row of microphone 0 for every microphone: sel[(b*M)*S + spk]",
+    "item0": "the sel rows of item 0 for every item: sel[m*S + spk]",
+    "inverse": "the inverse permutation: the q with sel[n*S + q] == spk",
+    "imag": "the imaginary plane of speaker spk instead of q: (S + spk) * plane",
+}
+# what a geometry must have for a variant to be able to differ from the healthy read (S, B) -> bool.  Two speakers cannot see the
+# inverse (every permutation of two is its own inverse), one item cannot see item0, one speaker nothing.
+READ_FAULT_NEEDS = {
+    "mic0": lambda S, B: S >= 2,
+    "item0": lambda S, B: S >= 2 and B >= 2,
+    "inverse": lambda S, B: S >= 3,
+    "imag": lambda S, B: S >= 2,
+}
+
+
+def read_est(raw, sel, M, S, fault=None):
+    """src_row in pipeline mode over every (b, spk, m): raw complex [B*M, S, T, F] (plane q of sample n = real plane q + i imaginary
+    plane S + q), sel [B, M, S] -> what step 4b / 5 reads as the estimate of aligned speaker spk at microphone m, [B, S, M, T, F].
+    ``fault``: one of READ_FAULTS planted in the index arithmetic."""
+    assert fault is None or fault in READ_FAULTS, fault
+    raw, sel = np.asarray(raw), np.asarray(sel)
+    B = sel.shape[0]
+    assert sel.shape == (B, M, S) and raw.shape[:2] == (B * M, S), (sel.shape, raw.shape, M, S)
+    out = np.empty((B, S, M) + raw.shape[2:], raw.dtype)
+    for b in range(B):
+        for m in range(M):
+            n = b * M + m
+            row = sel[b, 0] if fault == "mic0" else sel[0, m] if fault == "item0" else sel[b, m]
+            if fault == "inverse":
+                row = np.argsort(row)
+            for spk in range(S):
+                q = int(row[spk])
+                qi = spk if fault == "imag" else q
+                out[b, spk, m] = raw[n, q].real + 1j * raw[n, qi].imag
+    return out
+
+
 def _bits(x):
     x = np.ascontiguousarray(x)
     return x.view(np.uint32 if x.dtype == np.complex64 else np.uint64)

@@ -42,7 +42,8 @@ CASES = [
     (1, 3, 2, 2, 33, True, None),        # pit_*<1>; two output channels
     (2, 6, 0, 2, 130, True, None),       # the shipped geometry at Tp = 160
 ]
-WEIGHT_SEED = {(3, 6): 2, (4, 8): 6, (3, 5): 8, (2, 2): 7, (4, 7): 5, (1, 3): 3, (2, 6): 0}
+WEIGHT_SEED = {(3, 6): 2, (4, 8): 6, (3, 5): 8, (2, 2): 7, (4, 7): 5, (1, 3): 3, (2, 6): 0,
+               (3, 2): 4}                # S > M: tests/test_gpu_pipeline_steps.py, the refusal of the joint beamformers
 WAV_CASES = [CASES[3], CASES[4]]         # the waveform entry: one of them with M = 8
 WS_CASE = CASES[4]                       # the workspace's previous contents
 

@@ -5,7 +5,9 @@ stands for MISO_1: its outputs over the circular shifts are permuted copies of o
 network's are.  ``pipeline_glue_ref.emulate`` runs the fused pass's glue on it in NumPy.  At S = 3, M = 4, B = 2 the healthy emulation
 passes ``judge`` (what the device test asserts about the glue) and every fault of ``FAULTS`` is rejected; at S = 2 the two faults of
 ``BLIND_AT_S2`` (composition in the other order, gather with the inverse permutation) give the very same bits as the healthy pass --
-every permutation of two elements is its own inverse and all of them commute -- which is why the device test runs at S >= 3."""
+every permutation of two elements is its own inverse and all of them commute -- which is why the device test runs at S >= 3.
+``pipeline_glue_ref.read_est`` (the read path of steps 4b and 5, tests/test_gpu_pipeline_steps.py) gets the same treatment on synthetic
+planes and hand-made selections."""
 import numpy as np
 import pytest
 
@@ -129,6 +131,46 @@ def test_observed_sel_needs_exactly_one_bit_equal_plane(case3):
     m1[0, 1, 1] = m1[0, 0, 1]                                         # one plane twice: no permutation
     with pytest.raises(AssertionError, match="no permutation"):
         G.observed_sel(m1, k["raw"], k["M"])
+
+
+def test_planted_read_faults_and_what_two_speakers_cannot_see():
+    """``read_est`` (src_row in pipeline mode, the read path of steps 4b and 5) with one planted fault at a time, on synthetic raw
+    planes and hand-made selections.  S = 3, M = 3, B = 2 with per-microphone and per-item different, non-involutive rows tells every
+    variant apart by plain array inequality.  S = 2 cannot see the inverse permutation whatever its rows are, B = 1 cannot see the
+    rows of item 0, S = 1 sees nothing; and the geometry the fused-pass tests of the step-5 features share -- S = 2, here with the
+    same selection at every microphone and item, which nothing there rules out -- sees only the imaginary plane.  Hence the
+    geometries of tests/test_gpu_pipeline_steps.py: S >= 3, B >= 2, and the variants checked on each case's own selection."""
+    r = np.random.default_rng(80)
+
+    def raw_of(B, M, S):
+        return (r.standard_normal((B * M, S, T, F)) + 1j * r.standard_normal((B * M, S, T, F))).astype(np.complex64)
+
+    def seen(raw, sel, M, S):
+        healthy = G.read_est(raw, sel, M, S)
+        assert np.array_equal(healthy, G.gather(raw, sel, M))                # the healthy read is the exported miso1
+        return {f: not np.array_equal(G.read_est(raw, sel, M, S, f), healthy) for f in G.READ_FAULTS}
+
+    sel3 = np.array([[(1, 2, 0), (0, 1, 2), (2, 0, 1)], [(0, 2, 1), (2, 0, 1), (1, 0, 2)]])
+    assert seen(raw_of(2, 3, 3), sel3, 3, 3) == dict(mic0=True, item0=True, inverse=True, imag=True)
+    assert all(G.READ_FAULT_NEEDS[f](3, 2) for f in G.READ_FAULTS)
+    # two speakers: rows that differ per microphone and per item, and still no sight of the inverse
+    sel2 = np.array([[(1, 0), (0, 1), (1, 0)], [(0, 1), (0, 1), (1, 0)]])
+    got = seen(raw_of(2, 3, 2), sel2, 3, 2)
+    assert got == dict(mic0=True, item0=True, inverse=False, imag=True), got
+    assert [f for f in G.READ_FAULTS if not G.READ_FAULT_NEEDS[f](2, 2)] == ["inverse"]
+    # two speakers, one swap everywhere (every shift agrees with ref_ch, both items given in the same clean order)
+    got = seen(raw_of(2, 6, 2), np.tile(np.array([1, 0]), (2, 6, 1)), 6, 2)
+    assert got == dict(mic0=False, item0=False, inverse=False, imag=True), got
+    # ... and with the identity everywhere (no clean references, no re-ordered shift) nothing at all
+    got = seen(raw_of(2, 6, 2), np.tile(np.array([0, 1]), (2, 6, 1)), 6, 2)
+    assert not any(got.values()), got
+    # one item; one speaker
+    got = seen(raw_of(1, 3, 3), sel3[:1], 3, 3)
+    assert got == dict(mic0=True, item0=False, inverse=True, imag=True) and not G.READ_FAULT_NEEDS["item0"](3, 1)
+    got = seen(raw_of(2, 3, 1), np.zeros((2, 3, 1), np.int64), 3, 1)
+    assert not any(got.values()) and not any(G.READ_FAULT_NEEDS[f](1, 2) for f in G.READ_FAULTS)
+    with pytest.raises(AssertionError):
+        G.read_est(raw_of(2, 3, 3), sel3, 3, 3, "no such fault")
 
 
 def test_first_minimum_wins_and_undecided_items_are_bounded():
