@@ -18,6 +18,8 @@ fault at the bound the GPU tests use.
 The comparator measures one sample [C, T, F] of a level's output against the float64 oracle on the SAME input and bounds it by K
 times the distance of the float32 oracle (stock torch on the CPU) from that truth: for the whole tensor, the worst frame, the
 worst frequency row and the worst channel, each against the same figure of the float32 oracle.
+
+The channel widths the CPU and the GPU tests run are defined here once (WIDTH_SETS), with the layer list they give (conv_layers).
 """
 from collections import namedtuple
 
@@ -47,6 +49,69 @@ FAULTS = {
 }
 
 LEVELS = ("enc0_conv",) + tuple(f"enc{b}" for b in range(7)) + tuple(f"dec{b}" for b in range(7))
+
+# ---- channel widths --------------------------------------------------------------------------------------------------------
+# misonet_net_create admits every encoder list of positive multiples of 8 up to 128 with en[6] == 128 and de = en[::-1]; the conv
+# kernels are written around DEFAULT.  The two other sets reach what DEFAULT never does (tests/test_lib_abi.py pins the kernel of
+# every layer): f32w DenseBlocks that mix W1D + WINO and WINO + DIRECT (Cin > 192 or Cout > 64), WINO at 8 / 16 (the 16-row body
+# alone) / 40 / 48 / 56 / 64 output channels, 64-channel DIRECT groups at 72 ... 128 output channels and up to 384 input channels,
+# the stride-2 transposed layers at 8 / 16 / 40 / 48 / 56 / 64, dec0 at 72 and 128, a first layer of 40 output channels, bf16x6
+# tiles with Cout & 31 in {8, 16, 24} at two and more channel groups, and a last layer of 6 / 8 channels (3 / 4 speakers), which
+# is neither conv3x3_few nor the rows_in_m tile.  The small and odd widths sit on the rows with many frequency bins, the wide ones
+# where F <= 31, so the float64 oracle of a sample costs about what DEFAULT's does.
+# name: (encoder channels, num_spks); the decoder channels are the encoder's reversed
+WIDTH_SETS = {
+    "default": ((24, 32, 32, 32, 32, 64, 128), 2),
+    "narrow_to_wide": ((8, 16, 40, 48, 56, 72, 128), 3),
+    "wide_first": ((40, 24, 64, 8, 16, 128, 128), 4),
+}
+NARROW_TO_WIDE, WIDE_FIRST = WIDTH_SETS["narrow_to_wide"][0], WIDTH_SETS["wide_first"][0]
+OTHER_WIDTHS = ("narrow_to_wide", "wide_first")
+EN_F = (129, 127, 63, 31, 15, 7, 3, 1)             # frequency rows in front of encoder level b; EN_F[b + 1] behind it
+DE_F = EN_F[::-1]                                  # in front of decoder level b; DE_F[b + 1] behind it
+
+
+def widths(ws):
+    """(en, de, num_spks) of a width set"""
+    en, spks = WIDTH_SETS[ws]
+    return tuple(en), tuple(en[::-1]), spks
+
+
+def level_channels(ws, num_ch=6):
+    """(EN, DE): EN[b] the channels in front of encoder level b (EN[0] the network input) and EN[b + 1] behind it; DE[b] the
+    channels of EACH of the two inputs of decoder level b (the previous level's output and the skip) and DE[b + 1] behind it"""
+    en, de, spks = widths(ws)
+    return (2 * num_ch,) + en, de + (2 * spks,)
+
+
+def state_dict(ws, seed=3):
+    """seeded MISO_1 weights of a width set (6 microphones)"""
+    from misonet_amd import weights as W
+    en, de, spks = widths(ws)
+    return W.make_state_dict(W.miso1_spec(num_spks=spks, en_ch=en, de_ch=de), seed=seed)
+
+
+def conv_layers(ws, num_ch=6):
+    """the 64 conv layers of MISO_1 in launch order (encoders, then decoders), as dicts: name, Cin, Cout, F (output rows), act
+    (ELU + instance norm behind the conv), dense (a DenseBlock conv), block (the DenseBlock's name or None)"""
+    EN, DE = level_channels(ws, num_ch)
+    out = []
+
+    def add(name, cin, cout, f, act, block):
+        out.append({"name": name, "Cin": cin, "Cout": cout, "F": f, "act": act, "dense": block is not None, "block": block})
+
+    for b in range(7):
+        add(f"enc{b}.0", EN[b], EN[b + 1], EN_F[b + 1], b > 0, None)          # encoders.0.0.conv2d has no activation
+        if b < 5:
+            for i in range(5):
+                add(f"enc{b}.db{i + 1}", (i + 1) * EN[b + 1], EN[b + 1], EN_F[b + 1], True, f"enc{b}")
+    for b in range(7):
+        cin = 2 * DE[b]
+        if b >= 2:
+            for i in range(5):
+                add(f"dec{b}.db{i + 1}", cin + i * (cin // 2), cin // 2 if i < 4 else cin, DE_F[b], True, f"dec{b}")
+        add(f"dec{b}.t", cin, DE[b + 1], DE_F[b + 1], b < 6, None)             # the last deconv has none
+    return out
 
 # one conv: state_dict prefix, transposed, frequency stride, frequency padding (plain convs), ELU + instance norm, position in a
 # DenseBlock (None: not in one)

@@ -14,6 +14,8 @@ b. The workspace is ``torch.empty``: filled with 0xFF bytes (NaN as float32, bf1
    the output and every tap are the same bits.
 c. A sample inside a batch equals the same sample run alone, bit for bit at every tap, at the batch sizes that switch the tile
    walk of every conv kernel.
+
+Everything here runs the default channel widths; tests/test_gpu_conv_widths.py holds the same three properties at other widths.
 """
 import numpy as np
 import pytest

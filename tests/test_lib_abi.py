@@ -276,6 +276,102 @@ def test_conv_plan_kernel_per_layer(in_ch, out_ch, mode):
     lib.misonet_net_destroy(h)
 
 
+# kernel launches per kind of one forward at the other width sets of tests/conv_ref.py, as the library reports them
+WIDTH_PLAN = {
+    "narrow_to_wide": {0: {DIRECT: 64}, 5: {W1D: 17, WINO: 35, DIRECT: 12}, 3: {X6_FIRST: 1, X6: 63}},
+    "wide_first": {0: {DIRECT: 64}, 5: {W1D: 16, WINO: 38, DIRECT: 10}, 3: {DIRECT: 1, X6: 63}},
+}
+
+
+def _plan(ws, mode):
+    """(layers of conv_ref.conv_layers, kinds of misonet_net_conv_plan) of MISO_1 at the width set `ws`"""
+    import conv_ref
+    en, de, spks = conv_ref.widths(ws)
+    L, rc, h = _make(in_ch=12, out_ch=2 * spks, en=en, de=de)
+    assert rc == 0
+    kind = (C.c_int * 80)()
+    assert L.lib().misonet_net_conv_plan(h, mode, 80, kind) == 64
+    L.lib().misonet_net_destroy(h)
+    layers = conv_ref.conv_layers(ws)
+    assert len(layers) == 64 and sum(l["dense"] for l in layers) == 50
+    return layers, list(kind[:64])
+
+
+def test_conv_layers_of_the_default_widths():
+    """conv_ref.conv_layers is _conv_layers with the channels added, and its channels are those of the weights"""
+    import conv_ref
+    from misonet_amd import weights as W
+    layers = conv_ref.conv_layers("default")
+    assert [(l["act"], l["dense"]) for l in layers] == _conv_layers()
+    for ws in conv_ref.WIDTH_SETS:
+        en, de, spks = conv_ref.widths(ws)
+        shapes = [s for k, s in W.miso1_spec(num_spks=spks, en_ch=en, de_ch=de).items() if len(s) == 4]
+        got = []
+        for l in conv_ref.conv_layers(ws):
+            got.append((l["Cin"], l["Cout"], 3, 3) if l["name"].endswith(".t") else (l["Cout"], l["Cin"], 3, 3))
+        assert got == shapes, ws
+
+
+@pytest.mark.parametrize("mode", [0, 5, 3])                              # f32, f32w, bf16x6
+@pytest.mark.parametrize("ws", ["narrow_to_wide", "wide_first"])
+def test_conv_plan_kernel_per_layer_at_other_widths(ws, mode):
+    """The selection rules of csrc/conv_select.hpp at channel widths other than the default, layer by layer: what
+    tests/test_gpu_conv_widths.py says about the kernel under a level holds only while these do.
+
+    f32: conv3x3_few only for 2 / 4 output channels without activation (here the last layer has 6 / 8: none), DIRECT otherwise.
+    f32w: a DenseBlock conv is W1D with Cin < 24 (and Cout <= 32), WINO with 24 <= Cin <= 192 and Cout <= 64, DIRECT otherwise;
+    the first layer is W1D up to 32 output channels and DIRECT above; every other activated layer outside the blocks is W1D; the
+    last layer at 6 / 8 channels is DIRECT.  bf16x6: the first layer is X6_FIRST with Cin <= 16 and Cout <= 32 and DIRECT (writing
+    the oct3 layout) otherwise, every other layer X6."""
+    layers, kinds = _plan(ws, mode)
+    assert {k: kinds.count(k) for k in set(kinds)} == WIDTH_PLAN[ws][mode]
+    first, last = layers[0], layers[63]
+    assert not first["act"] and not last["act"] and last["Cout"] in (6, 8) and first["Cin"] == 12
+    for l, k in zip(layers, kinds):
+        if mode == 0:
+            want = FEW if (not l["act"] and l["Cout"] in (2, 4)) else DIRECT
+        elif mode == 3:
+            want = X6 if l is not first else (X6_FIRST if l["Cin"] <= 16 and l["Cout"] <= 32 else DIRECT)
+        elif l["dense"]:
+            want = W1D if (l["Cin"] < 24 and l["Cout"] <= 32) else (WINO if 24 <= l["Cin"] <= 192 and l["Cout"] <= 64 else DIRECT)
+        elif l is first:
+            want = W1D if l["Cout"] <= 32 else DIRECT
+        else:
+            want = W1D if l["act"] else DIRECT
+        assert k == want, (ws, mode, l, k, want)
+
+
+@pytest.mark.parametrize("ws", ["narrow_to_wide", "wide_first"])
+def test_width_sets_reach_the_paths_they_are_there_for(ws):
+    """Each set holds a WINO layer of 16 output channels (the 16-row body alone), an X6 layer with Cout % 32 == 16 in two or more
+    32-channel groups, f32w DenseBlocks whose convs run on two kernels -- W1D + WINO and WINO + DIRECT, writing channel slices of
+    one dense buffer and reading each other's statistics -- and all three kernels among its DenseBlock convs.
+
+    No admitted DenseBlock holds all three: W1D needs fewer than 24 input channels, so a growth of 8 or 16 (an encoder block of
+    that width, a decoder block on 2 x 8 channels), and then the block's widest conv reads 5 x 16 = 80 channels and writes at
+    most 16, far from DIRECT's Cin > 192 or Cout > 64.  The loop below walks every admitted width."""
+    import conv_ref
+    layers, kinds = _plan(ws, 5)
+    assert any(k == WINO and l["Cout"] == 16 for l, k in zip(layers, kinds))
+    blocks = {}
+    for l, k in zip(layers, kinds):
+        if l["dense"]:
+            blocks.setdefault(l["block"], set()).add(k)
+    assert len(blocks) == 10 and all(len(v) <= 2 for v in blocks.values())
+    assert {W1D, WINO} in blocks.values() and {WINO, DIRECT} in blocks.values()
+    assert set().union(*blocks.values()) == {W1D, WINO, DIRECT}
+    layers3, kinds3 = _plan(ws, 3)
+    assert any(k == X6 and l["Cout"] % 32 == 16 and (l["Cout"] + 31) // 32 >= 2 for l, k in zip(layers3, kinds3))
+    # every admitted block: encoder blocks of width g (convs (i + 1) g -> g), decoder blocks on c = 2 g channels (c + i c / 2 -> c / 2, the
+    # last -> c)
+    def kind(cin, cout):
+        return W1D if (cin < 24 and cout <= 32) else (WINO if 24 <= cin <= 192 and cout <= 64 else DIRECT)
+    for g in range(8, 129, 8):
+        enc = {kind((i + 1) * g, g) for i in range(5)}
+        dec = {kind(2 * g + i * g, g if i < 4 else 2 * g) for i in range(5)}
+        assert not ({W1D, DIRECT} <= enc) and not ({W1D, DIRECT} <= dec), g
+
+
 @pytest.mark.parametrize("in_ch", [4, 8, 10, 12, 14, 16, 18, 20])
 def test_first_layer_kernel_at_every_admitted_microphone_count(in_ch):
     """misonet_pipeline_create admits 2-8 microphones: first layers of 4 ... 16 (MISO_1) and 8 ... 20 (MISO_3) input channels.  f32 runs
