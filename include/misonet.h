@@ -341,6 +341,55 @@ int misonet_beamform_joint(const void* src_dev, const void* mix_dev, int B, int 
 int misonet_beamform_joint_debug(const void* ws_dev, int B, int S, int F, int M, const misonet_jbf_opts* opts, void* w_c128_dev,
                                  void* rtf_c128_dev, int* fail_dev, misonet_stream stream);
 
+/* ---- blind separation: AuxIVA (ABI 580) -------------------------------------------------------------------------------------
+ * A front end that needs no weights: auxiliary-function independent vector analysis with iterative source steering (AuxIVA-ISS;
+ * Ono 2011, Scheibler & Ono 2020), inverse-free, behind a per-bin PCA to K channels and projected back to all microphones by
+ * least squares.  Its images have the layout of the source estimates every beamformer above and the cACGMM consume.  This is the
+ * project's own definition in the pyroomacoustics / torchiva family (INTEGRATION.md 4n has it in full; tests/iva_ref.py restates
+ * it in NumPy float64); nothing here was compared against those packages.
+ * mix complex64 [B, F, M, T]; float64 after the loads; every recording b on its own; K = channels (0: K = S):
+ *   0. a bin (b, f) that holds a non-finite sample: fail |= 1, the bin is all zero in every step below, its images are 0
+ *   1. PCA per bin: R = X X^H / T, its eigenvectors by the cyclic complex Jacobi of the beamformers, eigenvalues descending (equal
+ *      ones: the lower index first), each eigenvector rotated so that its ref_ch component is real and >= 0 (left as it is when
+ *      that component is 0); an eigenvalue not above 1e-12 times the largest counts as 0 and its eigenvector (also in the diagnostic
+ *      export) is 0: a bin of lower rank than K -- T < K, dead or identical microphones, a zero bin -- has no such direction, its row
+ *      of Z is 0 in exact arithmetic, and the rounding noise that would stand there is not scaled up to a source;
+ *      Z = E_K^H X [K, T] (no whitening), Y = Z
+ *   2. per iteration, once, from the Y of all bins, the sum over f ascending:
+ *        model 0 "gauss":   phi_k[t] = 1 / max(1 / F sum_f |y_k[f, t]|^2, floor)
+ *        model 1 "laplace": phi_k[t] = 1 / max(2 sqrt(sum_f |y_k[f, t]|^2), floor)
+ *   3. per iteration and bin, for s = 0 .. K - 1 in order, y_s the row as it stands before the step:
+ *        num_k = sum_t phi_k[t] y_k[t] conj(y_s[t]),  den_k = sum_t phi_k[t] |y_s[t]|^2
+ *        k != s: v_k = num_k / den_k (0 when den_k = 0);  d = den_s / T, v_s = 1 - 1 / sqrt(d) (0 when d = 0)
+ *        y_k <- y_k - v_k y_s for all k;  a non-finite v_k is replaced by 0 and the bin gets fail |= 2
+ *   4. after the last iteration: A[f, m, k] = sum_t x_m[t] conj(y_k[t]) / sum_t |y_k[t]|^2 (0 when the denominator is 0),
+ *      power_k = sum_{f, t} |A[f, ref_ch, k] y_k[f, t]|^2, order = the S rows of largest power, descending (ties: the lower
+ *      index), images[b, s, f, m, t] = A[f, m, order_s] y_{order_s}[f, t], rounded once to complex64
+ * iterations = 0: steps 1 and 4 only.  Every sum over t runs in a fixed order, without atomics: the bits of a recording depend
+ * neither on B nor on its position in the batch.  One launch sequence on the stream (3 + 2 iterations kernels), no host
+ * synchronisation, no allocation: it can be captured in a HIP graph.  Up to misonet_auxiva_resident_frames(K) frames a bin's Y stays
+ * in registers through the K source steps of an iteration; beyond that it is walked in the workspace.
+ * 2 <= M <= 8, 1 <= S <= min(M, 4), S <= K <= M, B, F, T >= 1, 0 <= iterations <= 1000, floor finite and > 0, 0 <= ref_ch < M:
+ * anything else is MISONET_EINVAL with a message (the size function: -1) before any launch and before any pointer is looked at; a
+ * short workspace is MISONET_ENOMEM.  The workspace grows with T (it holds Y as complex128 [B, F, K, T]). */
+typedef struct {
+  int iterations;
+  int model;               /* 0 "gauss", 1 "laplace" */
+  int channels;            /* K; 0 = S */
+  int ref_ch;
+  double floor;
+} misonet_iva_opts;
+int misonet_iva_opts_default(misonet_iva_opts* opts);    /* 20, 0, 0, 0, 1e-10 */
+long long misonet_auxiva_workspace_bytes(int B, int S, int K, int F, int M, int T);    /* -1 on bad arguments */
+int misonet_auxiva_resident_frames(int K);
+/* images_out_dev complex64 [B, S, F, M, T]; order_out_dev int32 [B, S] (the chosen rows of Y) or NULL */
+int misonet_auxiva(const void* mix_dev, int B, int S, int F, int M, int T, const misonet_iva_opts* opts, void* images_out_dev,
+                   int* order_out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_auxiva, copy Y complex128 [B, F, K, T], A complex128 [B, F, M, K], the eigenvectors E_K complex128
+ * [B, F, M, K], power float64 [B, K] and fail int32 [B, F] to device buffers (any may be NULL) */
+int misonet_auxiva_debug(const void* ws_dev, int B, int K, int F, int M, int T, void* y_c128_dev, void* a_c128_dev,
+                         void* evec_c128_dev, double* power_dev, int* fail_dev, misonet_stream stream);
+
 /* ---- PIT speaker alignment (tester.py:1043-1065 and 889-915) ----------------------------------------------- */
 /* anchor_dev, cand_dev: complex64 [B, S, T, F]; sel_dev: int32 [B, S] with aligned speaker i = cand[sel[i]];
  * dist_dev (required: it is the call's only scratch, so the call allocates nothing and stays asynchronous): float64,

@@ -55,6 +55,11 @@ class JbfOpts(C.Structure):
                 ("ref_ch", C.c_int)]
 
 
+class IvaOpts(C.Structure):
+    """misonet_iva_opts (ABI 580): model 0 gauss / 1 laplace, channels 0 = the number of sources"""
+    _fields_ = [("iterations", C.c_int), ("model", C.c_int), ("channels", C.c_int), ("ref_ch", C.c_int), ("floor", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/misonet.h
 SIGNATURES = {
     "misonet_strerror": (C.c_char_p, [C.c_int]),
@@ -119,6 +124,13 @@ SIGNATURES = {
     "misonet_beamform_joint_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JbfOpts), C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_pipeline_set_joint": (C.c_int, [C.c_void_p, C.POINTER(JbfOpts)]),
+    "misonet_iva_opts_default": (C.c_int, [C.POINTER(IvaOpts)]),
+    "misonet_auxiva_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "misonet_auxiva_resident_frames": (C.c_int, [C.c_int]),
+    "misonet_auxiva": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(IvaOpts), C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_auxiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

@@ -1,0 +1,241 @@
+"""Blind separation as a weight-free front end (csrc/iva.hip, C ABI ``misonet_auxiva`` in include/misonet.h).
+
+Auxiliary-function independent vector analysis with iterative source steering (AuxIVA-ISS; Ono 2011, Scheibler & Ono 2020)
+behind a per-bin PCA to ``channels`` channels, projected back to all microphones by least squares.  Its images have the shape and
+the meaning of the source estimate that every block behind MISO1 consumes -- the beamformers of :mod:`misonet_amd.beamform`, the
+guided cACGMM of :mod:`misonet_amd.refine`, the writers and the scores -- so that whole back half runs on real recordings
+without a trained network.  This is the project's own definition in the pyroomacoustics / torchiva family; nothing here was
+compared against those packages.
+
+``auxiva(mix, num_spks, ...)``   -- the separation; images complex64 [B, S, F, M, T], optionally the chosen rows and the diagnostics
+``AuxIVA``                       -- the options as plain data
+``BlindSeparator``               -- the recording-level composition: AuxIVA -> (cACGMM) -> beamformer -> iSTFT -> files
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import stft as S
+from .beamform import Beamformer, JointBeamformer, _dev_c64
+
+MODELS = ("gauss", "laplace")                # the source models of misonet_iva_opts, in its numbering
+MAX_ITERATIONS = 1000
+
+
+@dataclasses.dataclass(frozen=True)
+class AuxIVA:
+    """One plain-data description of the separation (``misonet_iva_opts`` of include/misonet.h).
+
+    iterations   sweeps over the sources (weights once, then every source steered once); 0 returns the PCA projection's images
+    model        "gauss": time-varying Gaussian, phi = 1 / max(mean_f |y|^2, floor); "laplace": phi = 1 / max(2 sqrt(sum_f |y|^2),
+                 floor), the textbook model
+    channels     K, the channels kept by the per-bin PCA, S <= K <= M; None = the number of sources
+    floor        the floor under the weights' denominators (> 0)
+    ref_ch       the microphone the eigenvectors' phase and the sources' power are taken at
+    """
+    iterations: int = 20
+    model: str = "gauss"
+    channels: Optional[int] = None
+    floor: float = 1e-10
+    ref_ch: int = 0
+
+    @classmethod
+    def of(cls, spec) -> "AuxIVA":
+        """None or True (the defaults), an AuxIVA, a model name, or a dict of the fields above"""
+        if spec is None or spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            return cls(model=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown blind field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("blind must be None, True, an AuxIVA, a model name or a dict of its fields")
+
+    def validate(self, num_mic=None, num_spks=None) -> "AuxIVA":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        def integer(v):
+            return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+        if not integer(self.iterations) or not 0 <= self.iterations <= MAX_ITERATIONS:
+            raise ValueError(f"blind iterations must be an integer in [0, {MAX_ITERATIONS}], got {self.iterations!r}")
+        if self.model not in MODELS:
+            raise ValueError(f"blind model {self.model!r}: one of {MODELS}")
+        v = self.floor
+        if isinstance(v, bool) or not (isinstance(v, (int, float)) and math.isfinite(v) and v > 0):
+            raise ValueError(f"blind floor must be finite and > 0, got {v!r}")
+        if self.channels is not None and (not integer(self.channels) or self.channels < 1):
+            raise ValueError(f"blind channels must be None or a positive integer, got {self.channels!r}")
+        if not integer(self.ref_ch) or self.ref_ch < 0:
+            raise ValueError(f"blind ref_ch must be a non-negative integer, got {self.ref_ch!r}")
+        if num_mic is not None:
+            if not 2 <= num_mic <= 8:
+                raise ValueError(f"blind separation needs 2 <= M <= 8 microphones, got {num_mic}")
+            if self.ref_ch >= num_mic:
+                raise ValueError(f"blind ref_ch {self.ref_ch} outside [0, {num_mic})")
+        if num_spks is not None:
+            if not 1 <= num_spks <= 4 or (num_mic is not None and num_spks > num_mic):
+                raise ValueError(f"blind separation needs 1 <= S <= min(M, 4) sources, got {num_spks}")
+            if self.channels is not None and not num_spks <= self.channels <= (8 if num_mic is None else num_mic):
+                raise ValueError(f"blind channels must lie in [S, M], got {self.channels}")
+        return self
+
+    def num_channels(self, num_spks) -> int:
+        return int(num_spks if self.channels is None else self.channels)
+
+    def c_opts(self) -> "_lib.IvaOpts":
+        return _lib.IvaOpts(int(self.iterations), MODELS.index(self.model), int(self.channels or 0), int(self.ref_ch),
+                            float(self.floor))
+
+
+def resident_frames(channels: int) -> int:
+    """the largest T at which the steering kernel keeps a bin's Y in registers (``misonet_auxiva_resident_frames``)"""
+    return int(_lib.lib().misonet_auxiva_resident_frames(int(channels)))
+
+
+def auxiva(mix, num_spks, iterations=20, model="gauss", channels=None, floor=1e-10, ref_ch=0, device=None, return_order=False,
+           return_debug=False, *, blind=None):
+    """AuxIVA-ISS.  mix complex [B, F, M, T] (the beamformers' layout) -> the source images complex64 [B, S, F, M, T]:
+    ``images[:, s]`` is a ``source_stft`` of ``Apply_Beamforming``, the whole tensor the ``est`` of ``Apply_Beamforming_Joint``
+    and of ``masks_from_estimates``.  With ``return_order`` also the chosen rows int32 [B, S]; with ``return_debug`` also a dict
+    of device tensors: ``Y`` complex128 [B, F, K, T], ``A`` and ``evec`` complex128 [B, F, M, K], ``power`` float64 [B, K] and
+    ``fail`` int32 [B, F] (bit 0: a non-finite input sample, the bin was taken as zero; bit 1: a non-finite step was dropped).
+    The results are on the CPU when ``mix`` was an ndarray, on the device otherwise.  The options are the fields of
+    :class:`AuxIVA` (``blind``: a whole AuxIVA or dict, which wins)."""
+    opt = (AuxIVA(iterations=iterations, model=model, channels=channels, floor=floor, ref_ch=ref_ch) if blind is None
+           else AuxIVA.of(blind))
+    if np.ndim(mix) != 4:
+        raise ValueError(f"mix {tuple(np.shape(mix))} must be [B, F, M, T]")
+    B, F, M, T = np.shape(mix)
+    Sn = num_spks
+    if isinstance(Sn, bool) or not isinstance(Sn, (int, np.integer)):
+        raise ValueError(f"num_spks must be an integer, got {Sn!r}")
+    Sn = int(Sn)
+    opt.validate(M, Sn)                                                      # before any copy or launch
+    if T < 1 or B < 1 or F < 1:
+        raise ValueError("B, F and T must be positive")
+    K = opt.num_channels(Sn)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    y, np_in = _dev_c64(mix, device)
+    L = _lib.lib()
+    opts = opt.c_opts()
+    nws = L.misonet_auxiva_workspace_bytes(B, Sn, K, F, M, T)
+    if nws < 0:
+        _lib.check(_lib.EINVAL)
+    ws = torch.empty(max(int(nws), 8), dtype=torch.uint8, device=y.device)
+    images = torch.empty((B, Sn, F, M, T), dtype=torch.complex64, device=y.device)
+    order = torch.empty((B, Sn), dtype=torch.int32, device=y.device) if return_order else None
+    dbg = None
+    with torch.cuda.device(y.device):
+        st = _lib.stream_ptr(y.device)
+        _lib.check(L.misonet_auxiva(y.data_ptr(), B, Sn, F, M, T, C.byref(opts), images.data_ptr(),
+                                    order.data_ptr() if return_order else None, ws.data_ptr(), ws.numel(), st))
+        if return_debug:
+            dbg = dict(Y=torch.empty((B, F, K, T), dtype=torch.complex128, device=y.device),
+                       A=torch.empty((B, F, M, K), dtype=torch.complex128, device=y.device),
+                       evec=torch.empty((B, F, M, K), dtype=torch.complex128, device=y.device),
+                       power=torch.empty((B, K), dtype=torch.float64, device=y.device),
+                       fail=torch.empty((B, F), dtype=torch.int32, device=y.device))
+            _lib.check(L.misonet_auxiva_debug(ws.data_ptr(), B, K, F, M, T, dbg["Y"].data_ptr(), dbg["A"].data_ptr(),
+                                              dbg["evec"].data_ptr(), dbg["power"].data_ptr(), dbg["fail"].data_ptr(), st))
+    if np_in:
+        images = images.cpu()
+        order = order.cpu() if order is not None else None
+    res = [images] + ([order] if return_order else []) + ([dbg] if return_debug else [])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+class BlindSeparator:
+    """The recording-level composition behind a blind front end: AuxIVA -> (guided cACGMM) -> beamformer -> iSTFT -> files.  It
+    uses no networks and no pipeline handle; every stage is the drop-in entry point of its module.
+
+    ``blind``: None (the defaults), an :class:`AuxIVA`, a model name or a dict of its fields (its ``ref_ch`` is replaced by this
+    object's); ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer`, a kind name or a dict of
+    its fields, or a :class:`misonet_amd.beamform.JointBeamformer` instance; ``refine``: None (off), True, a
+    :class:`misonet_amd.refine.Refine`, a prior name or a dict of its fields."""
+
+    def __init__(self, num_spks: int = 2, num_ch: int = 6, ref_ch: int = 0, blind=None, beamformer=None, refine=None,
+                 device=None):
+        from .pipeline import Enhancer
+        from .refine import Refine
+        self.num_spks, self.num_ch, self.ref_ch = int(num_spks), int(num_ch), int(ref_ch)
+        self.blind = dataclasses.replace(AuxIVA.of(blind), ref_ch=self.ref_ch).validate(self.num_ch, self.num_spks)
+        if isinstance(beamformer, JointBeamformer):
+            self.beamformer = beamformer.validate(self.num_ch, self.num_spks)
+        else:
+            self.beamformer = Beamformer.of(beamformer).validate(self.num_ch)
+        self.refine = None if refine is None or refine is False else Refine.of(refine).validate(self.num_ch, self.num_spks)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # the microphone selection and the writers of the recording paths, as they are (pipeline.py): they read num_ch,
+        # num_spks, ref_ch and device of the object they are called on and nothing else
+        self._select_mics = Enhancer._select_mics.__get__(self)
+        self._write_speakers = Enhancer._write_speakers.__get__(self)
+        self._srmr_of = Enhancer._srmr_of.__get__(self)
+
+    def _images(self, mix_bf):
+        """mix complex64 [B, F, M, T] on the device -> images complex64 [B, S, F, M, T]"""
+        return auxiva(mix_bf, self.num_spks, blind=self.blind)
+
+    def _beamform(self, est, mix_bf):
+        """est [B, S, F, M, T], mix [B, F, M, T] -> [B, S, T, F]: the optional clustering, then the beamformer"""
+        from .beamform import Apply_Beamforming, Apply_Beamforming_Joint
+        from .refine import refined_images
+        if self.refine is not None:
+            est = refined_images(est, mix_bf, self.refine)
+        if isinstance(self.beamformer, JointBeamformer):                     # one joint solve for all speakers
+            return Apply_Beamforming_Joint(est, mix_bf, self.beamformer)
+        return torch.stack([Apply_Beamforming(est[:, s], mix_bf, beamformer=self.beamformer)
+                            for s in range(self.num_spks)], dim=1)
+
+    def _mix(self, mix):
+        if not isinstance(mix, torch.Tensor) or mix.dim() != 4 or not mix.is_complex():
+            raise ValueError("mix must be a 4-D complex tensor [B, M, T, F]")
+        if mix.shape[1] != self.num_ch:
+            raise ValueError(f"expected {self.num_ch} microphones, got {mix.shape[1]}")
+        return mix.to(self.device).to(torch.complex64).permute(0, 3, 1, 2).contiguous()          # [B, F, M, T]
+
+    def separate(self, mix: torch.Tensor) -> torch.Tensor:
+        """mix complex [B, M, T, F] -> the source images complex64 [B, S, M, T, F], the layout of ``Enhancer.separate``"""
+        return self._images(self._mix(mix)).permute(0, 1, 3, 4, 2)
+
+    def beamform_chunks(self, mix: torch.Tensor) -> torch.Tensor:
+        """mix complex [B, M, T, F] -> beamformer outputs complex64 [B, S, T, F]: the composition of
+        ``Enhancer.beamform_chunks`` with AuxIVA in the place of MISO1 (every item of the batch separated on its own)"""
+        mix_bf = self._mix(mix)
+        return self._beamform(self._images(mix_bf), mix_bf)
+
+    def separate_recording(self, wav, num_ch_utilize: Optional[int] = None, save_path: Optional[str] = None, fs: int = 16000,
+                           beamform: bool = True, srmr: bool = False):
+        """Recording in -> separated int16 waves out.  wav float32 [L, M_all] (time-major, as ``read_wav`` returns it) ->
+        int16 [S, L] (an ndarray).  The microphone selection of ``Enhancer.enhance_recording`` (``[0:M:M // num_ch_utilize]``),
+        ONE STFT over the recording zero-padded to whole hops, ONE AuxIVA over all its frames, then the optional clustering
+        and the beamformer -- or, with ``beamform=False``, the image at ``ref_ch`` -- the iSTFT, x 32767 -> int16, trimmed to
+        ``L``.  ``save_path`` = "<dir>/<name>" also writes ``<save_path>_{s}.wav`` as 24-bit PCM, the files
+        ``tools/score_eval.py`` reads.  ``srmr=True`` returns ``(pcm, Srmr)``, as ``enhance_recording``."""
+        if srmr:
+            from . import score as SC
+            SC.check_srmr_fs(fs)
+        mics, obs = self._select_mics(wav, num_ch_utilize)
+        L = obs.shape[0]
+        sig = torch.from_numpy(np.ascontiguousarray(obs[:, mics])).to(self.device)               # [L, M]
+        sig = torch.nn.functional.pad(sig, (0, 0, 0, (-L) % S.HOP))[None].contiguous()           # [1, Lp, M]
+        mix_bf = S.stft_hip(sig)[0].permute(2, 0, 1)[None].contiguous()                          # [1, F, M, Tt]
+        est = self._images(mix_bf)                                                               # [1, S, F, M, Tt]
+        if beamform:
+            out = self._beamform(est, mix_bf)[0]                                                 # [S, Tt, F]
+        else:
+            out = est[0, :, :, self.ref_ch, :].permute(0, 2, 1)
+        pcm = np.ascontiguousarray(S.istft_int16(out.contiguous())[:, :L].cpu().numpy())
+        if save_path is not None:
+            self._write_speakers(pcm, save_path, fs)
+        return (pcm, self._srmr_of(pcm, wav, num_ch_utilize, fs)) if srmr else pcm

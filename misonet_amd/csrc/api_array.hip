@@ -1,6 +1,7 @@
 // C ABI of the array processing (include/misonet.h): the drop-in beamformers misonet_mvdr* / misonet_bf_* / misonet_beamform*
 // (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), the WPD beamformer misonet_wpd* (wpd.hip), guided spatial clustering
-// misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), blind
+// separation misonet_auxiva* (iva.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
@@ -380,6 +381,67 @@ int misonet_beamform_joint_debug(const void* ws, int B, int S, int F, int M, con
   if (rtf && opts->kind != JBF_LCMV) return fail(MISONET_EINVAL, "the relative transfer functions exist for kind lcmv only");
   if (!ws) return fail(MISONET_EINVAL, "null argument");
   HIPCHK(launch_jbf_debug(ws, B, S, F, M, opts->kind, w, rtf, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- blind separation, AuxIVA-ISS (ABI 580) ---------------------------------------------------------------------------
+int misonet_iva_opts_default(misonet_iva_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->iterations = 20; o->model = 0; o->channels = 0; o->ref_ch = 0; o->floor = 1e-10;
+  return MISONET_OK;
+}
+
+// the geometry; K = the channels after the PCA (already resolved: never 0 here)
+static int iva_geometry(int B, int S, int K, int F, int M, int T) {
+  if (B <= 0 || F <= 0 || T <= 0) return fail(MISONET_EINVAL, "B, F and T must be positive (got %d, %d, %d)", B, F, T);
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (S < 1 || S > 4 || S > M) return fail(MISONET_EINVAL, "S must be in [1, min(M, 4)] (got S %d, M %d)", S, M);
+  if (K < S || K > M) return fail(MISONET_EINVAL, "channels must be in [S, M] = [%d, %d] (got %d)", S, M, K);
+  if ((long long)B * F > 0x7fffffffLL || (long long)B * K > 0x7fffffffLL || T > 65535 * 256)
+    return fail(MISONET_EINVAL, "B F, B channels and T / 256 must fit a launch grid (got B %d, F %d, T %d)", B, F, T);
+  return MISONET_OK;
+}
+
+static int iva_opts_check(const misonet_iva_opts* o, int S, int M) {
+  if (!o) return fail(MISONET_EINVAL, "null separation options");
+  if (o->iterations < 0 || o->iterations > 1000)
+    return fail(MISONET_EINVAL, "iterations must be in [0, 1000] (got %d)", o->iterations);
+  if (o->model != 0 && o->model != 1) return fail(MISONET_EINVAL, "model %d: 0 gauss, 1 laplace", o->model);
+  if (o->channels != 0 && (o->channels < S || o->channels > M))
+    return fail(MISONET_EINVAL, "channels must be 0 (= S) or in [S, M] = [%d, %d] (got %d)", S, M, o->channels);
+  if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "separation ref_ch %d outside [0, %d)", o->ref_ch, M);
+  if (!(o->floor > 0.0) || !std::isfinite(o->floor)) return fail(MISONET_EINVAL, "floor must be finite and > 0 (got %g)", o->floor);
+  return MISONET_OK;
+}
+
+long long misonet_auxiva_workspace_bytes(int B, int S, int K, int F, int M, int T) {
+  if (iva_geometry(B, S, K, F, M, T)) return -1;
+  return iva_ws_bytes(B, K, F, M, T);
+}
+
+int misonet_auxiva_resident_frames(int K) { return iva_resident_frames(K); }
+
+int misonet_auxiva(const void* mix, int B, int S, int F, int M, int T, const misonet_iva_opts* opts, void* images_out,
+                   int* order_out, void* ws, long long ws_bytes, misonet_stream stream) {
+  { int r = iva_geometry(B, S, S, F, M, T); if (r) return r; }
+  { int r = iva_opts_check(opts, S, M); if (r) return r; }
+  const int K = opts->channels ? opts->channels : S;
+  { int r = iva_geometry(B, S, K, F, M, T); if (r) return r; }
+  if (!mix || !images_out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (ws_bytes < iva_ws_bytes(B, K, F, M, T)) return fail(MISONET_ENOMEM, "workspace too small");
+  IvaArgs a;
+  a.mix = mix; a.images = images_out; a.order_out = order_out;
+  a.B = B; a.S = S; a.K = K; a.F = F; a.M = M; a.T = T;
+  a.iters = opts->iterations; a.laplace = opts->model; a.ref = opts->ref_ch; a.floor = opts->floor;
+  HIPCHK(launch_auxiva(a, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_auxiva_debug(const void* ws, int B, int K, int F, int M, int T, void* y, void* a, void* evec, double* power,
+                         int* fail_dev, misonet_stream stream) {
+  { int r = iva_geometry(B, 1, K, F, M, T); if (r) return r; }
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_auxiva_debug(ws, B, K, F, M, T, y, a, evec, power, fail_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

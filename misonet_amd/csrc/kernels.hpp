@@ -417,6 +417,25 @@ long long jbf_ws_bytes(int B, int S, int F, int M, int kind);
 hipError_t launch_jbf(const JbfArgs& a, const COut& out, void* ws, hipStream_t s);
 hipError_t launch_jbf_debug(const void* ws, int B, int S, int F, int M, int kind, void* w, void* d, int* fail, hipStream_t s);
 
+// Blind separation (iva.hip): AuxIVA-ISS behind a per-bin PCA to K channels, projected back to the M
+// microphones.  mix complex64 [B][F][M][T], images complex64 [B][S][F][M][T], order_out int [B][S] or nullptr.  The workspace
+// holds fail int [B F], the eigenvectors and the projection complex128 [B F][M][K], power double [B][K], the chosen rows, phi
+// double [B][K][T] and Y complex128 [B F][K][T], which launch_auxiva_debug copies out.  2 <= M <= 8, 1 <= S <= min(K, 4),
+// K <= M, T >= 1, iters >= 0, 0 <= ref < M: the caller checks them.
+struct IvaArgs {
+  const void* mix;
+  void* images;
+  int* order_out;
+  int B, S, K, F, M, T;
+  int iters, laplace, ref;
+  double floor;
+};
+long long iva_ws_bytes(int B, int K, int F, int M, int T);
+int iva_resident_frames(int K);                    // the largest T the steering kernel keeps in registers
+hipError_t launch_auxiva(const IvaArgs& a, void* ws, hipStream_t s);
+hipError_t launch_auxiva_debug(const void* ws, int B, int K, int F, int M, int T, void* y, void* a, void* evec, double* power,
+                               int* fail, hipStream_t s);
+
 // source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs,
 // MaskArgs or JbfArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
 template <typename Args>
