@@ -526,6 +526,42 @@ int misonet_stoi_resample(const void* est_dev, int est_is_i16, long long est_sb,
 int misonet_stoi_measure(const double* x10_dev, const int* len10_dev, int B, int NS, int R, long long n10, double* out_dev,
                          int* frames_dev, void* scratch_dev, long long scratch_bytes, misonet_stream stream);
 
+/* ---- polyphase resampler: recordings at any sample rate (ABI 590) ------------------------------------------------------- */
+/* scipy.signal.resample_poly's definition (= librosa's res_type="polyphase"; NOT librosa's default "soxr_hq", which was not
+ * available and was not compared), restated (INTEGRATION.md 4o in full; tests/resample_ref.py restates it in NumPy).  With
+ * p / q = fs_out / fs_in in lowest terms:
+ *   Lh = 10 max(p, q);  h = firwin(2 Lh + 1, 1 / max(p, q), window = ("kaiser", 5.0));  g = p h
+ *   y[m] = sum_j x[j] g[m q - j p + Lh],  j ascending over 0 <= j < n with the tap index inside [0, 2 Lh],  0 <= m < n_out
+ *   n_out = ceil(n p / q);  zeros outside the signal (padtype "constant");  every channel on its own
+ * p = q = 1 has Lh = 0 and g = {1}: an exact copy (or an exact conversion between the sample kinds below).  Admitted:
+ * 1 <= max(p, q) <= 1024 (8 / 16 / 22.05 / 32 / 44.1 / 48 / 96 kHz against each other), 1 <= n <= 2^28 per channel, 1 <= M <= 16
+ * channels, 1 <= B <= 65535 items; every index is 64-bit.  The taps are built on the host in float64 and kept on the device, one
+ * table per (device, p, q), built at the first use there (one allocation and one synchronous copy); after that the call is
+ * asynchronous on the stream, allocates nothing and can be captured in a HIP graph.  The sum is float64 in the order above and is
+ * rounded once; no atomics: bit-reproducible, independent of B and of the item's position in the batch.  A non-finite input
+ * sample reaches exactly the outputs whose support (tap index inside [0, 2 Lh]) contains it.
+ * Sample kinds: 0 float32, 1 int16.  An int16 input sample q stands for q / 32767, scaled once after the sum (the int16 rule of
+ * misonet_score_wave); an int16 output is the float64 result x 32767 rounded to nearest (ties to even) and saturated to
+ * [-32768, 32767] (a NaN gives 0).  NOTE: the iSTFT's int16 store truncates toward zero, as the reference's astype(int16) does;
+ * a resampler's output has no reference to follow and rounds.
+ * Views: source element (item b, channel c, sample j) at src_dev[b * src_sb + c * src_sc + j * src_st], in elements of its kind;
+ * the destination likewise with n_out samples.  Time-major [n][M] (a wav file) and channel-major [M][n] are both read with
+ * coalesced loads; any other strides work.  n_valid_dev int32 [B] or NULL: item b's own length (clamped to [0, n]); its outputs
+ * past ceil(n_valid p / q) are written as zeros, so every element of the destination view is written.
+ * misonet_resample_ratio: p and q (either pointer may be NULL).  misonet_resampled_len: n_out.  misonet_resample_taps: the
+ * number of taps 2 Lh + 1 and, where out_host is not NULL, g itself (cap = its capacity in doubles); host only, needs no GPU.
+ * misonet_resample_tile: the output samples one workgroup owns (256), for tests that probe the tile edges.
+ * MISONET_EINVAL (the size functions: -1), before any launch and before any pointer is looked at: a rate < 1, max(p, q) > 1024, n
+ * outside 1..2^28, a kind other than 0 / 1, B or M outside their ranges, a negative source stride or src_st < 1, a destination
+ * stride < 1 along an axis longer than 1, cap too small; then a null pointer. */
+int misonet_resample_ratio(int fs_in, int fs_out, int* p, int* q);
+long long misonet_resampled_len(long long n, int fs_in, int fs_out);
+int misonet_resample_taps(int fs_in, int fs_out, double* out_host, int cap);
+int misonet_resample_tile(void);
+int misonet_resample(const void* src_dev, int src_kind, long long src_sb, long long src_sc, long long src_st, int B, int M,
+                     long long n, const int* n_valid_dev, int fs_in, int fs_out, void* dst_dev, int dst_kind, long long dst_sb,
+                     long long dst_sc, long long dst_st, misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

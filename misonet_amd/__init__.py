@@ -9,13 +9,16 @@ Host-side mirror of the reference call surface:
   dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
+  resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
+                             definition, in front of and behind every recording path)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
 library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
-           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "Enhancer", "weights"]
+           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "resample", "resampled_len",
+           "load_wav", "Enhancer", "weights"]
 
 
 def __getattr__(name):
@@ -40,6 +43,9 @@ def __getattr__(name):
     if name in ("AuxIVA", "auxiva", "BlindSeparator"):
         import importlib
         return getattr(importlib.import_module(".blind", __name__), name)
+    if name in ("resample", "resampled_len", "load_wav"):
+        import importlib
+        return getattr(importlib.import_module(".resample", __name__), name)
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

@@ -161,6 +161,13 @@ SIGNATURES = {
                                         C.c_void_p]),
     "misonet_stoi_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_resample_ratio": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "misonet_resampled_len": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "misonet_resample_taps": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]),
+    "misonet_resample_tile": (C.c_int, []),
+    "misonet_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_longlong,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong,
+                                   C.c_void_p]),
     "misonet_reverb_frames": (C.c_longlong, [C.c_longlong, C.c_int]),
     "misonet_reverb_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
     "misonet_reverb_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p,

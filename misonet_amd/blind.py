@@ -215,13 +215,23 @@ class BlindSeparator:
         return self._beamform(self._images(mix_bf), mix_bf)
 
     def separate_recording(self, wav, num_ch_utilize: Optional[int] = None, save_path: Optional[str] = None, fs: int = 16000,
-                           beamform: bool = True, srmr: bool = False):
+                           beamform: bool = True, srmr: bool = False, fs_in=None, fs_out=None):
         """Recording in -> separated int16 waves out.  wav float32 [L, M_all] (time-major, as ``read_wav`` returns it) ->
         int16 [S, L] (an ndarray).  The microphone selection of ``Enhancer.enhance_recording`` (``[0:M:M // num_ch_utilize]``),
         ONE STFT over the recording zero-padded to whole hops, ONE AuxIVA over all its frames, then the optional clustering
         and the beamformer -- or, with ``beamform=False``, the image at ``ref_ch`` -- the iSTFT, x 32767 -> int16, trimmed to
         ``L``.  ``save_path`` = "<dir>/<name>" also writes ``<save_path>_{s}.wav`` as 24-bit PCM, the files
-        ``tools/score_eval.py`` reads.  ``srmr=True`` returns ``(pcm, Srmr)``, as ``enhance_recording``."""
+        ``tools/score_eval.py`` reads.  ``srmr=True`` returns ``(pcm, Srmr)``, as ``enhance_recording``.  ``fs_in`` / ``fs_out``: a
+        recording at another rate than the separation's ``fs``, as ``enhance_recording`` takes them; both
+        None adds nothing to the call."""
+        if fs_in is not None or fs_out is not None:
+            from . import resample as RS
+            RS.plan_rates(fs, fs_in, fs_out)                                 # a bad rate: before anything else
+            if srmr:
+                from . import score as SC
+                SC.check_srmr_fs(fs)
+            return RS.around(lambda w, _c, path: self.separate_recording(w, num_ch_utilize, path, fs, beamform, srmr),
+                             wav, None, fs, fs_in, fs_out, save_path, self._write_speakers, self.device)
         if srmr:
             from . import score as SC
             SC.check_srmr_fs(fs)

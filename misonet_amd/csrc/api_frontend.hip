@@ -1,6 +1,10 @@
 // C ABI of the STFT front-end (include/misonet.h): misonet_stft*, misonet_istft, misonet_frontend_init, and the twiddle tables of
-// stft.hip on every device that uses them.  Host code only.
+// stft.hip on every device that uses them; the resampler in front of it, misonet_resample* (resample.hip), and its tap tables.
+// Host code only.
 #include "api_common.hpp"
+
+#include <map>
+#include <tuple>
 
 using namespace mn;
 
@@ -31,7 +35,83 @@ int mn::get_twiddles(const float** out) {
   return frontend_tables(out, &itw);
 }
 
+// ---- the resampler's taps: one table per (device, p, q), built at the first use there and kept ------------------------------
+static std::mutex g_rs_mu;
+static std::map<std::tuple<int, int, int>, double*> g_rs_taps;
+static int resample_table(int p, int q, const double** out) {
+  const std::tuple<int, int, int> key(cur_dev(), p, q);
+  std::lock_guard<std::mutex> lk(g_rs_mu);
+  auto it = g_rs_taps.find(key);
+  if (it == g_rs_taps.end()) {
+    std::vector<double> t((size_t)(2 * resample_half_len(p, q) + 1));
+    resample_build_taps(p, q, t.data());
+    double* d = nullptr;
+    if (const int rc = dev_upload(t, &d)) return rc;
+    it = g_rs_taps.emplace(key, d).first;
+  }
+  *out = it->second;
+  return MISONET_OK;
+}
+static int resample_rates(int fs_in, int fs_out, int* p, int* q) {
+  if (!resample_ratio(fs_in, fs_out, p, q))
+    return fail(MISONET_EINVAL, "fs_in and fs_out must be positive with max(p, q) <= %d for p / q = fs_out / fs_in in lowest "
+                "terms (got %d -> %d)", RS_MAX_RATE, fs_in, fs_out);
+  return MISONET_OK;
+}
+constexpr long long RS_MAX_N = 1LL << 28;
+
 extern "C" {
+
+// ---- polyphase resampler (resample.hip) --------------------------------------------------------------------------------------
+int misonet_resample_ratio(int fs_in, int fs_out, int* p, int* q) {
+  int pp, qq;
+  if (const int rc = resample_rates(fs_in, fs_out, &pp, &qq)) return rc;
+  if (p) *p = pp;
+  if (q) *q = qq;
+  return MISONET_OK;
+}
+
+long long misonet_resampled_len(long long n, int fs_in, int fs_out) {
+  int p, q;
+  if (n < 1 || n > RS_MAX_N || !resample_ratio(fs_in, fs_out, &p, &q)) return -1;
+  return resample_len(n, p, q);
+}
+
+int misonet_resample_tile(void) { return resample_tile(); }
+
+int misonet_resample_taps(int fs_in, int fs_out, double* out, int cap) {
+  int p, q;
+  if (const int rc = resample_rates(fs_in, fs_out, &p, &q)) return rc;
+  const int nt = 2 * resample_half_len(p, q) + 1;
+  if (out) {
+    if (cap < nt) return fail(MISONET_EINVAL, "cap %d < %d taps", cap, nt);
+    resample_build_taps(p, q, out);
+  }
+  return nt;
+}
+
+int misonet_resample(const void* src_dev, int src_kind, long long src_sb, long long src_sc, long long src_st, int B, int M,
+                     long long n, const int* n_valid_dev, int fs_in, int fs_out, void* dst_dev, int dst_kind, long long dst_sb,
+                     long long dst_sc, long long dst_st, misonet_stream stream) {
+  int p, q;
+  if (const int rc = resample_rates(fs_in, fs_out, &p, &q)) return rc;
+  if ((src_kind != 0 && src_kind != 1) || (dst_kind != 0 && dst_kind != 1))
+    return fail(MISONET_EINVAL, "src_kind and dst_kind must be 0 (float32) or 1 (int16) (got %d, %d)", src_kind, dst_kind);
+  if (B < 1 || B > 65535) return fail(MISONET_EINVAL, "B must be in [1, 65535] (got %d)", B);
+  if (M < 1 || M > RS_MAX_CH) return fail(MISONET_EINVAL, "M must be in [1, %d] (got %d)", RS_MAX_CH, M);
+  if (n < 1 || n > RS_MAX_N) return fail(MISONET_EINVAL, "n must be in [1, 2^28] (got %lld)", n);
+  if (src_sb < 0 || src_sc < 0 || src_st < 1)
+    return fail(MISONET_EINVAL, "source strides must not be negative and the sample stride must be positive");
+  if (dst_st < 1 || (M > 1 && dst_sc < 1) || (B > 1 && dst_sb < 1) || dst_sc < 0 || dst_sb < 0)
+    return fail(MISONET_EINVAL, "destination strides must be positive along every axis longer than 1");
+  if (!src_dev || !dst_dev) return fail(MISONET_EINVAL, "null argument");
+  const double* taps;
+  if (const int rc = resample_table(p, q, &taps)) return rc;
+  const long long ss[3] = {src_sb, src_sc, src_st}, ds[3] = {dst_sb, dst_sc, dst_st};
+  HIPCHK(launch_resample(src_dev, src_kind, ss, B, M, n, n_valid_dev, p, q, taps, dst_dev, dst_kind, ds,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
 
 // misonet_net_commit and misonet_pipeline_create call it, so every path that runs a network has the tables before its first
 // asynchronous call -- a HIP graph may capture misonet_pipeline_run_wav / misonet_istft as the first call of a process.  A

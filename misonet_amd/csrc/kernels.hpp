@@ -297,6 +297,22 @@ hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long
 hipError_t launch_stoi_measure(const double* x10, const int* len10 /*[B] or nullptr*/, int B, int NS, int R, long long n10,
                                const double* table, double* out, int* meta, double* scratch, hipStream_t s);
 
+// Polyphase resampler for any rational rate (resample.hip): scipy.signal.resample_poly's definition, p / q =
+// fs_out / fs_in in lowest terms with max(p, q) <= RS_MAX_RATE.  The taps g[0 .. 2 Lh] of one (p, q) are built on the host
+// (resample_build_taps) and kept on the device by the caller.  src float32 or int16, element (b, c, j) at b ss[0] + c ss[1] +
+// j ss[2]; dst float32 or int16 likewise through ds; y[m] = sum_j x[j] g[m q - j p + Lh], j ascending, in float64, rounded once;
+// outputs past ceil(n_valid[b] p / q) are zeros.  1 <= M <= RS_MAX_CH, 1 <= B <= 65535: the caller checks them.
+constexpr int RS_MAX_RATE = 1024;
+constexpr int RS_MAX_CH = 16;
+bool resample_ratio(long long fs_in, long long fs_out, int* p, int* q);   // false: a rate < 1 or max(p, q) > RS_MAX_RATE
+int resample_half_len(int p, int q);                                      // Lh: 10 max(p, q), 0 for 1 / 1
+long long resample_len(long long n, int p, int q);                        // ceil(n p / q)
+void resample_build_taps(int p, int q, double* g /*[2 Lh + 1]*/);
+int resample_tile();                                                      // output samples per workgroup
+hipError_t launch_resample(const void* src, int src_i16, const long long* ss, int B, int M, long long n,
+                           const int* n_valid /*[B] or nullptr*/, int p, int q, const double* taps, void* dst, int dst_i16,
+                           const long long* ds, hipStream_t s);
+
 // Cepstral distance, LLR and fwSegSNR (reverb.hip).  The table (reverb_table_count() doubles, built on the
 // host): the twiddles of the 512-point transform and, per rate, the window, the 23 mel triangles and their bin ranges.  One call
 // reads the strided views of launch_score_wave (ms as for launch_stoi_resample) and writes out [B][E (+ 1)][R][6], count

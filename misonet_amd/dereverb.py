@@ -130,7 +130,7 @@ def dereverb(mix, power=None, *, taps=10, delay=3, iterations=3, diag_load=0.0, 
     return (out, dbg) if return_debug else out
 
 
-def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, **opts):
+def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None, fs_out=None, **opts):
     """Recording-wise dereverberation: wav float32 [L, M] (ndarray or tensor) -> float32 [L, M] of the same kind.
 
     The recording is zero-padded to whole hops, transformed in one piece (``misonet_stft``), dereverberated
@@ -141,7 +141,36 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, **opts):
     ``srmr=True``: returns ``(wav, Srmr)``: the speech-to-reverberation modulation energy ratio (the figure
     that needs no clean reference) of output channel ``ref_ch`` at rate ``fs`` (8000 or 16000), with input channel ``ref_ch``
     as the mixture, so that ``srmr_i`` is what the dereverberation gained.  Both are read on the device, in place, as
-    time-major views; the waves are bit for bit those of ``srmr=False``."""
+    time-major views; the waves are bit for bit those of ``srmr=False``.
+
+    ``fs_in`` / ``fs_out``: ``fs`` is the rate the dereverberation runs at.  ``fs_in`` other than ``fs``: ``wav``
+    is at ``fs_in`` and is taken to ``fs`` on the device first (:mod:`misonet_amd.resample`); ``fs_out`` (an integer rate or ``"in"``):
+    the float32 result is taken to that rate on the device, and has the input's length L when that is the input's rate.  The SRMR
+    is measured at ``fs``.  With both None not one launch is added."""
+    if fs_in is not None or fs_out is not None:
+        from . import resample as RS
+        r_in, r_out, _ = RS.plan_rates(fs, fs_in, fs_out)                  # a bad rate: before anything else
+        if srmr:
+            from . import score as SC
+            SC.check_srmr_fs(fs)
+        Dereverb(**opts)                                                   # ... and an unknown option
+        np_in = not isinstance(wav, torch.Tensor)
+        w = torch.as_tensor(wav)
+        if w.dim() != 2 or w.shape[0] <= w.shape[1]:
+            raise ValueError("wav must be [n_samples, n_mics] with n_samples > n_mics")
+        if device is None:
+            device = w.device if w.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        L0, x = int(w.shape[0]), w.to(device=device, dtype=torch.float32)
+        if r_in is not None:
+            x = RS.resample(x, r_in, fs)
+        res = dereverb_wav(x, fs, device=device, srmr=srmr, ref_ch=ref_ch, **opts)
+        y = res[0] if srmr else res
+        if r_out is not None:
+            y = RS.resample(y, fs, r_out)
+            if r_out == (fs if r_in is None else r_in) and y.shape[0] != L0:
+                y = torch.nn.functional.pad(y[:L0], (0, 0, 0, max(0, L0 - y.shape[0])))
+        y = y.cpu().numpy() if np_in else y
+        return (y, res[1]) if srmr else y
     from . import stft as S
     if srmr:
         from . import score as SC

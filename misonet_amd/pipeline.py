@@ -810,7 +810,7 @@ class Enhancer:
     def enhance_recording(self, wav_observe, wav_clean=None, num_ch_utilize: Optional[int] = None, chunk_size: int = 64000,
                           max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000, score: bool = False,
                           bss: bool = False, bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False,
-                          srmr: bool = False):
+                          srmr: bool = False, fs_in=None, fs_out=None):
         """Recording in -> enhanced int16 waves out: the reference's loader item AND its tester body as one device-side
         object (``AudioDataset_Test.__getitem__``, dataloader/data.py:524-597, + ``Tester_Enhance.inference``,
         tester.py:846-975), without host STFT dicts.
@@ -858,7 +858,19 @@ class Enhancer:
         holds the speech-to-reverberation modulation energy ratio, the one figure that takes no clean
         reference, of the stitched int16 result at rate ``fs`` (8000 or 16000), the original observation at ``ref_ch`` as the
         mixture: what ``score.srmr_waves(pcm, mix, fs)`` returns.  A recording shorter than one 256 ms frame gives an
-        invalid ``Srmr``, not an error."""
+        invalid ``Srmr``, not an error.
+
+        ``fs_in`` / ``fs_out``: ``fs`` is the rate the networks run at.  ``fs_in`` other than ``fs``: the
+        files are at ``fs_in``; the observation -- with its clean sources, as the items of one launch -- is taken to ``fs`` on the
+        device (:mod:`misonet_amd.resample`) before anything else.  ``fs_out``: an integer rate or ``"in"`` (= ``fs_in``): the
+        int16 result is taken to that rate on the device and written with that rate in the header; it has the input's length
+        when ``fs_out`` is the input's rate.  Every score is computed at ``fs``.  With both None not one launch is added."""
+        if fs_in is not None or fs_out is not None:
+            from . import resample as RS
+            RS.plan_rates(fs, fs_in, fs_out)                               # a bad rate: before anything else
+            return RS.around(lambda w, c, path: self.enhance_recording(w, c, num_ch_utilize, chunk_size, max_batch, path, fs,
+                                                                       score, bss, bss_filt_len, stoi, reverb, srmr),
+                             wav_observe, wav_clean, fs, fs_in, fs_out, save_path, self._write_speakers, self.device)
         if srmr:
             from . import score as SC
             SC.check_srmr_fs(fs)
@@ -991,7 +1003,7 @@ class Enhancer:
 
     def enhance_continuous(self, wav_observe, num_ch_utilize: Optional[int] = None, window: int = 64000,
                            hop: Optional[int] = None, max_batch: int = 16, save_path: Optional[str] = None,
-                           fs: int = 16000, return_perms: bool = False, srmr: bool = False):
+                           fs: int = 16000, return_perms: bool = False, srmr: bool = False, fs_in=None, fs_out=None):
         """A long recording WITHOUT clean references -> one speaker per output from start to end (continuous separation).
 
         wav_observe float32 [L, M_all] (as :meth:`enhance_recording` takes it; same microphone sub-sampling).  The recording
@@ -1014,7 +1026,16 @@ class Enhancer:
         observation at ``ref_ch`` as the mixture -- the figure to read when choosing ``taps``, ``delay`` or ``iterations``
         on recordings that have no references.  It is measured on the device from the int16 pieces the pass leaves there;
         the waves and P are bit for bit those of ``srmr=False``, and the figure is what
-        ``score.srmr_waves(pcm, observation[:, ref_ch], fs)`` returns."""
+        ``score.srmr_waves(pcm, observation[:, ref_ch], fs)`` returns.
+
+        ``fs_in`` / ``fs_out``: a recording at another rate than the networks' ``fs``, as :meth:`enhance_recording` takes them
+        (INTEGRATION.md 4o); ``window`` and ``hop`` count samples at ``fs``.  With both None not one launch is added."""
+        if fs_in is not None or fs_out is not None:
+            from . import resample as RS
+            RS.plan_rates(fs, fs_in, fs_out)                               # a bad rate: before anything else
+            return RS.around(lambda w, _c, path: self.enhance_continuous(w, num_ch_utilize, window, hop, max_batch, path, fs,
+                                                                         return_perms, srmr),
+                             wav_observe, None, fs, fs_in, fs_out, save_path, self._write_speakers, self.device)
         import collections
         from . import css
         if srmr:
@@ -1110,7 +1131,7 @@ class Enhancer:
                            max_batch: int = 16, save_path: Optional[str] = None, fs: int = 16000,
                            depth: int = 2, score: bool = False, bss: bool = False,
                            bss_filt_len: int = 512, stoi: bool = False, reverb: bool = False,
-                           srmr: bool = False) -> Dict[str, np.ndarray]:
+                           srmr: bool = False, fs_in=None, fs_out=None) -> Dict[str, np.ndarray]:
         """:meth:`enhance_recording` over many recordings, with every launch filled across them.
 
         ``recordings``: an iterable of ``(wav_observe, wav_clean or None, name)``, each as :meth:`enhance_recording` takes
@@ -1132,9 +1153,39 @@ class Enhancer:
         from the same padded, pinned batch on the same side stream.  ``srmr=True`` (needs neither ``score=True`` nor clean
         sources): a :class:`score.Srmr` (csrc/srmr.hip) is appended as the last element of every entry,
         ``(pcm, Srmr)`` on its own; the stitched recordings go in padded batches of ``BSS_GROUP`` with their observation at
-        ``ref_ch`` as the mixture, and each figure is what :meth:`enhance_recording` gives for the recording alone."""
+        ``ref_ch`` as the mixture, and each figure is what :meth:`enhance_recording` gives for the recording alone.
+
+        ``fs_in`` / ``fs_out``: as :meth:`enhance_recording` takes them, for every recording: each is taken
+        to ``fs`` on the device as it is drawn from ``recordings`` (one launch for the observation and its clean sources), and
+        each result to ``fs_out`` behind the pass; every entry is bit for bit what :meth:`enhance_recording` gives with the same
+        rates.  With both None not one launch is added."""
         import os
         from .coalesce import Item
+        if fs_in is not None or fs_out is not None:
+            from . import resample as RS
+            r_in, r_out, rate = RS.plan_rates(fs, fs_in, fs_out)           # a bad rate: before anything else
+            lengths = {}
+
+            def at_model_rate():
+                for wav_observe, wav_clean, name in recordings:
+                    lengths[name] = int(np.shape(wav_observe)[0])
+                    if r_in is not None:
+                        got = RS.to_rate([wav_observe] + list(wav_clean or []), r_in, fs, self.device)
+                        wav_observe, wav_clean = got[0], (got[1:] if wav_clean is not None else None)
+                    yield wav_observe, wav_clean, name
+
+            res = self.enhance_recordings(at_model_rate(), num_ch_utilize, chunk_size, max_batch,
+                                          None if r_out is not None else save_path, fs, depth, score, bss, bss_filt_len, stoi,
+                                          reverb, srmr)
+            if r_out is not None:
+                back = r_out == (fs if r_in is None else r_in)
+                for name, r in res.items():
+                    pcm = RS.pcm_to_rate(r[0] if isinstance(r, tuple) else r, fs, r_out, lengths[name] if back else None,
+                                         self.device)
+                    if save_path is not None:
+                        self._write_speakers(pcm, os.path.join(save_path, str(name)), rate)
+                    res[name] = (pcm,) + tuple(r[1:]) if isinstance(r, tuple) else pcm
+            return res
         if srmr:
             from . import score as SC
             SC.check_srmr_fs(fs)
