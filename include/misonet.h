@@ -562,6 +562,42 @@ int misonet_resample(const void* src_dev, int src_kind, long long src_sb, long l
                      long long n, const int* n_valid_dev, int fs_in, int fs_out, void* dst_dev, int dst_kind, long long dst_sb,
                      long long dst_sc, long long dst_st, misonet_stream stream);
 
+/* ---- room simulator: image-source RIRs of a shoebox, and scene mixing (ABI 600) ------------------------------------------ */
+/* The project's own definition in the Allen & Berkley (1979) family (INTEGRATION.md 4p in full; tests/room_ref.py restates it in
+ * NumPy).  pyroomacoustics, gpuRIR, rir_generator and sms_wsj were not available: not compared against any of them.
+ * misonet_room_rir.  All geometry as device pointers to doubles: room [B][3] the shoebox (Lx, Ly, Lz), one corner at the origin;
+ * beta [B][6] the reflection coefficients in [0, 1) ordered x0, x1, y0, y1, z0, z1 ("0": the wall at coordinate 0, "1": at L);
+ * src [B][S][3], mic [B][M][3].  With W = 80 and, per axis, N_i = ceil((Lh + W/2) c / (fs 2 L_i)): the images (n, q), n_i in
+ * [-N_i, N_i], q_i in {0, 1}, enumerated n_x, n_y, n_z ascending, then q = q_x q_y q_z from 000 to 111 (q_z fastest);
+ *   p_i = (1 - 2 q_i) s_i + 2 n_i L_i,  d = |p - r|,  tau = d fs / c,
+ *   g = prod_i beta_i0^|n_i - q_i| beta_i1^|n_i| (0^0 = 1),  rho = sum_i (|n_i - q_i| + |n_i|);
+ *   kept: g > 0 and (max_order < 0 or rho <= max_order);  a = g / (4 pi d);
+ *   h[n] = sum over the kept images with |x| < W/2 of a 1/2 (1 + cos(2 pi x / W)) sinc(x),  x = n - tau,  0 <= n < Lh,
+ * a float64 sum in the enumeration order; rir double [B][S][M][Lh].  fail int32 [B][S][M]: bit 0 a non-finite coordinate, a
+ * point outside the room, a beta outside [0, 1) or an edge <= 0 (the RIR is all zero); bit 1 a kept image closer than 1e-3 m (a
+ * source on a microphone), which is dropped; bit 2 more than 2^27 images or an N_i above 255 (the RIR is all zero).  max_order
+ * -1: no limit.
+ * misonet_room_mix.  src float32, element (b, s, j) at src_dev[b src_sb + s src_ss + j src_st]; rir double [B][S][M][Lh]; split
+ * int32 [B][S] or NULL (= Lh);  images[b][s][m][n] = sum_{k = 0}^{min(n, Lh - 1)} h[k] x[n - k], x = 0 past L, k ascending, in
+ * float64 FMAs, rounded once to float32, for 0 <= n < Lo; early the same sum over k < split[b][s]; mix[b][m][n] the float64 sum
+ * of the unrounded image sums over s ascending, rounded once.  images float32 [B][S][M][Lo], early likewise or NULL, mix float32
+ * [B][M][Lo] or NULL.
+ * Both calls are asynchronous on the stream, allocate nothing, use no workspace (so MISONET_ENOMEM cannot arise) and can be
+ * captured in a HIP graph; no atomics: bit-reproducible, independent of B and of the item's position in the batch; every
+ * element of every output is written.  misonet_room_tile: the taps / output samples one workgroup owns (256), for tests that
+ * probe the tile edges.  misonet_room_rir_len: B S M Lh; misonet_room_mix_len: the largest Lo, L + Lh - 1.
+ * Limits: 1 <= B <= 4096, 1 <= S <= 4, 1 <= M <= 16, 1 <= Lh <= 2^16, 1 <= L <= 2^24, 1 <= Lo <= L + Lh - 1, B M Lo < 2^32.
+ * MISONET_EINVAL (the size functions: -1) before any launch: outside these limits, fs or c not finite and > 0, max_order < -1,
+ * a negative source stride or src_st < 1; then a null pointer. */
+int misonet_room_tile(void);
+long long misonet_room_rir_len(int B, int S, int M, int Lh);
+long long misonet_room_mix_len(long long L, int Lh);
+int misonet_room_rir(const double* room_dev, const double* beta_dev, const double* src_dev, const double* mic_dev, int B, int S,
+                     int M, double fs, double c, int Lh, int max_order, double* rir_dev, int* fail_dev, misonet_stream stream);
+int misonet_room_mix(const float* src_dev, long long src_sb, long long src_ss, long long src_st, const double* rir_dev,
+                     const int* split_dev, int B, int S, int M, long long L, int Lh, long long Lo, float* images_dev,
+                     float* early_dev, float* mix_dev, misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

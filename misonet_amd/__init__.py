@@ -11,6 +11,8 @@ Host-side mirror of the reference call surface:
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
                              definition, in front of and behind every recording path)
+  Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
+                             what simulate returns)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
@@ -18,7 +20,7 @@ library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "resample", "resampled_len",
-           "load_wav", "Enhancer", "weights"]
+           "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Enhancer", "weights"]
 
 
 def __getattr__(name):
@@ -46,6 +48,9 @@ def __getattr__(name):
     if name in ("resample", "resampled_len", "load_wav"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
+    if name in ("Room", "Scene", "simulate", "beta_from_rt60"):
+        import importlib
+        return getattr(importlib.import_module(".room", __name__), name)
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

@@ -168,6 +168,13 @@ SIGNATURES = {
     "misonet_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_longlong,
                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong,
                                    C.c_void_p]),
+    "misonet_room_tile": (C.c_int, []),
+    "misonet_room_rir_len": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "misonet_room_mix_len": (C.c_longlong, [C.c_longlong, C.c_int]),
+    "misonet_room_rir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                   C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_room_mix": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_reverb_frames": (C.c_longlong, [C.c_longlong, C.c_int]),
     "misonet_reverb_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
     "misonet_reverb_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p,

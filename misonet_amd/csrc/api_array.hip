@@ -445,6 +445,56 @@ int misonet_auxiva_debug(const void* ws, int B, int K, int F, int M, int T, void
   return MISONET_OK;
 }
 
+// ---- room simulator (room.hip) ---------------------------------------------------------------------------------------------
+static int room_geometry(int B, int S, int M, int Lh) {
+  if (B < 1 || B > ROOM_MAX_B) return fail(MISONET_EINVAL, "B must be in [1, %d] (got %d)", ROOM_MAX_B, B);
+  if (S < 1 || S > ROOM_MAX_S) return fail(MISONET_EINVAL, "S must be in [1, %d] (got %d)", ROOM_MAX_S, S);
+  if (M < 1 || M > ROOM_MAX_M) return fail(MISONET_EINVAL, "M must be in [1, %d] (got %d)", ROOM_MAX_M, M);
+  if (Lh < 1 || Lh > ROOM_MAX_LH) return fail(MISONET_EINVAL, "Lh must be in [1, %d] (got %d)", ROOM_MAX_LH, Lh);
+  return MISONET_OK;
+}
+
+int misonet_room_tile(void) { return room_tile(); }
+
+long long misonet_room_rir_len(int B, int S, int M, int Lh) {
+  if (B < 1 || B > ROOM_MAX_B || S < 1 || S > ROOM_MAX_S || M < 1 || M > ROOM_MAX_M || Lh < 1 || Lh > ROOM_MAX_LH) return -1;
+  return (long long)B * S * M * Lh;
+}
+
+long long misonet_room_mix_len(long long L, int Lh) {
+  if (L < 1 || L > ROOM_MAX_L || Lh < 1 || Lh > ROOM_MAX_LH) return -1;
+  return L + Lh - 1;
+}
+
+int misonet_room_rir(const double* room_dev, const double* beta_dev, const double* src_dev, const double* mic_dev, int B, int S,
+                     int M, double fs, double c, int Lh, int max_order, double* rir_dev, int* fail_dev, misonet_stream stream) {
+  { int r = room_geometry(B, S, M, Lh); if (r) return r; }
+  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(MISONET_EINVAL, "fs must be finite and > 0 (got %g)", fs);
+  if (!(c > 0.0) || !std::isfinite(c)) return fail(MISONET_EINVAL, "c must be finite and > 0 (got %g)", c);
+  if (max_order < -1) return fail(MISONET_EINVAL, "max_order must be -1 (no limit) or >= 0 (got %d)", max_order);
+  if (!room_dev || !beta_dev || !src_dev || !mic_dev || !rir_dev || !fail_dev) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_room_rir(room_dev, beta_dev, src_dev, mic_dev, B, S, M, fs, c, Lh, max_order, rir_dev, fail_dev,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_room_mix(const float* src_dev, long long src_sb, long long src_ss, long long src_st, const double* rir_dev,
+                     const int* split_dev, int B, int S, int M, long long L, int Lh, long long Lo, float* images_dev,
+                     float* early_dev, float* mix_dev, misonet_stream stream) {
+  { int r = room_geometry(B, S, M, Lh); if (r) return r; }
+  if (L < 1 || L > ROOM_MAX_L) return fail(MISONET_EINVAL, "L must be in [1, 2^24] (got %lld)", L);
+  if (Lo < 1 || Lo > L + Lh - 1) return fail(MISONET_EINVAL, "Lo must be in [1, L + Lh - 1] = [1, %lld] (got %lld)", L + Lh - 1, Lo);
+  if (src_sb < 0 || src_ss < 0 || src_st < 1)
+    return fail(MISONET_EINVAL, "source strides must not be negative and the sample stride must be positive");
+  if (((Lo + room_tile() - 1) / room_tile()) * M * B * room_tile() >= (1LL << 32))
+    return fail(MISONET_EINVAL, "B x M x Lo = %d x %d x %lld is more than one call takes (2^32 output samples)", B, M, Lo);
+  if (!src_dev || !rir_dev || !images_dev) return fail(MISONET_EINVAL, "null argument");
+  const long long xs[3] = {src_sb, src_ss, src_st};
+  HIPCHK(launch_room_mix(src_dev, xs, rir_dev, split_dev, B, S, M, (int)L, Lh, (int)Lo, images_dev, early_dev, mix_dev,
+                         reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
 long long misonet_pit_scratch_bytes(int B, int S, int F) {
   if (B <= 0 || S <= 0 || F <= 0) return -1;
   return (long long)B * S * S * (F + 1) * (long long)sizeof(double);

@@ -452,6 +452,21 @@ hipError_t launch_auxiva(const IvaArgs& a, void* ws, hipStream_t s);
 hipError_t launch_auxiva_debug(const void* ws, int B, int K, int F, int M, int T, void* y, void* a, void* evec, double* power,
                                int* fail, hipStream_t s);
 
+// Room simulator (room.hip): image-source RIRs of a shoebox and the scene mixer.  room double [B][3], beta
+// double [B][6] (x0, x1, y0, y1, z0, z1), src double [B][S][3], mic double [B][M][3] -> rir double [B][S][M][Lh], fail int [B][S][M]
+// (bit 0: bad geometry, bit 1: an image closer than 1e-3 m was dropped, bit 2: more than ROOM_MAX_IMAGES images or an N_i above
+// ROOM_MAX_N; bits 0 and 2 leave a zero RIR).  The mixer: x float32 (b, s, j) at b xs[0] + s xs[1] + j xs[2], split int [B][S] or
+// nullptr -> images, early (or nullptr) float32 [B][S][M][Lo], mix (or nullptr) float32 [B][M][Lo].  The caller checks the limits.
+constexpr int ROOM_W = 80;                         // support of the fractional-delay kernel in samples
+constexpr int ROOM_MAX_N = 255;                    // the largest image index per axis the static tables hold
+constexpr double ROOM_MAX_IMAGES = 134217728.0;    // 2^27
+constexpr int ROOM_MAX_B = 4096, ROOM_MAX_S = 4, ROOM_MAX_M = 16, ROOM_MAX_LH = 1 << 16, ROOM_MAX_L = 1 << 24;
+int room_tile();                                   // taps / output samples per workgroup
+hipError_t launch_room_rir(const double* room, const double* beta, const double* src, const double* mic, int B, int S, int M,
+                           double fs, double c, int Lh, int max_order, double* rir, int* fail, hipStream_t s);
+hipError_t launch_room_mix(const float* x, const long long* xs, const double* rir, const int* split /*[B][S] or nullptr*/, int B,
+                           int S, int M, int L, int Lh, int Lo, float* images, float* early, float* mix, hipStream_t s);
+
 // source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs,
 // MaskArgs or JbfArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
 template <typename Args>
