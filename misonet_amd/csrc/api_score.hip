@@ -13,6 +13,27 @@ static int view_strides(long long est_sb, long long est_ss, long long est_st, lo
     return fail(MISONET_EINVAL, "strides must not be negative and the %s strides must be positive", unit);
   return MISONET_OK;
 }
+// the views of a waveform scorer (sig_view.hpp) from the arguments of its entry point, strides checked: estimates (float32, or
+// int16 where i16), references and the mixture, one signal per item; a call without references or without a mixture passes
+// nullptr there, with the strides {0, 0, 1} and {0, 1}
+struct ScoreViews { SigView est, ref, mix; };
+static int score_views(ScoreViews* v, const void* est, int i16, long long est_sb, long long est_ss, long long est_st,
+                       const float* ref, long long ref_sb, long long ref_ss, long long ref_st, const float* mix = nullptr,
+                       long long mix_sb = 0, long long mix_st = 1) {
+  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample", mix && (mix_sb < 0 || mix_st < 1)))
+    return rc;
+  *v = {{est, est_sb, est_ss, est_st, i16 != 0}, {ref, ref_sb, ref_ss, ref_st, 0}, {mix, mix ? mix_sb : 0, 0, mix ? mix_st : 1, 0}};
+  return MISONET_OK;
+}
+// the constant table of a scorer on the current device (window, twiddles, filter taps and the like), built on the host and
+// uploaded at the first use there: that one call allocates and copies synchronously; every later call only queues kernels
+static int score_table(DevTable<double>& tab, int count, void (*build)(double*), const double** out) {
+  return tab.get(out, [&](double** p) {
+    std::vector<double> t((size_t)count);
+    build(t.data());
+    return dev_upload(t, p);
+  });
+}
 // `sizing`: the call that gives `need`, as the message names it
 static int scratch_fits(long long scratch_bytes, long long need, const char* sizing) {
   if (scratch_bytes < need) return fail(MISONET_ENOMEM, "scratch %lld < %lld bytes (%s)", scratch_bytes, need, sizing);
@@ -52,11 +73,11 @@ int misonet_score_wave(const void* est, int est_is_i16, long long est_sb, long l
   if (!est || !ref || !stats || !scratch) return fail(MISONET_EINVAL, "null argument");
   if (const int rc = score_ranges(B, E, R)) return rc;
   if (n < 1 || n > (1LL << 40)) return fail(MISONET_EINVAL, "n must be in [1, 2^40] (got %lld)", n);
-  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample")) return rc;
+  ScoreViews v;
+  if (const int rc = score_views(&v, est, est_is_i16, est_sb, est_ss, est_st, ref, ref_sb, ref_ss, ref_st)) return rc;
   if (const int rc = scratch_fits(scratch_bytes, misonet_score_scratch_bytes(B, E, R, n), "misonet_score_scratch_bytes(B, E, R, n)"))
     return rc;
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
-  HIPCHK(launch_score_wave(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, reinterpret_cast<double*>(scratch), stats,
+  HIPCHK(launch_score_wave(v.est, v.ref, B, E, R, n, n_valid, reinterpret_cast<double*>(scratch), stats,
                            reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
@@ -109,12 +130,12 @@ int misonet_bss_corr(const void* est, int est_is_i16, long long est_sb, long lon
   if (!est || !ref || !Rrr || !Rre || !Eee || !scratch) return fail(MISONET_EINVAL, "null argument");
   if (const int rc = bss_ranges(B, E, R, Q)) return rc;
   if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample")) return rc;
+  ScoreViews v;
+  if (const int rc = score_views(&v, est, est_is_i16, est_sb, est_ss, est_st, ref, ref_sb, ref_ss, ref_st)) return rc;
   if (const int rc = scratch_fits(scratch_bytes, misonet_bss_scratch_bytes(B, E, R, n, Q), "misonet_bss_scratch_bytes(B, E, R, n, Q)"))
     return rc;
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st};
-  HIPCHK(launch_bss_corr(est, est_is_i16 != 0, es, ref, rs, B, E, R, n, n_valid, Q, reinterpret_cast<double*>(scratch), Rrr, Rre,
-                         Eee, reinterpret_cast<hipStream_t>(stream)));
+  HIPCHK(launch_bss_corr(v.est, v.ref, B, E, R, n, n_valid, Q, reinterpret_cast<double*>(scratch), Rrr, Rre, Eee,
+                         reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 
@@ -130,16 +151,8 @@ int misonet_bss_solve(const double* Rrr, const double* Rre, const double* Eee, i
 }
 
 // ---- STOI / ESTOI (stoi.hip) ------------------------------------------------------------------------------------------------
-// the table of the current device (window, twiddles, polyphase taps), built on first use: that one call allocates and copies
-// synchronously; every later call only queues kernels
-static DevTable<double> g_stoi_tab;
-static int get_stoi_table(const double** out) {
-  return g_stoi_tab.get(out, [](double** p) {
-    std::vector<double> t((size_t)stoi_table_count());
-    stoi_build_table(t.data());
-    return dev_upload(t, p);
-  });
-}
+static DevTable<double> g_stoi_tab;                   // window, twiddles, polyphase taps
+static int get_stoi_table(const double** out) { return score_table(g_stoi_tab, stoi_table_count(), stoi_build_table, out); }
 
 long long misonet_stoi_resampled_len(long long n, int fs) { return stoi_resampled_len(n, fs); }
 
@@ -172,12 +185,12 @@ int misonet_stoi_resample(const void* est, int est_is_i16, long long est_sb, lon
   if (const int rc = erb_ranges(B, E, R)) return rc;
   if (fs != 8000 && fs != 10000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000, 10000 or 16000 (got %d)", fs);
   if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample", mix && (mix_sb < 0 || mix_st < 1)))
+  ScoreViews v;
+  if (const int rc = score_views(&v, est, est_is_i16, est_sb, est_ss, est_st, ref, ref_sb, ref_ss, ref_st, mix, mix_sb, mix_st))
     return rc;
   const double* tab;
   if (const int rc = get_stoi_table(&tab)) return rc;
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
-  HIPCHK(launch_stoi_resample(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, x10, len10,
+  HIPCHK(launch_stoi_resample(v.est, v.ref, v.mix, B, E, R, n, n_valid, fs, tab, x10, len10,
                               reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
@@ -198,15 +211,9 @@ int misonet_stoi_measure(const double* x10, const int* len10, int B, int NS, int
 }
 
 // ---- cepstral distance, LLR, fwSegSNR (reverb.hip) -----------------------------------------------------------------------
-// the table of the current device (twiddles and, per rate, window, mel triangles, their bin ranges), built on first use as
-// the STOI table is
-static DevTable<double> g_reverb_tab;
+static DevTable<double> g_reverb_tab;                 // twiddles and, per rate, window, mel triangles, their bin ranges
 static int get_reverb_table(const double** out) {
-  return g_reverb_tab.get(out, [](double** p) {
-    std::vector<double> t((size_t)reverb_table_count());
-    reverb_build_table(t.data());
-    return dev_upload(t, p);
-  });
+  return score_table(g_reverb_tab, reverb_table_count(), reverb_build_table, out);
 }
 
 long long misonet_reverb_frames(long long n, int fs) { return reverb_frames(n, fs); }
@@ -226,7 +233,8 @@ int misonet_reverb_measure(const void* est, int est_is_i16, long long est_sb, lo
   if (const int rc = erb_ranges(B, E, R)) return rc;
   if (fs != 8000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000 or 16000 (got %d)", fs);
   if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (const int rc = view_strides(est_sb, est_ss, est_st, ref_sb, ref_ss, ref_st, "sample", mix && (mix_sb < 0 || mix_st < 1)))
+  ScoreViews v;
+  if (const int rc = score_views(&v, est, est_is_i16, est_sb, est_ss, est_st, ref, ref_sb, ref_ss, ref_st, mix, mix_sb, mix_st))
     return rc;
   const int NS = R + E + (mix ? 1 : 0);
   if (const int rc = scratch_fits(scratch_bytes, misonet_reverb_scratch_bytes(B, NS, R, n, fs),
@@ -234,23 +242,14 @@ int misonet_reverb_measure(const void* est, int est_is_i16, long long est_sb, lo
     return rc;
   const double* tab;
   if (const int rc = get_reverb_table(&tab)) return rc;
-  const long long es[3] = {est_sb, est_ss, est_st}, rs[3] = {ref_sb, ref_ss, ref_st}, ms[2] = {mix_sb, mix_st};
-  HIPCHK(launch_reverb_measure(est, est_is_i16 != 0, es, ref, rs, mix, ms, B, E, R, n, n_valid, fs, tab, out, count, frame,
+  HIPCHK(launch_reverb_measure(v.est, v.ref, v.mix, B, E, R, n, n_valid, fs, tab, out, count, frame,
                                reinterpret_cast<double*>(scratch), reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 
 // ---- SRMR (srmr.hip) ---------------------------------------------------------------------------------------------------------
-// the table of the current device (twiddles and, per rate, window, filter coefficients, transitions, ERB, cutoffs), built on first
-// use as the STOI table is
-static DevTable<double> g_srmr_tab;
-static int get_srmr_table(const double** out) {
-  return g_srmr_tab.get(out, [](double** p) {
-    std::vector<double> t((size_t)srmr_table_count());
-    srmr_build_table(t.data());
-    return dev_upload(t, p);
-  });
-}
+static DevTable<double> g_srmr_tab;   // twiddles and, per rate, window, filter coefficients, transitions, ERB, cutoffs
+static int get_srmr_table(const double** out) { return score_table(g_srmr_tab, srmr_table_count(), srmr_build_table, out); }
 
 long long misonet_srmr_frames(long long n, int fs) { return srmr_frames(n, fs); }
 int misonet_srmr_chunk(void) { return srmr_chunk(); }
@@ -268,15 +267,14 @@ int misonet_srmr_measure(const void* sig, int sig_is_i16, long long sig_sb, long
   if (B < 1 || B > 4096) return fail(MISONET_EINVAL, "B must be in [1, 4096] (got %d)", B);
   if (fs != 8000 && fs != 16000) return fail(MISONET_EINVAL, "fs must be 8000 or 16000 (got %d)", fs);
   if (n < 1 || n > (1LL << 24)) return fail(MISONET_EINVAL, "n must be in [1, 2^24] (got %lld)", n);
-  if (sig_sb < 0 || sig_ss < 0 || sig_st < 1 || (mix && (mix_sb < 0 || mix_st < 1)))
-    return fail(MISONET_EINVAL, "strides must not be negative and the sample strides must be positive");
+  ScoreViews v;
+  if (const int rc = score_views(&v, sig, sig_is_i16, sig_sb, sig_ss, sig_st, nullptr, 0, 0, 1, mix, mix_sb, mix_st)) return rc;
   const int NS = S + (mix ? 1 : 0);
   if (const int rc = scratch_fits(scratch_bytes, misonet_srmr_scratch_bytes(B, NS, n, fs), "misonet_srmr_scratch_bytes(B, S (+ 1), n, fs)"))
     return rc;
   const double* tab;
   if (const int rc = get_srmr_table(&tab)) return rc;
-  const long long ss[3] = {sig_sb, sig_ss, sig_st}, ms[2] = {mix_sb, mix_st};
-  HIPCHK(launch_srmr_measure(sig, sig_is_i16 != 0, ss, mix, ms, B, S, n, n_valid, fs, tab, out, count, energy,
+  HIPCHK(launch_srmr_measure(v.est, v.mix, B, S, n, n_valid, fs, tab, out, count, energy,
                              reinterpret_cast<double*>(scratch), reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }

@@ -28,51 +28,40 @@ constexpr int BSS_YS = BSS_CH + 1024; // y window of a staging round: BSS_CH + t
 constexpr int BSS_NB = 64;            // panel width of the factorisation (DESIGN: 32 KB diagonal block + 64 row values per thread)
 constexpr int BSS_XROWS = 4;          // rows reserved below every system for the right-hand sides (E <= 4)
 
-struct BssSig { const void* p; long long st; int i16; };
-
-__device__ __forceinline__ float bss_ld(const BssSig& s, long long m, long long nv) {
-  if (m < 0 || m >= nv) return 0.0f;
-  return s.i16 ? (float)reinterpret_cast<const int16_t*>(s.p)[m * s.st] : reinterpret_cast<const float*>(s.p)[m * s.st];
+// sample m of the signal at `base` of a view as stored (an int16 estimate is scaled after the sums), zero outside [0, nv)
+__device__ __forceinline__ float bss_ld(const SigView& v, long long base, long long m, long long nv) {
+  return m < 0 || m >= nv ? 0.0f : sig_raw(v, base, m);
 }
 
 __device__ __forceinline__ int bss_ypos(int i) { return i + (i >> 4); }   // one pad word per 16: the stride-16 reads of B spread over the banks
-
-struct BssView { const void* p; long long sb, ss, st; };
 
 // grid (segments, pairs, items), 64 * ceil(Q / 256) threads: wave w owns lags [256 w, 256 w + 256).
 // pair p < R R: (r_j, r_k), j = p / R; p < R R + R E: (r_j, e_i), j = q / E; else (e_i, e_i), of which only lag 0 is kept.
 // Segment s covers k in [4096 s, 4096 s + 4096) where row v of A reads x[k - v]: ceil((n + 15) / 4096) segments reach every
 // product.  Two accumulator chains (even and odd steps) are added once at the end.
-__global__ __launch_bounds__(256) void bss_corr_k(const BssView ve, int est_i16, const BssView vr, int E, int R, int Q,
-                                                  long long n, const int* n_valid, double* part) {
+__global__ __launch_bounds__(256) void bss_corr_k(const SigView ve, const SigView vr, int E, int R, int Q, long long n,
+                                                  const int* n_valid, double* part) {
   __shared__ float xs[BSS_CH + 16];
   __shared__ float ys[BSS_YS + BSS_YS / 16 + 1];
   const int seg = blockIdx.x, p = blockIdx.y, b = blockIdx.z;
   const int NP = R * R + R * E + E;
-  long long nv = n;
-  if (n_valid) {
-    const long long q = n_valid[b];
-    nv = q < 0 ? 0 : (q < n ? q : n);
-  }
-  BssSig x, y;
+  const long long nv = sig_nv(n_valid, b, n);
+  const long long be = (long long)b * ve.sb, br = (long long)b * vr.sb;
+  SigView x = vr, y = vr;
+  long long xo, yo;
   int tiles = (Q + BSS_TILE - 1) / BSS_TILE;
-  {
-    const char* pe = reinterpret_cast<const char*>(ve.p) + (long long)b * ve.sb * (est_i16 ? 2 : 4);
-    const char* pr = reinterpret_cast<const char*>(vr.p) + (long long)b * vr.sb * 4;
-    const int esz = est_i16 ? 2 : 4;
-    if (p < R * R) {
-      x = {pr + (long long)(p / R) * vr.ss * 4, vr.st, 0};
-      y = {pr + (long long)(p % R) * vr.ss * 4, vr.st, 0};
-    } else if (p < R * R + R * E) {
-      const int q = p - R * R;
-      x = {pr + (long long)(q / E) * vr.ss * 4, vr.st, 0};
-      y = {pe + (long long)(q % E) * ve.ss * esz, ve.st, est_i16};
-    } else {
-      const int i = p - R * R - R * E;
-      x = {pe + (long long)i * ve.ss * esz, ve.st, est_i16};
-      y = x;
-      tiles = 1;
-    }
+  if (p < R * R) {
+    xo = br + (long long)(p / R) * vr.ss;
+    yo = br + (long long)(p % R) * vr.ss;
+  } else if (p < R * R + R * E) {
+    const int q = p - R * R;
+    xo = br + (long long)(q / E) * vr.ss;
+    y = ve;
+    yo = be + (long long)(q % E) * ve.ss;
+  } else {
+    x = y = ve;
+    xo = yo = be + (long long)(p - R * R - R * E) * ve.ss;
+    tiles = 1;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int v = lane & 15, g = lane >> 4;                              // v: row of A and column of B of this lane; g: its k
@@ -85,8 +74,8 @@ __global__ __launch_bounds__(256) void bss_corr_k(const BssView ve, int est_i16,
     const long long k0 = k_seg + (long long)c * BSS_CH;
     if (k0 - 15 >= nv) break;                                          // x is zero from here on: the sums do not move
     __syncthreads();
-    for (int i = threadIdx.x; i < BSS_CH + 15; i += blockDim.x) xs[i] = bss_ld(x, k0 - 15 + i, nv);
-    for (int i = threadIdx.x; i < ywin; i += blockDim.x) ys[bss_ypos(i)] = bss_ld(y, k0 + i, nv);
+    for (int i = threadIdx.x; i < BSS_CH + 15; i += blockDim.x) xs[i] = bss_ld(x, xo, k0 - 15 + i, nv);
+    for (int i = threadIdx.x; i < ywin; i += blockDim.x) ys[bss_ypos(i)] = bss_ld(y, yo, k0 + i, nv);
     __syncthreads();
     if (active) {
       const int xb = g - v + 15, yb = g + wave * BSS_TILE + 16 * v;    // A[v][g] = x[k - v], B[g][u = v] = y[k + 16 u] at k = k0 + 4 s + g
@@ -129,17 +118,14 @@ __global__ __launch_bounds__(256) void bss_corr_fold_k(const double* part, int n
 
 long long bss_corr_segments(long long n) { return (n + 15 + BSS_SEG - 1) / BSS_SEG; }
 
-hipError_t launch_bss_corr(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs, int B,
-                           int E, int R, long long n, const int* n_valid, int Q, double* part, double* Rrr, double* Rre,
-                           double* Eee, hipStream_t s) {
+hipError_t launch_bss_corr(const SigView& est, const SigView& ref, int B, int E, int R, long long n, const int* n_valid, int Q,
+                           double* part, double* Rrr, double* Rre, double* Eee, hipStream_t s) {
   const int nseg = (int)bss_corr_segments(n), NP = R * R + R * E + E;
-  const BssView ve = {est, es[0], es[1], es[2]}, vr = {ref, rs[0], rs[1], rs[2]};
   const int tiles = (Q + BSS_TILE - 1) / BSS_TILE;
-  hipLaunchKernelGGL(bss_corr_k, dim3(nseg, NP, B), dim3(64 * tiles), 0, s, ve, est_is_i16, vr, E, R, Q, n, n_valid, part);
+  hipLaunchKernelGGL(bss_corr_k, dim3(nseg, NP, B), dim3(64 * tiles), 0, s, est, ref, E, R, Q, n, n_valid, part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(bss_corr_fold_k, dim3(NP, B), dim3(256), 0, s, part, nseg, E, R, Q, est_is_i16 ? 1.0 / 32767.0 : 1.0, Rrr,
-                     Rre, Eee);
+  hipLaunchKernelGGL(bss_corr_fold_k, dim3(NP, B), dim3(256), 0, s, part, nseg, E, R, Q, sig_unit(est), Rrr, Rre, Eee);
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "det_stats.hpp"
+#include "sig_view.hpp"
 
 namespace mn {
 
@@ -254,35 +255,33 @@ hipError_t launch_css_chain(const int* perm0, int* perm, int K, int S, hipStream
 hipError_t launch_css_stitch(const float* y, const int* perm, int K, int S, int W, int hop, long long base, long long n_out,
                              short* out_i16, float* out_f32, hipStream_t s);
 
-// Scores of separated output against clean references (score.hip).  Wave statistics: est int16 or float32, ref float32, each
-// a strided view (item, source, sample) in elements (es / rs = the three strides); per-segment partials
-// [B][score_wave_segments(n)][2E + 2R + E R] are folded in segment order into stats [B][E][R][5] =
-// (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j), an int16 estimate scaled by 1 / 32767 once.  1 <= E <= 5, 1 <= R <= 4.
+// Scores of separated output against clean references (score.hip).  Wave statistics over the estimates and the references
+// (SigView, sig_view.hpp): per-segment partials [B][score_wave_segments(n)][2E + 2R + E R] are folded in segment order into
+// stats [B][E][R][5] = (S e_i, S r_j, S e_i^2, S r_j^2, S e_i r_j), an int16 estimate scaled by 1 / 32767 once.
+// 1 <= E <= 5, 1 <= R <= 4.
 long long score_wave_segments(long long n);
-hipError_t launch_score_wave(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                             int B, int E, int R, long long n, const int* n_valid /*[B] or nullptr*/, double* part,
-                             double* stats, hipStream_t s);
+hipError_t launch_score_wave(const SigView& est, const SigView& ref, int B, int E, int R, long long n,
+                             const int* n_valid /*[B] or nullptr*/, double* part, double* stats, hipStream_t s);
 // The spectral training criterion per pair: p.a = estimates, p.b = references, sm = the source stride; per-bin partials
 // [B][F][E][R] folded in bin order into pair [B][E][R]; perm [B][R] / upit [B] (either may be nullptr; E == R): the uPIT pick
 hipError_t launch_score_spec(const PitArgs& p, int E, int R, double* part, double* pair, int* perm, double* upit,
                              hipStream_t s);
 
-// BSS-eval energies (bss.hip).  Lagged correlations over the same strided views as launch_score_wave: per-segment partials
+// BSS-eval energies (bss.hip).  Lagged correlations over the same views as launch_score_wave: per-segment partials
 // [B][bss_corr_segments(n)][R R + R E + E][Q] folded in segment order into Rrr [B][R][R][Q], Rre [B][R][E][Q], Eee [B][E].
 // The systems: per item bss_solve_doubles(R, Q) doubles of scratch; T [B][E][R], A [B][E], info [B] (-1, or the first row
 // whose pivot failed).  1 <= E, R <= 4, 16 | Q, 16 <= Q <= 1024.
 long long bss_corr_segments(long long n);
 long long bss_solve_doubles(int R, int Q);
-hipError_t launch_bss_corr(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs, int B,
-                           int E, int R, long long n, const int* n_valid /*[B] or nullptr*/, int Q, double* part, double* Rrr,
-                           double* Rre, double* Eee, hipStream_t s);
+hipError_t launch_bss_corr(const SigView& est, const SigView& ref, int B, int E, int R, long long n,
+                           const int* n_valid /*[B] or nullptr*/, int Q, double* part, double* Rrr, double* Rre, double* Eee,
+                           hipStream_t s);
 hipError_t launch_bss_solve(const double* Rrr, const double* Rre, int B, int E, int R, int Q, double* T, double* A, int* info,
                             double* scratch, hipStream_t s);
 
 // STOI / ESTOI (stoi.hip).  The table (stoi_table_count() doubles, built on the host): the window, the
-// twiddles of the 512-point transform and the polyphase taps of 16, 8 and 10 kHz.  The resampler reads the strided views of
-// launch_score_wave (ms = the item and sample strides of the mixture, which may be nullptr) and writes x10 [B][R + E (+ 1)][n10]
-// (references, estimates, mixture) and len10 [B].  The measure: per item stoi_item_doubles(NS, R, n10) doubles of scratch;
+// twiddles of the 512-point transform and the polyphase taps of 16, 8 and 10 kHz.  The resampler reads the three views (the
+// mixture's p may be nullptr) and writes x10 [B][R + E (+ 1)][n10] (references, estimates, mixture) and len10 [B].  The measure: per item stoi_item_doubles(NS, R, n10) doubles of scratch;
 // out [B][NS - R][R][2] = (STOI, ESTOI), meta [B][R][3] = (frames, kept frames, any sample != 0).
 int stoi_table_count();
 void stoi_build_table(double* t);
@@ -290,8 +289,7 @@ int stoi_taps(int fs);            // 2 Lh + 1, or -1 for a rate that is not serv
 int stoi_tap_offset(int fs);      // where those taps start in the table, or -1
 long long stoi_resampled_len(long long n, int fs);
 long long stoi_item_doubles(int NS, int R, long long n10);
-hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                                const float* mix, const long long* ms, int B, int E, int R, long long n,
+hipError_t launch_stoi_resample(const SigView& est, const SigView& ref, const SigView& mix, int B, int E, int R, long long n,
                                 const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* x10, int* len10,
                                 hipStream_t s);
 hipError_t launch_stoi_measure(const double* x10, const int* len10 /*[B] or nullptr*/, int B, int NS, int R, long long n10,
@@ -315,32 +313,31 @@ hipError_t launch_resample(const void* src, int src_i16, const long long* ss, in
 
 // Cepstral distance, LLR and fwSegSNR (reverb.hip).  The table (reverb_table_count() doubles, built on the
 // host): the twiddles of the 512-point transform and, per rate, the window, the 23 mel triangles and their bin ranges.  One call
-// reads the strided views of launch_score_wave (ms as for launch_stoi_resample) and writes out [B][E (+ 1)][R][6], count
+// reads the three views of launch_stoi_resample and writes out [B][E (+ 1)][R][6], count
 // [B][E (+ 1)][R][3] and, where frame_out is not nullptr, the values of every frame [B][E (+ 1)][R][3][frames of n]; per item
 // reverb_item_doubles(NS, R, n, fs) doubles of scratch, NS = R + E (+ 1).
 int reverb_table_count();
 void reverb_build_table(double* t);
 long long reverb_frames(long long n, int fs);      // -1 for a rate that is not served or n outside 1 .. 2^24
 long long reverb_item_doubles(int NS, int R, long long n, int fs);
-hipError_t launch_reverb_measure(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                                 const float* mix, const long long* ms, int B, int E, int R, long long n,
+hipError_t launch_reverb_measure(const SigView& est, const SigView& ref, const SigView& mix, int B, int E, int R, long long n,
                                  const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out, int* count,
                                  double* frame_out /*or nullptr*/, double* scratch, hipStream_t s);
 
 // SRMR, the speech-to-reverberation modulation energy ratio (srmr.hip).  The table (srmr_table_count() doubles,
 // built on the host): the twiddles of the transforms and, per rate, the window, the gammatone and modulation coefficients, their
-// chunk-to-chunk transitions A^C, ERB(cf_j) and the lower cutoffs ll_k.  One call reads S signals through the strided view of
-// launch_score_wave's estimates (ss) and, where mix is not nullptr, the mixture as one more signal, the last (ms as for
-// launch_stoi_resample), and writes out [B][S (+ 1)][3] = (SRMR, K*, BW), count [B][S (+ 1)] = the frames and, where energy is
-// not nullptr, the mean modulation energies [B][S (+ 1)][23][8]; srmr_scratch_doubles(B, S (+ 1), n, fs) doubles of scratch.
+// chunk-to-chunk transitions A^C, ERB(cf_j) and the lower cutoffs ll_k.  One call reads the S signals of sig and, where mix.p is
+// not nullptr, the mixture as one more signal, the last, and writes out [B][S (+ 1)][3] = (SRMR, K*, BW), count [B][S (+ 1)] =
+// the frames and, where energy is not nullptr, the mean modulation energies [B][S (+ 1)][23][8];
+// srmr_scratch_doubles(B, S (+ 1), n, fs) doubles of scratch.
 int srmr_table_count();
 void srmr_build_table(double* t);
 int srmr_chunk();                                  // C of the chunked scan
 long long srmr_frames(long long n, int fs);        // -1 for a rate that is not served or n outside 0 .. 2^24
 long long srmr_scratch_doubles(int B, int NS, long long n, int fs);   // -1 outside the limits
-hipError_t launch_srmr_measure(const void* sig, int sig_is_i16, const long long* ss, const float* mix, const long long* ms, int B,
-                               int S, long long n, const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out,
-                               int* count, double* energy /*or nullptr*/, double* scratch, hipStream_t s);
+hipError_t launch_srmr_measure(const SigView& sig, const SigView& mix, int B, int S, long long n,
+                               const int* n_valid /*[B] or nullptr*/, int fs, const double* table, double* out, int* count,
+                               double* energy /*or nullptr*/, double* scratch, hipStream_t s);
 
 // WPE dereverberation (wpe.hip).  mix / out complex64 [B][M][T][F], power float32 [B][T][F] or nullptr; the
 // workspace starts with fail int [B F] and G complex128 [B F][M taps][M], which launch_wpe_debug copies out.

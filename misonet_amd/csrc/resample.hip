@@ -43,23 +43,13 @@ int resample_half_len(int p, int q) { return (p == 1 && q == 1) ? 0 : 10 * (p > 
 
 long long resample_len(long long n, int p, int q) { return (n * p + q - 1) / q; }
 
-// modified Bessel function I0 as its power series: every term positive, converged long before 64 terms for x <= 5
-static double rs_i0(double x) {
-  double s = 1.0, t = 1.0;
-  for (int k = 1; k < 64; ++k) {
-    t *= (x / 2.0) / k;
-    s += t * t;
-  }
-  return s;
-}
-
 // g[0 .. 2 Lh]: SciPy's firwin step for step -- the ideal low-pass cutoff sinc(cutoff k), the Kaiser window of beta 5, the
 // division by the sum (unit gain at 0 Hz) -- times p
 void resample_build_taps(int p, int q, double* g) {
   const int Lh = resample_half_len(p, q);
   if (Lh == 0) { g[0] = 1.0; return; }
   const double pi = 3.14159265358979323846, beta = 5.0;
-  const double cutoff = 1.0 / (p > q ? p : q), i0b = rs_i0(beta);
+  const double cutoff = 1.0 / (p > q ? p : q), i0b = sig_i0(beta);
   double sum = 0.0, comp = 0.0;                                        // a compensated sum: up to 20481 terms of both signs
   for (int i = 0; i <= 2 * Lh; ++i) {
     const double k = (double)(i - Lh);
@@ -67,7 +57,7 @@ void resample_build_taps(int p, int q, double* g) {
     const double sinc = (i == Lh) ? 1.0 : std::sin(a) / a;
     const double u = k / Lh;
     const double r = 1.0 - u * u;
-    g[i] = cutoff * sinc * (rs_i0(beta * std::sqrt(r > 0.0 ? r : 0.0)) / i0b);
+    g[i] = cutoff * sinc * (sig_i0(beta * std::sqrt(r > 0.0 ? r : 0.0)) / i0b);
     const double t = sum + g[i];
     comp += std::fabs(sum) >= std::fabs(g[i]) ? (sum - t) + g[i] : (g[i] - t) + sum;
     sum = t;
@@ -92,11 +82,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_k(const void* src, RsView
   __shared__ float s_x[RS_LDS];
   const int b = blockIdx.y, tid = threadIdx.x;
   const long long m0 = (long long)blockIdx.x * RS_TILE;
-  long long nv = n;
-  if (n_valid) {
-    const long long v = n_valid[b];
-    nv = v < 0 ? 0 : (v < n ? v : n);
-  }
+  const long long nv = sig_nv(n_valid, b, n);
   const long long len = (nv * p + q - 1) / q;                          // this item's own output length
   const long long m_end = m0 + RS_TILE < n_out ? m0 + RS_TILE : n_out; // outputs [m0, m_end) are this tile's
   const long long m_live = m_end < len ? m_end : len;                  // ... and [m0, m_live) of them are not zeros

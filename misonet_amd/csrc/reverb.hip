@@ -99,59 +99,23 @@ long long reverb_item_doubles(int NS, int R, long long n, int fs) {
   return nfr < 0 ? -1 : rvb_layout(NS, R, nfr).total;
 }
 
-struct RvbSrc { const void* p; long long sb, ss, st; int i16; };
-
-__device__ __forceinline__ long long rvb_nv(const int* n_valid, int b, long long n) {
-  if (!n_valid) return n;
-  const long long v = n_valid[b];
-  return v < 0 ? 0 : (v < n ? v : n);
-}
-// sample m of signal s of item b: an int16 sample q stands for q / 32767
-__device__ __forceinline__ double rvb_load(const RvbSrc& v, long long base, long long m) {
-  return v.i16 ? (double)reinterpret_cast<const int16_t*>(v.p)[base + m * v.st] / 32767.0
-               : (double)reinterpret_cast<const float*>(v.p)[base + m * v.st];
-}
-
-// the 256 values of s[] added by a fixed tree; every thread gets the sum.  s[] is free again on return.
-__device__ __forceinline__ double rvb_tree(double* s, double v, int t) {
-  __syncthreads();
-  s[t] = v;
-  __syncthreads();
-  for (int k = 128; k >= 1; k >>= 1) {
-    if (t < k) s[t] += s[t + k];
-    __syncthreads();
-  }
-  return s[0];
-}
-__device__ __forceinline__ int rvb_tree_int(int* s, int v, int t) {
-  __syncthreads();
-  s[t] = v;
-  __syncthreads();
-  for (int k = 128; k >= 1; k >>= 1) {
-    if (t < k) s[t] += s[t + k];
-    __syncthreads();
-  }
-  return s[0];
-}
-
 // ---- the level -------------------------------------------------------------------------------------------------------------------
 // grid (NS, items), 256 threads.  Signal s < R: reference s; s < R + E: estimate s - R; else the mixture.  Thread t adds the
 // squares of samples t, t + 256, ... in that order, then the tree.
-__global__ __launch_bounds__(256) void rvb_level_k(const RvbSrc ref, const RvbSrc est, const RvbSrc mix, int R, int E, long long n,
+__global__ __launch_bounds__(256) void rvb_level_k(const SigView ref, const SigView est, const SigView mix, int R, int E, long long n,
                                                    const int* n_valid, long long nfr, double* scratch) {
   __shared__ double s_sum[256];
   const int s = blockIdx.x, b = blockIdx.y, NS = gridDim.x, t = threadIdx.x;
   const RvbLay L = rvb_layout(NS, R, nfr);
-  const long long nv = rvb_nv(n_valid, b, n);
-  const RvbSrc& v = s < R ? ref : (s < R + E ? est : mix);
-  const int src = s < R ? s : (s < R + E ? s - R : 0);
-  const long long base = (long long)b * v.sb + (long long)src * v.ss;
+  const long long nv = sig_nv(n_valid, b, n);
+  long long base;
+  const SigView& v = sig_pick(ref, est, mix, R, E, s, b, &base);
   double acc = 0.0;
   for (long long m = t; m < nv; m += 256) {
-    const double x = rvb_load(v, base, m);
+    const double x = sig_load(v, base, m);
     acc += x * x;
   }
-  const double P = rvb_tree(s_sum, acc, t);
+  const double P = sig_tree(s_sum, acc, t);
   if (t == 0) scratch[(long long)b * L.total + L.lvl + s] = P;
 }
 
@@ -160,27 +124,26 @@ __global__ __launch_bounds__(256) void rvb_level_k(const RvbSrc ref, const RvbSr
 // owns one butterfly per stage; 128 threads at NFFT = 256), |X| and ln max(|X|, 1e-15) of bins 0 .. NFFT / 2.  Then wave w takes
 // the cepstral coefficients q = w, w + 4, ... and the lags l = w, w + 4, ...: lane l adds its terms m = l, l + 64, ... in that
 // order, 64-lane butterfly; threads 0 .. 22 add a band each in bin order; thread 0 runs Levinson-Durbin in LDS.
-__global__ __launch_bounds__(256) void rvb_frame_k(const RvbSrc ref, const RvbSrc est, const RvbSrc mix, int R, int E, long long n,
+__global__ __launch_bounds__(256) void rvb_frame_k(const SigView ref, const SigView est, const SigView mix, int R, int E, long long n,
                                                    const int* n_valid, const RvbRate rt, long long nfr, const double* table,
                                                    double* scratch) {
   __shared__ double re[RV_MAXFFT], im[RV_MAXFFT], su[RV_MAXFFT], smag[RV_MAXBIN], slog[RV_MAXBIN];
   __shared__ double s_r[RV_NL], s_a[RV_NL], s_tmp[RV_NL], s_fail;
   const int s = blockIdx.y, b = blockIdx.z, NS = gridDim.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const long long fr = blockIdx.x;
-  const long long nv = rvb_nv(n_valid, b, n);
+  const long long nv = sig_nv(n_valid, b, n);
   const long long nfr_b = nv >= rt.N ? (nv - rt.N) / rt.H + 1 : 0;
   if (fr >= nfr_b) return;                                           // uniform over the workgroup
   const RvbLay L = rvb_layout(NS, R, nfr);
-  const RvbSrc& v = s < R ? ref : (s < R + E ? est : mix);
-  const int src = s < R ? s : (s < R + E ? s - R : 0);
-  const long long base = (long long)b * v.sb + (long long)src * v.ss;
+  long long base;
+  const SigView& v = sig_pick(ref, est, mix, R, E, s, b, &base);
   const double* tw = table + RV_T_TW;
   const double* w = table + rt.off;
   const double* tri = w + rt.N;
   const double* rng = tri + RV_NB * rt.nbin;
   const int NFFT = rt.NFFT, N = rt.N, half_n = NFFT >> 1;
   for (int i = t; i < NFFT; i += 256) {
-    const double u = i < N ? w[i] * rvb_load(v, base, fr * rt.H + i) : 0.0;      // fr H + i <= nv - 1 by the frame count
+    const double u = i < N ? w[i] * sig_load(v, base, fr * rt.H + i) : 0.0;      // fr H + i <= nv - 1 by the frame count
     const int at = (int)(__brev((unsigned)i) >> (32 - rt.LOG));
     su[i] = u;
     re[at] = u;
@@ -335,7 +298,7 @@ __global__ __launch_bounds__(256) void rvb_pair_k(int NS, int R, long long n, co
   __shared__ int s_int[256], s_pick[2];
   const int NE = NS - R, e = blockIdx.x / R, r = blockIdx.x % R, b = blockIdx.y, t = threadIdx.x;
   const RvbLay L = rvb_layout(NS, R, nfr);
-  const long long nv = rvb_nv(n_valid, b, n);
+  const long long nv = sig_nv(n_valid, b, n);
   const long long nf = nv >= rt.N ? (nv - rt.N) / rt.H + 1 : 0;
   const double* item = scratch + (long long)b * L.total;
   const double* fx = item + L.feat + (long long)r * RV_NF * L.nf;
@@ -348,13 +311,13 @@ __global__ __launch_bounds__(256) void rvb_pair_k(int NS, int R, long long n, co
 
   int used = 0;
   for (long long i = t; i < nf; i += 256) used += fx[(long long)RV_F_R * L.nf + i] > 0.0;
-  const int K = rvb_tree_int(s_int, used, t);
+  const int K = sig_tree(s_int, used, t);
   // the mean of d_t = c^x_t - c^y_t over the used frames
   for (int q = 0; q < RV_NQ; ++q) {
     double acc = 0.0;
     for (long long i = t; i < nf; i += 256)
       if (fx[(long long)RV_F_R * L.nf + i] > 0.0) acc += fx[(long long)(RV_F_CEP + q) * L.nf + i] - fy[(long long)(RV_F_CEP + q) * L.nf + i];
-    const double sum = rvb_tree(s_sum, acc, t);
+    const double sum = sig_tree(s_sum, acc, t);
     if (t == 0) s_dbar[q] = K > 0 ? sum / (double)K : 0.0;
   }
   __syncthreads();
@@ -414,8 +377,8 @@ __global__ __launch_bounds__(256) void rvb_pair_k(int NS, int R, long long n, co
     val[L.nf + i] = llr;
     val[2 * L.nf + i] = fw;
   }
-  const double sum_cd = rvb_tree(s_sum, a_cd, t), sum_llr = rvb_tree(s_sum, a_llr, t), sum_fw = rvb_tree(s_sum, a_fw, t);
-  const int K_llr = rvb_tree_int(s_int, n_llr, t);                     // its barriers also make val visible to the workgroup
+  const double sum_cd = sig_tree(s_sum, a_cd, t), sum_llr = sig_tree(s_sum, a_llr, t), sum_fw = sig_tree(s_sum, a_fw, t);
+  const int K_llr = sig_tree(s_int, n_llr, t);                     // its barriers also make val visible to the workgroup
   const bool valid = K >= 1 && Px > 0.0;
   double med_cd = nan, med_llr = nan, med_fw = nan;
   if (valid) {                                                         // uniform over the workgroup
@@ -438,22 +401,20 @@ __global__ __launch_bounds__(256) void rvb_pair_k(int NS, int R, long long n, co
   }
 }
 
-hipError_t launch_reverb_measure(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                                 const float* mix, const long long* ms, int B, int E, int R, long long n, const int* n_valid, int fs,
-                                 const double* table, double* out, int* count, double* frame_out, double* scratch, hipStream_t s) {
+hipError_t launch_reverb_measure(const SigView& est, const SigView& ref, const SigView& mix, int B, int E, int R, long long n,
+                                 const int* n_valid, int fs, const double* table, double* out, int* count, double* frame_out,
+                                 double* scratch, hipStream_t s) {
   RvbRate rt;
   if (!rvb_rate(fs, &rt)) return hipErrorInvalidValue;
   const long long nfr = reverb_frames(n, fs);
   if (nfr < 0) return hipErrorInvalidValue;
-  const RvbSrc vr = {ref, rs[0], rs[1], rs[2], 0}, ve = {est, es[0], es[1], es[2], est_is_i16};
-  const RvbSrc vm = {mix, mix ? ms[0] : 0, 0, mix ? ms[1] : 1, 0};
-  const int NS = R + E + (mix ? 1 : 0);
+  const int NS = R + E + (mix.p ? 1 : 0);
   hipError_t e;
-  hipLaunchKernelGGL(rvb_level_k, dim3(NS, B), dim3(256), 0, s, vr, ve, vm, R, E, n, n_valid, nfr, scratch);
+  hipLaunchKernelGGL(rvb_level_k, dim3(NS, B), dim3(256), 0, s, ref, est, mix, R, E, n, n_valid, nfr, scratch);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if (nfr > 0) {
-    hipLaunchKernelGGL(rvb_frame_k, dim3((unsigned)nfr, NS, B), dim3(256), 0, s, vr, ve, vm, R, E, n, n_valid, rt, nfr, table,
-                       scratch);
+    hipLaunchKernelGGL(rvb_frame_k, dim3((unsigned)nfr, NS, B), dim3(256), 0, s, ref, est, mix, R, E, n, n_valid, rt, nfr,
+                       table, scratch);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   hipLaunchKernelGGL(rvb_pair_k, dim3((NS - R) * R, B), dim3(256), 0, s, NS, R, n, n_valid, rt, nfr, scratch, frame_out, out, count);

@@ -41,7 +41,7 @@ __device__ __forceinline__ void load_group(const T* base, long long st, bool vec
   for (int k = 0; k < SCORE_GRP; ++k) v[k] = m0 + k < nv ? v[k] : 0.0f;
 }
 
-struct WaveView { const void* p; long long sb, ss, st; int vec; };     // element (item, source, sample); strides in elements
+struct WaveView { SigView v; int vec; };                               // vec: the view takes 16-byte loads (wave_vec)
 
 // grid (segments, items), 256 threads.  A lane adds its 16 samples of every signal in sample order, in double (the product
 // of two float32 values is exact there); 64-lane butterfly, then the four waves in wave order.
@@ -52,13 +52,9 @@ __global__ __launch_bounds__(256) void score_wave_k(const WaveView ve, const Wav
   constexpr int NS = 2 * E + 2 * R + E * R;
   __shared__ double s_tmp[4][NS];
   const int seg = blockIdx.x, b = blockIdx.y;
-  long long nv = n;
-  if (n_valid) {
-    const long long q = n_valid[b];
-    nv = q < 0 ? 0 : (q < n ? q : n);
-  }
-  const EstT* pe = reinterpret_cast<const EstT*>(ve.p) + (long long)b * ve.sb;
-  const float* pr = reinterpret_cast<const float*>(vr.p) + (long long)b * vr.sb;
+  const long long nv = sig_nv(n_valid, b, n);
+  const EstT* pe = reinterpret_cast<const EstT*>(ve.v.p) + (long long)b * ve.v.sb;
+  const float* pr = reinterpret_cast<const float*>(vr.v.p) + (long long)b * vr.v.sb;
   double acc[NS];
 #pragma unroll
   for (int i = 0; i < NS; ++i) acc[i] = 0.0;
@@ -68,9 +64,9 @@ __global__ __launch_bounds__(256) void score_wave_k(const WaveView ve, const Wav
     if (m0 >= nv) continue;                                            // nothing but zeros: the sums do not move
     float e[E][SCORE_GRP], r[R][SCORE_GRP];
 #pragma unroll
-    for (int i = 0; i < E; ++i) load_group(pe + (long long)i * ve.ss, ve.st, ve.vec != 0, m0, n, nv, e[i]);
+    for (int i = 0; i < E; ++i) load_group(pe + (long long)i * ve.v.ss, ve.v.st, ve.vec != 0, m0, n, nv, e[i]);
 #pragma unroll
-    for (int j = 0; j < R; ++j) load_group(pr + (long long)j * vr.ss, vr.st, vr.vec != 0, m0, n, nv, r[j]);
+    for (int j = 0; j < R; ++j) load_group(pr + (long long)j * vr.v.ss, vr.v.st, vr.vec != 0, m0, n, nv, r[j]);
 #pragma unroll
     for (int k = 0; k < SCORE_GRP; ++k) {
 #pragma unroll
@@ -164,21 +160,19 @@ static hipError_t wave_e(const WaveView& ve, const WaveView& vr, int B, int E, i
 long long score_wave_segments(long long n) { return (n + SCORE_SEG - 1) / SCORE_SEG; }
 
 // a view takes 16-byte loads when its samples are contiguous and every (item, source) row starts 16-byte aligned
-static int wave_vec(const void* p, long long sb, long long ss, long long st, int elem) {
-  const long long per = 16 / elem;
-  return st == 1 && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && sb % per == 0 && ss % per == 0;
+static int wave_vec(const SigView& v) {
+  const long long per = v.i16 ? 8 : 4;
+  return v.st == 1 && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0 && v.sb % per == 0 && v.ss % per == 0;
 }
 
-hipError_t launch_score_wave(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                             int B, int E, int R, long long n, const int* n_valid, double* part, double* stats,
-                             hipStream_t s) {
+hipError_t launch_score_wave(const SigView& est, const SigView& ref, int B, int E, int R, long long n, const int* n_valid,
+                             double* part, double* stats, hipStream_t s) {
   const int nseg = (int)score_wave_segments(n);
-  const WaveView ve = {est, es[0], es[1], es[2], wave_vec(est, es[0], es[1], es[2], est_is_i16 ? 2 : 4)};
-  const WaveView vr = {ref, rs[0], rs[1], rs[2], wave_vec(ref, rs[0], rs[1], rs[2], 4)};
-  const hipError_t e = est_is_i16 ? wave_e<int16_t>(ve, vr, B, E, R, n, nseg, n_valid, part, s)
-                                  : wave_e<float>(ve, vr, B, E, R, n, nseg, n_valid, part, s);
+  const WaveView ve = {est, wave_vec(est)}, vr = {ref, wave_vec(ref)};
+  const hipError_t e = est.i16 ? wave_e<int16_t>(ve, vr, B, E, R, n, nseg, n_valid, part, s)
+                               : wave_e<float>(ve, vr, B, E, R, n, nseg, n_valid, part, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(score_wave_fold_k, dim3(B), dim3(128), 0, s, part, nseg, E, R, est_is_i16 ? 1.0 / 32767.0 : 1.0, stats);
+  hipLaunchKernelGGL(score_wave_fold_k, dim3(B), dim3(128), 0, s, part, nseg, E, R, sig_unit(est), stats);
   return hipGetLastError();
 }
 

@@ -175,9 +175,8 @@ long long srmr_scratch_doubles(int B, int NS, long long n, int fs) {
   return pairs * SR_NMOD + srmr_group(pairs, L.slot) * L.slot;
 }
 
-struct SrmrSrc { const void* p; long long sb, ss, st; int i16; };
 struct SrmrArgs {
-  SrmrSrc sig, mix;
+  SigView sig, mix;
   int S, NS, Nw, Hw;
   long long n;
   const int* n_valid;
@@ -188,11 +187,7 @@ struct SrmrArgs {
   double* slots;
 };
 
-__device__ __forceinline__ long long sr_nv(const SrmrArgs& a, int b) {
-  if (!a.n_valid) return a.n;
-  const long long v = a.n_valid[b];
-  return v < 0 ? 0 : (v < a.n ? v : a.n);
-}
+__device__ __forceinline__ long long sr_nv(const SrmrArgs& a, int b) { return sig_nv(a.n_valid, b, a.n); }
 __device__ __forceinline__ int sr_log2_ceil(long long nv) {              // p with 2^p the smallest power of two >= nv (nv >= 1)
   return nv <= 1 ? 0 : 64 - __clzll((unsigned long long)(nv - 1));
 }
@@ -232,15 +227,12 @@ __global__ __launch_bounds__(64) void srmr_gt_k(const SrmrArgs a, long long g0, 
   if (PASS == 2) {
     z00 = st[0]; z01 = st[1]; z10 = st[2]; z11 = st[3]; z20 = st[4]; z21 = st[5]; z30 = st[6]; z31 = st[7];
   }
-  const SrmrSrc& v = pr.s < a.S ? a.sig : a.mix;
-  const long long base = (long long)pr.b * v.sb + (long long)(pr.s < a.S ? pr.s : 0) * v.ss;
-  const int16_t* p16 = reinterpret_cast<const int16_t*>(v.p);
-  const float* p32 = reinterpret_cast<const float*>(v.p);
+  long long base;
+  const SigView& v = sig_pick(a.sig, a.sig, a.mix, 0, a.S, pr.s, pr.b, &base);
   double* y = slot + m0;
 #pragma unroll 1
   for (int i = 0; i < len; ++i) {
-    const long long at = base + (m0 + i) * v.st;
-    const double x = (v.i16 ? (double)p16[at] / 32767.0 : (double)p32[at]) * gain;
+    const double x = sig_load(v, base, m0 + i) * gain;
     const double y0 = z00 + b0 * x;
     z00 = z01 + b10 * x - a1 * y0;
     z01 = -(a2 * y0);
@@ -603,16 +595,15 @@ __global__ __launch_bounds__(64) void srmr_final_k(const SrmrArgs a, double* out
   out[bs * 3 + 2] = bw;
 }
 
-hipError_t launch_srmr_measure(const void* sig, int sig_is_i16, const long long* ss, const float* mix, const long long* ms, int B,
-                               int S, long long n, const int* n_valid, int fs, const double* table, double* out, int* count,
-                               double* energy, double* scratch, hipStream_t s) {
+hipError_t launch_srmr_measure(const SigView& sig, const SigView& mix, int B, int S, long long n, const int* n_valid, int fs,
+                               const double* table, double* out, int* count, double* energy, double* scratch, hipStream_t s) {
   SrmrArgs a;
   int off;
   if (!srmr_rate(fs, &a.Nw, &a.Hw, &off)) return hipErrorInvalidValue;
-  a.sig = {sig, ss[0], ss[1], ss[2], sig_is_i16};
-  a.mix = {mix, mix ? ms[0] : 0, 0, mix ? ms[1] : 1, 0};
+  a.sig = sig;
+  a.mix = mix;
   a.S = S;
-  a.NS = S + (mix ? 1 : 0);
+  a.NS = S + (mix.p ? 1 : 0);
   a.n = n;
   a.n_valid = n_valid;
   a.tab = table;

@@ -69,15 +69,6 @@ int stoi_taps(int fs) {
   return stoi_rate(fs, &p, &q, &Lh, &off) ? 2 * Lh + 1 : -1;
 }
 
-static double bessel_i0(double x) {                     // sum_k ((x / 2)^k / k!)^2: every term positive
-  double s = 1.0, t = 1.0;
-  for (int k = 1; k < 64; ++k) {
-    t *= (x / 2.0) / k;
-    s += t * t;
-  }
-  return s;
-}
-
 void stoi_build_table(double* t) {
   const double pi = 3.14159265358979323846;
   for (int k = 0; k < ST_FRAME; ++k) t[ST_T_WIN + k] = 0.5 - 0.5 * std::cos(2.0 * pi * (k + 1) / (ST_FRAME + 1));
@@ -96,7 +87,7 @@ void stoi_build_table(double* t) {
       const double a = pi * 2.0 * fc * i;
       const double sinc = i == 0 ? 1.0 : std::sin(a) / a;
       const double u = (double)i / Lh;
-      const double kaiser = bessel_i0(beta * std::sqrt(1.0 - u * u)) / bessel_i0(beta);
+      const double kaiser = sig_i0(beta * std::sqrt(1.0 - u * u)) / sig_i0(beta);
       h[i + Lh] = 2.0 * p * fc * sinc * kaiser;
       sum += h[i + Lh];
     }
@@ -106,39 +97,31 @@ void stoi_build_table(double* t) {
 }
 
 // ---- the resampler -------------------------------------------------------------------------------------------------------
-struct StoiSrc { const void* p; long long sb, ss, st; int i16; };
-
 __device__ __forceinline__ long long stoi_len10(long long nv, int p, int q) { return (nv * p + q - 1) / q; }
-__device__ __forceinline__ long long stoi_nv(const int* n_valid, int b, long long n) {
-  if (!n_valid) return n;
-  const long long v = n_valid[b];
-  return v < 0 ? 0 : (v < n ? v : n);
-}
 
 // grid (ceil(n10 / 256), NS signals, items), 256 threads over the output samples.  Signal s < R: reference s; s < R + E:
 // estimate s - R; else the mixture.  Samples past the item's own length are written as zeros.
-__global__ __launch_bounds__(256) void stoi_resample_k(const StoiSrc ref, const StoiSrc est, const StoiSrc mix, int R, int E,
+__global__ __launch_bounds__(256) void stoi_resample_k(const SigView ref, const SigView est, const SigView mix, int R, int E,
                                                        long long n, const int* n_valid, int p, int q, int Lh, const double* g,
                                                        long long n10, double* x10, int* len10) {
   const int s = blockIdx.y, b = blockIdx.z, NS = gridDim.y;
   const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long nv = stoi_nv(n_valid, b, n);
+  const long long nv = sig_nv(n_valid, b, n);
   const long long l10 = stoi_len10(nv, p, q);
   if (m == 0 && s == 0) len10[b] = (int)l10;
   if (m >= n10) return;
-  const StoiSrc& v = s < R ? ref : (s < R + E ? est : mix);
-  const int src = s < R ? s : (s < R + E ? s - R : 0);
+  long long base;
+  const SigView& v = sig_pick(ref, est, mix, R, E, s, b, &base);
   double acc = 0.0;
   if (m < l10) {
     const long long c = m * q;
     long long j_lo = c - Lh <= 0 ? 0 : (c - Lh + p - 1) / p;          // ceil((m q - Lh) / p), not below 0
     long long j_hi = (c + Lh) / p;                                    // floor((m q + Lh) / p), not above nv - 1
     if (j_hi > nv - 1) j_hi = nv - 1;
-    const long long base = (long long)b * v.sb + (long long)src * v.ss;
     if (v.i16) {
       const int16_t* x = reinterpret_cast<const int16_t*>(v.p) + base;
       for (long long j = j_lo; j <= j_hi; ++j) acc += (double)x[j * v.st] * g[c - j * p + Lh];
-      acc *= 1.0 / 32767.0;                                           // the int16 rule of score.hip: scaled once, after the sum
+      acc *= SIG_I16_UNIT;                                            // scaled once, after the sum
     } else {
       const float* x = reinterpret_cast<const float*>(v.p) + base;
       for (long long j = j_lo; j <= j_hi; ++j) acc += (double)x[j * v.st] * g[c - j * p + Lh];
@@ -147,17 +130,14 @@ __global__ __launch_bounds__(256) void stoi_resample_k(const StoiSrc ref, const 
   x10[((long long)b * NS + s) * n10 + m] = acc;
 }
 
-hipError_t launch_stoi_resample(const void* est, int est_is_i16, const long long* es, const float* ref, const long long* rs,
-                                const float* mix, const long long* ms, int B, int E, int R, long long n, const int* n_valid,
-                                int fs, const double* table, double* x10, int* len10, hipStream_t s) {
+hipError_t launch_stoi_resample(const SigView& est, const SigView& ref, const SigView& mix, int B, int E, int R, long long n,
+                                const int* n_valid, int fs, const double* table, double* x10, int* len10, hipStream_t s) {
   int p, q, Lh, off;
   if (!stoi_rate(fs, &p, &q, &Lh, &off)) return hipErrorInvalidValue;
   const long long n10 = (n * p + q - 1) / q;
-  const StoiSrc vr = {ref, rs[0], rs[1], rs[2], 0}, ve = {est, es[0], es[1], es[2], est_is_i16};
-  const StoiSrc vm = {mix, mix ? ms[0] : 0, 0, mix ? ms[1] : 1, 0};
-  const int NS = R + E + (mix ? 1 : 0);
-  hipLaunchKernelGGL(stoi_resample_k, dim3((unsigned)((n10 + 255) / 256), NS, B), dim3(256), 0, s, vr, ve, vm, R, E, n, n_valid,
-                     p, q, Lh, table + off, n10, x10, len10);
+  const int NS = R + E + (mix.p ? 1 : 0);
+  hipLaunchKernelGGL(stoi_resample_k, dim3((unsigned)((n10 + 255) / 256), NS, B), dim3(256), 0, s, ref, est, mix, R, E, n,
+                     n_valid, p, q, Lh, table + off, n10, x10, len10);
   return hipGetLastError();
 }
 
@@ -180,12 +160,6 @@ __host__ __device__ inline StoiLay stoi_layout(int NS, int R, long long n10) {
 }
 long long stoi_item_doubles(int NS, int R, long long n10) { return stoi_layout(NS, R, n10).total; }
 
-__device__ __forceinline__ long long stoi_len(const int* len10, int b, long long n10) {
-  if (!len10) return n10;
-  const long long v = len10[b];
-  return v < 0 ? 0 : (v < n10 ? v : n10);
-}
-
 // grid (ceil(nf / 4), R, items), 256 threads: wave w takes frame 4 x + w.  Lane l adds the squares of samples l, l + 64,
 // l + 128, l + 192 in that order; 64-lane butterfly.
 __global__ __launch_bounds__(256) void stoi_energy_k(const double* x10, const int* len10, int NS, int R, long long n10,
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(256) void stoi_energy_k(const double* x10, const in
   const int r = blockIdx.y, b = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const StoiLay L = stoi_layout(NS, R, n10);
   const long long i = (long long)blockIdx.x * 4 + wave;
-  if (i >= stoi_frames(stoi_len(len10, b, n10))) return;
+  if (i >= stoi_frames(sig_nv(len10, b, n10))) return;
   const double* x = x10 + ((long long)b * NS + r) * n10 + i * ST_HOP;
   const double* w = table + ST_T_WIN;
   double v = 0.0;
@@ -216,7 +190,7 @@ __global__ __launch_bounds__(256) void stoi_mask_k(const double* x10, const int*
   __shared__ int s_nz[256];
   const int r = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   const StoiLay L = stoi_layout(NS, R, n10);
-  const long long len = stoi_len(len10, b, n10), nf = stoi_frames(len);
+  const long long len = sig_nv(len10, b, n10), nf = stoi_frames(len);
   const double* e = scratch + (long long)b * L.total + L.e + (long long)r * L.nf;
   int* idx = reinterpret_cast<int*>(scratch + (long long)b * L.total + L.idx) + (long long)r * L.nf;
   const double* x = x10 + ((long long)b * NS + r) * n10;

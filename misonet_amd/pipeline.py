@@ -877,20 +877,7 @@ class Enhancer:
             res = self.enhance_recording(wav_observe, wav_clean, num_ch_utilize, chunk_size, max_batch, save_path, fs, score,
                                          bss, bss_filt_len, stoi, reverb)
             return (res if isinstance(res, tuple) else (res,)) + (self._srmr_of(res, wav_observe, num_ch_utilize, fs),)
-        if bss and not score:
-            raise ValueError("bss=True needs score=True (and the clean sources)")
-        if stoi and not score:
-            raise ValueError("stoi=True needs score=True (and the clean sources)")
-        if reverb and not score:
-            raise ValueError("reverb=True needs score=True (and the clean sources)")
-        if score and wav_clean is None:
-            raise ValueError("score=True needs the clean sources (wav_clean)")
-        if stoi:
-            from . import score as SC
-            SC.check_stoi_fs(fs)
-        if reverb:
-            from . import score as SC
-            SC.check_reverb_fs(fs)
+        asked = self._side_asked(score, wav_clean is None, fs, bss_filt_len, bss=bss, stoi=stoi, reverb=reverb)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -909,18 +896,10 @@ class Enhancer:
             pcm = np.concatenate([g[0] for g in got], axis=0)
             rows = [(g[1][0][b], g[1][1][b]) for g in got for b in range(g[0].shape[0])]
             out, sc = self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs), self._recording_score(rows, nv)
-            if not bss and not stoi and not reverb:
+            if not asked:
                 return out, sc
-            from . import score as SC
             clean, mix = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
-            res = (out, sc)
-            if bss:
-                res = res + (SC.bss_eval_waves(out, clean, mix, filt_len=bss_filt_len, device=self.device),)
-            if stoi:
-                res = res + (SC.stoi_waves(out, clean, mix, fs=fs, device=self.device),)
-            if reverb:
-                res = res + (SC.reverb_waves(out, clean, mix, fs=fs, device=self.device),)
-            return res
+            return (out, sc) + tuple(f.waves(out, clean, mix, par, self.device) for f, par in asked)
 
         def batches():
             for lo in range(0, K, max_batch):
@@ -929,6 +908,19 @@ class Enhancer:
 
         pcm = np.concatenate(list(self.stream_wav(batches())), axis=0)     # [K, S, chunk]
         return self._finish_recording([pcm[k] for k in range(K)], gap, save_path, fs)
+
+    @staticmethod
+    def _side_asked(score, clean_missing, fs, bss_filt_len, **flags):
+        """the flags of the recording paths for the figures of ``score.SIDE_FIGURES`` that take the clean sources -> [(figure,
+        its parameter)] of those asked for, in the order they are appended; ValueError for a flag without ``score=True``, for
+        ``score=True`` without clean sources (``clean_missing``) and for a rate a figure is not defined at"""
+        from . import score as SC
+        figs = [f for f in SC.SIDE_FIGURES if f.needs_clean and flags[f.name]]
+        if figs and not score:
+            raise ValueError(f"{figs[0].name}=True needs score=True (and the clean sources)")
+        if score and clean_missing:
+            raise ValueError("score=True needs the clean sources (wav_clean)")
+        return [(f, bss_filt_len if f.rates is None else f.check(fs)) for f in figs]
 
     def _srmr_of(self, res, wav_observe, num_ch_utilize, fs):
         """the :class:`score.Srmr` of a recording's result (int16 [S, L], or a tuple that starts with it) with the original
@@ -1205,18 +1197,7 @@ class Enhancer:
                     res[k] = (res[k] if isinstance(res[k], tuple) else (res[k],)) + \
                         (SC.srmr_unpack(row, self.num_spks, int(fs), p.shape[1]),)
             return res
-        if bss and not score:
-            raise ValueError("bss=True needs score=True (and the clean sources)")
-        if stoi and not score:
-            raise ValueError("stoi=True needs score=True (and the clean sources)")
-        if reverb and not score:
-            raise ValueError("reverb=True needs score=True (and the clean sources)")
-        if stoi:
-            from . import score as SC
-            SC.check_stoi_fs(fs)
-        if reverb:
-            from . import score as SC
-            SC.check_reverb_fs(fs)
+        asked = self._side_asked(score, False, fs, bss_filt_len, bss=bss, stoi=stoi, reverb=reverb)
         self._ready()
         if self.model is None:
             raise RuntimeError("this Enhancer was built without MISO_3 (separation only): use separate() / beamform_*()")
@@ -1231,7 +1212,7 @@ class Enhancer:
                     key = key + ((1,),)                              # the chunk's valid count rides as a third input
                     if mpieces is not None:
                         key = key + (mpieces[0].shape,)              # and the original observation at ref_ch as a fourth
-                if bss or stoi or reverb:
+                if asked:
                     side_refs[i] = self._wave_refs(wav_observe, wav_clean, num_ch_utilize)
                 yield Item(i, 1, len(pieces), key, (pieces, cpieces, gap, name, mpieces))
 
@@ -1248,16 +1229,15 @@ class Enhancer:
 
         results = {}
         side_refs, side_wait, side_done = {}, [], []
-        if bss or stoi or reverb:
+        if asked:
             from . import score as SC
             side = torch.cuda.Stream(self.device)
 
             def side_flush():
                 with torch.cuda.stream(side):
-                    blocks = SC.side_queue(
-                        [w[1:] for w in side_wait], self.device, pinned=True, bss_filt_len=bss_filt_len if bss else None,
-                        stoi_fs=fs if stoi else None, reverb_fs=fs if reverb else None)   # one padded, pinned batch serves all
-                    side_done.append(([w[0] for w in side_wait],) + tuple(blocks[:2]) + (blocks[2] if reverb else None,))
+                    blocks = SC._side_blocks([w[1:] for w in side_wait], self.device, True,
+                                             {f.name: par for f, par in asked})   # one padded, pinned batch serves all
+                    side_done.append(([w[0] for w in side_wait], blocks))
                 side_wait.clear()
         for it in self._coalesced(items(), fill, self._wav_pass_score if score else self._wav_pass, torch.float32, max_batch,
                                   depth, lambda c: str(c.item.payload[3]),
@@ -1268,27 +1248,20 @@ class Enhancer:
                 n = pieces[0].shape[0]
                 pcm = self._finish_recording([o[0][0] for o in it.outputs], gap, path, fs)
                 results[name] = (pcm, self._recording_score([o[0][1:] for o in it.outputs], [n] * (len(pieces) - 1) + [n - gap]))
-                if bss or stoi or reverb:
+                if asked:
                     side_wait.append((name, pcm) + side_refs.pop(it.index))
                     if len(side_wait) >= self.BSS_GROUP:
                         side_flush()
             else:
                 results[name] = self._finish_recording([o[0] for o in it.outputs], gap, path, fs)
-        if bss or stoi or reverb:
+        if asked:
             if side_wait:
                 side_flush()
             side.synchronize()
-            for names, block, sblock, rblock in side_done:
-                if bss:
-                    for name, row in zip(names, block.cpu().numpy()):
-                        pcm, sc = results[name]
-                        results[name] = (pcm, sc, SC.bss_unpack(row, self.num_spks, int(bss_filt_len), pcm.shape[1]))
-                if stoi:
-                    for name, row in zip(names, sblock.cpu().numpy()):
-                        results[name] = results[name] + (SC.stoi_unpack(row, self.num_spks, int(fs), results[name][0].shape[1]),)
-                if reverb:
-                    for name, row in zip(names, rblock.cpu().numpy()):
-                        results[name] = results[name] + (SC.reverb_unpack(row, self.num_spks, int(fs), results[name][0].shape[1]),)
+            for names, blocks in side_done:
+                for f, par in asked:
+                    for name, row in zip(names, blocks[f.name].cpu().numpy()):
+                        results[name] = results[name] + (f.unpack(row, self.num_spks, par, results[name][0].shape[1]),)
         return results
 
     def inference(self, data_loader, saveDir, fs=16000, write=True, max_batch=32, coalesce=True, depth=2, score=False):

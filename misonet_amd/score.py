@@ -103,6 +103,10 @@ def upit(pair) -> Tuple[float, List[int]]:
     return float(vbest), best
 
 
+def _lst(x):
+    return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
+
+
 @dataclasses.dataclass
 class Score:
     """The scores of one recording, speaker j = reference j.  ``perm_best != identity`` means that the magnitude alignment
@@ -119,13 +123,11 @@ class Score:
     loss_enhance: Optional[np.ndarray] = None   # [S] criterion.py loss_Enhance of output j against reference j
 
     def as_dict(self) -> dict:
-        def lst(x):
-            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
-        return dict(si_sdr=lst(self.si_sdr), si_sdr_mix=lst(self.si_sdr_mix), si_sdri=lst(self.si_sdri), snr=lst(self.snr),
+        return dict(si_sdr=_lst(self.si_sdr), si_sdr_mix=_lst(self.si_sdr_mix), si_sdri=_lst(self.si_sdri), snr=_lst(self.snr),
                     valid=[bool(v) for v in self.valid], perm_best=[int(p) for p in self.perm_best],
-                    si_sdr_best=lst(self.si_sdr_best), n_samples=int(self.n_samples),
+                    si_sdr_best=_lst(self.si_sdr_best), n_samples=int(self.n_samples),
                     loss_miso1=None if self.loss_miso1 is None else float(self.loss_miso1),
-                    loss_enhance=lst(self.loss_enhance))
+                    loss_enhance=_lst(self.loss_enhance))
 
 
 def from_stats(stats_est, n, stats_mix=None, loss_miso1=None, loss_enhance=None) -> Score:
@@ -147,14 +149,21 @@ def from_stats(stats_est, n, stats_mix=None, loss_miso1=None, loss_enhance=None)
                  loss_miso1=loss_miso1, loss_enhance=None if loss_enhance is None else np.asarray(loss_enhance, np.float64))
 
 
+def _mean_valid(items, keys) -> dict:
+    """{key: the mean of item.key[j] over the items that have the figure and their valid speakers j where it is finite, or
+    None}: what every ``*_mean_of`` starts from"""
+    out = {}
+    for key in keys:
+        vals = [float(getattr(e, key)[j]) for e in items if getattr(e, key) is not None
+                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
+        out[key] = float(np.mean(vals)) if vals else None
+    return out
+
+
 def mean_of(scores: Sequence[Score]) -> dict:
     """The ``"mean"`` entry of scores.json: the dB figures averaged over the valid speakers of every recording, the
     criterion values over the recordings that have them."""
-    out = {}
-    for key in ("si_sdr", "si_sdr_mix", "si_sdri", "snr", "si_sdr_best"):
-        vals = [float(getattr(s, key)[j]) for s in scores if getattr(s, key) is not None
-                for j in range(len(s.valid)) if s.valid[j] and np.isfinite(getattr(s, key)[j])]
-        out[key] = float(np.mean(vals)) if vals else None
+    out = _mean_valid(scores, ("si_sdr", "si_sdr_mix", "si_sdri", "snr", "si_sdr_best"))
     l1 = [float(s.loss_miso1) for s in scores if s.loss_miso1 is not None]
     le = [float(v) for s in scores if s.loss_enhance is not None for v in s.loss_enhance]
     out["loss_miso1"] = float(np.mean(l1)) if l1 else None
@@ -181,6 +190,104 @@ def _wave_view(x, name, dtypes):
     return x
 
 
+def _check_counts(n_valid, B, dev, name="n_valid"):
+    import torch
+    if n_valid is not None and (not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev
+                                or n_valid.numel() != B or not n_valid.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous int32 device tensor of {B} entries")
+
+
+def _check_views(est, ref, mix, n_valid, what="est", most=4096):
+    """What the device steps of BSS-eval, STOI, the reverb figures and SRMR ask of their input: ``est`` (named ``what``) int16 or
+    float32 [B, E, n], ref float32 [B, R, n] or None (SRMR), mix float32 [B, 1, n] or None, all views on one device; 1 <= E, R
+    <= 4, n <= 2^24, 1 <= B <= ``most`` (None: any); n_valid a contiguous int32 device tensor of B entries or None.
+    Returns (B, E, R or None, n, device)."""
+    import torch
+    est = _wave_view(est, what, (torch.int16, torch.float32))
+    B, E, n = est.shape
+    dev, R = est.device, None
+    if ref is not None:
+        ref = _wave_view(ref, "ref", (torch.float32,))
+        if ref.shape[0] != B or ref.shape[2] != n or ref.device != dev:
+            raise ValueError("est and ref must agree in B, n and device")
+        R = ref.shape[1]
+        if not (1 <= E <= 4 and 1 <= R <= 4):
+            raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+    _signal_limits(E, n)
+    if B < 1 or (most is not None and B > most):
+        raise ValueError("at least one item" if most is None else f"1 <= B <= {most} items")
+    if mix is not None:
+        mix = _wave_view(mix, "mix", (torch.float32,))
+        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
+            raise ValueError(f"mix must be [B, 1, n] on the device of {what}")
+    _check_counts(n_valid, B, dev)
+    return B, E, R, n, dev
+
+
+def _ptr(x):
+    return x.data_ptr() if x is not None else None
+
+
+def _view_args(est, ref=None):
+    """the leading arguments of the C entry points: the estimates (pointer, int16 flag, three strides) and, unless None, the
+    references (pointer, three strides)"""
+    import torch
+    a = (est.data_ptr(), int(est.dtype == torch.int16)) + tuple(est.stride())
+    return a if ref is None else a + (ref.data_ptr(),) + tuple(ref.stride())
+
+
+def _mix_args(mix):
+    """the mixture [B, 1, n] or None as the C entry points take it: pointer, item stride, sample stride"""
+    return (mix.data_ptr(), mix.stride(0), mix.stride(2)) if mix is not None else (None, 0, 1)
+
+
+def _call(fn, dev, *args):
+    """one C entry point, queued on the current stream of ``dev``"""
+    import torch
+    with torch.cuda.device(dev):
+        _lib.check(fn(*args, _lib.stream_ptr(dev)))
+
+
+def _scratch(nb, dev):
+    import torch
+    return torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+
+
+def _limits(S, L, what="speakers"):
+    if not (1 <= S <= 4):
+        raise ValueError(f"1 <= S <= 4 {what} (got {S})")
+    if not (1 <= L <= 1 << 24):
+        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
+
+
+def _signal_limits(S, L):
+    _limits(S, L, "signals")
+
+
+def _check_fs(fs, rates, what):
+    if int(fs) != fs or int(fs) not in rates:
+        raise ValueError(f"{what} defined here for fs = {', '.join(str(r) for r in rates[:-1])} or {rates[-1]} Hz (got {fs})")
+    return int(fs)
+
+
+def _groups(B, per_item, cap, most=None):
+    """[(lo, hi)]: B items in runs whose scratch of ``per_item`` bytes each stays under ``cap``, of at most ``most`` items"""
+    g = max(1, min(B, cap // max(1, per_item), most or B))
+    return [(lo, min(B, lo + g)) for lo in range(0, B, g)]
+
+
+def _block_rows(groups, est, ref, mix, n_valid, measure):
+    """``measure(est, ref, mix, n_valid)`` -> tensors [b, ...] over every group of items; each item's flattened as float64 side
+    by side, the groups one under the other: the device block [B, W] of ``stoi_block`` and ``reverb_block``"""
+    import torch
+    rows = []
+    for lo, hi in groups:
+        got = measure(est[lo:hi], ref[lo:hi], mix[lo:hi] if mix is not None else None,
+                      n_valid[lo:hi] if n_valid is not None else None)
+        rows.append(torch.cat([t.to(torch.float64).reshape(hi - lo, -1) for t in got], dim=1))
+    return rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+
+
 def wave_stats(est, ref, n_valid=None):
     """est int16 or float32 [B, E, n], ref float32 [B, R, n] (device; strided views are read in place, e.g.
     ``clean_wav.transpose(1, 2)`` of a time-major [B, n, S]); n_valid int32 [B] (device) or None = n.  Returns float64
@@ -193,19 +300,12 @@ def wave_stats(est, ref, n_valid=None):
         raise ValueError("est and ref must agree in B, n and device")
     R = ref.shape[1]
     dev = est.device
-    if n_valid is not None:
-        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
-                or n_valid.numel() != B or not n_valid.is_contiguous():
-            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    _check_counts(n_valid, B, dev)
     out = torch.empty((B, E, R, 5), dtype=torch.float64, device=dev)
     L = _lib.lib()
-    nb = max(8, int(L.misonet_score_scratch_bytes(B, max(E, 1), max(R, 1), n))) if B > 0 and n > 0 else 8
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_score_wave(est.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
-                                        est.stride(2), ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), B, E, R,
-                                        n, n_valid.data_ptr() if n_valid is not None else None, out.data_ptr(),
-                                        scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    scratch = _scratch(int(L.misonet_score_scratch_bytes(B, max(E, 1), max(R, 1), n)) if B > 0 and n > 0 else 0, dev)
+    _call(L.misonet_score_wave, dev, *_view_args(est, ref), B, E, R, n, _ptr(n_valid), out.data_ptr(), scratch.data_ptr(),
+          scratch.numel())
     return out
 
 
@@ -230,13 +330,9 @@ def spec_pairs(est, ref, return_value=False):
     perm = torch.empty((B, R), dtype=torch.int32, device=dev) if pick else None
     val = torch.empty((B,), dtype=torch.float64, device=dev) if pick else None
     L = _lib.lib()
-    nb = max(8, int(L.misonet_score_scratch_bytes(B, max(E, 1), max(R, 1), F))) if B > 0 and F > 0 else 8
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_score_spec(est.data_ptr(), est.stride(0), est.stride(1), est.stride(2), ref.data_ptr(),
-                                        ref.stride(0), ref.stride(1), ref.stride(2), B, E, R, T, F, pair.data_ptr(),
-                                        perm.data_ptr() if pick else None, val.data_ptr() if pick else None,
-                                        scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    scratch = _scratch(int(L.misonet_score_scratch_bytes(B, max(E, 1), max(R, 1), F)) if B > 0 and F > 0 else 0, dev)
+    _call(L.misonet_score_spec, dev, est.data_ptr(), *est.stride()[:3], ref.data_ptr(), *ref.stride()[:3], B, E, R, T, F,
+          pair.data_ptr(), _ptr(perm), _ptr(val), scratch.data_ptr(), scratch.numel())
     return (pair, perm, val) if return_value else (pair, perm)
 
 
@@ -306,11 +402,9 @@ class BssEval:
     n_samples: int
 
     def as_dict(self) -> dict:
-        def lst(x):
-            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
-        return dict(sdr=lst(self.sdr), sir=lst(self.sir), sar=lst(self.sar), valid=[bool(v) for v in self.valid],
-                    ok=bool(self.ok), perm_best=[int(p) for p in self.perm_best], sdr_best=lst(self.sdr_best),
-                    sir_best=lst(self.sir_best), sar_best=lst(self.sar_best), sdr_mix=lst(self.sdr_mix), sdri=lst(self.sdri),
+        return dict(sdr=_lst(self.sdr), sir=_lst(self.sir), sar=_lst(self.sar), valid=[bool(v) for v in self.valid],
+                    ok=bool(self.ok), perm_best=[int(p) for p in self.perm_best], sdr_best=_lst(self.sdr_best),
+                    sir_best=_lst(self.sir_best), sar_best=_lst(self.sar_best), sdr_mix=_lst(self.sdr_mix), sdri=_lst(self.sdri),
                     filt_len=int(self.filt_len), n_samples=int(self.n_samples))
 
 
@@ -361,11 +455,7 @@ def bss_from_energies(T, A, Eee, valid=None, ok: bool = True, T_mix=None, Eee_mi
 def bss_mean_of(evals: Sequence[BssEval]) -> dict:
     """The ``"bss"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers of the
     recordings whose factorisation succeeded."""
-    out = {}
-    for key in ("sdr", "sir", "sar", "sdr_best", "sir_best", "sar_best", "sdr_mix", "sdri"):
-        vals = [float(getattr(e, key)[j]) for e in evals if e.ok and getattr(e, key) is not None
-                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
-        out[key] = float(np.mean(vals)) if vals else None
+    out = _mean_valid([e for e in evals if e.ok], ("sdr", "sir", "sar", "sdr_best", "sir_best", "sar_best", "sdr_mix", "sdri"))
     out["n_recordings"] = len(evals)
     out["n_failed"] = int(sum(1 for e in evals if not e.ok))
     return out
@@ -377,18 +467,11 @@ def bss_scratch_bytes(B: int, E: int, R: int, n: int, filt_len: int = 512) -> in
     return int(_lib.lib().misonet_bss_scratch_bytes(int(B), int(E), int(R), int(n), int(filt_len)))
 
 
-def _bss_limits(E, R, Q, n=1):
-    if not (1 <= E <= 4 and 1 <= R <= 4):
-        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+def _check_filt_len(filt_len):
+    Q = int(filt_len)
     if not (16 <= Q <= 1024) or Q % 16:
         raise ValueError(f"filt_len must be a multiple of 16 in [16, 1024] (got {Q})")
-    if not (1 <= n <= 1 << 24):
-        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
-
-
-def _bss_groups(B, per_item):
-    g = max(1, min(B, 4096, BSS_SCRATCH_CAP // max(1, per_item)))
-    return [(lo, min(B, lo + g)) for lo in range(0, B, g)]
+    return Q
 
 
 def bss_corr(est, ref, n_valid=None, filt_len: int = 512):
@@ -396,35 +479,18 @@ def bss_corr(est, ref, n_valid=None, filt_len: int = 512):
     [B] (device) or None.  Returns float64 (Rrr [B, R, R, Q], Rre [B, R, E, Q], Eee [B, E]).  Asynchronous on the current
     stream; an item's block does not depend on the batch."""
     import torch
-    est = _wave_view(est, "est", (torch.int16, torch.float32))
-    ref = _wave_view(ref, "ref", (torch.float32,))
-    B, E, n = est.shape
-    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
-        raise ValueError("est and ref must agree in B, n and device")
-    R, Q = ref.shape[1], int(filt_len)
-    _bss_limits(E, R, Q, n)
-    if B < 1:
-        raise ValueError("at least one item")
-    dev = est.device
-    if n_valid is not None:
-        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
-                or n_valid.numel() != B or not n_valid.is_contiguous():
-            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    B, E, R, n, dev = _check_views(est, ref, None, n_valid, most=None)
+    Q = _check_filt_len(filt_len)
     Rrr = torch.empty((B, R, R, Q), dtype=torch.float64, device=dev)
     Rre = torch.empty((B, R, E, Q), dtype=torch.float64, device=dev)
     Eee = torch.empty((B, E), dtype=torch.float64, device=dev)
     L = _lib.lib()
-    groups = _bss_groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, n, Q)))
-    nb = int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, n, Q))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        for lo, hi in groups:
-            e, r = est[lo:hi], ref[lo:hi]
-            _lib.check(L.misonet_bss_corr(e.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
-                                          est.stride(2), r.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2), hi - lo,
-                                          E, R, n, n_valid[lo:hi].data_ptr() if n_valid is not None else None, Q,
-                                          Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(), Eee[lo:hi].data_ptr(),
-                                          scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    groups = _groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, n, Q)), BSS_SCRATCH_CAP, 4096)
+    scratch = _scratch(int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, n, Q)), dev)
+    for lo, hi in groups:
+        _call(L.misonet_bss_corr, dev, *_view_args(est[lo:hi], ref[lo:hi]), hi - lo, E, R, n,
+              _ptr(n_valid[lo:hi] if n_valid is not None else None), Q, Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(),
+              Eee[lo:hi].data_ptr(), scratch.data_ptr(), scratch.numel())
     return Rrr, Rre, Eee
 
 
@@ -443,7 +509,9 @@ def bss_solve(Rrr, Rre, Eee):
     if R2 != R or tuple(Rre.shape) != (B, R, E, Q) or tuple(Eee.shape) != (B, E) or Rre.device != Rrr.device \
             or Eee.device != Rrr.device:
         raise ValueError("Rrr [B, R, R, Q], Rre [B, R, E, Q] and Eee [B, E] must agree")
-    _bss_limits(E, R, Q)
+    if not (1 <= E <= 4 and 1 <= R <= 4):
+        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
+    _check_filt_len(Q)
     if B < 1:
         raise ValueError("at least one item")
     dev = Rrr.device
@@ -451,14 +519,11 @@ def bss_solve(Rrr, Rre, Eee):
     A = torch.empty((B, E), dtype=torch.float64, device=dev)
     info = torch.empty((B,), dtype=torch.int32, device=dev)
     L = _lib.lib()
-    groups = _bss_groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, 1, Q)))
-    nb = int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, 1, Q))
-    scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        for lo, hi in groups:
-            _lib.check(L.misonet_bss_solve(Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(), Eee[lo:hi].data_ptr(), hi - lo, E, R,
-                                           Q, T[lo:hi].data_ptr(), A[lo:hi].data_ptr(), info[lo:hi].data_ptr(),
-                                           scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    groups = _groups(B, int(L.misonet_bss_scratch_bytes(1, E, R, 1, Q)), BSS_SCRATCH_CAP, 4096)
+    scratch = _scratch(int(L.misonet_bss_scratch_bytes(groups[0][1] - groups[0][0], E, R, 1, Q)), dev)
+    for lo, hi in groups:
+        _call(L.misonet_bss_solve, dev, Rrr[lo:hi].data_ptr(), Rre[lo:hi].data_ptr(), Eee[lo:hi].data_ptr(), hi - lo, E, R, Q,
+              T[lo:hi].data_ptr(), A[lo:hi].data_ptr(), info[lo:hi].data_ptr(), scratch.data_ptr(), scratch.numel())
     return T, A, info
 
 
@@ -496,32 +561,38 @@ def bss_unpack(row, S: int, filt_len: int, n_samples: int) -> BssEval:
 
 
 def _wave_batch(items, dev, pinned, limits):
-    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) -> the device tensors
-    (est [G, S, n], clean [G, S, n], mix [G, 1, n] or None, n_valid int32 [G] or None for a single recording), zero-padded to
-    the longest; ``limits(S, L)`` raises for what the caller does not take.  Must run under ``torch.cuda.device(dev)``."""
+    """items: a list of (est int16 or float32 [S, L], clean float32 [S, L] -- or None in every item: SRMR's signals have no clean
+    sources --, mix float32 [L] or None) -> the device tensors (est [G, S, n], clean [G, S, n] or None, mix [G, 1, n] or None,
+    n_valid int32 [G] or None for a single recording), zero-padded to the longest; ``limits(S, L)`` raises for what the caller
+    does not take.  Must run under ``torch.cuda.device(dev)``."""
     import torch
     recs = []
     for est, clean, mix in items:
-        est, clean = torch.as_tensor(est), torch.as_tensor(clean)
-        if est.dim() != 2 or clean.dim() != 2 or est.shape != clean.shape:
-            raise ValueError("est and clean must both be [S, L]")
+        est = torch.as_tensor(est)
+        if clean is not None:
+            clean = torch.as_tensor(clean)
+            if est.dim() != 2 or clean.dim() != 2 or est.shape != clean.shape:
+                raise ValueError("est and clean must both be [S, L]")
+            clean = clean.to(torch.float32)
+        elif est.dim() != 2:
+            raise ValueError("signals must be [S, L]")
         if est.dtype != torch.int16:
             est = est.to(torch.float32)
         if mix is not None:
-            mix = torch.as_tensor(mix).to(torch.float32).reshape(-1)
+            mix = torch.as_tensor(mix).to(torch.float32).reshape(1, -1)
             if mix.numel() != est.shape[1]:
                 raise ValueError("mix must hold L samples")
-        recs.append((est, clean.to(torch.float32), mix))
+        recs.append((est, clean, mix))
     if not recs:
         raise ValueError("at least one recording")
-    S, G = recs[0][0].shape[0], len(recs)
-    if any(r[0].shape[0] != S for r in recs) or any((r[2] is None) != (recs[0][2] is None) for r in recs):
+    S = recs[0][0].shape[0]
+    if any(r[0].shape[0] != S or (r[1] is None) != (recs[0][1] is None) or (r[2] is None) != (recs[0][2] is None) for r in recs):
         raise ValueError("every recording must have the same number of speakers, and all or none a mixture")
     for r in recs:
         limits(S, r[0].shape[1])
     if any(r[0].dtype != recs[0][0].dtype for r in recs):
         raise ValueError("int16 and float32 estimates cannot share a batch")
-    cols, nv = _pad_batch([(e, c, m.reshape(1, -1) if m is not None else None) for e, c, m in recs], dev, pinned)
+    cols, nv = _pad_batch(recs, dev, pinned)
     return cols[0], cols[1], cols[2], nv
 
 
@@ -555,6 +626,21 @@ def _pad_batch(recs, dev, pinned):
     return cols, nv
 
 
+def _side_blocks(items, dev, pinned, params):
+    """:func:`side_queue` by name: ``params`` = {name of a figure of SIDE_FIGURES: its parameter (the filter length of "bss",
+    the rate of the others), or None} -> {name: device block} of the figures asked for, all from one batch"""
+    import torch
+    figs = [(f, f.check(params[f.name])) for f in SIDE_FIGURES if params.get(f.name) is not None]
+
+    def limits(S, L):
+        for f, _ in figs:
+            f.limits(S, L)
+
+    with torch.cuda.device(dev):
+        est, clean, mix, nv = _wave_batch(items, dev, pinned, limits)
+        return {f.name: f.block(est, clean, mix, nv, par) if f.needs_clean else f.block(est, mix, nv, par) for f, par in figs}
+
+
 def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = None, stoi_fs: Optional[int] = None,
                reverb_fs: Optional[int] = None, srmr_fs: Optional[int] = None):
     """items: a list of (est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None) (ndarrays or tensors; the
@@ -566,32 +652,20 @@ def side_queue(items, dev, pinned: bool = False, bss_filt_len: Optional[int] = N
     ``reverb_fs`` (not None): a third entry, the block of :func:`reverb_block` at that rate, from the same batch; without it
     the pair is returned as it always was.  ``srmr_fs`` (not None): four entries, (bss, stoi, reverb or None, the block of
     :func:`srmr_block` of the estimates and the mixture at that rate), again from the same batch."""
+    got = _side_blocks(items, dev, pinned, dict(bss=bss_filt_len, stoi=stoi_fs, reverb=reverb_fs, srmr=srmr_fs))
+    return tuple(got.get(f.name) for f in SIDE_FIGURES)[:4 if srmr_fs is not None else 3 if reverb_fs is not None else 2]
+
+
+def _one_recording(est, limits, device, queue, unpack):
+    """What every ``*_waves`` does with its first argument [S, L] once the rate is checked: ``limits(S, L)`` before a device is
+    touched, the device, ``queue(est, device)`` -> a block of one row, ``unpack(row, S, L)``"""
     import torch
-    if srmr_fs is not None:
-        srmr_fs = check_srmr_fs(srmr_fs)
-    if stoi_fs is not None:
-        stoi_fs = check_stoi_fs(stoi_fs)
-    if reverb_fs is not None:
-        reverb_fs = check_reverb_fs(reverb_fs)
-
-    def limits(S, L):
-        if bss_filt_len is not None:
-            _bss_limits(S, S, int(bss_filt_len), L)
-        if stoi_fs is not None:
-            _stoi_limits(S, L)
-        if reverb_fs is not None:
-            _reverb_limits(S, L)
-        if srmr_fs is not None:
-            _srmr_limits(S, L)
-
-    with torch.cuda.device(dev):
-        est, clean, mix, nv = _wave_batch(items, dev, pinned, limits)
-        res = (bss_energies(est, clean, mix, nv, int(bss_filt_len)) if bss_filt_len is not None else None,
-               stoi_block(est, clean, mix, nv, stoi_fs) if stoi_fs is not None else None)
-        if srmr_fs is not None:
-            return res + (reverb_block(est, clean, mix, nv, reverb_fs) if reverb_fs is not None else None,
-                          srmr_block(est, mix, nv, srmr_fs))
-        return res if reverb_fs is None else res + (reverb_block(est, clean, mix, nv, reverb_fs),)
+    est = torch.as_tensor(est)
+    if est.dim() == 2:
+        limits(int(est.shape[0]), int(est.shape[1]))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    row = queue(est, dev)[0].cpu().numpy()
+    return unpack(row, int(est.shape[0]), int(est.shape[1]))
 
 
 def bss_queue(items, filt_len: int, dev, pinned: bool = False):
@@ -603,11 +677,8 @@ def bss_eval_waves(est, clean, mix=None, filt_len: int = 512, device=None) -> Bs
     """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
     :class:`BssEval` (1 <= S <= 4, L <= 2^24): the counterpart of :func:`score_waves` for BSS-eval SDR, SIR and SAR, for the
     output of ``enhance_continuous`` and for files read back from disk."""
-    import torch
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    est = torch.as_tensor(est)
-    row = bss_queue([(est, clean, mix)], filt_len, dev)[0].cpu().numpy()
-    return bss_unpack(row, int(est.shape[0]), int(filt_len), int(est.shape[1]))
+    return _one_recording(est, _limits, device, lambda e, dev: bss_queue([(e, clean, mix)], filt_len, dev),
+                          lambda row, S, L: bss_unpack(row, S, int(filt_len), L))
 
 
 # ---- STOI and ESTOI (INTEGRATION.md 4f) ----------------------------------------------------------------------------------
@@ -640,12 +711,10 @@ class Stoi:
     n_samples: int
 
     def as_dict(self) -> dict:
-        def lst(x):
-            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
-        return dict(stoi=lst(self.stoi), estoi=lst(self.estoi), valid=[bool(v) for v in self.valid],
-                    perm_best=[int(p) for p in self.perm_best], stoi_best=lst(self.stoi_best), estoi_best=lst(self.estoi_best),
-                    stoi_mix=lst(self.stoi_mix), estoi_mix=lst(self.estoi_mix), stoi_i=lst(self.stoi_i),
-                    estoi_i=lst(self.estoi_i), frames=[int(v) for v in self.frames],
+        return dict(stoi=_lst(self.stoi), estoi=_lst(self.estoi), valid=[bool(v) for v in self.valid],
+                    perm_best=[int(p) for p in self.perm_best], stoi_best=_lst(self.stoi_best), estoi_best=_lst(self.estoi_best),
+                    stoi_mix=_lst(self.stoi_mix), estoi_mix=_lst(self.estoi_mix), stoi_i=_lst(self.stoi_i),
+                    estoi_i=_lst(self.estoi_i), frames=[int(v) for v in self.frames],
                     frames_kept=[int(v) for v in self.frames_kept], fs=int(self.fs), n_samples=int(self.n_samples))
 
 
@@ -689,20 +758,14 @@ def stoi_from_matrices(stoi_m, estoi_m, frames, frames_kept, nonsilent, stoi_mix
 
 def stoi_mean_of(items: Sequence[Stoi]) -> dict:
     """The ``"stoi"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers"""
-    out = {}
-    for key in ("stoi", "estoi", "stoi_best", "estoi_best", "stoi_mix", "estoi_mix", "stoi_i", "estoi_i"):
-        vals = [float(getattr(e, key)[j]) for e in items if getattr(e, key) is not None
-                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
-        out[key] = float(np.mean(vals)) if vals else None
+    out = _mean_valid(items, ("stoi", "estoi", "stoi_best", "estoi_best", "stoi_mix", "estoi_mix", "stoi_i", "estoi_i"))
     out["n_recordings"] = len(items)
     out["n_speakers_valid"] = int(sum(int(np.sum(e.valid)) for e in items))
     return out
 
 
 def check_stoi_fs(fs):
-    if int(fs) != fs or int(fs) not in STOI_RATES:
-        raise ValueError(f"STOI is defined here for fs = 8000, 10000 or 16000 Hz (got {fs})")
-    return int(fs)
+    return _check_fs(fs, STOI_RATES, "STOI is")
 
 
 def stoi_resampled_len(n: int, fs: int) -> int:
@@ -735,38 +798,13 @@ def stoi_resample(est, ref, mix=None, n_valid=None, fs: int = 16000):
     Asynchronous on the current stream; an item's rows do not depend on the batch."""
     import torch
     fs = check_stoi_fs(fs)
-    est = _wave_view(est, "est", (torch.int16, torch.float32))
-    ref = _wave_view(ref, "ref", (torch.float32,))
-    B, E, n = est.shape
-    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
-        raise ValueError("est and ref must agree in B, n and device")
-    R = ref.shape[1]
-    if not (1 <= E <= 4 and 1 <= R <= 4):
-        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
-    if not (1 <= n <= 1 << 24):
-        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
-    if B < 1 or B > 4096:
-        raise ValueError("1 <= B <= 4096 items")
-    dev = est.device
-    if mix is not None:
-        mix = _wave_view(mix, "mix", (torch.float32,))
-        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
-            raise ValueError("mix must be [B, 1, n] on the device of est")
-    if n_valid is not None:
-        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
-                or n_valid.numel() != B or not n_valid.is_contiguous():
-            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    B, E, R, n, dev = _check_views(est, ref, mix, n_valid)
     L = _lib.lib()
     n10 = int(L.misonet_stoi_resampled_len(n, fs))
     x10 = torch.empty((B, R + E + (1 if mix is not None else 0), n10), dtype=torch.float64, device=dev)
     len10 = torch.empty((B,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_stoi_resample(est.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
-                                           est.stride(2), ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                                           mix.data_ptr() if mix is not None else None,
-                                           mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
-                                           B, E, R, n, n_valid.data_ptr() if n_valid is not None else None, fs,
-                                           x10.data_ptr(), len10.data_ptr(), _lib.stream_ptr(dev)))
+    _call(L.misonet_stoi_resample, dev, *_view_args(est, ref), *_mix_args(mix), B, E, R, n, _ptr(n_valid), fs, x10.data_ptr(),
+          len10.data_ptr())
     return x10, len10
 
 
@@ -783,21 +821,16 @@ def stoi_measure(x10, len10, R: int):
     B, NS, n10 = x10.shape
     R = int(R)
     dev = x10.device
-    if len10 is not None:
-        if not isinstance(len10, torch.Tensor) or len10.dtype != torch.int32 or len10.device != dev or len10.numel() != B \
-                or not len10.is_contiguous():
-            raise ValueError(f"len10 must be a contiguous int32 device tensor of {B} entries")
+    _check_counts(len10, B, dev, "len10")
     L = _lib.lib()
     nb = int(L.misonet_stoi_scratch_bytes(B, NS, R, n10))
     if nb < 0:
         raise ValueError(f"1 <= B <= 4096, 1 <= R <= 4, 1 <= NS - R <= 5, 1 <= n10 <= 5 * 2^22 (got {B}, {R}, {NS - R}, {n10})")
     out = torch.empty((B, NS - R, R, 2), dtype=torch.float64, device=dev)
     frames = torch.empty((B, R, 3), dtype=torch.int32, device=dev)
-    scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_stoi_measure(x10.data_ptr(), len10.data_ptr() if len10 is not None else None, B, NS, R, n10,
-                                          out.data_ptr(), frames.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                          _lib.stream_ptr(dev)))
+    scratch = _scratch(nb, dev)
+    _call(L.misonet_stoi_measure, dev, x10.data_ptr(), _ptr(len10), B, NS, R, n10, out.data_ptr(), frames.data_ptr(),
+          scratch.data_ptr(), scratch.numel())
     return out, frames
 
 
@@ -806,21 +839,13 @@ def stoi_block(est, ref, mix=None, n_valid=None, fs: int = 16000):
     None -> a device float64 block [B, W]: per item the (STOI, ESTOI) of every (estimate, reference) pair ([S (+ 1), S, 2], the
     mixture as the last estimate) and (frames, kept, not silent) per reference: what :func:`stoi_unpack` reads.  Everything
     is queued on the current stream; nothing synchronises.  Batches beyond 1 GiB of device memory run in groups."""
-    import torch
     B, E, n = est.shape
     R = ref.shape[1]
     NS = R + E + (1 if mix is not None else 0)
     n10 = stoi_resampled_len(n, check_stoi_fs(fs))
     per = 8 * NS * max(n10, 1) + max(stoi_scratch_bytes(1, NS, R, max(n10, 1)), 0)
-    g = max(1, min(B, STOI_SCRATCH_CAP // max(1, per)))
-    rows = []
-    for lo in range(0, B, g):
-        hi = min(B, lo + g)
-        x10, len10 = stoi_resample(est[lo:hi], ref[lo:hi], mix[lo:hi] if mix is not None else None,
-                                   n_valid[lo:hi] if n_valid is not None else None, fs)
-        out, frames = stoi_measure(x10, len10, R)
-        rows.append(torch.cat([out.reshape(hi - lo, -1), frames.to(torch.float64).reshape(hi - lo, -1)], dim=1))
-    return rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+    return _block_rows(_groups(B, per, STOI_SCRATCH_CAP), est, ref, mix, n_valid,
+                       lambda e, r, m, nv: stoi_measure(*stoi_resample(e, r, m, nv, fs), R))
 
 
 def stoi_unpack(row, S: int, fs: int, n_samples: int) -> Stoi:
@@ -837,13 +862,6 @@ def stoi_unpack(row, S: int, fs: int, n_samples: int) -> Stoi:
                               n_samples=n_samples)
 
 
-def _stoi_limits(S, L):
-    if not (1 <= S <= 4):
-        raise ValueError(f"1 <= S <= 4 speakers (got {S})")
-    if not (1 <= L <= 1 << 24):
-        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
-
-
 def stoi_queue(items, fs: int, dev, pinned: bool = False):
     """:func:`side_queue` for STOI / ESTOI alone: the device block [len(items), W] of :func:`stoi_block`"""
     return side_queue(items, dev, pinned, stoi_fs=fs)[1]
@@ -853,14 +871,9 @@ def stoi_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Stoi:
     """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
     :class:`Stoi` (1 <= S <= 4, L <= 2^24, fs 8000, 10000 or 16000): the counterpart of :func:`score_waves` for STOI and
     ESTOI, for the output of ``enhance_continuous`` and for files read back from disk."""
-    import torch
     fs = check_stoi_fs(fs)
-    est = torch.as_tensor(est)
-    if est.dim() == 2:
-        _stoi_limits(int(est.shape[0]), int(est.shape[1]))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    row = stoi_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
-    return stoi_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))
+    return _one_recording(est, _limits, device, lambda e, dev: stoi_queue([(e, clean, mix)], fs, dev),
+                          lambda row, S, L: stoi_unpack(row, S, fs, L))
 
 
 # ---- cepstral distance, LLR and fwSegSNR (INTEGRATION.md 4j) -------------------------------------------------------------
@@ -913,12 +926,10 @@ class Reverb:
     n_samples: int
 
     def as_dict(self) -> dict:
-        def lst(x):
-            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
         out = {}
         for key in REVERB_FIGURES:
             for suffix in ("", "_best", "_mix", "_i"):
-                out[key + suffix] = lst(getattr(self, key + suffix))
+                out[key + suffix] = _lst(getattr(self, key + suffix))
         out.update(perm_best=[int(p) for p in self.perm_best], frames=[int(v) for v in self.frames],
                    frames_used=[int(v) for v in self.frames_used], frames_llr=[int(v) for v in self.frames_llr],
                    valid=[bool(v) for v in self.valid], fs=int(self.fs), n_samples=int(self.n_samples))
@@ -948,21 +959,14 @@ def reverb_from_matrices(figures, counts, fs: int = 16000, n_samples: int = 0) -
 
 def reverb_mean_of(items: Sequence[Reverb]) -> dict:
     """The ``"reverb"`` part of the ``"mean"`` entry of scores.json: every figure averaged over the valid speakers"""
-    out = {}
-    for key in REVERB_FIGURES:
-        for suffix in ("", "_best", "_mix", "_i"):
-            vals = [float(getattr(e, key + suffix)[j]) for e in items if getattr(e, key + suffix) is not None
-                    for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key + suffix)[j])]
-            out[key + suffix] = float(np.mean(vals)) if vals else None
+    out = _mean_valid(items, [key + suffix for key in REVERB_FIGURES for suffix in ("", "_best", "_mix", "_i")])
     out["n_recordings"] = len(items)
     out["n_speakers_valid"] = int(sum(int(np.sum(e.valid)) for e in items))
     return out
 
 
 def check_reverb_fs(fs):
-    if int(fs) != fs or int(fs) not in REVERB_RATES:
-        raise ValueError(f"CD, LLR and fwSegSNR are defined here for fs = 8000 or 16000 Hz (got {fs})")
-    return int(fs)
+    return _check_fs(fs, REVERB_RATES, "CD, LLR and fwSegSNR are")
 
 
 def reverb_frames(n: int, fs: int) -> int:
@@ -977,13 +981,6 @@ def reverb_scratch_bytes(B: int, NS: int, R: int, n: int, fs: int) -> int:
     return int(_lib.lib().misonet_reverb_scratch_bytes(int(B), int(NS), int(R), int(n), int(fs)))
 
 
-def _reverb_limits(S, L):
-    if not (1 <= S <= 4):
-        raise ValueError(f"1 <= S <= 4 speakers (got {S})")
-    if not (1 <= L <= 1 << 24):
-        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
-
-
 def reverb_measure(est, ref, mix=None, n_valid=None, fs: int = 16000, frame_values: bool = False):
     """est int16 or float32 [B, E, n], ref float32 [B, R, n] (device views as :func:`wave_stats` takes them), mix float32
     [B, 1, n] or None (measured as one more estimate, the last), n_valid int32 [B] (device) or None.  Returns (out float64
@@ -992,27 +989,7 @@ def reverb_measure(est, ref, mix=None, n_valid=None, fs: int = 16000, frame_valu
     every frame, NaN where it is not counted).  Asynchronous on the current stream; an item's rows do not depend on the batch."""
     import torch
     fs = check_reverb_fs(fs)
-    est = _wave_view(est, "est", (torch.int16, torch.float32))
-    ref = _wave_view(ref, "ref", (torch.float32,))
-    B, E, n = est.shape
-    if ref.shape[0] != B or ref.shape[2] != n or ref.device != est.device:
-        raise ValueError("est and ref must agree in B, n and device")
-    R = ref.shape[1]
-    if not (1 <= E <= 4 and 1 <= R <= 4):
-        raise ValueError(f"1 <= estimates, references <= 4 (got {E}, {R})")
-    if not (1 <= n <= 1 << 24):
-        raise ValueError(f"1 <= n <= 2^24 samples (got {n})")
-    if B < 1 or B > 4096:
-        raise ValueError("1 <= B <= 4096 items")
-    dev = est.device
-    if mix is not None:
-        mix = _wave_view(mix, "mix", (torch.float32,))
-        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
-            raise ValueError("mix must be [B, 1, n] on the device of est")
-    if n_valid is not None:
-        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
-                or n_valid.numel() != B or not n_valid.is_contiguous():
-            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    B, E, R, n, dev = _check_views(est, ref, mix, n_valid)
     L = _lib.lib()
     NE = E + (1 if mix is not None else 0)
     nb = int(L.misonet_reverb_scratch_bytes(B, R + NE, R, n, fs))
@@ -1021,16 +998,10 @@ def reverb_measure(est, ref, mix=None, n_valid=None, fs: int = 16000, frame_valu
     frame = None
     if frame_values:
         frame = torch.full((B, NE, R, 3, int(L.misonet_reverb_frames(n, fs))), float("nan"), dtype=torch.float64, device=dev)
-    scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_reverb_measure(est.data_ptr(), 1 if est.dtype == torch.int16 else 0, est.stride(0), est.stride(1),
-                                            est.stride(2), ref.data_ptr(), ref.stride(0), ref.stride(1), ref.stride(2),
-                                            mix.data_ptr() if mix is not None else None,
-                                            mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
-                                            B, E, R, n, n_valid.data_ptr() if n_valid is not None else None, fs,
-                                            out.data_ptr(), count.data_ptr(),
-                                            frame.data_ptr() if frame is not None and frame.numel() else None,
-                                            scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(dev)))
+    scratch = _scratch(nb, dev)
+    _call(L.misonet_reverb_measure, dev, *_view_args(est, ref), *_mix_args(mix), B, E, R, n, _ptr(n_valid), fs, out.data_ptr(),
+          count.data_ptr(), frame.data_ptr() if frame is not None and frame.numel() else None, scratch.data_ptr(),
+          scratch.numel())
     return out, count, frame
 
 
@@ -1046,19 +1017,12 @@ def reverb_block(est, ref, mix=None, n_valid=None, fs: int = 16000):
     None -> a device float64 block [B, W]: per item the six figures of every (estimate, reference) pair ([S (+ 1), S, 6], the
     mixture as the last estimate) and (frames, K, K_llr) per pair ([S (+ 1), S, 3]): what :func:`reverb_unpack` reads.
     Everything is queued on the current stream; nothing synchronises.  Batches beyond 1 GiB of scratch run in groups."""
-    import torch
     B, E, n = est.shape
     R = ref.shape[1]
     NS = R + E + (1 if mix is not None else 0)
-    per = max(reverb_scratch_bytes(1, NS, R, max(n, 1), check_reverb_fs(fs)), 1)
-    g = max(1, min(B, REVERB_SCRATCH_CAP // per))
-    rows = []
-    for lo in range(0, B, g):
-        hi = min(B, lo + g)
-        out, count, _ = reverb_measure(est[lo:hi], ref[lo:hi], mix[lo:hi] if mix is not None else None,
-                                       n_valid[lo:hi] if n_valid is not None else None, fs)
-        rows.append(torch.cat([out.reshape(hi - lo, -1), count.to(torch.float64).reshape(hi - lo, -1)], dim=1))
-    return rows[0] if len(rows) == 1 else torch.cat(rows, dim=0)
+    per = reverb_scratch_bytes(1, NS, R, max(n, 1), check_reverb_fs(fs))
+    return _block_rows(_groups(B, per, REVERB_SCRATCH_CAP), est, ref, mix, n_valid,
+                       lambda e, r, m, nv: reverb_measure(e, r, m, nv, fs)[:2])
 
 
 def reverb_unpack(row, S: int, fs: int, n_samples: int) -> Reverb:
@@ -1079,14 +1043,9 @@ def reverb_waves(est, clean, mix=None, fs: int = 16000, device=None) -> Reverb:
     """est int16 or float32 [S, L], clean float32 [S, L], mix float32 [L] or None (ndarrays or tensors, host or device) ->
     :class:`Reverb` (1 <= S <= 4, L <= 2^24, fs 8000 or 16000): the counterpart of :func:`score_waves` for cepstral distance,
     LLR and fwSegSNR, for the output of ``enhance_continuous`` and for files read back from disk."""
-    import torch
     fs = check_reverb_fs(fs)
-    est = torch.as_tensor(est)
-    if est.dim() == 2:
-        _reverb_limits(int(est.shape[0]), int(est.shape[1]))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    row = reverb_queue([(est, clean, mix)], fs, dev)[0].cpu().numpy()
-    return reverb_unpack(row, int(est.shape[0]), fs, int(est.shape[1]))
+    return _one_recording(est, _limits, device, lambda e, dev: reverb_queue([(e, clean, mix)], fs, dev),
+                          lambda row, S, L: reverb_unpack(row, S, fs, L))
 
 
 # ---- SRMR: the figure that needs no clean reference ------------------------------------------------------------------------------
@@ -1116,18 +1075,14 @@ class Srmr:
     n_samples: int
 
     def as_dict(self) -> dict:
-        def lst(x):
-            return None if x is None else [float(v) for v in np.asarray(x, dtype=np.float64)]
-        return dict(srmr=lst(self.srmr), k_star=[int(v) for v in self.k_star], bw90=lst(self.bw90),
+        return dict(srmr=_lst(self.srmr), k_star=[int(v) for v in self.k_star], bw90=_lst(self.bw90),
                     frames=[int(v) for v in self.frames], valid=[bool(v) for v in self.valid],
-                    srmr_mix=None if self.srmr_mix is None else float(self.srmr_mix), srmr_i=lst(self.srmr_i),
+                    srmr_mix=None if self.srmr_mix is None else float(self.srmr_mix), srmr_i=_lst(self.srmr_i),
                     fs=int(self.fs), n_samples=int(self.n_samples))
 
 
 def check_srmr_fs(fs):
-    if int(fs) != fs or int(fs) not in SRMR_RATES:
-        raise ValueError(f"SRMR is defined here for fs = 8000 or 16000 Hz (got {fs})")
-    return int(fs)
+    return _check_fs(fs, SRMR_RATES, "SRMR is")
 
 
 def srmr_frames(n: int, fs: int) -> int:
@@ -1147,13 +1102,6 @@ def srmr_scratch_bytes(B: int, NS: int, n: int, fs: int) -> int:
     return int(_lib.lib().misonet_srmr_scratch_bytes(int(B), int(NS), int(n), int(fs)))
 
 
-def _srmr_limits(S, L):
-    if not (1 <= S <= 4):
-        raise ValueError(f"1 <= S <= 4 signals (got {S})")
-    if not (1 <= L <= 1 << 24):
-        raise ValueError(f"1 <= L <= 2^24 samples (got {L})")
-
-
 def srmr_measure(sig, mix=None, n_valid=None, fs: int = 16000, energy: bool = False, scratch=None):
     """sig int16 or float32 [B, S, n] (a device view as :func:`wave_stats` takes its estimates), mix float32 [B, 1, n] or None
     (measured as one more signal, the last), n_valid int32 [B] (device) or None.  Returns (out float64 [B, S (+ 1), 3] = (SRMR,
@@ -1162,20 +1110,7 @@ def srmr_measure(sig, mix=None, n_valid=None, fs: int = 16000, energy: bool = Fa
     :func:`srmr_scratch_bytes` bytes to work in (its contents do not matter); by default one is allocated."""
     import torch
     fs = check_srmr_fs(fs)
-    sig = _wave_view(sig, "sig", (torch.int16, torch.float32))
-    B, S, n = sig.shape
-    _srmr_limits(S, n)
-    if B < 1 or B > 4096:
-        raise ValueError("1 <= B <= 4096 items")
-    dev = sig.device
-    if mix is not None:
-        mix = _wave_view(mix, "mix", (torch.float32,))
-        if tuple(mix.shape) != (B, 1, n) or mix.device != dev:
-            raise ValueError("mix must be [B, 1, n] on the device of sig")
-    if n_valid is not None:
-        if not isinstance(n_valid, torch.Tensor) or n_valid.dtype != torch.int32 or n_valid.device != dev \
-                or n_valid.numel() != B or not n_valid.is_contiguous():
-            raise ValueError(f"n_valid must be a contiguous int32 device tensor of {B} entries")
+    B, S, _, n, dev = _check_views(sig, None, mix, n_valid, what="sig")
     L = _lib.lib()
     NS = S + (1 if mix is not None else 0)
     nb = int(L.misonet_srmr_scratch_bytes(B, NS, n, fs))
@@ -1183,17 +1118,12 @@ def srmr_measure(sig, mix=None, n_valid=None, fs: int = 16000, energy: bool = Fa
     count = torch.empty((B, NS), dtype=torch.int32, device=dev)
     en = torch.empty((B, NS, SRMR_CHANNELS, SRMR_MODULATIONS), dtype=torch.float64, device=dev) if energy else None
     if scratch is None:
-        scratch = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+        scratch = _scratch(nb, dev)
     elif not isinstance(scratch, torch.Tensor) or scratch.dtype != torch.uint8 or scratch.device != dev \
             or not scratch.is_contiguous() or scratch.numel() < nb or scratch.data_ptr() % 16:
         raise ValueError(f"scratch must be a contiguous uint8 device tensor of at least {nb} bytes, 16-byte aligned")
-    with torch.cuda.device(dev):
-        _lib.check(L.misonet_srmr_measure(sig.data_ptr(), 1 if sig.dtype == torch.int16 else 0, sig.stride(0), sig.stride(1),
-                                          sig.stride(2), mix.data_ptr() if mix is not None else None,
-                                          mix.stride(0) if mix is not None else 0, mix.stride(2) if mix is not None else 1,
-                                          B, S, n, n_valid.data_ptr() if n_valid is not None else None, fs, out.data_ptr(),
-                                          count.data_ptr(), en.data_ptr() if en is not None else None, scratch.data_ptr(),
-                                          scratch.numel(), _lib.stream_ptr(dev)))
+    _call(L.misonet_srmr_measure, dev, *_view_args(sig), *_mix_args(mix), B, S, n, _ptr(n_valid), fs, out.data_ptr(),
+          count.data_ptr(), _ptr(en), scratch.data_ptr(), scratch.numel())
     return out, count, en
 
 
@@ -1237,11 +1167,7 @@ def srmr_unpack(row, S: int, fs: int, n_samples: int) -> Srmr:
 
 def srmr_mean_of(items: Sequence[Srmr]) -> dict:
     """The ``"srmr"`` part of the ``"mean"`` entry of scores.json: the figures averaged over the valid signals"""
-    out = {}
-    for key in ("srmr", "srmr_i"):
-        vals = [float(getattr(e, key)[j]) for e in items if getattr(e, key) is not None
-                for j in range(len(e.valid)) if e.valid[j] and np.isfinite(getattr(e, key)[j])]
-        out[key] = float(np.mean(vals)) if vals else None
+    out = _mean_valid(items, ("srmr", "srmr_i"))
     mixes = [float(e.srmr_mix) for e in items if e.srmr_mix is not None and np.isfinite(e.srmr_mix)]
     out["srmr_mix"] = float(np.mean(mixes)) if mixes else None
     out["n_recordings"] = len(items)
@@ -1256,38 +1182,8 @@ def srmr_queue(items, fs: int, dev, pinned: bool = False):
     import torch
     fs = check_srmr_fs(fs)
     with torch.cuda.device(dev):
-        recs = [(torch.as_tensor(sig), torch.as_tensor(mix) if mix is not None else None) for sig, mix in items]
-        for sig, _ in recs:
-            if sig.dim() != 2:
-                raise ValueError("signals must be [S, L]")
-        sig, mix, nv = _srmr_batch(recs, dev, pinned)
+        sig, _, mix, nv = _wave_batch([(sig, None, mix) for sig, mix in items], dev, pinned, _signal_limits)
         return srmr_block(sig, mix, nv, fs)
-
-
-def _srmr_batch(recs, dev, pinned):
-    """recs: (signals [S, L], mix [L] or None) tensors -> (sig [G, S, n], mix [G, 1, n] or None, n_valid int32 [G] or None),
-    zero-padded to the longest by :func:`_pad_batch`, as :func:`_wave_batch` forms its batch"""
-    import torch
-    out = []
-    for sig, mix in recs:
-        if sig.dtype != torch.int16:
-            sig = sig.to(torch.float32)
-        if mix is not None:
-            mix = mix.to(torch.float32).reshape(-1)
-            if mix.numel() != sig.shape[1]:
-                raise ValueError("mix must hold L samples")
-        out.append((sig, mix))
-    if not out:
-        raise ValueError("at least one recording")
-    S, G = out[0][0].shape[0], len(out)
-    if any(r[0].shape[0] != S for r in out) or any((r[1] is None) != (out[0][1] is None) for r in out):
-        raise ValueError("every recording must have the same number of signals, and all or none a mixture")
-    for r in out:
-        _srmr_limits(S, r[0].shape[1])
-    if any(r[0].dtype != out[0][0].dtype for r in out):
-        raise ValueError("int16 and float32 signals cannot share a batch")
-    cols, nv = _pad_batch([(x, m.reshape(1, -1) if m is not None else None) for x, m in out], dev, pinned)
-    return cols[0], cols[1], nv
 
 
 def srmr_waves(waves, mix=None, fs: int = 16000, device=None) -> Srmr:
@@ -1299,7 +1195,29 @@ def srmr_waves(waves, mix=None, fs: int = 16000, device=None) -> Srmr:
     waves = torch.as_tensor(waves)
     if waves.dim() != 2:
         raise ValueError("waves must be [S, L]")
-    _srmr_limits(int(waves.shape[0]), int(waves.shape[1]))
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    row = srmr_queue([(waves, mix)], fs, dev)[0].cpu().numpy()
-    return srmr_unpack(row, int(waves.shape[0]), fs, int(waves.shape[1]))
+    return _one_recording(waves, _signal_limits, device, lambda w, dev: srmr_queue([(w, mix)], fs, dev),
+                          lambda row, S, L: srmr_unpack(row, S, fs, L))
+
+
+# ---- the figures beside the scores: one table for side_queue and for the recording paths of pipeline.py ------------------
+@dataclasses.dataclass(frozen=True)
+class SideFigure:
+    """A figure computed from the stitched result of a recording.  ``name`` is the flag of ``Enhancer.enhance_recording`` /
+    ``enhance_recordings``; its parameter is the filter length for "bss" and the rate ``fs`` for the others."""
+    name: str
+    rates: Optional[Tuple[int, ...]]      # the rates it is defined for, None: any
+    check: object                         # parameter -> the parameter as the calls below take it, or ValueError
+    limits: object                        # (S, L): ValueError for a recording the figure does not take
+    block: object                         # (est, clean, mix, n_valid, parameter) -> device block [B, W]; SRMR: without clean
+    unpack: object                        # (host row, S, parameter, n_samples) -> the dataclass
+    waves: object                         # (est [S, L], clean, mix, parameter, device) -> the dataclass of one recording
+    needs_clean: bool                     # takes the clean sources, hence score=True
+
+
+SIDE_FIGURES = (
+    SideFigure("bss", None, _check_filt_len, _limits, bss_energies, bss_unpack, bss_eval_waves, True),
+    SideFigure("stoi", STOI_RATES, check_stoi_fs, _limits, stoi_block, stoi_unpack, stoi_waves, True),
+    SideFigure("reverb", REVERB_RATES, check_reverb_fs, _limits, reverb_block, reverb_unpack, reverb_waves, True),
+    SideFigure("srmr", SRMR_RATES, check_srmr_fs, _signal_limits, srmr_block, srmr_unpack,
+               lambda est, clean, mix, fs, device: srmr_waves(est, mix, fs, device), False),
+)
