@@ -598,6 +598,59 @@ int misonet_room_mix(const float* src_dev, long long src_sb, long long src_ss, l
                      const int* split_dev, int B, int S, int M, long long L, int Lh, long long Lo, float* images_dev,
                      float* early_dev, float* mix_dev, misonet_stream stream);
 
+/* ---- source localisation: SRP, SRP-PHAT and MUSIC maps over a delay table, and their peaks (ABI 610) -------------------- */
+/* The project's own definition in the SRP-PHAT / MUSIC family (DiBiase 2000; Schmidt 1986; INTEGRATION.md 4q in full,
+ * tests/doa_ref.py restates it in NumPy float64).  pyroomacoustics was not available: nothing here was compared against it.
+ * mix complex64 [B, F, M, T]; weight float32 [B, K, F, T] (the layout of the cACGMM masks) or NULL (K = 1, w = 1); tau float64
+ * [Bg, D, M], the delay of candidate d at microphone m in seconds, Bg 1 or B, built on the host (far-field directions and
+ * near-field points alike); pts float64 [D, 3], the candidates' coordinates, used only to keep peaks apart.  nfft = 2 (F - 1),
+ * and 2 when F = 1; omega_f = 2 pi f fs / nfft.  Everything is float64 after the loads.
+ * Blocks: block = 0 is one block over all T frames; otherwise hop = 0 means hop = block, N = 1 + (T - block) / hop in integer
+ * division, block n covers the frames [n hop, n hop + block), the frames behind the last full block are not read.
+ *   1. per (b, k, n, f), f_lo <= f <= f_hi:  R = sum_t w[b,k,f,t] x~_t x~_t^H over the block's frames, t ascending; kind
+ *      srp_phat: x~_m = x_m / |x_m| and 0 where x_m = 0; otherwise x~ = x.  A bin that holds a non-finite sample, or a non-finite
+ *      weight of class k, in that block is skipped and fail[b,k,n] |= 1; a bin with tr R = 0 is skipped.  srp, srp_phat:
+ *      C_f = R.  music with S = num_src: the eigenpairs of R by the cyclic Jacobi of the beamformers, eigenvalues descending,
+ *      equal ones lower index first; lambda_{S-1} <= 1e-12 lambda_0: the bin is skipped (its signal subspace has rank below S);
+ *      otherwise C_f = (1 / M) sum_{r >= S} e_r e_r^H.  used[b,k,n] = the bins not skipped; used = 0: fail |= 2 and q = 0.
+ *   2. per (b, k, n, d):  q = g sum_{f used, ascending} ( sum_m C_f[m,m] + 2 Re sum_{m<n} C_f[m,n] e^{+j omega_f (tau[d,m] - tau[d,n])} )
+ *      = g sum_f a^H C_f a with a_m = e^{-j omega_f tau[d,m]};  g = 1 for srp and srp_phat (large at a source), g = 1 / used for
+ *      music (q in [0, 1], small at a source).  q float64 [B, K, N, D].
+ *   3. per (b, k, n), S rounds: the best candidate left -- the maximum of q, the minimum for music, ties to the lower index -- is
+ *      taken; it and every candidate with |pts_d - pts_best|^2 < min_sep^2 are retired.  peak int32 [B, K, N, S], -1 once no
+ *      candidate is left; value float64 [B, K, N, S], q at the peak, 0 beside a peak of -1.
+ * Every sum has one fixed order and every output one writer: the results are bit-reproducible and the bits of a recording depend
+ * neither on B nor on its position in the batch.  Three launches on the stream, no host synchronisation, no allocation: the call
+ * can be captured in a HIP graph.  Every element of q, peak, value and fail is written.
+ * Limits: 2 <= M <= 8, 1 <= K <= 8 (K = 1 without weights), 1 <= num_src <= min(4, D), music: num_src <= M - 1, 1 <= D <= 65536,
+ * B, F, T >= 1, 0 <= f_lo <= f_hi < F (f_hi = -1, the default: F - 1), 0 <= block <= T, hop >= 0, min_sep finite and >= 0,
+ * B K N D < 2^31, and the launch grids B N F < 2^26 and B K N ceil(D / tile) tile < 2^32, Bg 1 or B, fs finite and > 0; the
+ * workspace 16-byte aligned.  Anything else is MISONET_EINVAL with a
+ * message (misonet_doa_workspace_bytes and misonet_doa_blocks: -1) before any launch; then a null pointer; a short workspace is
+ * MISONET_ENOMEM.  tau must be finite: the caller checks that on the host.
+ * misonet_doa_tile: the candidates one workgroup of the steering kernel owns; misonet_doa_bin_chunk: the bins it stages at a
+ * time; both for tests that probe the edges. */
+typedef struct {
+  int kind;                /* 0 "srp", 1 "srp_phat", 2 "music" */
+  int num_src;             /* S: the peaks taken; for music also the dimension of the signal subspace */
+  int block;               /* frames per block; 0 = all T */
+  int hop;                 /* frames between blocks; 0 = block */
+  int f_lo, f_hi;          /* the band, inclusive; f_hi -1 = F - 1 */
+  double min_sep;          /* peaks are kept at least this far apart, in the unit of pts */
+} misonet_doa_opts;
+int misonet_doa_opts_default(misonet_doa_opts* opts);    /* 1, 1, 0, 0, 0, -1, 0.0 */
+int misonet_doa_tile(void);
+int misonet_doa_bin_chunk(void);
+int misonet_doa_blocks(int T, int block, int hop);       /* N; -1 on bad arguments */
+long long misonet_doa_workspace_bytes(int B, int K, int F, int M, int T, int D, const misonet_doa_opts* opts);
+int misonet_doa(const void* mix_dev, const float* weight_dev_or_null, const double* tau_dev, int Bg, const double* pts_dev, int B,
+                int K, int F, int M, int T, int D, double fs, const misonet_doa_opts* opts, double* q_out_dev, int* peak_out_dev,
+                double* value_out_dev, int* fail_out_dev, void* ws_dev, long long ws_bytes, misonet_stream stream);
+/* diagnostic: after misonet_doa with the same geometry and options, copy C complex128 [B, K, N, F, M, M] (0 for a bin that was
+ * skipped or lies outside the band), used int32 [B, K, N] and fail int32 [B, K, N] to device buffers (any may be NULL) */
+int misonet_doa_debug(const void* ws_dev, int B, int K, int F, int M, int T, int D, const misonet_doa_opts* opts,
+                      void* c_c128_dev, int* used_dev, int* fail_dev, misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

@@ -13,6 +13,9 @@ Host-side mirror of the reference call surface:
                              definition, in front of and behind every recording path)
   Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
                              what simulate returns)
+  Localizer, localize, localize_wav, DoaResult  (source localisation: SRP, SRP-PHAT and MUSIC maps over a delay table and their
+                             peaks, misonet_amd.localize; directions, far_field_delays, near_field_delays, angular_error: its
+                             host helpers)
   Enhancer                  (reference tester.py:846-975, the Tester_Enhance hot loop, kept on-device)
   tester.Tester_Enhance     (reference tester.py:798-975: the harness class itself, same constructor / test / inference)
 The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol without the built
@@ -20,7 +23,8 @@ library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "resample", "resampled_len",
-           "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Enhancer", "weights"]
+           "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
+           "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
 
 
 def __getattr__(name):
@@ -51,6 +55,10 @@ def __getattr__(name):
     if name in ("Room", "Scene", "simulate", "beta_from_rt60"):
         import importlib
         return getattr(importlib.import_module(".room", __name__), name)
+    if name in ("Localizer", "localize", "localize_wav", "DoaResult", "directions", "far_field_delays", "near_field_delays",
+                "angular_error"):
+        import importlib
+        return getattr(importlib.import_module(".localize", __name__), name)
     if name == "Enhancer":
         from .pipeline import Enhancer
         return Enhancer

@@ -55,6 +55,12 @@ class JbfOpts(C.Structure):
                 ("ref_ch", C.c_int)]
 
 
+class DoaOpts(C.Structure):
+    """misonet_doa_opts (ABI 610): kind 0 srp / 1 srp_phat / 2 music, block 0 = all frames, hop 0 = block, f_hi -1 = F - 1"""
+    _fields_ = [("kind", C.c_int), ("num_src", C.c_int), ("block", C.c_int), ("hop", C.c_int), ("f_lo", C.c_int),
+                ("f_hi", C.c_int), ("min_sep", C.c_double)]
+
+
 class IvaOpts(C.Structure):
     """misonet_iva_opts (ABI 580): model 0 gauss / 1 laplace, channels 0 = the number of sources"""
     _fields_ = [("iterations", C.c_int), ("model", C.c_int), ("channels", C.c_int), ("ref_ch", C.c_int), ("floor", C.c_double)]
@@ -175,6 +181,16 @@ SIGNATURES = {
                                    C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_room_mix": (C.c_int, [C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_doa_opts_default": (C.c_int, [C.POINTER(DoaOpts)]),
+    "misonet_doa_tile": (C.c_int, []),
+    "misonet_doa_bin_chunk": (C.c_int, []),
+    "misonet_doa_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "misonet_doa_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DoaOpts)]),
+    "misonet_doa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_int, C.c_double, C.POINTER(DoaOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_doa_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(DoaOpts),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_reverb_frames": (C.c_longlong, [C.c_longlong, C.c_int]),
     "misonet_reverb_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int]),
     "misonet_reverb_measure": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p,

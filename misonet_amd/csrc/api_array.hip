@@ -495,6 +495,90 @@ int misonet_room_mix(const float* src_dev, long long src_sb, long long src_ss, l
   return MISONET_OK;
 }
 
+// ---- source localisation (doa.hip) ----------------------------------------------------------------------------------------------
+int misonet_doa_opts_default(misonet_doa_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->kind = DOA_SRP_PHAT; o->num_src = 1; o->block = 0; o->hop = 0; o->f_lo = 0; o->f_hi = -1; o->min_sep = 0.0;
+  return MISONET_OK;
+}
+
+int misonet_doa_tile(void) { return doa_tile(); }
+int misonet_doa_bin_chunk(void) { return doa_bin_chunk(); }
+
+int misonet_doa_blocks(int T, int block, int hop) {
+  if (T < 1 || block < 0 || hop < 0 || block > T) return -1;
+  if (block == 0) return 1;
+  return 1 + (T - block) / (hop ? hop : block);
+}
+
+// every limit of the call; *N, *f_hi: the resolved block count and last bin.  quiet: the size function sets no message
+static int doa_check(int B, int K, int F, int M, int T, int D, const misonet_doa_opts* o, int* N, int* f_hi, bool quiet) {
+#define DOA_BAD(...) return quiet ? MISONET_EINVAL : fail(MISONET_EINVAL, __VA_ARGS__)
+  if (!o) DOA_BAD("null localisation options");
+  if (B < 1 || F < 1 || T < 1) DOA_BAD("B, F and T must be positive (got %d, %d, %d)", B, F, T);
+  if (M < 2 || M > 8) DOA_BAD("M must be in [2, 8] (got %d)", M);
+  if (K < 1 || K > DOA_MAX_K) DOA_BAD("K must be in [1, %d] (got %d)", DOA_MAX_K, K);
+  if (D < 1 || D > DOA_MAX_D) DOA_BAD("D must be in [1, %d] (got %d)", DOA_MAX_D, D);
+  if (o->kind != DOA_SRP && o->kind != DOA_SRP_PHAT && o->kind != DOA_MUSIC) DOA_BAD("kind %d: 0 srp, 1 srp_phat, 2 music", o->kind);
+  if (o->num_src < 1 || o->num_src > DOA_MAX_S || o->num_src > D)
+    DOA_BAD("num_src must be in [1, min(%d, D)] (got %d, D %d)", DOA_MAX_S, o->num_src, D);
+  if (o->kind == DOA_MUSIC && o->num_src > M - 1) DOA_BAD("music needs num_src <= M - 1 = %d (got %d)", M - 1, o->num_src);
+  if (o->block < 0 || o->hop < 0 || o->block > T) DOA_BAD("block must be in [0, T] and hop >= 0 (got block %d, hop %d, T %d)", o->block, o->hop, T);
+  const int fh = o->f_hi == -1 ? F - 1 : o->f_hi;
+  if (o->f_lo < 0 || o->f_lo > fh || fh >= F) DOA_BAD("0 <= f_lo <= f_hi < F does not hold (got %d, %d, F %d)", o->f_lo, o->f_hi, F);
+  if (!(o->min_sep >= 0.0) || !std::isfinite(o->min_sep)) DOA_BAD("min_sep must be finite and >= 0 (got %g)", o->min_sep);
+  const int n = misonet_doa_blocks(T, o->block, o->hop);
+  if ((long long)B * K * n * D >= (1LL << 31)) DOA_BAD("B K N D must stay under 2^31 (got B %d, K %d, N %d, D %d)", B, K, n, D);
+  // the launch grids: one 64-thread workgroup per (b, n, f), one doa_tile()-thread workgroup per (b, k, n, tile), under 2^32 threads
+  const long long tiles = (D + doa_tile() - 1) / doa_tile();
+  if ((long long)B * n * F * 64 >= (1LL << 32) || (long long)B * K * n * tiles * doa_tile() >= (1LL << 32))
+    DOA_BAD("B N F = %lld bins or B K N ceil(D / %d) = %lld tiles are more than one call takes (2^26 bins, 2^32 / %d tiles)",
+            (long long)B * n * F, doa_tile(), (long long)B * K * n * tiles, doa_tile());
+#undef DOA_BAD
+  *N = n;
+  *f_hi = fh;
+  return MISONET_OK;
+}
+
+long long misonet_doa_workspace_bytes(int B, int K, int F, int M, int T, int D, const misonet_doa_opts* opts) {
+  int N = 0, fh = 0;
+  if (doa_check(B, K, F, M, T, D, opts, &N, &fh, true)) return -1;
+  return doa_ws_bytes(B, K, N, F, M);
+}
+
+int misonet_doa(const void* mix, const float* weight, const double* tau, int Bg, const double* pts, int B, int K, int F, int M,
+                int T, int D, double fs, const misonet_doa_opts* opts, double* q_out, int* peak_out, double* value_out,
+                int* fail_out, void* ws, long long ws_bytes, misonet_stream stream) {
+  int N = 0, fh = 0;
+  { int r = doa_check(B, K, F, M, T, D, opts, &N, &fh, false); if (r) return r; }
+  if (Bg != 1 && Bg != B) return fail(MISONET_EINVAL, "the delay table's batch must be 1 or B = %d (got %d)", B, Bg);
+  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(MISONET_EINVAL, "fs must be finite and > 0 (got %g)", fs);
+  if (!weight && K != 1) return fail(MISONET_EINVAL, "without weights K must be 1 (got %d)", K);
+  if (!mix || !tau || !pts || !q_out || !peak_out || !value_out || !fail_out || !ws) return fail(MISONET_EINVAL, "null argument");
+  if (ws_bytes < doa_ws_bytes(B, K, N, F, M)) return fail(MISONET_ENOMEM, "workspace too small");
+  DoaArgs a;
+  a.mix = reinterpret_cast<const float2*>(mix); a.weight = weight; a.tau = tau; a.pts = pts;
+  a.Bg = Bg; a.B = B; a.K = K; a.F = F; a.M = M; a.T = T; a.D = D;
+  a.fs = fs;
+  a.kind = opts->kind; a.S = opts->num_src;
+  a.block = opts->block ? opts->block : T;
+  a.hop = opts->block ? (opts->hop ? opts->hop : opts->block) : T;
+  a.N = N; a.f_lo = opts->f_lo; a.f_hi = fh;
+  a.min_sep = opts->min_sep;
+  a.q = q_out; a.peak = peak_out; a.value = value_out; a.fail = fail_out;
+  HIPCHK(launch_doa(a, ws, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_doa_debug(const void* ws, int B, int K, int F, int M, int T, int D, const misonet_doa_opts* opts, void* c_c128_dev,
+                      int* used_dev, int* fail_dev, misonet_stream stream) {
+  int N = 0, fh = 0;
+  { int r = doa_check(B, K, F, M, T, D, opts, &N, &fh, false); if (r) return r; }
+  if (!ws) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_doa_debug(ws, B, K, N, F, M, c_c128_dev, used_dev, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
 long long misonet_pit_scratch_bytes(int B, int S, int F) {
   if (B <= 0 || S <= 0 || F <= 0) return -1;
   return (long long)B * S * S * (F + 1) * (long long)sizeof(double);

@@ -464,6 +464,33 @@ hipError_t launch_room_rir(const double* room, const double* beta, const double*
 hipError_t launch_room_mix(const float* x, const long long* xs, const double* rir, const int* split /*[B][S] or nullptr*/, int B,
                            int S, int M, int L, int Lh, int Lo, float* images, float* early, float* mix, hipStream_t s);
 
+// Source localisation (doa.hip): SRP, SRP-PHAT and MUSIC maps over a delay table, and their peaks.  mix
+// complex64 [B][F][M][T], weight float32 [B][K][F][T] or nullptr (K = 1), tau double [Bg][D][M] (Bg 1 or B), pts double [D][3] ->
+// q double [B][K][N][D], peak int / value double [B][K][N][S], fail int [B][K][N].  The workspace holds C complex128
+// [B][K][N][F][M][M], the state of every bin and used / fail per map, which launch_doa_debug copies out.  block, hop and N are
+// resolved (block >= 1, hop >= 1); the caller checks every limit.
+constexpr int DOA_SRP = 0, DOA_SRP_PHAT = 1, DOA_MUSIC = 2;
+constexpr int DOA_MAX_K = 8, DOA_MAX_S = 4, DOA_MAX_D = 65536;
+struct DoaArgs {
+  const float2* mix;
+  const float* weight;
+  const double* tau;
+  const double* pts;
+  int Bg, B, K, F, M, T, D;
+  double fs;
+  int kind, S, block, hop, N, f_lo, f_hi;
+  double min_sep;
+  double* q;
+  int* peak;
+  double* value;
+  int* fail;
+};
+int doa_tile();                                    // candidates per workgroup of the steering kernel
+int doa_bin_chunk();                               // bins per staged chunk of the steering kernel
+long long doa_ws_bytes(long long B, long long K, long long N, long long F, long long M);
+hipError_t launch_doa(const DoaArgs& a, void* ws, hipStream_t s);
+hipError_t launch_doa_debug(const void* ws, int B, int K, int N, int F, int M, void* c, int* used, int* fail, hipStream_t s);
+
 // source estimate of aligned speaker `spk` at microphone m: pointers to its frame row for bin f.  Args: MvdrArgs, WpdArgs,
 // MaskArgs or JbfArgs (est / est_bstride / sel in pipeline mode, src when est == nullptr)
 template <typename Args>
