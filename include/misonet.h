@@ -651,6 +651,51 @@ int misonet_doa(const void* mix_dev, const float* weight_dev_or_null, const doub
 int misonet_doa_debug(const void* ws_dev, int B, int K, int F, int M, int T, int D, const misonet_doa_opts* opts,
                       void* c_c128_dev, int* used_dev, int* fail_dev, misonet_stream stream);
 
+/* ---- online WPE: frame-recursive dereverberation, its state carried from call to call (ABI 620) -------------------------- */
+/* The project's own definition in the RLS-WPE family (Yoshioka & Nakatani 2012; Caroselli et al. 2017; nara_wpe's online_wpe_step;
+ * INTEGRATION.md 4r in full, tests/owpe_ref.py restates it in NumPy float64).  nara_wpe was not available: nothing here was compared
+ * against it.  Audio is fed as it arrives: a call takes any T >= 1 new frames and advances the state; the memory does not grow.
+ * Per (item b, bin f), independent of every other, N = M taps.  State: P complex128 [N, N], G complex128 [N, M], the last
+ * delay + taps - 1 observed frames (the complex64 that was read), the mean-over-microphones powers of the last `context` frames,
+ * n (the frames seen) and the fail word.  misonet_owpe_reset: P = init I, everything else 0.  Per new frame y, float64 after the load:
+ *   1. z[k M + m] = y[m, t - delay - k]   (k = 0 .. taps - 1; the row order of misonet_wpe; 0 before the start of the stream)
+ *   2. x = y - G^H z                      the output, rounded to complex64 once
+ *   3. lambda = max(mean of p over the min(n, context) + 1 most recent frames, this one included, power_floor), p = mean_m |y_m|^2
+ *      (the floor is absolute: one relative to max_t p would not be causal)
+ *   4. u = P z;  d = alpha lambda + Re(z^H u);  k = u / d
+ *   5. P <- (P - k u^H) / alpha           the lower triangle is computed and mirrored: P stays exactly Hermitian
+ *   6. G <- G + k x^H
+ *   7. the frame enters the frame ring, p the power ring, n <- n + 1 (n stops at 2^31 - 1)
+ * A failing frame -- a non-finite sample in it, or d not finite or not > 0 -- is passed through: x = y, P and G stay, the frame
+ * enters the frame ring as zeros and p as 0, fail[b, f] |= 1, n advances.  Nothing is clamped.  (Silence with alpha < 1 multiplies
+ * P by 1 / alpha per frame; reset the stream before that overflows, after 7e5 frames at alpha 0.999.)
+ * Every sum runs in one fixed order, without atomics: the bits of an item depend neither on B, nor on its position in the batch,
+ * nor on how the stream is cut into calls.  misonet_owpe is one launch, with no host synchronisation and no allocation: it can be
+ * captured in a HIP graph (after one misonet_owpe_reset on that device outside the capture).
+ * mix_dev and out_dev are complex64 [B, M, T, F]; they must not be the same buffer.  state_dev: misonet_owpe_state_bytes bytes,
+ * 16-byte aligned, written by misonet_owpe_reset before the first call; its size does not depend on T.  1 <= M <= 8,
+ * M taps <= 80, delay >= 1 (and small enough for the frame ring to fit the 160 KB of LDS beside P: misonet_owpe_lds_bytes),
+ * 0 <= context <= 16, 0 < alpha <= 1, power_floor and init finite and > 0, B F < 2^31: anything else is refused on the host with
+ * MISONET_EINVAL and a message (the size functions: -1), before any launch; a short state is MISONET_ENOMEM. */
+typedef struct {
+  int taps;
+  int delay;
+  int context;             /* earlier frames in the power estimate */
+  double alpha;            /* forgetting factor */
+  double power_floor;      /* absolute */
+  double init;             /* P = init I at reset */
+} misonet_owpe_opts;
+int misonet_owpe_opts_default(misonet_owpe_opts* opts);  /* 10, 3, 0, 0.999, 1e-10, 1.0 */
+long long misonet_owpe_state_bytes(int B, int M, int F, const misonet_owpe_opts* opts);
+int misonet_owpe_lds_bytes(int M, const misonet_owpe_opts* opts);   /* the LDS one workgroup takes; -1 on bad arguments */
+int misonet_owpe_reset(void* state_dev, int B, int M, int F, const misonet_owpe_opts* opts, misonet_stream stream);
+int misonet_owpe(const void* mix_dev, int B, int M, int T, int F, const misonet_owpe_opts* opts, void* out_dev, void* state_dev,
+                 long long state_bytes, misonet_stream stream);
+/* diagnostic: copy G complex128 [B, F, M taps, M], P complex128 [B, F, M taps, M taps], fail int32 [B, F] and n int32 [B, F] out
+ * of the state to device buffers (any may be NULL) */
+int misonet_owpe_debug(const void* state_dev, int B, int M, int F, const misonet_owpe_opts* opts, void* g_c128_dev,
+                       void* p_c128_dev, int* fail_dev, int* n_dev, misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

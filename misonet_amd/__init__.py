@@ -7,6 +7,8 @@ Host-side mirror of the reference call surface:
                              of the WPD convolutional beamformer, kind "wpd")
   Apply_Beamforming_Joint   (the joint multi-speaker beamformers: LCMV, SDW-MWF, rank-1 MWF; JointBeamformer: their options)
   dereverb, dereverb_wav    (WPE dereverberation of spectrograms / of a whole recording; Dereverb: its options)
+  DereverbStream, dereverb_online  (online WPE: the frame-recursive form, fed audio as it arrives, its state carried from call
+                             to call; OnlineDereverb: its options)
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
@@ -22,6 +24,7 @@ The compute lives in csrc/ (libmisonet_hip.so); importing a compute symbol witho
 library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
+           "OnlineDereverb", "DereverbStream", "dereverb_online",
            "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "resample", "resampled_len",
            "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
            "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
@@ -40,7 +43,7 @@ def __getattr__(name):
     if name in ("Apply_Beamforming_Joint", "JointBeamformer"):
         from . import beamform
         return getattr(beamform, name)
-    if name in ("Dereverb", "dereverb", "dereverb_wav"):
+    if name in ("Dereverb", "dereverb", "dereverb_wav", "OnlineDereverb", "DereverbStream", "dereverb_online"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)
     if name in ("Refine", "cacgmm", "masks_from_estimates"):

@@ -38,6 +38,12 @@ class WpeOpts(C.Structure):
                 ("power_floor", C.c_double)]
 
 
+class OwpeOpts(C.Structure):
+    """misonet_owpe_opts (ABI 620)"""
+    _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("context", C.c_int), ("alpha", C.c_double),
+                ("power_floor", C.c_double), ("init", C.c_double)]
+
+
 class WpdOpts(C.Structure):
     """misonet_wpd_opts (ABI 530)"""
     _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("diag_load", C.c_double), ("power_floor", C.c_double),
@@ -107,6 +113,14 @@ SIGNATURES = {
                               C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_wpe_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(WpeOpts), C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "misonet_owpe_opts_default": (C.c_int, [C.POINTER(OwpeOpts)]),
+    "misonet_owpe_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.POINTER(OwpeOpts)]),
+    "misonet_owpe_lds_bytes": (C.c_int, [C.c_int, C.POINTER(OwpeOpts)]),
+    "misonet_owpe_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OwpeOpts), C.c_void_p]),
+    "misonet_owpe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OwpeOpts), C.c_void_p, C.c_void_p,
+                               C.c_longlong, C.c_void_p]),
+    "misonet_owpe_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OwpeOpts), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_wpd_opts_default": (C.c_int, [C.POINTER(WpdOpts)]),
     "misonet_wpd_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts)]),
     "misonet_wpd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WpdOpts), C.c_void_p,

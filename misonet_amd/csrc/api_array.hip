@@ -1,5 +1,6 @@
 // C ABI of the array processing (include/misonet.h): the drop-in beamformers misonet_mvdr* / misonet_bf_* / misonet_beamform*
-// (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip), the WPD beamformer misonet_wpd* (wpd.hip), guided spatial clustering
+// (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip) and its online form misonet_owpe* (owpe.hip), the WPD beamformer
+// misonet_wpd* (wpd.hip), guided spatial clustering
 // misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), blind
 // separation misonet_auxiva* (iva.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
@@ -234,6 +235,87 @@ int misonet_wpe_debug(const void* ws, int B, int M, int F, const misonet_wpe_opt
   if (!ws) return fail(MISONET_EINVAL, "null argument");
   { int r = wpe_check(B, M, 2, F, opts); if (r) return r; }
   HIPCHK(launch_wpe_debug(ws, B, M, F, opts->taps, g, fail_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- online WPE: frame-recursive, state carried (ABI 620) ------------------------------------------------------------
+int misonet_owpe_opts_default(misonet_owpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->taps = 10; o->delay = 3; o->context = 0; o->alpha = 0.999; o->power_floor = 1e-10; o->init = 1.0;
+  return MISONET_OK;
+}
+
+// host-side check of every field and of the geometry they are used with
+static int owpe_check(int B, int M, int F, const misonet_owpe_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null online dereverberation options");
+  if (B < 1 || F < 1 || (long long)B * F > 0x7fffffffLL)
+    return fail(MISONET_EINVAL, "B and F must be positive with B * F < 2^31 (got %d, %d)", B, F);
+  if (M < 1 || M > 8) return fail(MISONET_EINVAL, "M must be in [1, 8] (got %d)", M);
+  if (o->taps < 1 || (long long)M * o->taps > 80)
+    return fail(MISONET_EINVAL, "taps must be >= 1 and M * taps <= 80 (got taps %d, M %d)", o->taps, M);
+  if (o->delay < 1) return fail(MISONET_EINVAL, "delay must be >= 1 (got %d)", o->delay);
+  if (owpe_lds_bytes(M, o->taps, o->delay) > OWPE_LDS_LIMIT)
+    return fail(MISONET_EINVAL, "delay %d with taps %d and M %d: the frame ring does not fit the 160 KB of LDS", o->delay, o->taps, M);
+  if (o->context < 0 || o->context > OWPE_CTX)
+    return fail(MISONET_EINVAL, "context must be in [0, %d] (got %d)", OWPE_CTX, o->context);
+  if (!(o->alpha > 0.0 && o->alpha <= 1.0)) return fail(MISONET_EINVAL, "alpha must be in (0, 1] (got %g)", o->alpha);
+  if (!(o->power_floor > 0.0) || !std::isfinite(o->power_floor))
+    return fail(MISONET_EINVAL, "power_floor must be finite and > 0 (got %g)", o->power_floor);
+  if (!(o->init > 0.0) || !std::isfinite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
+  return MISONET_OK;
+}
+
+// the dynamic-LDS attribute of owpe_k: once per device, never inside an asynchronous call after that
+static int owpe_ready() {
+  static std::atomic<bool> done[MAX_DEV];
+  static std::mutex mu;
+  const int d = cur_dev();
+  if (done[d].load(std::memory_order_acquire)) return MISONET_OK;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!done[d].load(std::memory_order_acquire)) {
+    HIPCHK(owpe_init());
+    done[d].store(true, std::memory_order_release);
+  }
+  return MISONET_OK;
+}
+
+long long misonet_owpe_state_bytes(int B, int M, int F, const misonet_owpe_opts* opts) {
+  if (owpe_check(B, M, F, opts)) return -1;
+  return owpe_state_bytes((long long)B * F, M, opts->taps, opts->delay);
+}
+
+int misonet_owpe_lds_bytes(int M, const misonet_owpe_opts* opts) {
+  if (owpe_check(1, M, 1, opts)) return -1;
+  return (int)owpe_lds_bytes(M, opts->taps, opts->delay);
+}
+
+int misonet_owpe_reset(void* state, int B, int M, int F, const misonet_owpe_opts* opts, misonet_stream stream) {
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  { int r = owpe_check(B, M, F, opts); if (r) return r; }
+  { int r = owpe_ready(); if (r) return r; }
+  HIPCHK(launch_owpe_reset(state, B, M, F, opts->taps, opts->delay, opts->init, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_owpe(const void* mix, int B, int M, int T, int F, const misonet_owpe_opts* opts, void* out, void* state,
+                 long long state_bytes, misonet_stream stream) {
+  if (!mix || !out || !state) return fail(MISONET_EINVAL, "null argument");
+  if (out == mix) return fail(MISONET_EINVAL, "out_dev must not be mix_dev");
+  { int r = owpe_check(B, M, F, opts); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be >= 1 (got %d)", T);
+  if (state_bytes < owpe_state_bytes((long long)B * F, M, opts->taps, opts->delay))
+    return fail(MISONET_ENOMEM, "state too small");
+  { int r = owpe_ready(); if (r) return r; }
+  HIPCHK(launch_owpe(mix, B, M, T, F, opts->taps, opts->delay, opts->context, opts->alpha, opts->power_floor, out, state,
+                     reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_owpe_debug(const void* state, int B, int M, int F, const misonet_owpe_opts* opts, void* g, void* p, int* fail_dev,
+                       int* n_dev, misonet_stream stream) {
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  { int r = owpe_check(B, M, F, opts); if (r) return r; }
+  HIPCHK(launch_owpe_debug(state, B, M, F, opts->taps, opts->delay, g, p, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

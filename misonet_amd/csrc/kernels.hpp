@@ -347,6 +347,21 @@ hipError_t launch_wpe(const void* mix, const float* power, int B, int M, int T, 
                       double diag_load, double power_floor, void* out, void* ws, hipStream_t s);
 hipError_t launch_wpe_debug(const void* ws, int B, int M, int F, int taps, void* g, int* fail, hipStream_t s);
 
+// Online WPE (owpe.hip): the frame-recursive form, its state carried from call to call.  mix / out complex64
+// [B][M][T][F], any T >= 1; the state holds fail int [B F], n int [B F], G complex128 [B F][M taps][M] and P complex128
+// [B F][M taps][M taps], which launch_owpe_debug copies out, and the two rings.  1 <= M <= 8, M taps <= 80, delay >= 1,
+// 0 <= context <= OWPE_CTX, owpe_lds_bytes(M, taps, delay) <= OWPE_LDS_LIMIT, B F < 2^31: the caller checks them.  owpe_init()
+// once per device (the kernel's dynamic-LDS attribute).
+constexpr int OWPE_CTX = 16, OWPE_LDS_LIMIT = 160 * 1024;
+long long owpe_state_bytes(long long bins, int M, int taps, int delay);
+long long owpe_lds_bytes(int M, int taps, int delay);
+hipError_t owpe_init();
+hipError_t launch_owpe_reset(void* state, int B, int M, int F, int taps, int delay, double init, hipStream_t s);
+hipError_t launch_owpe(const void* mix, int B, int M, int T, int F, int taps, int delay, int context, double alpha,
+                       double power_floor, void* out, void* state, hipStream_t s);
+hipError_t launch_owpe_debug(const void* state, int B, int M, int F, int taps, int delay, void* g, void* p, int* fail, int* n,
+                             hipStream_t s);
+
 // WPD convolutional beamformer (wpd.hip): one filter of order K = M (taps + 1) per (b, speaker, bin) from the
 // observation and the source estimate, both read as launch_mvdr reads them (mix through a CView; the source through est /
 // est_bstride / sel in pipeline mode or through src when est == nullptr), applied to the stacked observation and written through

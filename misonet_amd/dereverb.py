@@ -4,6 +4,11 @@
                          (Nakatani et al. 2010; with the defaults nara_wpe's ``wpe_v8``), float64 on the matrix cores
 ``dereverb_wav(wav)``    float32 [L, M] -> float32 [L, M]: STFT of the whole recording -> WPE -> iSTFT, on the device
 ``Dereverb``             the options as one plain-data object, used by every layer (``Enhancer(dereverb=...)``)
+
+Online WPE (csrc/owpe.hip, C ABI ``misonet_owpe``): the frame-recursive form, fed audio as it arrives.
+``DereverbStream(M)``    owns the state of one stream: ``process(block)`` takes any T >= 1 new frames; the memory does not grow
+``dereverb_online(mix)`` the one-shot call: reset, then process
+``OnlineDereverb``       its options (``dereverb_wav(online=...)``, ``Enhancer(dereverb=OnlineDereverb(...))``)
 """
 from __future__ import annotations
 
@@ -77,6 +82,159 @@ class Dereverb:
                             float(self.power_floor))
 
 
+@dataclasses.dataclass(frozen=True)
+class OnlineDereverb:
+    """One plain-data description of the online dereverberation (``misonet_owpe_opts`` of include/misonet.h).
+
+    taps         prediction filter length per microphone (M taps <= 80)
+    delay        prediction delay in frames (>= 1)
+    context      earlier frames in the power estimate (0 .. 16)
+    alpha        forgetting factor, 0 < alpha <= 1
+    power_floor  lambda = max(mean of the latest powers, power_floor): absolute, > 0
+    init         P = init I at reset, > 0
+    """
+    taps: int = 10
+    delay: int = 3
+    context: int = 0
+    alpha: float = 0.999
+    power_floor: float = 1e-10
+    init: float = 1.0
+
+    @classmethod
+    def of(cls, spec) -> "OnlineDereverb":
+        """None or True (the defaults), an OnlineDereverb, or a dict of the fields above"""
+        if spec is None or spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown online dereverb field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("online dereverb must be None, True, an OnlineDereverb or a dict of its fields")
+
+    def validate(self, num_mic: Optional[int] = None) -> "OnlineDereverb":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        for name in ("taps", "delay", "context"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"online dereverb {name} must be an integer, got {v!r}")
+        if num_mic is not None and not 1 <= num_mic <= 8:
+            raise ValueError(f"online dereverb takes 1 .. 8 microphones, got {num_mic}")
+        if self.taps < 1 or self.taps * (num_mic if num_mic is not None else 1) > 80:
+            raise ValueError(f"online dereverb taps must be >= 1 with M * taps <= 80, got taps {self.taps}"
+                             + (f" at M = {num_mic}" if num_mic is not None else ""))
+        if self.delay < 1:
+            raise ValueError(f"online dereverb delay must be >= 1, got {self.delay}")
+        if not 0 <= self.context <= 16:
+            raise ValueError(f"online dereverb context must be in [0, 16], got {self.context}")
+        for name in ("alpha", "power_floor", "init"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or not v > 0:
+                raise ValueError(f"online dereverb {name} must be finite and > 0, got {v!r}")
+        if self.alpha > 1:
+            raise ValueError(f"online dereverb alpha must be in (0, 1], got {self.alpha!r}")
+        return self
+
+    def c_opts(self) -> "_lib.OwpeOpts":
+        return _lib.OwpeOpts(int(self.taps), int(self.delay), int(self.context), float(self.alpha), float(self.power_floor),
+                             float(self.init))
+
+
+class DereverbStream:
+    """The state of one stream of online WPE, on the device: ``batch`` recordings of ``num_mic`` microphones and ``num_bins``
+    bins.  ``opts``: the fields of :class:`OnlineDereverb`.  The state is allocated once; a call allocates only its output."""
+
+    def __init__(self, num_mic, num_bins=129, batch=1, *, device=None, **opts):
+        self.opts = OnlineDereverb(**opts).validate(int(num_mic))
+        self.num_mic, self.num_bins, self.batch = int(num_mic), int(num_bins), int(batch)
+        if self.num_bins < 1 or self.batch < 1:
+            raise ValueError(f"num_bins and batch must be positive, got {num_bins}, {batch}")
+        self._c = self.opts.c_opts()
+        n = _lib.lib().misonet_owpe_state_bytes(self.batch, self.num_mic, self.num_bins, C.byref(self._c))
+        if n < 0:
+            _lib.check(_lib.EINVAL)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """P = init I, G = 0, the rings empty, no frame seen, no flag"""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_owpe_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins,
+                                                     C.byref(self._c), _lib.stream_ptr(self.device)))
+        return self
+
+    def process_into(self, block: torch.Tensor, out: torch.Tensor):
+        """block, out: complex64 [B, M, T, F] contiguous on the stream's device, not the same buffer.  One launch, nothing
+        allocated: the call a HIP graph captures."""
+        B, M, T, F = block.shape
+        if (B, M, F) != (self.batch, self.num_mic, self.num_bins):
+            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_owpe(block.data_ptr(), B, M, T, F, C.byref(self._c), out.data_ptr(),
+                                               self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
+        return out
+
+    def process(self, block):
+        """The next T >= 1 frames of the stream: complex [B, M, T, F] -> complex64 of the same shape, on the device for device
+        input and on the CPU for an ndarray.  The bits do not depend on how the stream is cut into calls."""
+        shape = np.shape(block)
+        if len(shape) != 4 or shape[2] < 1:
+            raise ValueError(f"block {tuple(shape)} must be [B, M, T, F] with T >= 1")
+        if (shape[0], shape[1], shape[3]) != (self.batch, self.num_mic, self.num_bins):
+            raise ValueError(f"block {tuple(shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        x, np_in = _dev_c64(block, self.device)
+        out = self.process_into(x, torch.empty_like(x))
+        return out.cpu() if np_in else out
+
+    def _debug(self, want=("G", "P", "fail", "n")):
+        """copies of the named parts of the state, on the device"""
+        B, M, F, N = self.batch, self.num_mic, self.num_bins, self.num_mic * self.opts.taps
+        shapes = dict(G=((B, F, N, M), torch.complex128), P=((B, F, N, N), torch.complex128), fail=((B, F), torch.int32),
+                      n=((B, F), torch.int32))
+        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
+        ptr = lambda k: d[k].data_ptr() if k in d else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_owpe_debug(self.state.data_ptr(), B, M, F, C.byref(self._c), ptr("G"), ptr("P"),
+                                                     ptr("fail"), ptr("n"), _lib.stream_ptr(self.device)))
+        return d
+
+    def filters(self):
+        """the prediction filter G complex128 [B, F, M taps, M] as it stands, on the device"""
+        return self._debug(("G",))["G"]
+
+    def covariance(self):
+        """the inverse correlation matrix P complex128 [B, F, M taps, M taps] as it stands, on the device"""
+        return self._debug(("P",))["P"]
+
+    @property
+    def frames_seen(self) -> int:
+        return int(self._debug(("n",))["n"].max().item())
+
+    @property
+    def fail(self) -> torch.Tensor:
+        """int32 [B, F] on the device: bit 0 set once a frame of that bin was passed through"""
+        return self._debug(("fail",))["fail"]
+
+
+def dereverb_online(mix, *, return_debug=False, device=None, **opts):
+    """Online WPE of a batch of spectrograms in one call: reset, then process.  mix complex [B, M, T, F], any T >= 1 -> complex64
+    of the same shape, on the device for device input and on the CPU for an ndarray.  ``opts``: the fields of
+    :class:`OnlineDereverb`.  ``return_debug`` adds, on the device, ``G``, ``P``, ``fail`` and ``n`` of the final state.  Causal:
+    frame t of the output depends on no later frame.  It does not dereverberate better than :func:`dereverb`."""
+    shape = np.shape(mix)
+    o = OnlineDereverb(**opts).validate(shape[1] if len(shape) == 4 else None)
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F], all positive")
+    if device is None:
+        device = mix.device if isinstance(mix, torch.Tensor) and mix.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    st = DereverbStream(shape[1], shape[3], shape[0], device=device, **dataclasses.asdict(o))
+    out = st.process(mix)
+    return (out, st._debug()) if return_debug else out
+
+
 def _wpe_device(mix: torch.Tensor, power: Optional[torch.Tensor], opts: "_lib.WpeOpts", return_debug: bool):
     """mix complex64 [B, M, T, F] contiguous on the device (power float32 [B, T, F] or None) -> out (and the debug dict)"""
     B, M, T, F = mix.shape
@@ -130,7 +288,7 @@ def dereverb(mix, power=None, *, taps=10, delay=3, iterations=3, diag_load=0.0, 
     return (out, dbg) if return_debug else out
 
 
-def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None, fs_out=None, **opts):
+def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None, fs_out=None, online=None, **opts):
     """Recording-wise dereverberation: wav float32 [L, M] (ndarray or tensor) -> float32 [L, M] of the same kind.
 
     The recording is zero-padded to whole hops, transformed in one piece (``misonet_stft``), dereverberated
@@ -146,7 +304,17 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None
     ``fs_in`` / ``fs_out``: ``fs`` is the rate the dereverberation runs at.  ``fs_in`` other than ``fs``: ``wav``
     is at ``fs_in`` and is taken to ``fs`` on the device first (:mod:`misonet_amd.resample`); ``fs_out`` (an integer rate or ``"in"``):
     the float32 result is taken to that rate on the device, and has the input's length L when that is the input's rate.  The SRMR
-    is measured at ``fs``.  With both None not one launch is added."""
+    is measured at ``fs``.  With both None not one launch is added.
+
+    ``online``: None -- the offline filter above, every bit and every launch as before; True, an
+    :class:`OnlineDereverb` or a dict of its fields -- the frame-recursive form between the same STFT and iSTFT
+    (``misonet_owpe_reset``, one ``misonet_owpe`` over all frames); ``opts`` must then be empty."""
+    if online is not None and online is not False:
+        if opts:
+            raise ValueError(f"with online= the options go into it, not beside it: {sorted(opts)}")
+        online = OnlineDereverb.of(online)
+    else:
+        online = None
     if fs_in is not None or fs_out is not None:
         from . import resample as RS
         r_in, r_out, _ = RS.plan_rates(fs, fs_in, fs_out)                  # a bad rate: before anything else
@@ -154,6 +322,8 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None
             from . import score as SC
             SC.check_srmr_fs(fs)
         Dereverb(**opts)                                                   # ... and an unknown option
+        if online is not None:
+            opts = dict(online=online)
         np_in = not isinstance(wav, torch.Tensor)
         w = torch.as_tensor(wav)
         if w.dim() != 2 or w.shape[0] <= w.shape[1]:
@@ -175,7 +345,7 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None
     if srmr:
         from . import score as SC
         SC.check_srmr_fs(fs)
-    d = Dereverb(**opts)
+    d = Dereverb(**opts) if online is None else online
     np_in = not isinstance(wav, torch.Tensor)
     w = torch.as_tensor(wav)
     if w.dim() != 2 or w.shape[0] <= w.shape[1]:
@@ -188,7 +358,10 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None
     padded = torch.zeros((1, Lp, M), dtype=torch.float32, device=device)
     padded[0, :L] = w.to(device=device, dtype=torch.float32)
     spec = S.stft_hip(padded)                                          # [1, M, Lp / 64 + 1, 129]
-    out, _ = _wpe_device(spec, None, d.c_opts(), False)
+    if online is None:
+        out, _ = _wpe_device(spec, None, d.c_opts(), False)
+    else:
+        out = DereverbStream(M, spec.shape[3], 1, device=device, **dataclasses.asdict(d)).process(spec)
     y = S._istft_hip(out, False)[0, :, :L].transpose(0, 1).contiguous()    # [L, M]
     if srmr:
         if not 0 <= int(ref_ch) < M:

@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from . import stft as S
 from .beamform import Beamformer, JointBeamformer
-from .dereverb import Dereverb, dereverb_wav
+from .dereverb import Dereverb, OnlineDereverb, dereverb_wav
 from .model import MISO_1, MISO_3
 from .refine import Refine, refined_images
 from .weights import N_FREQ
@@ -217,7 +217,8 @@ class Enhancer:
         ``beamformer``: None (the reference's MVDR), a :class:`misonet_amd.beamform.Beamformer` or a dict of its fields, or a
         :class:`misonet_amd.beamform.JointBeamformer` instance (one joint solve for all speakers); it reaches the fused pass and
         every ``beamform_*`` method (:meth:`set_beamformer`).
-        ``dereverb``: None (no dereverberation), True, a :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields:
+        ``dereverb``: None (no dereverberation), True, a :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields, or a
+        :class:`misonet_amd.dereverb.OnlineDereverb` instance:
         the recording paths dereverberate the observation first (:meth:`set_dereverb`).
         ``refine``: None (off), True, a :class:`misonet_amd.refine.Refine` or a dict of its fields: guided spatial clustering
         between the separation and the beamformer (:meth:`set_refine`)."""
@@ -254,18 +255,24 @@ class Enhancer:
     def set_dereverb(self, dereverb=None):
         """WPE dereverberation in front of the recording paths (:meth:`enhance_recording`, :meth:`enhance_recordings`,
         :meth:`enhance_continuous`): None (off, the default: the existing path, no extra launch), True (the defaults), a
-        :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields.  When set, the selected microphones of the whole
+        :class:`misonet_amd.dereverb.Dereverb` or a dict of its fields, or a :class:`misonet_amd.dereverb.OnlineDereverb`
+        INSTANCE (the frame-recursive form, ``dereverb_wav(online=...)``).  When set, the selected microphones of the whole
         recording go through :func:`misonet_amd.dereverb.dereverb_wav` on the device before they are cut into chunks or
         windows; everything downstream is untouched, and with ``score=True`` the mixture baseline (SI-SDRi, BSS-eval, STOI)
         stays the ORIGINAL observation at ``ref_ch``.  :meth:`enhance`, the ``beamform_*`` methods and the loader-driven
         :meth:`inference` receive ready spectrograms and are not changed: put ``dereverb(mix)`` in front of them.  Legal
         between passes; ValueError for a bad field."""
+        if isinstance(dereverb, OnlineDereverb):
+            self.dereverb = dereverb.validate(self.num_ch)
+            return
         self.dereverb = None if dereverb is None or dereverb is False else Dereverb.of(dereverb).validate(self.num_ch)
 
     def _observe(self, obs):
         """the selected microphones of one recording, float32 [L, M], as the networks will see them"""
         if self.dereverb is None:
             return obs
+        if isinstance(self.dereverb, OnlineDereverb):
+            return dereverb_wav(np.ascontiguousarray(obs), device=self.device, online=self.dereverb)
         return dereverb_wav(np.ascontiguousarray(obs), device=self.device, **dataclasses.asdict(self.dereverb))
 
     def set_beamformer(self, beamformer=None):

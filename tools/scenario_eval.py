@@ -11,8 +11,8 @@ off each RIR by Schroeder integration on the host is printed beside it), sensor 
 tests/golden/g16_stoi.npz (8 s, 8 kHz).  Nothing outside the repository is read.
 
 Front ends, all through ``BlindSeparator.separate_recording``: the AuxIVA image at ``ref_ch``; AuxIVA followed by each
-beamformer kind (MVDR, MPDR, Souden, GEV with BAN, WPD, LCMV, SDW-MWF, r1-MWF); the same with WPE (``dereverb_wav``) in front; the
-beamformer arms with the guided cACGMM between AuxIVA and the beamformer.  Every output is scored against the EARLY images at
+beamformer kind (MVDR, MPDR, Souden, GEV with BAN, WPD, LCMV, SDW-MWF, r1-MWF); the same with WPE (``dereverb_wav``) in front;
+online WPE (``dereverb_wav(online=True)``: causal, frame-recursive) in front of AuxIVA alone and of MVDR and LCMV; the beamformer arms with the guided cACGMM between AuxIVA and the beamformer.  Every output is scored against the EARLY images at
 ``ref_ch`` (the direct path and the first 50 ms) on the device: SI-SDR of the best assignment and its improvement over the
 mixture, BSS-eval SDR, STOI, cepstral distance, LLR, fwSegSNR and SRMR, averaged over the speakers and the scenes.  No figure is
 required to come out any particular way: the table is what was measured, a front end that makes things worse included.
@@ -51,7 +51,7 @@ def draw_scene(rng, i):
 
 
 def arms(which):
-    """name -> (WPE in front, beamform, BlindSeparator keywords)"""
+    """name -> (WPE in front: False, True or "online", beamform, BlindSeparator keywords)"""
     from misonet_amd.beamform import Beamformer, JointBeamformer
     bfs = {"mvdr": Beamformer(kind="mvdr"), "mpdr": Beamformer(kind="mvdr", noise="mix"), "souden": Beamformer(kind="souden"),
            "gev+ban": Beamformer(kind="gev", ban=True), "wpd": Beamformer(kind="wpd"), "lcmv": JointBeamformer(kind="lcmv"),
@@ -62,6 +62,8 @@ def arms(which):
     out.update({f"auxiva+{k}": (False, True, dict(beamformer=b)) for k, b in bfs.items()})
     out["wpe+auxiva"] = (True, False, {})
     out.update({f"wpe+auxiva+{k}": (True, True, dict(beamformer=b)) for k, b in bfs.items()})
+    out["owpe+auxiva"] = ("online", False, {})
+    out.update({f"owpe+auxiva+{k}": ("online", True, dict(beamformer=bfs[k])) for k in ("mvdr", "lcmv")})
     out.update({f"auxiva+cacgmm+{k}": (False, True, dict(beamformer=b, refine=True)) for k, b in bfs.items()})
     return out
 
@@ -118,13 +120,13 @@ def main(argv=None):
         print(head[-1], flush=True)
         ref = np.ascontiguousarray(sc.early[:, :, a.ref_ch])
         mixture = np.ascontiguousarray(sc.wav[:, a.ref_ch])
-        dewav = None
+        dewav = {}
         for name, (wpe, beamform, kw) in table.items():
             wav = sc.wav
             if wpe:
-                if dewav is None:
-                    dewav = dereverb_wav(sc.wav, fs=FS)
-                wav = dewav
+                if wpe not in dewav:
+                    dewav[wpe] = dereverb_wav(sc.wav, fs=FS, online=True if wpe == "online" else None)
+                wav = dewav[wpe]
             try:
                 sep = mz.BlindSeparator(2, 6, ref_ch=a.ref_ch, **kw)
                 pcm = sep.separate_recording(wav, fs=FS, beamform=beamform)
