@@ -15,10 +15,12 @@ the place where the faults are planted that the bars of the device tests have to
 """
 import numpy as np
 
-from wpe_ref import _pivots_ok, stack
+from wpe_ref import _pivots_ok, stack, stack_hist
 
-# every fault wpd_bin can plant; "floor" shows only where the floor binds (power_floor large enough)
-FAULTS = ("delay", "floor", "ref_ch", "conj", "seam", "block")
+# every fault wpd_bin can plant; "floor" shows only where the floor binds (power_floor large enough), the TILE_FAULTS only where
+# T reaches past one tile of the kernel
+FAULTS = ("delay", "floor", "ref_ch", "conj", "seam", "block", "tail", "hist")
+TILE_FAULTS = ("tail", "hist")
 TILE = 64           # frames per LDS tile of the kernel: where a stale frame would sit
 
 
@@ -29,10 +31,15 @@ def wpd_bin(Y, S, taps=5, delay=3, diag_load=0.0, power_floor=1e-10, ref_ch=0, s
     S = np.asarray(S).astype(np.complex128)
     M, T = Y.shape
     K = M * (taps + 1)
-    ybar = np.concatenate([Y, stack(Y, taps, delay + (1 if fault == "delay" else 0))], axis=0)
+    if fault == "hist":                                               # z reads 0 wherever its frame lies in an earlier tile
+        ybar = np.concatenate([Y, stack_hist(Y, taps, delay)], axis=0)
+    else:
+        ybar = np.concatenate([Y, stack(Y, taps, delay + (1 if fault == "delay" else 0))], axis=0)
     p = np.mean(np.abs(S) ** 2, axis=0)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         w = 1.0 / np.maximum(p, (0.0 if fault == "floor" else power_floor) * np.max(p))
+        if fault == "tail":                                           # the frames past the last whole tile carry no weight in R
+            w = np.where(np.arange(T) < T // TILE * TILE, w, 0.0)
         lhs = ybar.copy()
         if fault == "seam":                                       # the first frame of a tile (the last frame where there is
             ts = TILE if T > TILE else T - 1                      # one tile only) is the one before it
