@@ -696,6 +696,61 @@ int misonet_owpe(const void* mix_dev, int B, int M, int T, int F, const misonet_
 int misonet_owpe_debug(const void* state_dev, int B, int M, int F, const misonet_owpe_opts* opts, void* g_c128_dev,
                        void* p_c128_dev, int* fail_dev, int* n_dev, misonet_stream stream);
 
+/* ---- online AuxIVA: frame-recursive blind separation, its state carried from call to call (ABI 630) ---------------------- */
+/* The project's own definition in the online-AuxIVA family (Taniguchi, Ono, Kawamura & Sagayama 2014; INTEGRATION.md 4s in full,
+ * tests/oiva_ref.py restates it in NumPy float64).  pyroomacoustics and torchiva were not available: nothing here was compared
+ * against them.  Audio is fed as it arrives: a call takes any T >= 1 new frames and advances the state; the memory does not grow.
+ * Each item b runs on its own.  The determined case only: K = M sources, no PCA, 2 <= M <= 8.
+ * State per (b, f): W complex128 [M, M] (row k is w_k^H, y = W x), V complex128 [M, M, M] (one Hermitian M x M matrix per
+ * source), n int32 (the frames seen; it stops at 2^31 - 1) and fail int32.  misonet_oiva_reset: W = I, V_k = init I, n = 0,
+ * fail = 0; it writes every byte of the state.  Per new frame, x_f the frame's M samples of bin f, float64 after the load:
+ *   0. a bin whose frame holds a non-finite sample: fail |= 1; its x_f counts as 0 in steps 1-2, step 3 is skipped for it (W
+ *      and V stay) and its outputs for this frame are 0
+ *   1. yt_k[f] = sum_m W_f[k, m] x_f[m], m ascending, with W as it stood before this frame
+ *   2. r_k = sum_f |yt_k[f]|^2, in one fixed order that depends on M and F alone (not on B, T or the cut);
+ *      model 0 "gauss": phi_k = 1 / max(r_k / F, floor);  model 1 "laplace": phi_k = 1 / max(2 sqrt(r_k), floor)
+ *      (the formulas of misonet_auxiva with one frame in the place of all)
+ *   3. per bin, for k = 0 .. M - 1 in order:
+ *        V_k <- alpha V_k + (1 - alpha) phi_k x x^H   the lower triangle is computed and mirrored, the diagonal's imaginary part
+ *                                                     is exactly 0: V_k stays exactly Hermitian
+ *        (W V_k) u = e_k                              W with the rows already replaced in this frame.  Gaussian elimination with
+ *                                                     partial pivoting and back substitution; the pivot is the largest
+ *                                                     |re| + |im| of the column (a non-finite one counts as the largest), ties
+ *                                                     go to the lower row
+ *        d = Re(u^H V_k u)
+ *        a pivot 0 or non-finite, or d not finite or not > 0: row k stays and fail |= 2; otherwise row k of W <- conj(u) / sqrt(d)
+ *   4. y = W x with the new W;  A = W^-1 by the same elimination (one column per e_j);  est[k] = A[ref_ch, k] y_k,
+ *      images[k, m] = A[m, k] y_k, each rounded once to complex64;  W singular: fail |= 4 and the outputs of this (f, t) are 0
+ *   5. n <- n + 1
+ * Nothing is clamped.  Every sum runs in one fixed order, without atomics: the bits of an item depend neither on B, nor on its
+ * position in the batch, nor on how the stream is cut into calls.  misonet_oiva is one launch for any T >= 1, with no host
+ * synchronisation and no allocation: it can be captured in a HIP graph (after one misonet_oiva_reset outside the capture).
+ * Every element of every output is written.
+ * mix_dev complex64 [B, M, T, F]; est_out_dev complex64 [B, M(k), T, F]; images_out_dev (may be NULL) complex64
+ * [B, M(k), M, T, F]; no two of them may overlap.  state_dev: misonet_oiva_state_bytes bytes, 16-byte aligned, written by
+ * misonet_oiva_reset before the first call; its size does not depend on T.  2 <= M <= 8, B >= 1, T >= 1, 1 <= F <= 1025,
+ * 0 < alpha < 1 (1 would freeze V), floor and init finite and > 0, 0 <= ref_ch < M, B F < 2^31: anything else is refused on the
+ * host with MISONET_EINVAL and a message (the size functions: -1), before any launch and before any pointer is looked at; a
+ * short state is MISONET_ENOMEM.  misonet_oiva_bins_per_pass: the bins of an item that one workgroup covers at once (for tests
+ * that probe the edges). */
+typedef struct {
+  int model;               /* 0 gauss, 1 laplace */
+  int ref_ch;              /* the microphone est is projected to */
+  double alpha;            /* forgetting factor */
+  double floor;            /* under the weights' denominators, absolute */
+  double init;             /* V_k = init I at reset */
+} misonet_oiva_opts;
+int misonet_oiva_opts_default(misonet_oiva_opts* opts);  /* 0, 0, 0.98, 1e-10, 1.0 */
+long long misonet_oiva_state_bytes(int B, int M, int F);
+int misonet_oiva_bins_per_pass(int M);
+int misonet_oiva_reset(void* state_dev, int B, int M, int F, const misonet_oiva_opts* opts, misonet_stream stream);
+int misonet_oiva(const void* mix_dev, int B, int M, int T, int F, const misonet_oiva_opts* opts, void* est_out_dev,
+                 void* images_out_dev_or_null, void* state_dev, long long state_bytes, misonet_stream stream);
+/* diagnostic: copy W complex128 [B, F, M, M], V complex128 [B, F, M, M, M], fail int32 [B, F] and n int32 [B, F] out of the state
+ * to device buffers (any may be NULL) */
+int misonet_oiva_debug(const void* state_dev, int B, int M, int F, void* w_c128_dev, void* v_c128_dev, int* fail_dev, int* n_dev,
+                       misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

@@ -11,6 +11,7 @@ Host-side mirror of the reference call surface:
                              to call; OnlineDereverb: its options)
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
+  SeparateStream, auxiva_online   (online AuxIVA: frame-recursive separation, state carried; OnlineAuxIVA: its options)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
                              definition, in front of and behind every recording path)
   Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
@@ -25,7 +26,7 @@ library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "OnlineDereverb", "DereverbStream", "dereverb_online",
-           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "resample", "resampled_len",
+           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online", "resample", "resampled_len",
            "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
            "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
 
@@ -49,7 +50,7 @@ def __getattr__(name):
     if name in ("Refine", "cacgmm", "masks_from_estimates"):
         import importlib
         return getattr(importlib.import_module(".refine", __name__), name)
-    if name in ("AuxIVA", "auxiva", "BlindSeparator"):
+    if name in ("AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online"):
         import importlib
         return getattr(importlib.import_module(".blind", __name__), name)
     if name in ("resample", "resampled_len", "load_wav"):

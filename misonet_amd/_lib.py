@@ -44,6 +44,11 @@ class OwpeOpts(C.Structure):
                 ("power_floor", C.c_double), ("init", C.c_double)]
 
 
+class OivaOpts(C.Structure):
+    """misonet_oiva_opts (ABI 630): model 0 gauss / 1 laplace"""
+    _fields_ = [("model", C.c_int), ("ref_ch", C.c_int), ("alpha", C.c_double), ("floor", C.c_double), ("init", C.c_double)]
+
+
 class WpdOpts(C.Structure):
     """misonet_wpd_opts (ABI 530)"""
     _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("diag_load", C.c_double), ("power_floor", C.c_double),
@@ -151,6 +156,14 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_auxiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_oiva_opts_default": (C.c_int, [C.POINTER(OivaOpts)]),
+    "misonet_oiva_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "misonet_oiva_bins_per_pass": (C.c_int, [C.c_int]),
+    "misonet_oiva_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OivaOpts), C.c_void_p]),
+    "misonet_oiva": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OivaOpts), C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_oiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

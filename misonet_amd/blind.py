@@ -10,6 +10,14 @@ compared against those packages.
 ``auxiva(mix, num_spks, ...)``   -- the separation; images complex64 [B, S, F, M, T], optionally the chosen rows and the diagnostics
 ``AuxIVA``                       -- the options as plain data
 ``BlindSeparator``               -- the recording-level composition: AuxIVA -> (cACGMM) -> beamformer -> iSTFT -> files
+
+Online AuxIVA (csrc/oiva.hip, C ABI ``misonet_oiva``): the frame-recursive form of the determined case
+(K = M, no PCA; Taniguchi, Ono, Kawamura & Sagayama 2014), fed audio as it arrives in the stream layout [B, M, T, F] of
+:class:`misonet_amd.dereverb.DereverbStream`.  It is not a better separator than :func:`auxiva`.
+
+``SeparateStream``               -- the state of one stream; ``process(block)`` takes any T >= 1 new frames
+``auxiva_online(mix, ...)``      -- the one-shot call: reset, then process
+``OnlineAuxIVA``                 -- its options as plain data
 """
 from __future__ import annotations
 
@@ -95,6 +103,170 @@ class AuxIVA:
     def c_opts(self) -> "_lib.IvaOpts":
         return _lib.IvaOpts(int(self.iterations), MODELS.index(self.model), int(self.channels or 0), int(self.ref_ch),
                             float(self.floor))
+
+
+@dataclasses.dataclass(frozen=True)
+class OnlineAuxIVA:
+    """One plain-data description of the online separation (``misonet_oiva_opts`` of include/misonet.h).
+
+    alpha    forgetting factor of the weighted covariances, 0 < alpha < 1 (1 would freeze them)
+    model    "gauss": phi = 1 / max(mean_f |y|^2, floor); "laplace": phi = 1 / max(2 sqrt(sum_f |y|^2), floor), per frame
+    floor    the floor under the weights' denominators (> 0)
+    init     V_k = init I at reset (> 0)
+    ref_ch   the microphone ``est`` is projected to
+    """
+    alpha: float = 0.98
+    model: str = "gauss"
+    floor: float = 1e-10
+    init: float = 1.0
+    ref_ch: int = 0
+
+    @classmethod
+    def of(cls, spec) -> "OnlineAuxIVA":
+        """None or True (the defaults), an OnlineAuxIVA, a model name, or a dict of the fields above"""
+        if spec is None or spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            return cls(model=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown online blind field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("online must be None, True, an OnlineAuxIVA, a model name or a dict of its fields")
+
+    def validate(self, num_mic: Optional[int] = None) -> "OnlineAuxIVA":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        if self.model not in MODELS:
+            raise ValueError(f"online blind model {self.model!r}: one of {MODELS}")
+        for name in ("alpha", "floor", "init"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or not v > 0:
+                raise ValueError(f"online blind {name} must be finite and > 0, got {v!r}")
+        if not self.alpha < 1:
+            raise ValueError(f"online blind alpha must be in (0, 1), got {self.alpha!r}")
+        r = self.ref_ch
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0:
+            raise ValueError(f"online blind ref_ch must be a non-negative integer, got {r!r}")
+        if num_mic is not None:
+            if not 2 <= num_mic <= 8:
+                raise ValueError(f"online blind separation needs 2 <= M <= 8 microphones, got {num_mic}")
+            if r >= num_mic:
+                raise ValueError(f"online blind ref_ch {r} outside [0, {num_mic})")
+        return self
+
+    def c_opts(self) -> "_lib.OivaOpts":
+        return _lib.OivaOpts(MODELS.index(self.model), int(self.ref_ch), float(self.alpha), float(self.floor), float(self.init))
+
+
+def bins_per_pass(num_mic: int) -> int:
+    """the bins of an item that one workgroup of the online kernel covers at once (``misonet_oiva_bins_per_pass``)"""
+    return int(_lib.lib().misonet_oiva_bins_per_pass(int(num_mic)))
+
+
+class SeparateStream:
+    """The state of one stream of online AuxIVA, on the device: ``batch`` recordings of ``num_mic`` microphones (= sources) and
+    ``num_bins`` bins.  ``opts``: the fields of :class:`OnlineAuxIVA`.  The state is allocated once; a call allocates only its
+    outputs.  The stream returns all M rows, in no particular order of the sources."""
+
+    def __init__(self, num_mic, num_bins=129, batch=1, *, device=None, **opts):
+        self.opts = OnlineAuxIVA(**opts).validate(int(num_mic))
+        self.num_mic, self.num_bins, self.batch = int(num_mic), int(num_bins), int(batch)
+        if not 1 <= self.num_bins <= 1025 or self.batch < 1:
+            raise ValueError(f"num_bins must be in [1, 1025] and batch positive, got {num_bins}, {batch}")
+        self._c = self.opts.c_opts()
+        n = _lib.lib().misonet_oiva_state_bytes(self.batch, self.num_mic, self.num_bins)
+        if n < 0:
+            _lib.check(_lib.EINVAL)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """W = I, V_k = init I, no frame seen, no flag"""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_oiva_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins,
+                                                     C.byref(self._c), _lib.stream_ptr(self.device)))
+        return self
+
+    def process_into(self, block: torch.Tensor, est: torch.Tensor, images: Optional[torch.Tensor] = None):
+        """block, est: complex64 [B, M, T, F], images: complex64 [B, M, M, T, F] or None, contiguous on the stream's device and
+        not overlapping.  One launch, nothing allocated: the call a HIP graph captures."""
+        B, M, T, F = block.shape
+        if (B, M, F) != (self.batch, self.num_mic, self.num_bins):
+            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_oiva(block.data_ptr(), B, M, T, F, C.byref(self._c), est.data_ptr(),
+                                               images.data_ptr() if images is not None else None, self.state.data_ptr(),
+                                               self.state.numel(), _lib.stream_ptr(self.device)))
+        return est if images is None else (est, images)
+
+    def process(self, block, images=False):
+        """The next T >= 1 frames of the stream: complex [B, M, T, F] -> est complex64 [B, M, T, F] (row k at ``ref_ch``), with
+        ``images=True`` also the images complex64 [B, M(k), M, T, F]; on the device for device input and on the CPU for an
+        ndarray.  The bits do not depend on how the stream is cut into calls."""
+        shape = np.shape(block)
+        if len(shape) != 4 or shape[2] < 1:
+            raise ValueError(f"block {tuple(shape)} must be [B, M, T, F] with T >= 1")
+        if (shape[0], shape[1], shape[3]) != (self.batch, self.num_mic, self.num_bins):
+            raise ValueError(f"block {tuple(shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        x, np_in = _dev_c64(block, self.device)
+        est = torch.empty_like(x)
+        img = torch.empty((shape[0], shape[1]) + tuple(x.shape[1:]), dtype=torch.complex64, device=x.device) if images else None
+        self.process_into(x, est, img)
+        if np_in:
+            est, img = est.cpu(), (img.cpu() if images else None)
+        return (est, img) if images else est
+
+    def _debug(self, want=("W", "V", "fail", "n")):
+        """copies of the named parts of the state, on the device"""
+        B, M, F = self.batch, self.num_mic, self.num_bins
+        shapes = dict(W=((B, F, M, M), torch.complex128), V=((B, F, M, M, M), torch.complex128), fail=((B, F), torch.int32),
+                      n=((B, F), torch.int32))
+        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
+        ptr = lambda k: d[k].data_ptr() if k in d else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_oiva_debug(self.state.data_ptr(), B, M, F, ptr("W"), ptr("V"), ptr("fail"), ptr("n"),
+                                                     _lib.stream_ptr(self.device)))
+        return d
+
+    def demixing(self):
+        """the demixing matrices W complex128 [B, F, M, M] as they stand (row k = w_k^H), on the device"""
+        return self._debug(("W",))["W"]
+
+    def covariance(self):
+        """the weighted covariances V complex128 [B, F, M(k), M, M] as they stand, on the device"""
+        return self._debug(("V",))["V"]
+
+    @property
+    def frames_seen(self) -> int:
+        return int(self._debug(("n",))["n"].max().item())
+
+    @property
+    def fail(self) -> torch.Tensor:
+        """int32 [B, F] on the device: bit 0 a non-finite sample, bit 1 a row update that was dropped, bit 2 a singular W"""
+        return self._debug(("fail",))["fail"]
+
+
+def auxiva_online(mix, *, return_debug=False, images=False, device=None, **opts):
+    """Online AuxIVA of a batch of spectrograms in one call: reset, then process.  mix complex [B, M, T, F], any T >= 1 -> est
+    complex64 of the same shape (with ``images=True``: ``(est, images [B, M, M, T, F])``), on the device for device input and on
+    the CPU for an ndarray.  ``opts``: the fields of :class:`OnlineAuxIVA`.  ``return_debug`` adds, on the device, ``W``, ``V``,
+    ``fail`` and ``n`` of the final state.  Causal: frame t of the output depends on no later frame.  It does not separate better
+    than :func:`auxiva`."""
+    shape = np.shape(mix)
+    o = OnlineAuxIVA(**opts).validate(shape[1] if len(shape) == 4 else None)
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F], all positive")
+    if device is None:
+        device = mix.device if isinstance(mix, torch.Tensor) and mix.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    st = SeparateStream(shape[1], shape[3], shape[0], device=device, **dataclasses.asdict(o))
+    out = st.process(mix, images=images)
+    if not return_debug:
+        return out
+    return (out + (st._debug(),)) if images else (out, st._debug())
 
 
 def resident_frames(channels: int) -> int:
@@ -214,8 +386,23 @@ class BlindSeparator:
         mix_bf = self._mix(mix)
         return self._beamform(self._images(mix_bf), mix_bf)
 
+    def _online_rows(self, spec, online, dereverb):
+        """spec complex64 [1, M, Tt, F] on the device -> the num_spks strongest rows of the online separation [S, Tt, F]"""
+        M = spec.shape[1]
+        online.validate(M)
+        if self.num_spks > M:
+            raise ValueError(f"online separation returns M = {M} rows; {self.num_spks} speakers were asked for")
+        if dereverb is not None:
+            from .dereverb import DereverbStream
+            spec = DereverbStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(dereverb.validate(M))).process(spec)
+        est = SeparateStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(online)).process(spec)[0]
+        power = (est.real.double() ** 2 + est.imag.double() ** 2).sum(dim=(1, 2))                # [M]
+        rows = torch.sort(power, descending=True, stable=True).indices[:self.num_spks]
+        return est[rows].contiguous()
+
     def separate_recording(self, wav, num_ch_utilize: Optional[int] = None, save_path: Optional[str] = None, fs: int = 16000,
-                           beamform: bool = True, srmr: bool = False, fs_in=None, fs_out=None):
+                           beamform: Optional[bool] = None, srmr: bool = False, fs_in=None, fs_out=None, online=None,
+                           dereverb=None):
         """Recording in -> separated int16 waves out.  wav float32 [L, M_all] (time-major, as ``read_wav`` returns it) ->
         int16 [S, L] (an ndarray).  The microphone selection of ``Enhancer.enhance_recording`` (``[0:M:M // num_ch_utilize]``),
         ONE STFT over the recording zero-padded to whole hops, ONE AuxIVA over all its frames, then the optional clustering
@@ -223,14 +410,38 @@ class BlindSeparator:
         ``L``.  ``save_path`` = "<dir>/<name>" also writes ``<save_path>_{s}.wav`` as 24-bit PCM, the files
         ``tools/score_eval.py`` reads.  ``srmr=True`` returns ``(pcm, Srmr)``, as ``enhance_recording``.  ``fs_in`` / ``fs_out``: a
         recording at another rate than the separation's ``fs``, as ``enhance_recording`` takes them; both
-        None adds nothing to the call."""
+        None adds nothing to the call.
+
+        ``online``: None -- the offline path above, bit for bit; True, an :class:`OnlineAuxIVA`, a model name or
+        a dict of its fields (its ``ref_ch`` is replaced by this object's) -- ONE STFT, optionally a
+        :class:`misonet_amd.dereverb.DereverbStream` over the frames (``dereverb``: None, True, an
+        :class:`misonet_amd.dereverb.OnlineDereverb` or a dict of its fields), a :class:`SeparateStream` over the frames with all
+        the selected microphones as sources, then the ``num_spks`` rows of largest sum |est|^2 over the recording, descending, ties
+        to the lower index, the iSTFT and the int16 waves as above.  That row selection is made on the device with torch after the
+        whole recording has been seen: it is NOT causal -- the stream itself returns all M rows and leaves the choice to its
+        caller.  ``beamform``: None is True on the offline path, as it always was, and False with ``online``; ``beamform=True`` with
+        ``online`` is refused: the beamformers here are block algorithms.  ``dereverb`` without ``online`` is refused."""
+        if online is None or online is False:
+            if dereverb is not None:
+                raise ValueError("dereverb= belongs to the online path: set online= as well, or dereverberate with dereverb_wav first")
+            online = None
+            beamform = True if beamform is None else beamform
+        else:
+            if beamform:
+                raise ValueError("online= with beamform=True: the beamformers here are block algorithms; pass beamform=False")
+            beamform = False
+            online = dataclasses.replace(OnlineAuxIVA.of(online), ref_ch=self.ref_ch)
+            if dereverb is not None:
+                from .dereverb import OnlineDereverb
+                dereverb = OnlineDereverb.of(dereverb)
         if fs_in is not None or fs_out is not None:
             from . import resample as RS
             RS.plan_rates(fs, fs_in, fs_out)                                 # a bad rate: before anything else
             if srmr:
                 from . import score as SC
                 SC.check_srmr_fs(fs)
-            return RS.around(lambda w, _c, path: self.separate_recording(w, num_ch_utilize, path, fs, beamform, srmr),
+            return RS.around(lambda w, _c, path: self.separate_recording(w, num_ch_utilize, path, fs, beamform, srmr,
+                                                                         online=online, dereverb=dereverb),
                              wav, None, fs, fs_in, fs_out, save_path, self._write_speakers, self.device)
         if srmr:
             from . import score as SC
@@ -239,6 +450,12 @@ class BlindSeparator:
         L = obs.shape[0]
         sig = torch.from_numpy(np.ascontiguousarray(obs[:, mics])).to(self.device)               # [L, M]
         sig = torch.nn.functional.pad(sig, (0, 0, 0, (-L) % S.HOP))[None].contiguous()           # [1, Lp, M]
+        if online is not None:
+            out = self._online_rows(S.stft_hip(sig), online, dereverb)                           # [S, Tt, F]
+            pcm = np.ascontiguousarray(S.istft_int16(out)[:, :L].cpu().numpy())
+            if save_path is not None:
+                self._write_speakers(pcm, save_path, fs)
+            return (pcm, self._srmr_of(pcm, wav, num_ch_utilize, fs)) if srmr else pcm
         mix_bf = S.stft_hip(sig)[0].permute(2, 0, 1)[None].contiguous()                          # [1, F, M, Tt]
         est = self._images(mix_bf)                                                               # [1, S, F, M, Tt]
         if beamform:

@@ -2,7 +2,7 @@
 // (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip) and its online form misonet_owpe* (owpe.hip), the WPD beamformer
 // misonet_wpd* (wpd.hip), guided spatial clustering
 // misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), blind
-// separation misonet_auxiva* (iva.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// separation misonet_auxiva* (iva.hip) and its online form misonet_oiva* (oiva.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
@@ -316,6 +316,78 @@ int misonet_owpe_debug(const void* state, int B, int M, int F, const misonet_owp
   if (!state) return fail(MISONET_EINVAL, "null argument");
   { int r = owpe_check(B, M, F, opts); if (r) return r; }
   HIPCHK(launch_owpe_debug(state, B, M, F, opts->taps, opts->delay, g, p, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- online AuxIVA: frame-recursive separation, state carried (ABI 630) ----------------------------------------------
+int misonet_oiva_opts_default(misonet_oiva_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->model = 0; o->ref_ch = 0; o->alpha = 0.98; o->floor = 1e-10; o->init = 1.0;
+  return MISONET_OK;
+}
+
+static int oiva_geom_check(int B, int M, int F) {
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (B < 1) return fail(MISONET_EINVAL, "B must be positive (got %d)", B);
+  if (F < 1 || F > 1025) return fail(MISONET_EINVAL, "F must be in [1, 1025] (got %d)", F);
+  if ((long long)B * F > 0x7fffffffLL) return fail(MISONET_EINVAL, "B * F must be < 2^31 (got %d, %d)", B, F);
+  return MISONET_OK;
+}
+
+// host-side check of every field and of the geometry they are used with
+static int oiva_check(int B, int M, int F, const misonet_oiva_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null online separation options");
+  { int r = oiva_geom_check(B, M, F); if (r) return r; }
+  if (o->model != 0 && o->model != 1) return fail(MISONET_EINVAL, "model %d: 0 gauss, 1 laplace", o->model);
+  if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "ref_ch %d outside [0, %d)", o->ref_ch, M);
+  if (!(o->alpha > 0.0 && o->alpha < 1.0))
+    return fail(MISONET_EINVAL, "alpha must be in (0, 1): 1 would freeze the covariances (got %g)", o->alpha);
+  if (!(o->floor > 0.0) || !std::isfinite(o->floor)) return fail(MISONET_EINVAL, "floor must be finite and > 0 (got %g)", o->floor);
+  if (!(o->init > 0.0) || !std::isfinite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
+  return MISONET_OK;
+}
+
+long long misonet_oiva_state_bytes(int B, int M, int F) {
+  if (oiva_geom_check(B, M, F)) return -1;
+  return oiva_state_bytes((long long)B * F, M);
+}
+
+int misonet_oiva_bins_per_pass(int M) {
+  if (M < 2 || M > 8) { fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M); return -1; }
+  return oiva_bins_per_pass(M);
+}
+
+int misonet_oiva_reset(void* state, int B, int M, int F, const misonet_oiva_opts* opts, misonet_stream stream) {
+  { int r = oiva_check(B, M, F, opts); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_oiva_reset(state, B, M, F, opts->init, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool oiva_overlap(const void* a, long long na, const void* b, long long nb) {
+  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+int misonet_oiva(const void* mix, int B, int M, int T, int F, const misonet_oiva_opts* opts, void* est, void* images, void* state,
+                 long long state_bytes, misonet_stream stream) {
+  { int r = oiva_check(B, M, F, opts); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be >= 1 (got %d)", T);
+  if (!mix || !est || !state) return fail(MISONET_EINVAL, "null argument");
+  const long long n = (long long)B * M * T * F * 8;
+  if (oiva_overlap(mix, n, est, n) || (images && (oiva_overlap(mix, n, images, n * M) || oiva_overlap(est, n, images, n * M))))
+    return fail(MISONET_EINVAL, "mix_dev, est_out_dev and images_out_dev must not overlap");
+  if (state_bytes < oiva_state_bytes((long long)B * F, M)) return fail(MISONET_ENOMEM, "state too small");
+  HIPCHK(launch_oiva(mix, B, M, T, F, opts->model, opts->ref_ch, opts->alpha, opts->floor, est, images, state,
+                     reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_oiva_debug(const void* state, int B, int M, int F, void* w, void* v, int* fail_dev, int* n_dev, misonet_stream stream) {
+  { int r = oiva_geom_check(B, M, F); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_oiva_debug(state, B, M, F, w, v, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -362,6 +362,18 @@ hipError_t launch_owpe(const void* mix, int B, int M, int T, int F, int taps, in
 hipError_t launch_owpe_debug(const void* state, int B, int M, int F, int taps, int delay, void* g, void* p, int* fail, int* n,
                              hipStream_t s);
 
+// Online AuxIVA (oiva.hip): the frame-recursive separation of the determined case, its state carried from
+// call to call.  mix / est complex64 [B][M][T][F], images complex64 [B][M][M][T][F] or nullptr, any T >= 1; the state holds fail
+// int [B F], n int [B F], W complex128 [B F][M][M] and V complex128 [B F][M][M][M], which launch_oiva_debug copies out.
+// 2 <= M <= 8, 1 <= F <= 1025, B F < 2^31, 0 < alpha < 1: the caller checks them.  oiva_bins_per_pass(M): the bins one workgroup
+// covers at once (-1 outside 2 .. 8).
+long long oiva_state_bytes(long long bins, int M);
+int oiva_bins_per_pass(int M);
+hipError_t launch_oiva_reset(void* state, int B, int M, int F, double init, hipStream_t s);
+hipError_t launch_oiva(const void* mix, int B, int M, int T, int F, int model, int ref_ch, double alpha, double floor, void* est,
+                       void* images, void* state, hipStream_t s);
+hipError_t launch_oiva_debug(const void* state, int B, int M, int F, void* w, void* v, int* fail, int* n, hipStream_t s);
+
 // WPD convolutional beamformer (wpd.hip): one filter of order K = M (taps + 1) per (b, speaker, bin) from the
 // observation and the source estimate, both read as launch_mvdr reads them (mix through a CView; the source through est /
 // est_bstride / sel in pipeline mode or through src when est == nullptr), applied to the stacked observation and written through

@@ -12,7 +12,10 @@ tests/golden/g16_stoi.npz (8 s, 8 kHz).  Nothing outside the repository is read.
 
 Front ends, all through ``BlindSeparator.separate_recording``: the AuxIVA image at ``ref_ch``; AuxIVA followed by each
 beamformer kind (MVDR, MPDR, Souden, GEV with BAN, WPD, LCMV, SDW-MWF, r1-MWF); the same with WPE (``dereverb_wav``) in front;
-online WPE (``dereverb_wav(online=True)``: causal, frame-recursive) in front of AuxIVA alone and of MVDR and LCMV; the beamformer arms with the guided cACGMM between AuxIVA and the beamformer.  Every output is scored against the EARLY images at
+online WPE (``dereverb_wav(online=True)``: causal, frame-recursive) in front of AuxIVA alone and of MVDR and LCMV; the beamformer arms with the guided cACGMM between AuxIVA and the beamformer;
+online AuxIVA (``separate_recording(online=True)``: causal, frame-recursive, M sources at M microphones) on 2 of the 6 microphones
+(``[0:6:3]``) and on all 6 with the two strongest rows kept, alone (``oiva``, ``oiva6``) and behind the online WPE stream
+(``owpe+oiva``, ``owpe+oiva6``).  Every output is scored against the EARLY images at
 ``ref_ch`` (the direct path and the first 50 ms) on the device: SI-SDR of the best assignment and its improvement over the
 mixture, BSS-eval SDR, STOI, cepstral distance, LLR, fwSegSNR and SRMR, averaged over the speakers and the scenes.  No figure is
 required to come out any particular way: the table is what was measured, a front end that makes things worse included.
@@ -65,6 +68,11 @@ def arms(which):
     out["owpe+auxiva"] = ("online", False, {})
     out.update({f"owpe+auxiva+{k}": ("online", True, dict(beamformer=bfs[k])) for k in ("mvdr", "lcmv")})
     out.update({f"auxiva+cacgmm+{k}": (False, True, dict(beamformer=b, refine=True)) for k, b in bfs.items()})
+    # the causal chain: "mics" = the microphones (and so the rows) of the online AuxIVA, "owpe" = the online WPE stream in front
+    out["oiva"] = (False, False, dict(mics=2))
+    out["owpe+oiva"] = (False, False, dict(mics=2, owpe=True))
+    out["oiva6"] = (False, False, dict(mics=6))
+    out["owpe+oiva6"] = (False, False, dict(mics=6, owpe=True))
     return out
 
 
@@ -128,8 +136,12 @@ def main(argv=None):
                     dewav[wpe] = dereverb_wav(sc.wav, fs=FS, online=True if wpe == "online" else None)
                 wav = dewav[wpe]
             try:
-                sep = mz.BlindSeparator(2, 6, ref_ch=a.ref_ch, **kw)
-                pcm = sep.separate_recording(wav, fs=FS, beamform=beamform)
+                if "mics" in kw:
+                    sep = mz.BlindSeparator(2, kw["mics"], ref_ch=a.ref_ch)
+                    pcm = sep.separate_recording(wav, fs=FS, online=True, dereverb=True if kw.get("owpe") else None)
+                else:
+                    sep = mz.BlindSeparator(2, 6, ref_ch=a.ref_ch, **kw)
+                    pcm = sep.separate_recording(wav, fs=FS, beamform=beamform)
                 got, base = score_all(pcm, ref, mixture)
             except Exception as exc:                       # an arm that cannot run is a finding to print, not a reason to stop
                 failed[name] = f"{type(exc).__name__}: {exc}"
