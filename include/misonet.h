@@ -751,6 +751,61 @@ int misonet_oiva(const void* mix_dev, int B, int M, int T, int F, const misonet_
 int misonet_oiva_debug(const void* state_dev, int B, int M, int F, void* w_c128_dev, void* v_c128_dev, int* fail_dev, int* n_dev,
                        misonet_stream stream);
 
+/* ---- online beamformer: frame-recursive MVDR / MWF, its state carried from call to call (ABI 640) ------------------------ */
+/* The project's own definition in the family of mask- or estimate-driven beamformers with exponentially forgotten spatial
+ * covariance matrices, re-solved every frame (Souden, Benesty & Affes 2010 for the filter; Higuchi et al. 2017 and Boeddeker et
+ * al. 2018 for the recursive use; INTEGRATION.md 4t in full, tests/obf_ref.py restates it in NumPy float64).  pb_bss, ESPnet,
+ * nara_wpe and pyroomacoustics were not available: nothing here was compared against them.  Audio is fed as it arrives: a call
+ * takes any T >= 1 new frames and advances the state; the memory does not grow.  Every cell (item b, source s, bin f) runs on
+ * its own: nothing couples bins, sources or items.
+ * State per cell: Phi_s and Phi_n complex128 [M, M], Hermitian; w complex128 [M], the filter of the last frame (stored for
+ * misonet_obf_debug, never read by the recursion); n int32 (the frames seen; it stops at 2^31 - 1) and fail int32.
+ * misonet_obf_reset: Phi_s = 0, Phi_n = init I, w = 0, n = 0, fail = 0; it writes every byte of the state.  Per new frame t, y the
+ * M samples of mix and x the M samples of images[b, s], float64 after the loads:
+ *   0. a non-finite sample in y or x: fail |= 1; Phi_s, Phi_n and w stay, out = 0 for this frame; step 7 still runs
+ *   1. v = y - x for noise 0 "residual"; v = y for noise 1 "mix" (MPDR)
+ *   2. Phi_s <- alpha Phi_s + (1 - alpha) x x^H, Phi_n <- alpha Phi_n + (1 - alpha) v v^H: the lower triangle is computed and
+ *      mirrored, the diagonal's imaginary part is exactly 0: the stored matrices are exactly Hermitian
+ *   3. R = Phi_n + (diag_load tr(Phi_n) / M + epsi) I, tr the sum of the real diagonal with m ascending
+ *   4. R = L L^H without pivoting, column by column, the inner sums over k ascending; 1 / L[c][c] is formed once and multiplies
+ *      wherever L[c][c] divides.  A pivot not finite or not > 0: fail |= 2, w = 0 and out = 0 for this frame (step 2 stays)
+ *   5. G = R^-1 Phi_s by the two triangular solves (forward with k ascending, backward with k descending);
+ *      den = mu + sum_m G[m, m], m ascending (the complex trace).  den not finite: fail |= 4, w = 0, out = 0.  den exactly 0 (a
+ *      source silent so far): w = 0, out = 0, no flag.  Otherwise w = G[:, ref_ch] (1 / den), the reciprocal in Smith's form.
+ *      mu = 0 is the Souden MVDR, mu > 0 the rank-1 / speech-distortion-weighted MWF
+ *   6. out = sum_m conj(w_m) y_m, m ascending, rounded once to complex64
+ *   7. n <- n + 1
+ * Nothing is clamped.  The filter of frame t uses frame t's own sample and no later one: causal, no look-ahead.  Every sum runs in
+ * one fixed order that depends on M alone, without atomics: the bits of a cell depend neither on B, nor on its position in the
+ * batch, nor on how the stream is cut into calls.  misonet_obf is one launch for any T >= 1, with no host synchronisation and no
+ * allocation: it can be captured in a HIP graph (after one misonet_obf_reset outside the capture).  Every element of out is
+ * written.
+ * mix_dev complex64 [B, M, T, F]; images_dev complex64 [B, S, M, T, F]; out_dev complex64 [B, S, T, F]; none of them and the state
+ * may overlap.  state_dev: misonet_obf_state_bytes bytes, 16-byte aligned, written by misonet_obf_reset before the first call;
+ * its size does not depend on T.  2 <= M <= 8, 1 <= S <= 8, B >= 1, T >= 1, 1 <= F <= 1025, B S F < 2^31, noise 0 or 1,
+ * 0 <= ref_ch < M, 0 < alpha < 1 (1 would freeze Phi), mu, diag_load, epsi and init finite and >= 0: anything else is refused on
+ * the host with MISONET_EINVAL and a message (the size functions: -1), before any launch and before any pointer is looked at; a
+ * short state is MISONET_ENOMEM.  misonet_obf_cells_per_block: the cells one workgroup covers (for tests that probe the edges). */
+typedef struct {
+  int noise;               /* 0 residual (v = y - x), 1 mix (v = y) */
+  int ref_ch;              /* the reference microphone */
+  double alpha;            /* forgetting factor */
+  double mu;               /* 0: Souden MVDR; > 0: rank-1 / SDW multichannel Wiener filter */
+  double diag_load;        /* R = Phi_n + (diag_load tr(Phi_n) / M + epsi) I */
+  double epsi;
+  double init;             /* Phi_n = init I at reset */
+} misonet_obf_opts;
+int misonet_obf_opts_default(misonet_obf_opts* opts);  /* 0, 0, 0.98, 0.0, 1e-3, 1e-10, 1.0 */
+long long misonet_obf_state_bytes(int B, int S, int M, int F);
+int misonet_obf_cells_per_block(int M);
+int misonet_obf_reset(void* state_dev, int B, int S, int M, int F, const misonet_obf_opts* opts, misonet_stream stream);
+int misonet_obf(const void* mix_dev, const void* images_dev, int B, int S, int M, int T, int F, const misonet_obf_opts* opts,
+                void* out_dev, void* state_dev, long long state_bytes, misonet_stream stream);
+/* diagnostic: copy Phi_s and Phi_n complex128 [B, S, F, M, M], w complex128 [B, S, F, M], fail int32 [B, S, F] and n int32
+ * [B, S, F] out of the state to device buffers (any may be NULL) */
+int misonet_obf_debug(const void* state_dev, int B, int S, int M, int F, void* phi_s_c128_dev, void* phi_n_c128_dev,
+                      void* w_c128_dev, int* fail_dev, int* n_dev, misonet_stream stream);
+
 /* ---- cepstral distance, LLR, fwSegSNR: the dereverberation figures (ABI 540) ------------------------------------------- */
 /* The three measures the REVERB challenge judges dereverberation by, of an estimate y against a clean reference x, as
  * INTEGRATION.md 4j defines them in full (tests/reverb_ref.py restates it; the challenge's MATLAB tools were not available, so

@@ -12,6 +12,8 @@ Host-side mirror of the reference call surface:
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
   SeparateStream, auxiva_online   (online AuxIVA: frame-recursive separation, state carried; OnlineAuxIVA: its options)
+  BeamformStream, beamform_online  (online beamformer: frame-recursive Souden MVDR / rank-1 MWF behind the online separation,
+                             state carried; OnlineBeamformer: its options)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
                              definition, in front of and behind every recording path)
   Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
@@ -26,7 +28,8 @@ library raises -- there is no CPU fallback.
 """
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "OnlineDereverb", "DereverbStream", "dereverb_online",
-           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online", "resample", "resampled_len",
+           "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online",
+           "OnlineBeamformer", "BeamformStream", "beamform_online", "resample", "resampled_len",
            "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
            "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
 
@@ -41,7 +44,7 @@ def __getattr__(name):
     if name == "Beamformer":
         from .beamform import Beamformer
         return Beamformer
-    if name in ("Apply_Beamforming_Joint", "JointBeamformer"):
+    if name in ("Apply_Beamforming_Joint", "JointBeamformer", "OnlineBeamformer", "BeamformStream", "beamform_online"):
         from . import beamform
         return getattr(beamform, name)
     if name in ("Dereverb", "dereverb", "dereverb_wav", "OnlineDereverb", "DereverbStream", "dereverb_online"):

@@ -49,6 +49,12 @@ class OivaOpts(C.Structure):
     _fields_ = [("model", C.c_int), ("ref_ch", C.c_int), ("alpha", C.c_double), ("floor", C.c_double), ("init", C.c_double)]
 
 
+class ObfOpts(C.Structure):
+    """misonet_obf_opts (ABI 640): noise 0 residual / 1 mix"""
+    _fields_ = [("noise", C.c_int), ("ref_ch", C.c_int), ("alpha", C.c_double), ("mu", C.c_double), ("diag_load", C.c_double),
+                ("epsi", C.c_double), ("init", C.c_double)]
+
+
 class WpdOpts(C.Structure):
     """misonet_wpd_opts (ABI 530)"""
     _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("diag_load", C.c_double), ("power_floor", C.c_double),
@@ -164,6 +170,14 @@ SIGNATURES = {
                                C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_oiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "misonet_obf_opts_default": (C.c_int, [C.POINTER(ObfOpts)]),
+    "misonet_obf_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "misonet_obf_cells_per_block": (C.c_int, [C.c_int]),
+    "misonet_obf_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ObfOpts), C.c_void_p]),
+    "misonet_obf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ObfOpts), C.c_void_p,
+                              C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_obf_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "misonet_pit_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "misonet_pit_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_longlong, C.c_void_p]),

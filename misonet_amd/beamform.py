@@ -8,7 +8,12 @@
 ``Apply_Beamforming_Joint(sources_stft, mix_stft)``  -- the joint multi-speaker beamformers (:class:`JointBeamformer`: LCMV,
                                                        SDW-MWF, rank-1 MWF): all speakers of a bin in one solve
 
-All run as HIP kernels through the C ABI (misonet_beamform / misonet_beamform_joint / misonet_pit_select in include/misonet.h).
+``BeamformStream`` / ``beamform_online``             -- the online beamformer (:class:`OnlineBeamformer`: the frame-recursive Souden
+                                                       MVDR / rank-1 MWF of INTEGRATION.md 4t, its state carried from call to
+                                                       call; csrc/obf.hip, C ABI ``misonet_obf``)
+
+All run as HIP kernels through the C ABI (misonet_beamform / misonet_beamform_joint / misonet_pit_select / misonet_obf in
+include/misonet.h).
 """
 from __future__ import annotations
 
@@ -351,6 +356,193 @@ def Apply_Beamforming_Joint(sources_stft, mix_stft, beamformer="lcmv", *, noise=
     if np_in:
         out = out.cpu()
     return (out, dbg) if return_debug else out
+
+
+@dataclasses.dataclass(frozen=True)
+class OnlineBeamformer:
+    """One plain-data description of the online beamformer (``misonet_obf_opts`` of include/misonet.h).
+
+    noise      "residual": Phi_n from y - x; "mix": from y (MPDR).  0 and 1 are taken as well
+    ref_ch     the reference microphone
+    alpha      forgetting factor of Phi_s and Phi_n, 0 < alpha < 1 (1 would freeze them)
+    mu         0: the Souden MVDR, w = G[:, ref_ch] / tr G; > 0: the rank-1 / speech-distortion-weighted MWF, / (mu + tr G)
+    diag_load  R = Phi_n + (diag_load tr(Phi_n) / M + epsi) I
+    epsi
+    init       Phi_n = init I at reset
+    The defaults are choices, not tuned values.
+    """
+    noise: object = "residual"
+    ref_ch: int = 0
+    alpha: float = 0.98
+    mu: float = 0.0
+    diag_load: float = 1e-3
+    epsi: float = 1e-10
+    init: float = 1.0
+
+    @classmethod
+    def of(cls, spec) -> "OnlineBeamformer":
+        """None or True (the defaults), an OnlineBeamformer, a noise name, or a dict of the fields above"""
+        if spec is None or spec is True:
+            return cls()
+        if isinstance(spec, cls):
+            return spec
+        if isinstance(spec, str):
+            return cls(noise=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+            if unknown:
+                raise ValueError(f"unknown online beamformer field(s) {sorted(unknown)}")
+            return cls(**spec)
+        raise TypeError("an online beamformer must be None, True, an OnlineBeamformer, a noise name or a dict of its fields")
+
+    @property
+    def noise_index(self) -> int:
+        n = self.noise
+        if isinstance(n, str) and n in NOISES:
+            return NOISES.index(n)
+        if not isinstance(n, bool) and isinstance(n, (int, np.integer)) and 0 <= n < len(NOISES):
+            return int(n)
+        raise ValueError(f"online beamformer noise {n!r}: one of {NOISES} (or 0, 1)")
+
+    def validate(self, num_mic: Optional[int] = None, num_src: Optional[int] = None) -> "OnlineBeamformer":
+        """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
+        self.noise_index
+        a = self.alpha
+        if isinstance(a, bool) or not isinstance(a, (int, float, np.floating)) or not 0 < a < 1:
+            raise ValueError(f"online beamformer alpha must be in (0, 1), got {a!r}")
+        for name in ("mu", "diag_load", "epsi", "init"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"online beamformer {name} must be finite and >= 0, got {v!r}")
+        r = self.ref_ch
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0:
+            raise ValueError(f"online beamformer ref_ch must be a non-negative integer, got {r!r}")
+        if num_mic is not None:
+            if not 2 <= num_mic <= 8:
+                raise ValueError(f"the online beamformer needs 2 <= M <= 8 microphones, got {num_mic}")
+            if r >= num_mic:
+                raise ValueError(f"online beamformer ref_ch {r} outside [0, {num_mic})")
+        if num_src is not None and not 1 <= num_src <= 8:
+            raise ValueError(f"the online beamformer takes 1 <= S <= 8 sources, got {num_src}")
+        return self
+
+    def c_opts(self) -> "_lib.ObfOpts":
+        return _lib.ObfOpts(self.noise_index, int(self.ref_ch), float(self.alpha), float(self.mu), float(self.diag_load),
+                            float(self.epsi), float(self.init))
+
+
+def cells_per_block(num_mic: int) -> int:
+    """the cells (item, source, bin) one workgroup of the online beamformer covers (``misonet_obf_cells_per_block``)"""
+    return int(_lib.lib().misonet_obf_cells_per_block(int(num_mic)))
+
+
+class BeamformStream:
+    """The state of one stream of the online beamformer, on the device: ``batch`` recordings of ``num_mic`` microphones,
+    ``num_src`` sources and ``num_bins`` bins.  ``opts``: the fields of :class:`OnlineBeamformer`.  The state is allocated once; a
+    call allocates only its output."""
+
+    def __init__(self, num_mic, num_src, num_bins=129, batch=1, *, device=None, **opts):
+        self.num_mic, self.num_src, self.num_bins, self.batch = int(num_mic), int(num_src), int(num_bins), int(batch)
+        self.opts = OnlineBeamformer(**opts).validate(self.num_mic, self.num_src)
+        if not 1 <= self.num_bins <= 1025 or self.batch < 1:
+            raise ValueError(f"num_bins must be in [1, 1025] and batch positive, got {num_bins}, {batch}")
+        self._c = self.opts.c_opts()
+        n = _lib.lib().misonet_obf_state_bytes(self.batch, self.num_src, self.num_mic, self.num_bins)
+        if n < 0:
+            _lib.check(_lib.EINVAL)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """Phi_s = 0, Phi_n = init I, w = 0, no frame seen, no flag"""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_obf_reset(self.state.data_ptr(), self.batch, self.num_src, self.num_mic, self.num_bins,
+                                                    C.byref(self._c), _lib.stream_ptr(self.device)))
+        return self
+
+    def _geometry(self, ishape, mshape):
+        B, S, M, F = self.batch, self.num_src, self.num_mic, self.num_bins
+        if len(ishape) != 5 or len(mshape) != 4 or ishape[3] < 1:
+            raise ValueError(f"images {tuple(ishape)} must be [B, S, M, T, F] and mix {tuple(mshape)} [B, M, T, F] with T >= 1")
+        T = ishape[3]
+        if tuple(ishape) != (B, S, M, T, F) or tuple(mshape) != (B, M, T, F):
+            raise ValueError(f"images {tuple(ishape)} must be [{B}, {S}, {M}, T, {F}] and mix {tuple(mshape)} [{B}, {M}, T, {F}]")
+        return T
+
+    def process_into(self, images: torch.Tensor, mix: torch.Tensor, out: torch.Tensor):
+        """images complex64 [B, S, M, T, F], mix complex64 [B, M, T, F], out complex64 [B, S, T, F], contiguous on the stream's
+        device and not overlapping.  One launch, nothing allocated: the call a HIP graph captures."""
+        T = self._geometry(images.shape, mix.shape)
+        B, S, M, F = self.batch, self.num_src, self.num_mic, self.num_bins
+        if tuple(out.shape) != (B, S, T, F):
+            raise ValueError(f"out {tuple(out.shape)} must be [{B}, {S}, {T}, {F}]")
+        for name, t in (("images", images), ("mix", mix), ("out", out)):
+            if t.dtype != torch.complex64 or not t.is_contiguous() or t.device != self.state.device:
+                raise ValueError(f"{name} must be a contiguous complex64 tensor on {self.state.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_obf(mix.data_ptr(), images.data_ptr(), B, S, M, T, F, C.byref(self._c), out.data_ptr(),
+                                              self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
+        return out
+
+    def process(self, images, mix):
+        """The next T >= 1 frames of the stream: images complex [B, S, M, T, F] (what ``SeparateStream.process(images=True)``
+        returns, or ``mask * mix`` formed by the caller) and mix complex [B, M, T, F] -> out complex64 [B, S, T, F]; on the device
+        for device input and on the CPU when ``images`` was an ndarray.  The bits do not depend on how the stream is cut into
+        calls."""
+        self._geometry(np.shape(images), np.shape(mix))
+        x, np_in = _dev_c64(images, self.device)
+        y, _ = _dev_c64(mix, self.device)
+        out = torch.empty((x.shape[0], x.shape[1], x.shape[3], x.shape[4]), dtype=torch.complex64, device=x.device)
+        self.process_into(x, y, out)
+        return out.cpu() if np_in else out
+
+    def _debug(self, want=("phi_s", "phi_n", "w", "fail", "n")):
+        """copies of the named parts of the state, on the device"""
+        B, S, M, F = self.batch, self.num_src, self.num_mic, self.num_bins
+        shapes = dict(phi_s=((B, S, F, M, M), torch.complex128), phi_n=((B, S, F, M, M), torch.complex128),
+                      w=((B, S, F, M), torch.complex128), fail=((B, S, F), torch.int32), n=((B, S, F), torch.int32))
+        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
+        ptr = lambda k: d[k].data_ptr() if k in d else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_obf_debug(self.state.data_ptr(), B, S, M, F, ptr("phi_s"), ptr("phi_n"), ptr("w"),
+                                                    ptr("fail"), ptr("n"), _lib.stream_ptr(self.device)))
+        return d
+
+    def filters(self):
+        """the filters w complex128 [B, S, F, M] of the last frame (out = w^H y), on the device"""
+        return self._debug(("w",))["w"]
+
+    def covariances(self):
+        """(Phi_s, Phi_n), complex128 [B, S, F, M, M] each, as they stand, on the device"""
+        d = self._debug(("phi_s", "phi_n"))
+        return d["phi_s"], d["phi_n"]
+
+    @property
+    def frames_seen(self) -> int:
+        return int(self._debug(("n",))["n"].max().item())
+
+    @property
+    def fail(self) -> torch.Tensor:
+        """int32 [B, S, F] on the device: bit 0 a non-finite sample, bit 1 a Cholesky pivot not > 0, bit 2 a non-finite mu + tr G"""
+        return self._debug(("fail",))["fail"]
+
+
+def beamform_online(images, mix, *, return_debug=False, device=None, **opts):
+    """The online beamformer over a batch of spectrograms in one call: reset, then process.  images complex [B, S, M, T, F], mix
+    complex [B, M, T, F], any T >= 1 -> out complex64 [B, S, T, F], on the device for device input and on the CPU for an ndarray.
+    ``opts``: the fields of :class:`OnlineBeamformer`.  ``return_debug`` adds, on the device, ``phi_s``, ``phi_n``, ``w``, ``fail``
+    and ``n`` of the final state.  Causal: frame t of the output depends on no later frame."""
+    ishape, mshape = np.shape(images), np.shape(mix)
+    o = OnlineBeamformer(**opts).validate(ishape[2] if len(ishape) == 5 else None, ishape[1] if len(ishape) == 5 else None)
+    if len(ishape) != 5 or len(mshape) != 4 or min(ishape) < 1 or tuple(mshape) != (ishape[0],) + tuple(ishape[2:]):
+        raise ValueError(f"images {tuple(ishape)} must be [B, S, M, T, F], all positive, and mix {tuple(mshape)} [B, M, T, F]")
+    if device is None:
+        device = (images.device if isinstance(images, torch.Tensor) and images.is_cuda
+                  else torch.device("cuda", torch.cuda.current_device()))
+    st = BeamformStream(ishape[2], ishape[1], ishape[4], ishape[0], device=device, **dataclasses.asdict(o))
+    out = st.process(images, mix)
+    return (out, st._debug()) if return_debug else out
 
 
 def pit_select(anchor, cand, return_dist=False):

@@ -386,19 +386,31 @@ class BlindSeparator:
         mix_bf = self._mix(mix)
         return self._beamform(self._images(mix_bf), mix_bf)
 
-    def _online_rows(self, spec, online, dereverb):
-        """spec complex64 [1, M, Tt, F] on the device -> the num_spks strongest rows of the online separation [S, Tt, F]"""
+    def _online_pick(self, est):
+        """est [M, Tt, F] -> the indices of the num_spks rows of largest sum |est|^2, descending, ties to the lower index"""
+        power = (est.real.double() ** 2 + est.imag.double() ** 2).sum(dim=(1, 2))                # [M]
+        return torch.sort(power, descending=True, stable=True).indices[:self.num_spks]
+
+    def _online_rows(self, spec, online, dereverb, beamform=None):
+        """spec complex64 [1, M, Tt, F] on the device -> the num_spks strongest rows of the online separation [S, Tt, F]; with
+        ``beamform`` (an OnlineBeamformer) the rows of the online beamformer at the same indices"""
         M = spec.shape[1]
         online.validate(M)
+        if beamform is not None:
+            beamform.validate(M, M)
         if self.num_spks > M:
             raise ValueError(f"online separation returns M = {M} rows; {self.num_spks} speakers were asked for")
         if dereverb is not None:
             from .dereverb import DereverbStream
             spec = DereverbStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(dereverb.validate(M))).process(spec)
-        est = SeparateStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(online)).process(spec)[0]
-        power = (est.real.double() ** 2 + est.imag.double() ** 2).sum(dim=(1, 2))                # [M]
-        rows = torch.sort(power, descending=True, stable=True).indices[:self.num_spks]
-        return est[rows].contiguous()
+        sep = SeparateStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(online))
+        if beamform is None:
+            est = sep.process(spec)[0]
+            return est[self._online_pick(est)].contiguous()
+        from .beamform import BeamformStream
+        est, images = sep.process(spec, images=True)
+        out = BeamformStream(M, M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(beamform)).process(images, spec)
+        return out[0][self._online_pick(est[0])].contiguous()
 
     def separate_recording(self, wav, num_ch_utilize: Optional[int] = None, save_path: Optional[str] = None, fs: int = 16000,
                            beamform: Optional[bool] = None, srmr: bool = False, fs_in=None, fs_out=None, online=None,
@@ -420,7 +432,19 @@ class BlindSeparator:
         to the lower index, the iSTFT and the int16 waves as above.  That row selection is made on the device with torch after the
         whole recording has been seen: it is NOT causal -- the stream itself returns all M rows and leaves the choice to its
         caller.  ``beamform``: None is True on the offline path, as it always was, and False with ``online``; ``beamform=True`` with
-        ``online`` is refused: the beamformers here are block algorithms.  ``dereverb`` without ``online`` is refused."""
+        ``online`` is refused: the beamformers here are block algorithms.  ``beamform=`` a
+        :class:`misonet_amd.beamform.OnlineBeamformer` instance (only an instance selects it, and its ``ref_ch``
+        is replaced by this object's) adds the one beamformer that is not: the :class:`SeparateStream` also returns its images, a
+        :class:`misonet_amd.beamform.BeamformStream` with M sources runs on those images and on the spectrum AuxIVA saw (behind
+        ``dereverb``: the dereverberated one), the rows are chosen as above, by the power of ``est``, and the beamformed rows of
+        those indices go to the iSTFT.  An ``OnlineBeamformer`` without ``online`` is refused; so is ``dereverb`` without
+        ``online``."""
+        from .beamform import OnlineBeamformer
+        online_bf = None
+        if isinstance(beamform, OnlineBeamformer):
+            if online is None or online is False:
+                raise ValueError("beamform=OnlineBeamformer(...) belongs to the online path: set online= as well")
+            online_bf, beamform = dataclasses.replace(beamform, ref_ch=self.ref_ch).validate(), None
         if online is None or online is False:
             if dereverb is not None:
                 raise ValueError("dereverb= belongs to the online path: set online= as well, or dereverberate with dereverb_wav first")
@@ -440,7 +464,8 @@ class BlindSeparator:
             if srmr:
                 from . import score as SC
                 SC.check_srmr_fs(fs)
-            return RS.around(lambda w, _c, path: self.separate_recording(w, num_ch_utilize, path, fs, beamform, srmr,
+            return RS.around(lambda w, _c, path: self.separate_recording(w, num_ch_utilize, path, fs,
+                                                                         beamform if online_bf is None else online_bf, srmr,
                                                                          online=online, dereverb=dereverb),
                              wav, None, fs, fs_in, fs_out, save_path, self._write_speakers, self.device)
         if srmr:
@@ -451,7 +476,7 @@ class BlindSeparator:
         sig = torch.from_numpy(np.ascontiguousarray(obs[:, mics])).to(self.device)               # [L, M]
         sig = torch.nn.functional.pad(sig, (0, 0, 0, (-L) % S.HOP))[None].contiguous()           # [1, Lp, M]
         if online is not None:
-            out = self._online_rows(S.stft_hip(sig), online, dereverb)                           # [S, Tt, F]
+            out = self._online_rows(S.stft_hip(sig), online, dereverb, online_bf)                # [S, Tt, F]
             pcm = np.ascontiguousarray(S.istft_int16(out)[:, :L].cpu().numpy())
             if save_path is not None:
                 self._write_speakers(pcm, save_path, fs)

@@ -2,11 +2,12 @@
 // (mvdr.hip), WPE dereverberation misonet_wpe* (wpe.hip) and its online form misonet_owpe* (owpe.hip), the WPD beamformer
 // misonet_wpd* (wpd.hip), guided spatial clustering
 // misonet_cacgmm* / misonet_masks_from_estimates (cacgmm.hip), the joint beamformers misonet_beamform_joint* (jbf.hip), blind
-// separation misonet_auxiva* (iva.hip) and its online form misonet_oiva* (oiva.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
+// separation misonet_auxiva* (iva.hip) and its online form misonet_oiva* (oiva.hip), the online beamformer misonet_obf* (obf.hip), PIT alignment misonet_pit_* (mvdr.hip) and continuous separation
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
 #include <cmath>
+#include <cstdint>
 
 using namespace mn;
 
@@ -388,6 +389,87 @@ int misonet_oiva_debug(const void* state, int B, int M, int F, void* w, void* v,
   { int r = oiva_geom_check(B, M, F); if (r) return r; }
   if (!state) return fail(MISONET_EINVAL, "null argument");
   HIPCHK(launch_oiva_debug(state, B, M, F, w, v, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- online beamformer: frame-recursive MVDR / MWF, state carried (ABI 640) ---------------------------------------------
+int misonet_obf_opts_default(misonet_obf_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null argument");
+  o->noise = 0; o->ref_ch = 0; o->alpha = 0.98; o->mu = 0.0; o->diag_load = 1e-3; o->epsi = 1e-10; o->init = 1.0;
+  return MISONET_OK;
+}
+
+static int obf_geom_check(int B, int S, int M, int F) {
+  if (M < 2 || M > 8) return fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M);
+  if (S < 1 || S > 8) return fail(MISONET_EINVAL, "S must be in [1, 8] (got %d)", S);
+  if (B < 1) return fail(MISONET_EINVAL, "B must be positive (got %d)", B);
+  if (F < 1 || F > 1025) return fail(MISONET_EINVAL, "F must be in [1, 1025] (got %d)", F);
+  if ((long long)B * S * F > 0x7fffffffLL) return fail(MISONET_EINVAL, "B * S * F must be < 2^31 (got %d, %d, %d)", B, S, F);
+  return MISONET_OK;
+}
+
+static bool obf_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
+
+// host-side check of every field and of the geometry they are used with
+static int obf_check(int B, int S, int M, int F, const misonet_obf_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null online beamformer options");
+  { int r = obf_geom_check(B, S, M, F); if (r) return r; }
+  if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "noise %d: 0 residual, 1 mix", o->noise);
+  if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "ref_ch %d outside [0, %d)", o->ref_ch, M);
+  if (!(o->alpha > 0.0 && o->alpha < 1.0))
+    return fail(MISONET_EINVAL, "alpha must be in (0, 1): 1 would freeze the covariances (got %g)", o->alpha);
+  if (!obf_nonneg(o->mu)) return fail(MISONET_EINVAL, "mu must be finite and >= 0 (got %g)", o->mu);
+  if (!obf_nonneg(o->diag_load)) return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!obf_nonneg(o->epsi)) return fail(MISONET_EINVAL, "epsi must be finite and >= 0 (got %g)", o->epsi);
+  if (!obf_nonneg(o->init)) return fail(MISONET_EINVAL, "init must be finite and >= 0 (got %g)", o->init);
+  return MISONET_OK;
+}
+
+long long misonet_obf_state_bytes(int B, int S, int M, int F) {
+  if (obf_geom_check(B, S, M, F)) return -1;
+  return obf_state_bytes((long long)B * S * F, M);
+}
+
+int misonet_obf_cells_per_block(int M) {
+  if (M < 2 || M > 8) { fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M); return -1; }
+  return obf_cells_per_block(M);
+}
+
+int misonet_obf_reset(void* state, int B, int S, int M, int F, const misonet_obf_opts* opts, misonet_stream stream) {
+  { int r = obf_check(B, S, M, F, opts); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_obf_reset(state, B, S, M, F, opts->init, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte; the sizes of a long stream do not fit 64 bits
+static bool obf_overlap(const void* a, unsigned __int128 na, const void* b, unsigned __int128 nb) {
+  const unsigned __int128 pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+int misonet_obf(const void* mix, const void* images, int B, int S, int M, int T, int F, const misonet_obf_opts* opts, void* out,
+                void* state, long long state_bytes, misonet_stream stream) {
+  { int r = obf_check(B, S, M, F, opts); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be >= 1 (got %d)", T);
+  if (!mix || !images || !out || !state) return fail(MISONET_EINVAL, "null argument");
+  const long long need = obf_state_bytes((long long)B * S * F, M);
+  const unsigned __int128 plane = (unsigned __int128)B * T * F * 8, nm = plane * M, no = plane * S, ni = no * M;
+  const unsigned __int128 ns = (unsigned __int128)(state_bytes < need ? (state_bytes > 0 ? state_bytes : 0) : need);
+  if (obf_overlap(mix, nm, images, ni) || obf_overlap(mix, nm, out, no) || obf_overlap(images, ni, out, no) ||
+      obf_overlap(state, ns, mix, nm) || obf_overlap(state, ns, images, ni) || obf_overlap(state, ns, out, no))
+    return fail(MISONET_EINVAL, "mix_dev, images_dev, out_dev and state_dev must not overlap");
+  if (state_bytes < need) return fail(MISONET_ENOMEM, "state too small");
+  HIPCHK(launch_obf(mix, images, B, S, M, T, F, opts->noise, opts->ref_ch, opts->alpha, opts->mu, opts->diag_load, opts->epsi, out,
+                    state, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_obf_debug(const void* state, int B, int S, int M, int F, void* phi_s, void* phi_n, void* w, int* fail_dev, int* n_dev,
+                      misonet_stream stream) {
+  { int r = obf_geom_check(B, S, M, F); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_obf_debug(state, B, S, M, F, phi_s, phi_n, w, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -374,6 +374,19 @@ hipError_t launch_oiva(const void* mix, int B, int M, int T, int F, int model, i
                        void* images, void* state, hipStream_t s);
 hipError_t launch_oiva_debug(const void* state, int B, int M, int F, void* w, void* v, int* fail, int* n, hipStream_t s);
 
+// Online beamformer (obf.hip): the frame-recursive Souden MVDR / rank-1 MWF, its state carried from call to
+// call.  mix complex64 [B][M][T][F], images complex64 [B][S][M][T][F], out complex64 [B][S][T][F], any T >= 1; the state holds fail
+// int [B S F], n int [B S F], Phi_s and Phi_n complex128 [B S F][M][M] and w complex128 [B S F][M], which launch_obf_debug copies
+// out.  2 <= M <= 8, 1 <= S <= 8, 1 <= F <= 1025, B S F < 2^31, 0 < alpha < 1, 0 <= ref_ch < M: the caller checks them.
+// obf_cells_per_block(M): the cells (b, s, f) one workgroup covers (-1 outside 2 .. 8).
+long long obf_state_bytes(long long cells, int M);
+int obf_cells_per_block(int M);
+hipError_t launch_obf_reset(void* state, int B, int S, int M, int F, double init, hipStream_t s);
+hipError_t launch_obf(const void* mix, const void* images, int B, int S, int M, int T, int F, int noise, int ref_ch, double alpha,
+                      double mu, double diag_load, double epsi, void* out, void* state, hipStream_t s);
+hipError_t launch_obf_debug(const void* state, int B, int S, int M, int F, void* phi_s, void* phi_n, void* w, int* fail, int* n,
+                            hipStream_t s);
+
 // WPD convolutional beamformer (wpd.hip): one filter of order K = M (taps + 1) per (b, speaker, bin) from the
 // observation and the source estimate, both read as launch_mvdr reads them (mix through a CView; the source through est /
 // est_bstride / sel in pipeline mode or through src when est == nullptr), applied to the stacked observation and written through

@@ -15,7 +15,8 @@ beamformer kind (MVDR, MPDR, Souden, GEV with BAN, WPD, LCMV, SDW-MWF, r1-MWF); 
 online WPE (``dereverb_wav(online=True)``: causal, frame-recursive) in front of AuxIVA alone and of MVDR and LCMV; the beamformer arms with the guided cACGMM between AuxIVA and the beamformer;
 online AuxIVA (``separate_recording(online=True)``: causal, frame-recursive, M sources at M microphones) on 2 of the 6 microphones
 (``[0:6:3]``) and on all 6 with the two strongest rows kept, alone (``oiva``, ``oiva6``) and behind the online WPE stream
-(``owpe+oiva``, ``owpe+oiva6``).  Every output is scored against the EARLY images at
+(``owpe+oiva``, ``owpe+oiva6``), and with the online beamformer on the images of the online AuxIVA
+(``separate_recording(online=True, beamform=OnlineBeamformer())``, its defaults: ``oiva+obf``, ``oiva6+obf``, ``owpe+oiva6+obf``).  Every output is scored against the EARLY images at
 ``ref_ch`` (the direct path and the first 50 ms) on the device: SI-SDR of the best assignment and its improvement over the
 mixture, BSS-eval SDR, STOI, cepstral distance, LLR, fwSegSNR and SRMR, averaged over the speakers and the scenes.  No figure is
 required to come out any particular way: the table is what was measured, a front end that makes things worse included.
@@ -73,6 +74,9 @@ def arms(which):
     out["owpe+oiva"] = (False, False, dict(mics=2, owpe=True))
     out["oiva6"] = (False, False, dict(mics=6))
     out["owpe+oiva6"] = (False, False, dict(mics=6, owpe=True))
+    out["oiva+obf"] = (False, False, dict(mics=2, obf=True))
+    out["oiva6+obf"] = (False, False, dict(mics=6, obf=True))
+    out["owpe+oiva6+obf"] = (False, False, dict(mics=6, owpe=True, obf=True))
     return out
 
 
@@ -138,7 +142,8 @@ def main(argv=None):
             try:
                 if "mics" in kw:
                     sep = mz.BlindSeparator(2, kw["mics"], ref_ch=a.ref_ch)
-                    pcm = sep.separate_recording(wav, fs=FS, online=True, dereverb=True if kw.get("owpe") else None)
+                    pcm = sep.separate_recording(wav, fs=FS, online=True, dereverb=True if kw.get("owpe") else None,
+                                                 beamform=mz.OnlineBeamformer() if kw.get("obf") else None)
                 else:
                     sep = mz.BlindSeparator(2, 6, ref_ch=a.ref_ch, **kw)
                     pcm = sep.separate_recording(wav, fs=FS, beamform=beamform)
