@@ -948,6 +948,53 @@ int misonet_stft(const float* wav_dev, int B, int n_samples, int M, void* out_de
  * these builds them inside its first call, which therefore synchronises and must not sit inside a stream capture. */
 int misonet_istft(const void* spec_dev, int N, int T, void* out_i16_dev, float* out_f32_dev, misonet_stream stream);
 
+/* ---- streaming STFT and iSTFT: waveform blocks in, frames out; frames in, waveform blocks out (ABI 650) ------------------
+ * The two transforms above fed piece by piece, with their state on the device.  Window, hop, twiddles and
+ * scaling are those above: periodic hann-256, hop 64, un-normalised, F = 129.  The bits do not depend on how a stream is cut
+ * into calls, and a stream that ends with `flush` has emitted, concatenated, the result of misonet_stft / misonet_istft of
+ * the whole signal BIT FOR BIT.
+ *
+ * Analysis.  A stream has seen N = n_seen samples per channel; X_t[f] = sum_{j<256} x[64 t - 128 + j] hann[j] e^{-2 pi i f j/256}
+ * with x = 0 outside the samples that exist.  Frame t is complete once sample 64 t + 127 has arrived: after N samples the stream
+ * has emitted e(N) = max(0, N / 64 - 1) frames.  A call with n_new samples emits the frames [e(N), E): E = e(N + n_new) without
+ * flush, E = (N + n_new) / 64 + 1 with it (everything beyond sample N + n_new counts as zero, as misonet_stft treats
+ * l >= n_samples).  misonet_stft_stream_frames returns E - e(N); it may be 0, and the call still advances the state.
+ *   wav_dev    float32 [B, n_new, M], the layout of misonet_stft (may be NULL when n_new == 0)
+ *   out_c64_dev complex64 [B, M, Tn, 129], Tn = misonet_stft_stream_frames(...), every element written (may be NULL when Tn == 0)
+ *   state_dev  misonet_stft_stream_state_bytes(B, M) bytes: per (b, m) the last 255 samples of the stream, aligned to its end,
+ *              zero where the stream has not begun (enough: 64 e(N) - 128 >= N - 255).  misonet_stft_stream_reset writes every
+ *              byte with zeros.  After a flushing call the state is spent until the next reset.
+ * Synthesis.  A stream of R rows has seen Tc = t_seen frames.  Output hop h covers the samples 64 h .. 64 h + 63 and needs the
+ * frames h - 1 .. h + 2: after Tc frames the stream has emitted g(Tc) = max(0, Tc - 2) hops.  A call with t_new frames emits the
+ * hops [g(Tc), G): G = g(Tc + t_new) without flush, G = max(0, Tc + t_new - 1) with it.  Per sample
+ * y = sum w[k] z_t[k] / sum w[k]^2 over the frames t in {h - 1, h, h + 1, h + 2} that exist -- 0 <= t, and at a flush also
+ * t < Tc + t_new -- t ascending, the quotient in float32, as misonet_istft.  A frame that does not exist is skipped, not added
+ * as zero: only hop 0 and the flush hop have partial envelopes.  misonet_istft_stream_hops returns G - g(Tc).  A stream flushed
+ * with fewer than 2 frames emits nothing.
+ *   spec_dev   complex64 [R, t_new, 129] (may be NULL when t_new == 0)
+ *   out_i16_dev / out_f32_dev  int16 / float32 [R, 64 H], H = misonet_istft_stream_hops(...): (short)(int)(y * 32767.0f) and / or
+ *              y; either may be NULL, both when H == 0
+ *   state_dev  misonet_istft_stream_state_bytes(R) bytes: per row the last 3 frames, complex64 [3][129]; reset writes zeros
+ * The host passes n_seen (t_seen): the kernels keep no counter on the device.  A launch depends on them only through the ranges
+ * above and through n_seen mod 64; for n_seen >= 128 (t_seen >= 3) on nothing else, so a steady-state call (say, blocks of 256
+ * samples) can be captured into a HIP graph and replayed.  A call is one launch for the output (none when it emits nothing) and
+ * one small launch behind it that moves the state on (none at a flush); no host synchronisation, no allocation, no atomics.
+ * Limits: 1 <= B <= 65535, 1 <= M <= 64, 1 <= R <= 65535, 0 <= n_new <= 2^28, 0 <= t_new <= 2^22 (>= 1 unless flush), n_seen,
+ * t_seen >= 0; anything else is MISONET_EINVAL (-1 from the count functions) before any launch and before any pointer is looked
+ * at; a short state is MISONET_ENOMEM.  The tables are those of misonet_frontend_init: the first use on a device builds them
+ * and must not sit inside a stream capture.
+ * Latency: output sample 64 h needs input sample 64 h + 255 -- 255 samples for the pair, plus the block. */
+long long misonet_stft_stream_state_bytes(int B, int M);
+int misonet_stft_stream_reset(void* state_dev, int B, int M, misonet_stream stream);
+long long misonet_stft_stream_frames(long long n_seen, long long n_new, int flush);      /* -1 on bad arguments */
+int misonet_stft_stream(const float* wav_dev, int B, long long n_new, int M, long long n_seen, int flush, void* out_c64_dev,
+                        void* state_dev, long long state_bytes, misonet_stream stream);
+long long misonet_istft_stream_state_bytes(int R);
+int misonet_istft_stream_reset(void* state_dev, int R, misonet_stream stream);
+long long misonet_istft_stream_hops(long long t_seen, long long t_new, int flush);       /* -1 on bad arguments */
+int misonet_istft_stream(const void* spec_dev, int R, long long t_new, long long t_seen, int flush, void* out_i16_dev,
+                         float* out_f32_dev, void* state_dev, long long state_bytes, misonet_stream stream);
+
 /* ---- per-launch timing (bench.py roofline leg): while enabled, the library brackets every conv launch, the TCN
  * section and the beamforming section of each forward with HIP events on the caller's stream.  kinds: 0 = 3x3 conv kernel
  * launches, 1 = TCN sections, 2 = beamforming sections (whichever beamformer is set), 3 = other (conv_wprep_k, the per-sample weight preparation of the

@@ -14,6 +14,10 @@ Host-side mirror of the reference call surface:
   SeparateStream, auxiva_online   (online AuxIVA: frame-recursive separation, state carried; OnlineAuxIVA: its options)
   BeamformStream, beamform_online  (online beamformer: frame-recursive Souden MVDR / rank-1 MWF behind the online separation,
                              state carried; OnlineBeamformer: its options)
+  StftStream, IstftStream   (streaming STFT / iSTFT: waveform blocks in, frames out; frames in, waveform blocks out; the bits
+                             of the offline kernels however the stream is cut)
+  StreamSeparator, separate_stream  (the causal chain from waveform block to waveform block: StftStream -> online WPE ->
+                             online AuxIVA -> online beamformer -> IstftStream, misonet_amd.stream)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
                              definition, in front of and behind every recording path)
   Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
@@ -29,7 +33,8 @@ library raises -- there is no CPU fallback.
 __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamforming_Joint", "JointBeamformer", "Dereverb", "dereverb", "dereverb_wav", "Refine", "cacgmm",
            "OnlineDereverb", "DereverbStream", "dereverb_online",
            "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online",
-           "OnlineBeamformer", "BeamformStream", "beamform_online", "resample", "resampled_len",
+           "OnlineBeamformer", "BeamformStream", "beamform_online", "StftStream", "IstftStream", "StreamSeparator",
+           "separate_stream", "resample", "resampled_len",
            "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
            "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
 
@@ -56,6 +61,12 @@ def __getattr__(name):
     if name in ("AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online"):
         import importlib
         return getattr(importlib.import_module(".blind", __name__), name)
+    if name in ("StftStream", "IstftStream"):
+        import importlib
+        return getattr(importlib.import_module(".stft", __name__), name)
+    if name in ("StreamSeparator", "separate_stream"):
+        import importlib
+        return getattr(importlib.import_module(".stream", __name__), name)
     if name in ("resample", "resampled_len", "load_wav"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)

@@ -257,6 +257,16 @@ SIGNATURES = {
     "misonet_stft": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_frontend_init": (C.c_int, []),
     "misonet_istft": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "misonet_stft_stream_state_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "misonet_stft_stream_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "misonet_stft_stream_frames": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int]),
+    "misonet_stft_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_longlong, C.c_void_p]),
+    "misonet_istft_stream_state_bytes": (C.c_longlong, [C.c_int]),
+    "misonet_istft_stream_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "misonet_istft_stream_hops": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int]),
+    "misonet_istft_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_pipeline_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_profile_begin": (C.c_int, [C.c_int]),
     "misonet_profile_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

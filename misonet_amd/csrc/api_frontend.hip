@@ -1,5 +1,5 @@
-// C ABI of the STFT front-end (include/misonet.h): misonet_stft*, misonet_istft, misonet_frontend_init, and the twiddle tables of
-// stft.hip on every device that uses them; the resampler in front of it, misonet_resample* (resample.hip), and its tap tables.
+// C ABI of the STFT front-end (include/misonet.h): misonet_stft*, misonet_istft, misonet_frontend_init, the streaming forms
+// misonet_stft_stream* / misonet_istft_stream*, and the twiddle tables of stft.hip on every device that uses them; the resampler in front of it, misonet_resample* (resample.hip), and its tap tables.
 // Host code only.
 #include "api_common.hpp"
 
@@ -27,6 +27,7 @@ static int frontend_tables(const float** tw, const float** itw) {
     istft_build_twiddles(t.data());
     if (const int rc = dev_upload(t, p)) return rc;
     HIPCHK(istft_init());
+    HIPCHK(stft_stream_init());
     return MISONET_OK;
   });
 }
@@ -154,6 +155,95 @@ int misonet_stft(const float* wav_dev, int B, int n_samples, int M, void* out_c6
   const long long bs = 2LL * M * F * Tp;
   HIPCHK(launch_stft_pack(wav_dev, B, n_samples, M, T, tw, planar, bs, Tp, F, 0, M, 1, s));
   HIPCHK(launch_unpack(planar, bs, Tp, M, T, F, reinterpret_cast<float2*>(out_c64), B, nullptr, s));
+  return MISONET_OK;
+}
+
+// ---- streaming STFT / iSTFT: waveform blocks in, frames out; frames in, hops out (ABI 650) ---------------
+constexpr long long SS_MAX_N = 1LL << 28, SS_MAX_T = 1LL << 22;
+static long long ss_emitted(long long N) { return N / 64 - 1 > 0 ? N / 64 - 1 : 0; }        // e(N)
+static long long iss_emitted(long long Tc) { return Tc - 2 > 0 ? Tc - 2 : 0; }              // g(Tc)
+static bool ss_counts_ok(long long seen, long long add, int flush, long long cap) {
+  return seen >= 0 && add >= 0 && add <= cap && (add >= 1 || flush) && seen <= (1LL << 62);
+}
+
+long long misonet_stft_stream_state_bytes(int B, int M) {
+  if (B < 1 || B > 65535 || M < 1 || M > 64) return -1;
+  return stft_stream_state_bytes((long long)B * M);
+}
+
+long long misonet_stft_stream_frames(long long n_seen, long long n_new, int flush) {
+  if (!ss_counts_ok(n_seen, n_new, flush, SS_MAX_N)) return -1;
+  const long long E = flush ? (n_seen + n_new) / 64 + 1 : ss_emitted(n_seen + n_new);
+  return E - ss_emitted(n_seen);
+}
+
+int misonet_stft_stream_reset(void* state_dev, int B, int M, misonet_stream stream) {
+  const long long nb = misonet_stft_stream_state_bytes(B, M);
+  if (nb < 0) return fail(MISONET_EINVAL, "B must be in [1, 65535] and M in [1, 64] (got %d, %d)", B, M);
+  if (!state_dev) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(hipMemsetAsync(state_dev, 0, (size_t)nb, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_stft_stream(const float* wav_dev, int B, long long n_new, int M, long long n_seen, int flush, void* out_c64_dev,
+                        void* state_dev, long long state_bytes, misonet_stream stream) {
+  const long long nb = misonet_stft_stream_state_bytes(B, M);
+  if (nb < 0) return fail(MISONET_EINVAL, "B must be in [1, 65535] and M in [1, 64] (got %d, %d)", B, M);
+  const long long Tn = misonet_stft_stream_frames(n_seen, n_new, flush);
+  if (Tn < 0)
+    return fail(MISONET_EINVAL, "n_seen must be >= 0 and n_new in [%d, 2^28] (got %lld, %lld, flush %d)", flush ? 0 : 1, n_seen,
+                n_new, flush);
+  if (!state_dev || (n_new > 0 && !wav_dev) || (Tn > 0 && !out_c64_dev)) return fail(MISONET_EINVAL, "null argument");
+  if (state_bytes < nb) return fail(MISONET_ENOMEM, "state too small: %lld < %lld bytes", state_bytes, nb);
+  const float* tw;
+  if (const int r = get_twiddles(&tw)) return r;
+  // the first frame of the call starts 64 e(n_seen) - 128 - n_seen samples from the block's first one: -128 - n_seen before the
+  // stream has 128 samples, -192 - n_seen mod 64 ever after
+  const int off0 = (int)(64 * ss_emitted(n_seen) - 128 - n_seen);
+  HIPCHK(launch_stft_stream(wav_dev, B, (int)n_new, M, (int)Tn, off0, !flush, tw, reinterpret_cast<float2*>(out_c64_dev),
+                            reinterpret_cast<float*>(state_dev), reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+long long misonet_istft_stream_state_bytes(int R) {
+  if (R < 1 || R > 65535) return -1;
+  return istft_stream_state_bytes(R);
+}
+
+long long misonet_istft_stream_hops(long long t_seen, long long t_new, int flush) {
+  if (!ss_counts_ok(t_seen, t_new, flush, SS_MAX_T)) return -1;
+  const long long Tt = t_seen + t_new;
+  const long long G = flush ? (Tt - 1 > 0 ? Tt - 1 : 0) : iss_emitted(Tt);
+  return G - iss_emitted(t_seen);
+}
+
+int misonet_istft_stream_reset(void* state_dev, int R, misonet_stream stream) {
+  const long long nb = misonet_istft_stream_state_bytes(R);
+  if (nb < 0) return fail(MISONET_EINVAL, "R must be in [1, 65535] (got %d)", R);
+  if (!state_dev) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(hipMemsetAsync(state_dev, 0, (size_t)nb, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_istft_stream(const void* spec_dev, int R, long long t_new, long long t_seen, int flush, void* out_i16_dev,
+                         float* out_f32_dev, void* state_dev, long long state_bytes, misonet_stream stream) {
+  const long long nb = misonet_istft_stream_state_bytes(R);
+  if (nb < 0) return fail(MISONET_EINVAL, "R must be in [1, 65535] (got %d)", R);
+  const long long H = misonet_istft_stream_hops(t_seen, t_new, flush);
+  if (H < 0)
+    return fail(MISONET_EINVAL, "t_seen must be >= 0 and t_new in [%d, 2^22] (got %lld, %lld, flush %d)", flush ? 0 : 1, t_seen,
+                t_new, flush);
+  if (!state_dev || (t_new > 0 && !spec_dev) || (H > 0 && !out_i16_dev && !out_f32_dev))
+    return fail(MISONET_EINVAL, "null argument");
+  if (state_bytes < nb) return fail(MISONET_ENOMEM, "state too small: %lld < %lld bytes", state_bytes, nb);
+  const float *tw, *itw;
+  if (const int r = frontend_tables(&tw, &itw)) return r;
+  // hop 0 of the call needs the frames g(t_seen) - 1 .. + 2: counted from the first new frame that is -3 once two frames have
+  // been seen; min(t_seen, 3) of the carried frames exist
+  const int fr0 = (int)(iss_emitted(t_seen) - 1 - t_seen), lead = (int)(t_seen < 3 ? t_seen : 3);
+  HIPCHK(launch_istft_stream(spec_dev, R, (int)t_new, lead, fr0, (int)H, !flush && t_new > 0, itw,
+                             reinterpret_cast<short*>(out_i16_dev), out_f32_dev, state_dev,
+                             reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

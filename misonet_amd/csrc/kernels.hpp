@@ -204,6 +204,19 @@ hipError_t launch_istft(const void* spec, int N, int T, const float* itw, short*
 hipError_t istft_init();
 void istft_build_twiddles(float* tw);
 int istft_twiddle_count();
+// The streaming forms: the same tables, and stft_stream_init() once per device.  The state of the analysis
+// is float [B M][256] (the last 255 samples, then one zero), that of the synthesis complex64 [R][3][129] (the last 3 frames);
+// zero bytes are the reset.  launch_stft_stream: Tn frames, the first starting off0 in [-255, 0] samples from the block's first
+// sample (nothing is launched for Tn == 0), then, with `update`, the tail after the block's n samples.  launch_istft_stream: H
+// hops, hop 0 of the call summing the frames fr0 .. fr0 + 3 counted from the first new frame, of which the `lead` <= 3 last
+// carried ones and the Tn new ones exist; then, with `update`, the carried frames after the Tn >= 1 new ones.
+long long stft_stream_state_bytes(long long BM);
+long long istft_stream_state_bytes(long long R);
+hipError_t stft_stream_init();
+hipError_t launch_stft_stream(const float* wav, int B, int n, int Mw, int Tn, int off0, int update, const float* twid,
+                              float2* out, float* tail, hipStream_t s);
+hipError_t launch_istft_stream(const void* spec, int R, int Tn, int lead, int fr0, int H, int update, const float* itw,
+                               short* out_i16, float* out_f32, void* carry, hipStream_t s);
 
 // ---- MVDR + PIT -------------------------------------------------------------------------------------------------
 // Accessor for a multichannel complex STFT with frames contiguous: element (b, f, m, t) =

@@ -95,6 +95,183 @@ def istft_int16(spec: torch.Tensor) -> torch.Tensor:
     return (istft(spec) * MAX_INT16).to(torch.int16)
 
 
+def _stream_device(device):
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+class StftStream:
+    """The analysis half of the streaming front end, on the device (csrc/stft.hip ``stft_stream_k``, C ABI
+    ``misonet_stft_stream``): ``batch`` recordings of ``num_mic`` microphones, fed in blocks of any length.
+    The stream carries its last 255 samples; after N samples it has emitted ``max(0, N // 64 - 1)`` frames, and after
+    :meth:`flush` the ``N // 64 + 1`` frames of :func:`stft_hip` of the whole signal, bit for bit and however it was cut.  The
+    state is allocated once; a call allocates only its output."""
+
+    def __init__(self, num_mic, batch=1, device=None):
+        self.num_mic, self.batch = int(num_mic), int(batch)
+        from . import _lib
+        n = _lib.lib().misonet_stft_stream_state_bytes(self.batch, self.num_mic)
+        if n < 0:
+            raise ValueError(f"num_mic must be in [1, 64] and batch in [1, 65535], got {num_mic}, {batch}")
+        self.device = _stream_device(device)
+        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """no sample seen: the carried tail is zero"""
+        from . import _lib
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_stft_stream_reset(self.state.data_ptr(), self.batch, self.num_mic,
+                                                            _lib.stream_ptr(self.device)))
+        self.samples_seen, self.frames_out, self._spent = 0, 0, False
+        return self
+
+    def frames(self, n_new: int, flush: bool = False) -> int:
+        """the frames the next call emits for ``n_new`` samples (``misonet_stft_stream_frames``)"""
+        from . import _lib
+        t = int(_lib.lib().misonet_stft_stream_frames(self.samples_seen, int(n_new), int(bool(flush))))
+        if t < 0:
+            raise ValueError(f"a block must hold 1 .. 2^28 samples (0 with flush), got {n_new}")
+        return t
+
+    def _block(self, block):
+        if self._spent:
+            raise ValueError("the stream was flushed: reset() before the next block")
+        if not isinstance(block, torch.Tensor) or block.device != self.state.device or block.dtype != torch.float32:
+            raise ValueError(f"block must be a float32 tensor on {self.state.device}")
+        if block.dim() == 2 and self.batch == 1:
+            block = block[None]
+        if block.dim() != 3 or (block.shape[0], block.shape[2]) != (self.batch, self.num_mic):
+            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, n, {self.num_mic}]")
+        return block
+
+    def process_into(self, block: torch.Tensor, out, flush: bool = False):
+        """block float32 [B, n, M], out complex64 [B, M, Tn, 129] with ``Tn = frames(n, flush)`` (None when Tn == 0), contiguous
+        on the stream's device.  Two launches, nothing allocated: the call a HIP graph captures (once the stream has seen 128
+        samples a launch depends on ``samples_seen`` through ``samples_seen % 64`` alone: replay it with blocks of that length)."""
+        from . import _lib
+        block = self._block(block)
+        n = block.shape[1]
+        Tn = self.frames(n, flush)
+        if not block.is_contiguous():
+            raise ValueError("block must be contiguous")
+        if Tn > 0 and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (self.batch, self.num_mic, Tn, N_FREQ)
+                       or out.dtype != torch.complex64 or not out.is_contiguous() or out.device != self.state.device):
+            raise ValueError(f"out must be a contiguous complex64 tensor [{self.batch}, {self.num_mic}, {Tn}, {N_FREQ}] on "
+                             f"{self.state.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_stft_stream(block.data_ptr() if n else None, self.batch, n, self.num_mic,
+                                                      self.samples_seen, int(bool(flush)), out.data_ptr() if Tn else None,
+                                                      self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
+        self.samples_seen += n
+        self.frames_out += Tn
+        self._spent = bool(flush)
+        return out
+
+    def process(self, block, flush: bool = False):
+        """The next n >= 1 samples: float32 [B, n, M] (or [n, M] when batch == 1) on the device -> complex64 [B, M, Tn, 129], the
+        frames these samples complete; Tn may be 0, which gives an empty tensor."""
+        block = self._block(block).contiguous()
+        out = torch.empty((self.batch, self.num_mic, self.frames(block.shape[1], flush), N_FREQ), dtype=torch.complex64,
+                          device=self.device)
+        self.process_into(block, out, flush)
+        return out
+
+    def flush(self, block=None):
+        """The end of the stream, with or without a last block: the frames still owed, everything beyond the last sample counted as
+        zero -- ``samples_seen // 64 + 1`` frames in all.  The stream is spent until :meth:`reset`."""
+        if block is None:
+            if self._spent:
+                raise ValueError("the stream was flushed: reset() before the next block")
+            block = torch.empty((self.batch, 0, self.num_mic), dtype=torch.float32, device=self.device)
+        return self.process(block, flush=True)
+
+
+class IstftStream:
+    """The synthesis half (csrc/stft.hip ``istft_stream_k``, C ABI ``misonet_istft_stream``): ``rows``
+    spectrogram rows fed in blocks of frames.  The stream carries its last 3 frames; after Tc frames it has emitted
+    ``max(0, Tc - 2)`` hops of 64 samples, and after :meth:`flush` the ``64 (Tc - 1)`` samples of :func:`istft` (``int16=True``:
+    of :func:`istft_int16`) of all its frames, bit for bit and however they were cut."""
+
+    def __init__(self, rows, int16=False, device=None):
+        from . import _lib
+        self.rows, self.int16 = int(rows), bool(int16)
+        n = _lib.lib().misonet_istft_stream_state_bytes(self.rows)
+        if n < 0:
+            raise ValueError(f"rows must be in [1, 65535], got {rows}")
+        self.device = _stream_device(device)
+        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """no frame seen"""
+        from . import _lib
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_istft_stream_reset(self.state.data_ptr(), self.rows, _lib.stream_ptr(self.device)))
+        self.frames_seen, self.samples_out, self._spent = 0, 0, False
+        return self
+
+    def hops(self, t_new: int, flush: bool = False) -> int:
+        """the hops of 64 samples the next call emits for ``t_new`` frames (``misonet_istft_stream_hops``)"""
+        from . import _lib
+        h = int(_lib.lib().misonet_istft_stream_hops(self.frames_seen, int(t_new), int(bool(flush))))
+        if h < 0:
+            raise ValueError(f"a block must hold 1 .. 2^22 frames (0 with flush), got {t_new}")
+        return h
+
+    def _spec(self, spec):
+        if self._spent:
+            raise ValueError("the stream was flushed: reset() before the next block")
+        if not isinstance(spec, torch.Tensor) or spec.device != self.state.device or spec.dtype != torch.complex64:
+            raise ValueError(f"spec must be a complex64 tensor on {self.state.device}")
+        if spec.dim() < 2 or spec.shape[-1] != N_FREQ or int(np.prod(spec.shape[:-2], dtype=np.int64)) != self.rows:
+            raise ValueError(f"spec {tuple(spec.shape)} must be [..., Tn, {N_FREQ}] with {self.rows} rows in all")
+        return spec
+
+    def process_into(self, spec: torch.Tensor, out, flush: bool = False):
+        """spec complex64 [..., Tn, 129], out [..., 64 H] with ``H = hops(Tn, flush)`` (None when H == 0) of the stream's sample
+        type, contiguous on the stream's device.  Two launches, nothing allocated: the call a HIP graph captures (once the stream
+        has seen 3 frames a launch does not depend on ``frames_seen``)."""
+        from . import _lib
+        spec = self._spec(spec)
+        Tn = spec.shape[-2]
+        H = self.hops(Tn, flush)
+        if not spec.is_contiguous():
+            raise ValueError("spec must be contiguous")
+        want = torch.int16 if self.int16 else torch.float32
+        if H > 0 and (not isinstance(out, torch.Tensor) or out.numel() != self.rows * HOP * H or out.shape[-1] != HOP * H
+                      or out.dtype != want or not out.is_contiguous() or out.device != self.state.device):
+            raise ValueError(f"out must be a contiguous {want} tensor [..., {HOP * H}] of {self.rows} rows on {self.state.device}")
+        ptr = out.data_ptr() if H else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().misonet_istft_stream(spec.data_ptr() if Tn else None, self.rows, Tn, self.frames_seen,
+                                                       int(bool(flush)), ptr if self.int16 else None,
+                                                       None if self.int16 else ptr, self.state.data_ptr(), self.state.numel(),
+                                                       _lib.stream_ptr(self.device)))
+        self.frames_seen += Tn
+        self.samples_out += HOP * H
+        self._spent = bool(flush)
+        return out
+
+    def process(self, spec, flush: bool = False):
+        """The next Tn >= 1 frames: complex64 [..., Tn, 129] on the device -> float32 (int16) [..., 64 H], the hops these frames
+        complete; H may be 0, which gives an empty tensor."""
+        spec = self._spec(spec).contiguous()
+        out = torch.empty(tuple(spec.shape[:-2]) + (HOP * self.hops(spec.shape[-2], flush),),
+                          dtype=torch.int16 if self.int16 else torch.float32, device=self.device)
+        self.process_into(spec, out, flush)
+        return out
+
+    def flush(self, spec=None):
+        """The end of the stream, with or without a last block of frames: the hops still owed, the last one divided by its partial
+        envelope -- ``64 (frames_seen - 1)`` samples in all, none for fewer than 2 frames.  ``spec=None`` returns [rows, 64 H].
+        The stream is spent until :meth:`reset`."""
+        if spec is None:
+            if self._spent:
+                raise ValueError("the stream was flushed: reset() before the next block")
+            spec = torch.empty((self.rows, 0, N_FREQ), dtype=torch.complex64, device=self.device)
+        return self.process(spec, flush=True)
+
+
 def split_chunks(wav: np.ndarray, chunk: int) -> Tuple[List[np.ndarray], int]:
     """data.py:555-595: wav [L, M] -> list of [chunk, M] pieces (last one zero-padded) and the pad length ``gap``.
 
