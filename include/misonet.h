@@ -562,6 +562,47 @@ int misonet_resample(const void* src_dev, int src_kind, long long src_sb, long l
                      long long n, const int* n_valid_dev, int fs_in, int fs_out, void* dst_dev, int dst_kind, long long dst_sb,
                      long long dst_sc, long long dst_st, misonet_stream stream);
 
+/* ---- streaming polyphase resampler: waveform blocks in at one rate, blocks out at another (ABI 660) -----------------------
+ * misonet_resample fed piece by piece, with its state on the device.  Ratio, taps, sum, sample kinds and
+ * views are those above.  The bits do not depend on how a stream is cut into calls, and a stream that ends with `flush` has
+ * emitted, concatenated, the result of misonet_resample of the whole signal BIT FOR BIT, for all four pairs of sample kinds.
+ *
+ * A stream has seen N = n_seen samples per channel.  Output m is complete once its last input floor((m q + Lh) / p) has arrived:
+ * after N samples the stream has emitted e(N) outputs, e(N) = 0 where N p - 1 - Lh < 0 and floor((N p - 1 - Lh) / q) + 1
+ * otherwise.  A call with n_new samples emits the outputs [e(N), E): E = e(N + n_new) without flush, E = ceil((N + n_new) p / q),
+ * the offline length, with it (the last outputs skip the inputs past the end, as misonet_resample does).
+ * misonet_resample_stream_outputs returns E - e(N); it may be 0, and the call still advances the state.  A stream flushed before
+ * any sample emits nothing.
+ *   src_dev    block of n_new samples, element (b, c, j) at src_dev[b * src_sb + c * src_sc + j * src_st] (NULL when n_new == 0)
+ *   dst_dev    the call's outputs, output e(N) + i of (b, c) at dst_dev[b * dst_sb + c * dst_sc + i * dst_st], every one written
+ *              (may be NULL when the call emits nothing)
+ *   state_dev  misonet_resample_stream_state_bytes(B, M, fs_in, fs_out) bytes: float32 [B][M][C], the last
+ *              C = misonet_resample_stream_carry(fs_in, fs_out) = floor(2 Lh / p) samples of the stream, aligned to its end, zero
+ *              where the stream has not begun; an int16 sample is carried as its integer value.  No output needs more (the bound
+ *              is tight): 60 samples for 48 -> 16 kHz, 20 for 16 -> 48 kHz, 55 for 44.1 -> 16 kHz, 20480 for 1 / 1024, 0 for
+ *              1 / 1, where state_dev may be NULL and state_bytes 0.  misonet_resample_stream_reset writes every byte with zeros.
+ *              After a flushing call the state is spent until the next reset.
+ * The host passes n_seen: the kernels keep no counter on the device, and a launch depends on n_seen only through
+ * e(N) q - N p, the place of the first output against the block's first sample in tap units, and through the counts.  Once
+ * e(n_seen) > 0 a call whose n_new is a multiple of q can be captured into a HIP graph and replayed over the following blocks of
+ * that length.  A call is one launch for the outputs (none when it emits nothing) and one small launch behind it that moves the
+ * state on (none at a flush, none for 1 / 1); after the first use of a ratio on a device (its taps: one allocation, one synchronous
+ * copy, not inside a capture) no host synchronisation and no allocation; no atomics; independent of B.
+ * misonet_resample_stream_tile: the outputs one workgroup owns (32), for tests that probe the tile edges.
+ * Latency: Lh / p input samples (30 samples, 0.625 ms, for 48 -> 16 kHz), plus the block.
+ * Limits: 1 <= B <= 65535, 1 <= M <= 16, 0 <= n_new <= 2^28 (>= 1 unless flush), 0 <= n_seen <= 2^50, kinds 0 / 1, strides as
+ * misonet_resample; anything else is MISONET_EINVAL (-1 from the size and count functions) before any launch and before any
+ * pointer is looked at; then a null pointer; a short state is MISONET_ENOMEM. */
+long long misonet_resample_stream_carry(long long fs_in, long long fs_out);                    /* C; -1 on a bad ratio */
+long long misonet_resample_stream_state_bytes(int B, int M, long long fs_in, long long fs_out);
+long long misonet_resample_stream_outputs(long long n_seen, long long n_new, int flush, long long fs_in, long long fs_out);  /* -1 on bad arguments */
+int misonet_resample_stream_tile(void);
+int misonet_resample_stream_reset(void* state_dev, int B, int M, long long fs_in, long long fs_out, misonet_stream stream);
+int misonet_resample_stream(const void* src_dev, int src_i16, long long src_sb, long long src_sc, long long src_st, int B, int M,
+                            long long n_new, long long n_seen, int flush, long long fs_in, long long fs_out, void* dst_dev,
+                            int dst_i16, long long dst_sb, long long dst_sc, long long dst_st, void* state_dev,
+                            long long state_bytes, misonet_stream stream);
+
 /* ---- room simulator: image-source RIRs of a shoebox, and scene mixing (ABI 600) ------------------------------------------ */
 /* The project's own definition in the Allen & Berkley (1979) family (INTEGRATION.md 4p in full; tests/room_ref.py restates it in
  * NumPy).  pyroomacoustics, gpuRIR, rir_generator and sms_wsj were not available: not compared against any of them.

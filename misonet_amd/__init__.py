@@ -20,6 +20,8 @@ Host-side mirror of the reference call surface:
                              online AuxIVA -> online beamformer -> IstftStream, misonet_amd.stream)
   resample, resampled_len, load_wav  (recordings at any sample rate: the polyphase resampler of scipy.signal.resample_poly's
                              definition, in front of and behind every recording path)
+  ResampleStream            (the same resampler fed in blocks, state carried: the bits of resample however the stream is cut;
+                             the two ends of StreamSeparator at any rate)
   Room, simulate, beta_from_rt60  (room simulator: image-source RIRs of a shoebox and scene mixing, misonet_amd.room; Scene:
                              what simulate returns)
   Localizer, localize, localize_wav, DoaResult  (source localisation: SRP, SRP-PHAT and MUSIC maps over a delay table and their
@@ -34,7 +36,7 @@ __all__ = ["MISO_1", "MISO_3", "Apply_Beamforming", "Beamformer", "Apply_Beamfor
            "OnlineDereverb", "DereverbStream", "dereverb_online",
            "masks_from_estimates", "AuxIVA", "auxiva", "BlindSeparator", "OnlineAuxIVA", "SeparateStream", "auxiva_online",
            "OnlineBeamformer", "BeamformStream", "beamform_online", "StftStream", "IstftStream", "StreamSeparator",
-           "separate_stream", "resample", "resampled_len",
+           "separate_stream", "resample", "resampled_len", "ResampleStream",
            "load_wav", "Room", "Scene", "simulate", "beta_from_rt60", "Localizer", "localize", "localize_wav",
            "DoaResult", "directions", "far_field_delays", "near_field_delays", "angular_error", "Enhancer", "weights"]
 
@@ -67,7 +69,7 @@ def __getattr__(name):
     if name in ("StreamSeparator", "separate_stream"):
         import importlib
         return getattr(importlib.import_module(".stream", __name__), name)
-    if name in ("resample", "resampled_len", "load_wav"):
+    if name in ("resample", "resampled_len", "load_wav", "ResampleStream"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
     if name in ("Room", "Scene", "simulate", "beta_from_rt60"):

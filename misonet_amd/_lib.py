@@ -215,6 +215,14 @@ SIGNATURES = {
     "misonet_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_longlong,
                                    C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong,
                                    C.c_void_p]),
+    "misonet_resample_stream_carry": (C.c_longlong, [C.c_longlong, C.c_longlong]),
+    "misonet_resample_stream_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_longlong, C.c_longlong]),
+    "misonet_resample_stream_outputs": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_longlong, C.c_longlong]),
+    "misonet_resample_stream_tile": (C.c_int, []),
+    "misonet_resample_stream_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "misonet_resample_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int,
+                                          C.c_longlong, C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int,
+                                          C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_room_tile": (C.c_int, []),
     "misonet_room_rir_len": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "misonet_room_mix_len": (C.c_longlong, [C.c_longlong, C.c_int]),

@@ -1,5 +1,5 @@
 // C ABI of the STFT front-end (include/misonet.h): misonet_stft*, misonet_istft, misonet_frontend_init, the streaming forms
-// misonet_stft_stream* / misonet_istft_stream*, and the twiddle tables of stft.hip on every device that uses them; the resampler in front of it, misonet_resample* (resample.hip), and its tap tables.
+// misonet_stft_stream* / misonet_istft_stream*, and the twiddle tables of stft.hip on every device that uses them; the resampler in front of it, misonet_resample* (resample.hip), its streaming form misonet_resample_stream* (resample_stream.hip), and their tap tables.
 // Host code only.
 #include "api_common.hpp"
 
@@ -111,6 +111,83 @@ int misonet_resample(const void* src_dev, int src_kind, long long src_sb, long l
   const long long ss[3] = {src_sb, src_sc, src_st}, ds[3] = {dst_sb, dst_sc, dst_st};
   HIPCHK(launch_resample(src_dev, src_kind, ss, B, M, n, n_valid_dev, p, q, taps, dst_dev, dst_kind, ds,
                          reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+// ---- streaming polyphase resampler (resample_stream.hip; ABI 660) -----------------------------------------
+constexpr long long RSS_MAX_SEEN = 1LL << 50;
+static bool rss_counts_ok(long long seen, long long add, int flush) {
+  return seen >= 0 && seen <= RSS_MAX_SEEN && add >= 0 && add <= RS_MAX_N && (add >= 1 || flush);
+}
+
+long long misonet_resample_stream_carry(long long fs_in, long long fs_out) {
+  int p, q;
+  if (!resample_ratio(fs_in, fs_out, &p, &q)) return -1;
+  return resample_stream_carry(p, q);
+}
+
+long long misonet_resample_stream_state_bytes(int B, int M, long long fs_in, long long fs_out) {
+  int p, q;
+  if (B < 1 || B > 65535 || M < 1 || M > RS_MAX_CH || !resample_ratio(fs_in, fs_out, &p, &q)) return -1;
+  return (long long)B * M * resample_stream_carry(p, q) * (long long)sizeof(float);
+}
+
+long long misonet_resample_stream_outputs(long long n_seen, long long n_new, int flush, long long fs_in, long long fs_out) {
+  int p, q;
+  if (!rss_counts_ok(n_seen, n_new, flush) || !resample_ratio(fs_in, fs_out, &p, &q)) return -1;
+  const long long E = flush ? resample_len(n_seen + n_new, p, q) : resample_stream_emitted(n_seen + n_new, p, q);
+  return E - resample_stream_emitted(n_seen, p, q);
+}
+
+int misonet_resample_stream_tile(void) { return resample_stream_tile(); }
+
+static int rss_shape(int B, int M, long long fs_in, long long fs_out, long long* nb) {
+  int p, q;
+  if (!resample_ratio(fs_in, fs_out, &p, &q))
+    return fail(MISONET_EINVAL, "fs_in and fs_out must be positive with max(p, q) <= %d for p / q = fs_out / fs_in in lowest "
+                "terms (got %lld -> %lld)", RS_MAX_RATE, fs_in, fs_out);
+  if (B < 1 || B > 65535) return fail(MISONET_EINVAL, "B must be in [1, 65535] (got %d)", B);
+  if (M < 1 || M > RS_MAX_CH) return fail(MISONET_EINVAL, "M must be in [1, %d] (got %d)", RS_MAX_CH, M);
+  *nb = misonet_resample_stream_state_bytes(B, M, fs_in, fs_out);
+  return MISONET_OK;
+}
+
+int misonet_resample_stream_reset(void* state_dev, int B, int M, long long fs_in, long long fs_out, misonet_stream stream) {
+  long long nb;
+  if (const int rc = rss_shape(B, M, fs_in, fs_out, &nb)) return rc;
+  if (nb == 0) return MISONET_OK;                                       // 1 / 1 carries nothing
+  if (!state_dev) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(hipMemsetAsync(state_dev, 0, (size_t)nb, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_resample_stream(const void* src_dev, int src_i16, long long src_sb, long long src_sc, long long src_st, int B, int M,
+                            long long n_new, long long n_seen, int flush, long long fs_in, long long fs_out, void* dst_dev,
+                            int dst_i16, long long dst_sb, long long dst_sc, long long dst_st, void* state_dev,
+                            long long state_bytes, misonet_stream stream) {
+  long long nb;
+  if (const int rc = rss_shape(B, M, fs_in, fs_out, &nb)) return rc;
+  if ((src_i16 != 0 && src_i16 != 1) || (dst_i16 != 0 && dst_i16 != 1))
+    return fail(MISONET_EINVAL, "src_i16 and dst_i16 must be 0 (float32) or 1 (int16) (got %d, %d)", src_i16, dst_i16);
+  const long long n_out = misonet_resample_stream_outputs(n_seen, n_new, flush, fs_in, fs_out);
+  if (n_out < 0)
+    return fail(MISONET_EINVAL, "n_seen must be in [0, 2^50] and n_new in [%d, 2^28] (got %lld, %lld, flush %d)", flush ? 0 : 1,
+                n_seen, n_new, flush);
+  if (src_sb < 0 || src_sc < 0 || src_st < 1)
+    return fail(MISONET_EINVAL, "source strides must not be negative and the sample stride must be positive");
+  if (dst_st < 1 || (M > 1 && dst_sc < 1) || (B > 1 && dst_sb < 1) || dst_sc < 0 || dst_sb < 0)
+    return fail(MISONET_EINVAL, "destination strides must be positive along every axis longer than 1");
+  if ((nb > 0 && !state_dev) || (n_new > 0 && !src_dev) || (n_out > 0 && !dst_dev)) return fail(MISONET_EINVAL, "null argument");
+  if (state_bytes < nb) return fail(MISONET_ENOMEM, "state too small: %lld < %lld bytes", state_bytes, nb);
+  int p, q;
+  resample_ratio(fs_in, fs_out, &p, &q);
+  const double* taps;
+  if (const int rc = resample_table(p, q, &taps)) return rc;
+  // the first output of the call against the block's first sample, in tap units: all a launch knows of n_seen
+  const long long D = resample_stream_emitted(n_seen, p, q) * q - n_seen * p;
+  const long long ss[3] = {src_sb, src_sc, src_st}, ds[3] = {dst_sb, dst_sc, dst_st};
+  HIPCHK(launch_resample_stream(src_dev, src_i16, ss, B, M, n_new, D, n_out, !flush, p, q, taps, dst_dev, dst_i16, ds,
+                                reinterpret_cast<float*>(state_dev), reinterpret_cast<hipStream_t>(stream)));
   return MISONET_OK;
 }
 

@@ -324,6 +324,17 @@ hipError_t launch_resample(const void* src, int src_i16, const long long* ss, in
                            const int* n_valid /*[B] or nullptr*/, int p, int q, const double* taps, void* dst, int dst_i16,
                            const long long* ds, hipStream_t s);
 
+// The streaming form (resample_stream.hip): the same taps.  After N samples a stream has emitted
+// resample_stream_emitted(N) outputs and carries its last resample_stream_carry(p, q) samples, float32 [B][M][C] aligned to its
+// end, zero where it has not begun.  launch_resample_stream: the n_out outputs from e(N) on (nothing is launched for n_out == 0),
+// D = e(N) q - N p, then, with `update`, the tail after the block's n_new samples.  N itself is no argument.
+int resample_stream_tile();                                               // output samples per workgroup
+int resample_stream_carry(int p, int q);                                  // C = floor(2 Lh / p)
+long long resample_stream_emitted(long long N, int p, int q);             // e(N)
+hipError_t launch_resample_stream(const void* src, int src_i16, const long long* ss, int B, int M, long long n_new, long long D,
+                                  long long n_out, int update, int p, int q, const double* taps, void* dst, int dst_i16,
+                                  const long long* ds, float* tail /*nullptr where C == 0*/, hipStream_t s);
+
 // Cepstral distance, LLR and fwSegSNR (reverb.hip).  The table (reverb_table_count() doubles, built on the
 // host): the twiddles of the 512-point transform and, per rate, the window, the 23 mel triangles and their bin ranges.  One call
 // reads the three views of launch_stoi_resample and writes out [B][E (+ 1)][R][6], count

@@ -16,6 +16,7 @@
 // Work item i = k 256 + thread of the tile is (output i / M, channel i % M): neighbouring lanes read neighbouring LDS words, share
 // the tap (one address per output) and keep their sums in registers across the chunks, which keeps j ascending.
 #include "kernels.hpp"
+#include "resample_round.hpp"
 
 #include <cmath>
 #include <numeric>
@@ -64,12 +65,6 @@ void resample_build_taps(int p, int q, double* g) {
   }
   sum += comp;
   for (int i = 0; i <= 2 * Lh; ++i) g[i] = g[i] / sum * p;
-}
-
-__device__ __forceinline__ short rs_to_i16(double y) {
-  const double v = rint(y * 32767.0);                                 // to nearest, ties to even
-  if (!(v == v)) return 0;                                            // a NaN has no int16: 0
-  return (short)(int)(v < -32768.0 ? -32768.0 : (v > 32767.0 ? 32767.0 : v));
 }
 
 struct RsView { long long sb, sc, st; int i16; };

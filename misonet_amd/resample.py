@@ -239,6 +239,123 @@ def around(run, wav_observe, wav_clean, fs, fs_in, fs_out, save_path, write, dev
     return (pcm,) + tuple(res[1:]) if isinstance(res, tuple) else pcm
 
 
+# ---- the streaming form ----------------------------------------------------------------------------------------------------
+class ResampleStream:
+    """The resampler fed in blocks, on the device (csrc/resample_stream.hip, C ABI ``misonet_resample_stream``; INTEGRATION.md
+    4v): ``batch`` recordings of ``channels`` channels at ``fs_in``, blocks of any length in, blocks at ``fs_out`` out.  The stream
+    carries its last ``carry`` = floor(2 Lh / p) samples; after N samples it has emitted every output whose last input has arrived
+    (``latency`` = Lh / p input samples behind), and after :meth:`flush` the ``ceil(N p / q)`` samples of :func:`resample` of the
+    whole signal, bit for bit and however it was cut.  ``in_int16`` / ``out_int16``: the sample kinds, with the rules of
+    :func:`resample`.  The state is allocated once; a call allocates only its output.  More than 16 channels go in groups of 16,
+    each on its own slice of the state."""
+
+    def __init__(self, channels, fs_in, fs_out, batch=1, in_int16=False, out_int16=False, device=None):
+        self.fs_in, self.fs_out = _rate(fs_in, "fs_in"), _rate(fs_out, "fs_out")
+        self.p, self.q = ratio(self.fs_in, self.fs_out)
+        self.channels, self.batch = int(channels), int(batch)
+        if self.channels < 1 or not 1 <= self.batch <= MAX_B:
+            raise ValueError(f"channels must be >= 1 and batch in [1, {MAX_B}], got {channels}, {batch}")
+        self.in_int16, self.out_int16 = bool(in_int16), bool(out_int16)
+        L = _lib.lib()
+        self.carry = int(L.misonet_resample_stream_carry(self.fs_in, self.fs_out))
+        half = 0 if self.p == self.q == 1 else 10 * max(self.p, self.q)
+        self.latency = half / self.p
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        # (first channel, channels, first byte, bytes) of every group
+        self._groups, at = [], 0
+        for c0 in range(0, self.channels, MAX_CH):
+            m = min(MAX_CH, self.channels - c0)
+            nb = int(L.misonet_resample_stream_state_bytes(self.batch, m, self.fs_in, self.fs_out))
+            self._groups.append((c0, m, at, nb))
+            at += nb
+        self.state = torch.empty(at, dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """no sample seen: the carried tail is zero"""
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            for _c0, m, at, nb in self._groups:
+                _lib.check(L.misonet_resample_stream_reset(self.state.data_ptr() + at if nb else None, self.batch, m, self.fs_in,
+                                                           self.fs_out, _lib.stream_ptr(self.device)))
+        self.samples_seen, self.samples_out, self._spent = 0, 0, False
+        return self
+
+    def outputs(self, n_new: int, flush: bool = False) -> int:
+        """the samples the next call emits for ``n_new`` samples (``misonet_resample_stream_outputs``)"""
+        n = int(_lib.lib().misonet_resample_stream_outputs(self.samples_seen, int(n_new), int(bool(flush)), self.fs_in,
+                                                           self.fs_out))
+        if n < 0:
+            raise ValueError(f"a block must hold 1 .. 2^28 samples (0 with flush), got {n_new}")
+        return n
+
+    def _block(self, block):
+        if self._spent:
+            raise ValueError("the stream was flushed: reset() before the next block")
+        want = torch.int16 if self.in_int16 else torch.float32
+        if not isinstance(block, torch.Tensor) or block.device != self.state.device or block.dtype != want:
+            raise ValueError(f"block must be a {want} tensor on {self.state.device}")
+        if block.dim() == 2 and self.batch == 1:
+            block = block[None]
+        if block.dim() != 3 or (block.shape[0], block.shape[2]) != (self.batch, self.channels):
+            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, n, {self.channels}]")
+        if block.shape[1] > 1 and block.stride(1) < 1:
+            raise ValueError("block must advance in memory from sample to sample: a time axis made by expand() (stride 0) is "
+                             "not a block of samples")
+        return block
+
+    def process_into(self, block: torch.Tensor, out, flush: bool = False):
+        """block [B, n, M] and out [B, n_out, M] with ``n_out = outputs(n, flush)`` (None when n_out == 0): device tensors of the
+        stream's sample kinds, any strides (out without overlap).  Two launches per group of 16 channels, nothing allocated: the
+        call a HIP graph captures (once the stream emits, a launch depends on ``samples_seen`` only through the place of the first
+        output against the block: replay it with blocks of that length, a multiple of q).  The counters ``samples_seen`` and
+        ``samples_out`` live on the host and advance once per call of this method: a capture advances them with no device work
+        behind it, and replays of the graph do not move them -- the owner of a graph keeps its own count."""
+        L = _lib.lib()
+        block = self._block(block)
+        n = block.shape[1]
+        n_out = self.outputs(n, flush)
+        want = torch.int16 if self.out_int16 else torch.float32
+        if n_out > 0 and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (self.batch, n_out, self.channels)
+                          or out.dtype != want or out.device != self.state.device):
+            raise ValueError(f"out must be a {want} tensor [{self.batch}, {n_out}, {self.channels}] on {self.state.device}")
+        if n_out > 0 and any(size > 1 and stride < 1 for size, stride in zip(out.shape, out.stride())):
+            raise ValueError("out must not overlap itself: a stride of 0 along an axis longer than 1")
+        with torch.cuda.device(self.device):
+            st = _lib.stream_ptr(self.device)
+            for c0, m, at, nb in self._groups:
+                s = block[:, :, c0:c0 + m]
+                d = out[:, :, c0:c0 + m] if n_out else None
+                _lib.check(L.misonet_resample_stream(
+                    s.data_ptr() if n else None, int(self.in_int16), s.stride(0), s.stride(2), s.stride(1) if n > 1 else 1, self.batch, m,
+                    n, self.samples_seen, int(bool(flush)), self.fs_in, self.fs_out, d.data_ptr() if n_out else None,
+                    int(self.out_int16), d.stride(0) if n_out else 1, d.stride(2) if n_out else 1, d.stride(1) if n_out else 1,
+                    self.state.data_ptr() + at if nb else None, nb, st))
+        self.samples_seen += n
+        self.samples_out += n_out
+        self._spent = bool(flush)
+        return out
+
+    def process(self, block, flush: bool = False):
+        """The next n >= 1 samples: [B, n, M] (or [n, M] when batch == 1) on the device, read in place through its strides ->
+        [B, n_out, M], the outputs these samples complete; n_out may be 0, which gives an empty tensor."""
+        block = self._block(block)
+        out = torch.empty((self.batch, self.outputs(block.shape[1], flush), self.channels),
+                          dtype=torch.int16 if self.out_int16 else torch.float32, device=self.device)
+        self.process_into(block, out, flush)
+        return out
+
+    def flush(self, block=None):
+        """The end of the stream, with or without a last block: the outputs still owed -- ``ceil(samples_seen p / q)`` in all.
+        The stream is spent until :meth:`reset`."""
+        if block is None:
+            if self._spent:
+                raise ValueError("the stream was flushed: reset() before the next block")
+            block = torch.empty((self.batch, 0, self.channels), dtype=torch.int16 if self.in_int16 else torch.float32,
+                                device=self.device)
+        return self.process(block, flush=True)
+
+
 # ``misonet_amd.resample`` names both this module and the function above: once the module is imported the package attribute is
 # the module, so the module itself is made callable -- ``misonet_amd.resample(x, 48000, 16000)`` works either way (as
 # ``misonet_amd.dereverb`` does).
