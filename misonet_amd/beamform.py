@@ -26,16 +26,8 @@ import numpy as np
 import torch
 
 from . import _lib
-
-
-def _dev_c64(x, device):
-    was_numpy = not isinstance(x, torch.Tensor)
-    t = torch.as_tensor(x)
-    if not t.is_complex():
-        raise TypeError("expected a complex array")
-    if t.device.type != "cuda":
-        t = t.to(device)
-    return t.to(torch.complex64).contiguous(), was_numpy
+from ._online import OnlineStream, check_index, check_real, default_device, spec_of
+from ._online import _dev_c64                   # also under this module's name: tests and tools import it from here
 
 
 KINDS = ("mvdr", "souden", "gev")            # the kinds of misonet_bf_opts, in its numbering
@@ -84,18 +76,8 @@ class Beamformer:
     @classmethod
     def of(cls, spec) -> "Beamformer":
         """None (the defaults), a Beamformer, a kind name, or a dict of the fields above"""
-        if spec is None:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(kind=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown beamformer field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("beamformer must be None, a Beamformer, a kind name or a dict of its fields")
+        return spec_of(cls, spec, "beamformer", "beamformer must be None, a Beamformer, a kind name or a dict of its fields", "kind",
+                       true_ok=False)
 
     def with_epsi(self, default: float) -> "Beamformer":
         return self if self.epsi is not None else dataclasses.replace(self, epsi=float(default))
@@ -265,18 +247,8 @@ class JointBeamformer:
     @classmethod
     def of(cls, spec) -> "JointBeamformer":
         """None (the defaults), a JointBeamformer, a kind name, or a dict of the fields above"""
-        if spec is None:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(kind=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown joint beamformer field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("joint beamformer must be None, a JointBeamformer, a kind name or a dict of its fields")
+        return spec_of(cls, spec, "joint beamformer",
+                       "joint beamformer must be None, a JointBeamformer, a kind name or a dict of its fields", "kind", true_ok=False)
 
     def validate(self, num_mic: Optional[int] = None, num_spks: Optional[int] = None) -> "JointBeamformer":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
@@ -382,18 +354,8 @@ class OnlineBeamformer:
     @classmethod
     def of(cls, spec) -> "OnlineBeamformer":
         """None or True (the defaults), an OnlineBeamformer, a noise name, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(noise=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown online beamformer field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("an online beamformer must be None, True, an OnlineBeamformer, a noise name or a dict of its fields")
+        return spec_of(cls, spec, "online beamformer",
+                       "an online beamformer must be None, True, an OnlineBeamformer, a noise name or a dict of its fields", "noise")
 
     @property
     def noise_index(self) -> int:
@@ -411,12 +373,9 @@ class OnlineBeamformer:
         if isinstance(a, bool) or not isinstance(a, (int, float, np.floating)) or not 0 < a < 1:
             raise ValueError(f"online beamformer alpha must be in (0, 1), got {a!r}")
         for name in ("mu", "diag_load", "epsi", "init"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or v < 0:
-                raise ValueError(f"online beamformer {name} must be finite and >= 0, got {v!r}")
+            check_real("online beamformer", name, getattr(self, name), positive=False)
         r = self.ref_ch
-        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0:
-            raise ValueError(f"online beamformer ref_ch must be a non-negative integer, got {r!r}")
+        check_index("online beamformer", "ref_ch", r)
         if num_mic is not None:
             if not 2 <= num_mic <= 8:
                 raise ValueError(f"the online beamformer needs 2 <= M <= 8 microphones, got {num_mic}")
@@ -436,7 +395,7 @@ def cells_per_block(num_mic: int) -> int:
     return int(_lib.lib().misonet_obf_cells_per_block(int(num_mic)))
 
 
-class BeamformStream:
+class BeamformStream(OnlineStream):
     """The state of one stream of the online beamformer, on the device: ``batch`` recordings of ``num_mic`` microphones,
     ``num_src`` sources and ``num_bins`` bins.  ``opts``: the fields of :class:`OnlineBeamformer`.  The state is allocated once; a
     call allocates only its output."""
@@ -447,19 +406,12 @@ class BeamformStream:
         if not 1 <= self.num_bins <= 1025 or self.batch < 1:
             raise ValueError(f"num_bins must be in [1, 1025] and batch positive, got {num_bins}, {batch}")
         self._c = self.opts.c_opts()
-        n = _lib.lib().misonet_obf_state_bytes(self.batch, self.num_src, self.num_mic, self.num_bins)
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
-        self.reset()
+        self._alloc(_lib.lib().misonet_obf_state_bytes(self.batch, self.num_src, self.num_mic, self.num_bins), device)
 
-    def reset(self):
+    def _reset_call(self):
         """Phi_s = 0, Phi_n = init I, w = 0, no frame seen, no flag"""
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_obf_reset(self.state.data_ptr(), self.batch, self.num_src, self.num_mic, self.num_bins,
-                                                    C.byref(self._c), _lib.stream_ptr(self.device)))
-        return self
+        return _lib.lib().misonet_obf_reset(self.state.data_ptr(), self.batch, self.num_src, self.num_mic, self.num_bins,
+                                            C.byref(self._c), _lib.stream_ptr(self.device))
 
     def _geometry(self, ishape, mshape):
         B, S, M, F = self.batch, self.num_src, self.num_mic, self.num_bins
@@ -497,17 +449,14 @@ class BeamformStream:
         self.process_into(x, y, out)
         return out.cpu() if np_in else out
 
-    def _debug(self, want=("phi_s", "phi_n", "w", "fail", "n")):
-        """copies of the named parts of the state, on the device"""
+    def _parts(self):
         B, S, M, F = self.batch, self.num_src, self.num_mic, self.num_bins
-        shapes = dict(phi_s=((B, S, F, M, M), torch.complex128), phi_n=((B, S, F, M, M), torch.complex128),
-                      w=((B, S, F, M), torch.complex128), fail=((B, S, F), torch.int32), n=((B, S, F), torch.int32))
-        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
-        ptr = lambda k: d[k].data_ptr() if k in d else None
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_obf_debug(self.state.data_ptr(), B, S, M, F, ptr("phi_s"), ptr("phi_n"), ptr("w"),
-                                                    ptr("fail"), ptr("n"), _lib.stream_ptr(self.device)))
-        return d
+        return dict(phi_s=((B, S, F, M, M), torch.complex128), phi_n=((B, S, F, M, M), torch.complex128),
+                    w=((B, S, F, M), torch.complex128), fail=((B, S, F), torch.int32), n=((B, S, F), torch.int32))
+
+    def _debug_call(self, ptr):
+        return _lib.lib().misonet_obf_debug(self.state.data_ptr(), self.batch, self.num_src, self.num_mic, self.num_bins,
+                                            ptr("phi_s"), ptr("phi_n"), ptr("w"), ptr("fail"), ptr("n"), _lib.stream_ptr(self.device))
 
     def filters(self):
         """the filters w complex128 [B, S, F, M] of the last frame (out = w^H y), on the device"""
@@ -518,14 +467,8 @@ class BeamformStream:
         d = self._debug(("phi_s", "phi_n"))
         return d["phi_s"], d["phi_n"]
 
-    @property
-    def frames_seen(self) -> int:
-        return int(self._debug(("n",))["n"].max().item())
-
-    @property
-    def fail(self) -> torch.Tensor:
-        """int32 [B, S, F] on the device: bit 0 a non-finite sample, bit 1 a Cholesky pivot not > 0, bit 2 a non-finite mu + tr G"""
-        return self._debug(("fail",))["fail"]
+    fail = property(OnlineStream.fail.fget, doc="int32 [B, S, F] on the device: bit 0 a non-finite sample, bit 1 a Cholesky pivot "
+                                                "not > 0, bit 2 a non-finite mu + tr G")
 
 
 def beamform_online(images, mix, *, return_debug=False, device=None, **opts):
@@ -537,10 +480,7 @@ def beamform_online(images, mix, *, return_debug=False, device=None, **opts):
     o = OnlineBeamformer(**opts).validate(ishape[2] if len(ishape) == 5 else None, ishape[1] if len(ishape) == 5 else None)
     if len(ishape) != 5 or len(mshape) != 4 or min(ishape) < 1 or tuple(mshape) != (ishape[0],) + tuple(ishape[2:]):
         raise ValueError(f"images {tuple(ishape)} must be [B, S, M, T, F], all positive, and mix {tuple(mshape)} [B, M, T, F]")
-    if device is None:
-        device = (images.device if isinstance(images, torch.Tensor) and images.is_cuda
-                  else torch.device("cuda", torch.cuda.current_device()))
-    st = BeamformStream(ishape[2], ishape[1], ishape[4], ishape[0], device=device, **dataclasses.asdict(o))
+    st = BeamformStream(ishape[2], ishape[1], ishape[4], ishape[0], device=default_device(images, device), **dataclasses.asdict(o))
     out = st.process(images, mix)
     return (out, st._debug()) if return_debug else out
 

@@ -31,7 +31,8 @@ import torch
 
 from . import _lib
 from . import stft as S
-from .beamform import Beamformer, JointBeamformer, _dev_c64
+from ._online import OnlineStream, _dev_c64, check_index, check_real, default_device, spec_of
+from .beamform import Beamformer, JointBeamformer
 
 MODELS = ("gauss", "laplace")                # the source models of misonet_iva_opts, in its numbering
 MAX_ITERATIONS = 1000
@@ -57,18 +58,7 @@ class AuxIVA:
     @classmethod
     def of(cls, spec) -> "AuxIVA":
         """None or True (the defaults), an AuxIVA, a model name, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(model=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown blind field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("blind must be None, True, an AuxIVA, a model name or a dict of its fields")
+        return spec_of(cls, spec, "blind", "blind must be None, True, an AuxIVA, a model name or a dict of its fields", "model")
 
     def validate(self, num_mic=None, num_spks=None) -> "AuxIVA":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
@@ -83,8 +73,7 @@ class AuxIVA:
             raise ValueError(f"blind floor must be finite and > 0, got {v!r}")
         if self.channels is not None and (not integer(self.channels) or self.channels < 1):
             raise ValueError(f"blind channels must be None or a positive integer, got {self.channels!r}")
-        if not integer(self.ref_ch) or self.ref_ch < 0:
-            raise ValueError(f"blind ref_ch must be a non-negative integer, got {self.ref_ch!r}")
+        check_index("blind", "ref_ch", self.ref_ch)
         if num_mic is not None:
             if not 2 <= num_mic <= 8:
                 raise ValueError(f"blind separation needs 2 <= M <= 8 microphones, got {num_mic}")
@@ -124,32 +113,19 @@ class OnlineAuxIVA:
     @classmethod
     def of(cls, spec) -> "OnlineAuxIVA":
         """None or True (the defaults), an OnlineAuxIVA, a model name, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(model=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown online blind field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("online must be None, True, an OnlineAuxIVA, a model name or a dict of its fields")
+        return spec_of(cls, spec, "online blind",
+                       "online must be None, True, an OnlineAuxIVA, a model name or a dict of its fields", "model")
 
     def validate(self, num_mic: Optional[int] = None) -> "OnlineAuxIVA":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
         if self.model not in MODELS:
             raise ValueError(f"online blind model {self.model!r}: one of {MODELS}")
         for name in ("alpha", "floor", "init"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or not v > 0:
-                raise ValueError(f"online blind {name} must be finite and > 0, got {v!r}")
+            check_real("online blind", name, getattr(self, name), positive=True)
         if not self.alpha < 1:
             raise ValueError(f"online blind alpha must be in (0, 1), got {self.alpha!r}")
         r = self.ref_ch
-        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0:
-            raise ValueError(f"online blind ref_ch must be a non-negative integer, got {r!r}")
+        check_index("online blind", "ref_ch", r)
         if num_mic is not None:
             if not 2 <= num_mic <= 8:
                 raise ValueError(f"online blind separation needs 2 <= M <= 8 microphones, got {num_mic}")
@@ -166,7 +142,7 @@ def bins_per_pass(num_mic: int) -> int:
     return int(_lib.lib().misonet_oiva_bins_per_pass(int(num_mic)))
 
 
-class SeparateStream:
+class SeparateStream(OnlineStream):
     """The state of one stream of online AuxIVA, on the device: ``batch`` recordings of ``num_mic`` microphones (= sources) and
     ``num_bins`` bins.  ``opts``: the fields of :class:`OnlineAuxIVA`.  The state is allocated once; a call allocates only its
     outputs.  The stream returns all M rows, in no particular order of the sources."""
@@ -177,26 +153,18 @@ class SeparateStream:
         if not 1 <= self.num_bins <= 1025 or self.batch < 1:
             raise ValueError(f"num_bins must be in [1, 1025] and batch positive, got {num_bins}, {batch}")
         self._c = self.opts.c_opts()
-        n = _lib.lib().misonet_oiva_state_bytes(self.batch, self.num_mic, self.num_bins)
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
-        self.reset()
+        self._alloc(_lib.lib().misonet_oiva_state_bytes(self.batch, self.num_mic, self.num_bins), device)
 
-    def reset(self):
+    def _reset_call(self):
         """W = I, V_k = init I, no frame seen, no flag"""
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_oiva_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins,
-                                                     C.byref(self._c), _lib.stream_ptr(self.device)))
-        return self
+        return _lib.lib().misonet_oiva_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, C.byref(self._c),
+                                             _lib.stream_ptr(self.device))
 
     def process_into(self, block: torch.Tensor, est: torch.Tensor, images: Optional[torch.Tensor] = None):
         """block, est: complex64 [B, M, T, F], images: complex64 [B, M, M, T, F] or None, contiguous on the stream's device and
         not overlapping.  One launch, nothing allocated: the call a HIP graph captures."""
         B, M, T, F = block.shape
-        if (B, M, F) != (self.batch, self.num_mic, self.num_bins):
-            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        self._same_geometry(block.shape)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().misonet_oiva(block.data_ptr(), B, M, T, F, C.byref(self._c), est.data_ptr(),
                                                images.data_ptr() if images is not None else None, self.state.data_ptr(),
@@ -208,10 +176,7 @@ class SeparateStream:
         ``images=True`` also the images complex64 [B, M(k), M, T, F]; on the device for device input and on the CPU for an
         ndarray.  The bits do not depend on how the stream is cut into calls."""
         shape = np.shape(block)
-        if len(shape) != 4 or shape[2] < 1:
-            raise ValueError(f"block {tuple(shape)} must be [B, M, T, F] with T >= 1")
-        if (shape[0], shape[1], shape[3]) != (self.batch, self.num_mic, self.num_bins):
-            raise ValueError(f"block {tuple(shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        self._check_block(shape)
         x, np_in = _dev_c64(block, self.device)
         est = torch.empty_like(x)
         img = torch.empty((shape[0], shape[1]) + tuple(x.shape[1:]), dtype=torch.complex64, device=x.device) if images else None
@@ -220,17 +185,14 @@ class SeparateStream:
             est, img = est.cpu(), (img.cpu() if images else None)
         return (est, img) if images else est
 
-    def _debug(self, want=("W", "V", "fail", "n")):
-        """copies of the named parts of the state, on the device"""
+    def _parts(self):
         B, M, F = self.batch, self.num_mic, self.num_bins
-        shapes = dict(W=((B, F, M, M), torch.complex128), V=((B, F, M, M, M), torch.complex128), fail=((B, F), torch.int32),
-                      n=((B, F), torch.int32))
-        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
-        ptr = lambda k: d[k].data_ptr() if k in d else None
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_oiva_debug(self.state.data_ptr(), B, M, F, ptr("W"), ptr("V"), ptr("fail"), ptr("n"),
-                                                     _lib.stream_ptr(self.device)))
-        return d
+        return dict(W=((B, F, M, M), torch.complex128), V=((B, F, M, M, M), torch.complex128), fail=((B, F), torch.int32),
+                    n=((B, F), torch.int32))
+
+    def _debug_call(self, ptr):
+        return _lib.lib().misonet_oiva_debug(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, ptr("W"), ptr("V"),
+                                             ptr("fail"), ptr("n"), _lib.stream_ptr(self.device))
 
     def demixing(self):
         """the demixing matrices W complex128 [B, F, M, M] as they stand (row k = w_k^H), on the device"""
@@ -240,14 +202,8 @@ class SeparateStream:
         """the weighted covariances V complex128 [B, F, M(k), M, M] as they stand, on the device"""
         return self._debug(("V",))["V"]
 
-    @property
-    def frames_seen(self) -> int:
-        return int(self._debug(("n",))["n"].max().item())
-
-    @property
-    def fail(self) -> torch.Tensor:
-        """int32 [B, F] on the device: bit 0 a non-finite sample, bit 1 a row update that was dropped, bit 2 a singular W"""
-        return self._debug(("fail",))["fail"]
+    fail = property(OnlineStream.fail.fget, doc="int32 [B, F] on the device: bit 0 a non-finite sample, bit 1 a row update that "
+                                                "was dropped, bit 2 a singular W")
 
 
 def auxiva_online(mix, *, return_debug=False, images=False, device=None, **opts):
@@ -260,9 +216,7 @@ def auxiva_online(mix, *, return_debug=False, images=False, device=None, **opts)
     o = OnlineAuxIVA(**opts).validate(shape[1] if len(shape) == 4 else None)
     if len(shape) != 4 or min(shape) < 1:
         raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F], all positive")
-    if device is None:
-        device = mix.device if isinstance(mix, torch.Tensor) and mix.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    st = SeparateStream(shape[1], shape[3], shape[0], device=device, **dataclasses.asdict(o))
+    st = SeparateStream(shape[1], shape[3], shape[0], device=default_device(mix, device), **dataclasses.asdict(o))
     out = st.process(mix, images=images)
     if not return_debug:
         return out

@@ -6,9 +6,6 @@
 // misonet_css_* (css.hip).  Host code only.
 #include "api_common.hpp"
 
-#include <cmath>
-#include <cstdint>
-
 using namespace mn;
 
 // host-side check of every field; M = the number of microphones ref_ch is counted in
@@ -57,16 +54,8 @@ void mn::wpd_opts_apply(const misonet_wpd_opts& o, WpdArgs& a) {
 
 // the dynamic-LDS attribute of wpd_bin_k: once per device, never inside an asynchronous call after that
 int mn::wpd_ready() {
-  static std::atomic<bool> done[MAX_DEV];
-  static std::mutex mu;
-  const int d = cur_dev();
-  if (done[d].load(std::memory_order_acquire)) return MISONET_OK;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!done[d].load(std::memory_order_acquire)) {
-    HIPCHK(wpd_init());
-    done[d].store(true, std::memory_order_release);
-  }
-  return MISONET_OK;
+  static DeviceOnce latch;
+  return latch.once([] { HIPCHK(wpd_init()); return (int)MISONET_OK; });
 }
 
 // cACGMM: every field (the geometry is checked by the calls)
@@ -260,24 +249,15 @@ static int owpe_check(int B, int M, int F, const misonet_owpe_opts* o) {
   if (o->context < 0 || o->context > OWPE_CTX)
     return fail(MISONET_EINVAL, "context must be in [0, %d] (got %d)", OWPE_CTX, o->context);
   if (!(o->alpha > 0.0 && o->alpha <= 1.0)) return fail(MISONET_EINVAL, "alpha must be in (0, 1] (got %g)", o->alpha);
-  if (!(o->power_floor > 0.0) || !std::isfinite(o->power_floor))
-    return fail(MISONET_EINVAL, "power_floor must be finite and > 0 (got %g)", o->power_floor);
-  if (!(o->init > 0.0) || !std::isfinite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
+  if (!pos_finite(o->power_floor)) return fail(MISONET_EINVAL, "power_floor must be finite and > 0 (got %g)", o->power_floor);
+  if (!pos_finite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
   return MISONET_OK;
 }
 
 // the dynamic-LDS attribute of owpe_k: once per device, never inside an asynchronous call after that
 static int owpe_ready() {
-  static std::atomic<bool> done[MAX_DEV];
-  static std::mutex mu;
-  const int d = cur_dev();
-  if (done[d].load(std::memory_order_acquire)) return MISONET_OK;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!done[d].load(std::memory_order_acquire)) {
-    HIPCHK(owpe_init());
-    done[d].store(true, std::memory_order_release);
-  }
-  return MISONET_OK;
+  static DeviceOnce latch;
+  return latch.once([] { HIPCHK(owpe_init()); return (int)MISONET_OK; });
 }
 
 long long misonet_owpe_state_bytes(int B, int M, int F, const misonet_owpe_opts* opts) {
@@ -341,10 +321,10 @@ static int oiva_check(int B, int M, int F, const misonet_oiva_opts* o) {
   { int r = oiva_geom_check(B, M, F); if (r) return r; }
   if (o->model != 0 && o->model != 1) return fail(MISONET_EINVAL, "model %d: 0 gauss, 1 laplace", o->model);
   if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "ref_ch %d outside [0, %d)", o->ref_ch, M);
-  if (!(o->alpha > 0.0 && o->alpha < 1.0))
+  if (!in_open_unit(o->alpha))
     return fail(MISONET_EINVAL, "alpha must be in (0, 1): 1 would freeze the covariances (got %g)", o->alpha);
-  if (!(o->floor > 0.0) || !std::isfinite(o->floor)) return fail(MISONET_EINVAL, "floor must be finite and > 0 (got %g)", o->floor);
-  if (!(o->init > 0.0) || !std::isfinite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
+  if (!pos_finite(o->floor)) return fail(MISONET_EINVAL, "floor must be finite and > 0 (got %g)", o->floor);
+  if (!pos_finite(o->init)) return fail(MISONET_EINVAL, "init must be finite and > 0 (got %g)", o->init);
   return MISONET_OK;
 }
 
@@ -365,19 +345,15 @@ int misonet_oiva_reset(void* state, int B, int M, int F, const misonet_oiva_opts
   return MISONET_OK;
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-static bool oiva_overlap(const void* a, long long na, const void* b, long long nb) {
-  const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 int misonet_oiva(const void* mix, int B, int M, int T, int F, const misonet_oiva_opts* opts, void* est, void* images, void* state,
                  long long state_bytes, misonet_stream stream) {
   { int r = oiva_check(B, M, F, opts); if (r) return r; }
   if (T < 1) return fail(MISONET_EINVAL, "T must be >= 1 (got %d)", T);
   if (!mix || !est || !state) return fail(MISONET_EINVAL, "null argument");
-  const long long n = (long long)B * M * T * F * 8;
-  if (oiva_overlap(mix, n, est, n) || (images && (oiva_overlap(mix, n, images, n * M) || oiva_overlap(est, n, images, n * M))))
+  // the 128-bit predicate of misonet_obf.  For every block that fits the address space (n M < 2^63) the 64-bit comparison this
+  // call used before never wrapped, and the two agree
+  const unsigned __int128 n = (unsigned __int128)B * M * T * F * 8;
+  if (ranges_overlap(mix, n, est, n) || (images && (ranges_overlap(mix, n, images, n * M) || ranges_overlap(est, n, images, n * M))))
     return fail(MISONET_EINVAL, "mix_dev, est_out_dev and images_out_dev must not overlap");
   if (state_bytes < oiva_state_bytes((long long)B * F, M)) return fail(MISONET_ENOMEM, "state too small");
   HIPCHK(launch_oiva(mix, B, M, T, F, opts->model, opts->ref_ch, opts->alpha, opts->floor, est, images, state,
@@ -408,20 +384,18 @@ static int obf_geom_check(int B, int S, int M, int F) {
   return MISONET_OK;
 }
 
-static bool obf_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
-
 // host-side check of every field and of the geometry they are used with
 static int obf_check(int B, int S, int M, int F, const misonet_obf_opts* o) {
   if (!o) return fail(MISONET_EINVAL, "null online beamformer options");
   { int r = obf_geom_check(B, S, M, F); if (r) return r; }
   if (o->noise != 0 && o->noise != 1) return fail(MISONET_EINVAL, "noise %d: 0 residual, 1 mix", o->noise);
   if (o->ref_ch < 0 || o->ref_ch >= M) return fail(MISONET_EINVAL, "ref_ch %d outside [0, %d)", o->ref_ch, M);
-  if (!(o->alpha > 0.0 && o->alpha < 1.0))
+  if (!in_open_unit(o->alpha))
     return fail(MISONET_EINVAL, "alpha must be in (0, 1): 1 would freeze the covariances (got %g)", o->alpha);
-  if (!obf_nonneg(o->mu)) return fail(MISONET_EINVAL, "mu must be finite and >= 0 (got %g)", o->mu);
-  if (!obf_nonneg(o->diag_load)) return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
-  if (!obf_nonneg(o->epsi)) return fail(MISONET_EINVAL, "epsi must be finite and >= 0 (got %g)", o->epsi);
-  if (!obf_nonneg(o->init)) return fail(MISONET_EINVAL, "init must be finite and >= 0 (got %g)", o->init);
+  if (!nonneg_finite(o->mu)) return fail(MISONET_EINVAL, "mu must be finite and >= 0 (got %g)", o->mu);
+  if (!nonneg_finite(o->diag_load)) return fail(MISONET_EINVAL, "diag_load must be finite and >= 0 (got %g)", o->diag_load);
+  if (!nonneg_finite(o->epsi)) return fail(MISONET_EINVAL, "epsi must be finite and >= 0 (got %g)", o->epsi);
+  if (!nonneg_finite(o->init)) return fail(MISONET_EINVAL, "init must be finite and >= 0 (got %g)", o->init);
   return MISONET_OK;
 }
 
@@ -442,12 +416,6 @@ int misonet_obf_reset(void* state, int B, int S, int M, int F, const misonet_obf
   return MISONET_OK;
 }
 
-// [a, a + na) and [b, b + nb) share a byte; the sizes of a long stream do not fit 64 bits
-static bool obf_overlap(const void* a, unsigned __int128 na, const void* b, unsigned __int128 nb) {
-  const unsigned __int128 pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
 int misonet_obf(const void* mix, const void* images, int B, int S, int M, int T, int F, const misonet_obf_opts* opts, void* out,
                 void* state, long long state_bytes, misonet_stream stream) {
   { int r = obf_check(B, S, M, F, opts); if (r) return r; }
@@ -456,8 +424,8 @@ int misonet_obf(const void* mix, const void* images, int B, int S, int M, int T,
   const long long need = obf_state_bytes((long long)B * S * F, M);
   const unsigned __int128 plane = (unsigned __int128)B * T * F * 8, nm = plane * M, no = plane * S, ni = no * M;
   const unsigned __int128 ns = (unsigned __int128)(state_bytes < need ? (state_bytes > 0 ? state_bytes : 0) : need);
-  if (obf_overlap(mix, nm, images, ni) || obf_overlap(mix, nm, out, no) || obf_overlap(images, ni, out, no) ||
-      obf_overlap(state, ns, mix, nm) || obf_overlap(state, ns, images, ni) || obf_overlap(state, ns, out, no))
+  if (ranges_overlap(mix, nm, images, ni) || ranges_overlap(mix, nm, out, no) || ranges_overlap(images, ni, out, no) ||
+      ranges_overlap(state, ns, mix, nm) || ranges_overlap(state, ns, images, ni) || ranges_overlap(state, ns, out, no))
     return fail(MISONET_EINVAL, "mix_dev, images_dev, out_dev and state_dev must not overlap");
   if (state_bytes < need) return fail(MISONET_ENOMEM, "state too small");
   HIPCHK(launch_obf(mix, images, B, S, M, T, F, opts->noise, opts->ref_ch, opts->alpha, opts->mu, opts->diag_load, opts->epsi, out,

@@ -1,10 +1,13 @@
 // What the host files behind the C ABI of include/misonet.h share (net.hip and the api_*.hip files, one per domain): the error
-// report, per-launch profiling, and the per-device lazily built table.  Host code only; no kernel file includes it.
+// report, per-launch profiling, the per-device lazily built table and once-latch, and the small argument checks.  Host code
+// only; no kernel file includes it.
 #pragma once
 #include "kernels.hpp"
 #include "../../include/misonet.h"
 
 #include <atomic>
+#include <cmath>
+#include <cstdint>
 #include <mutex>
 #include <vector>
 
@@ -81,12 +84,40 @@ struct DevTable {
     return MISONET_OK;
   }
 };
+// Something that has to happen once on every device before the first asynchronous call there (a kernel attribute): once() runs
+// `init` under the lock at the first use on the CURRENT device; an error is returned and the next call tries again.
+struct DeviceOnce {
+  std::atomic<bool> done[MAX_DEV] = {};
+  std::mutex mu;
+  template <class Init>
+  int once(Init init) {
+    const int d = cur_dev();
+    if (done[d].load(std::memory_order_acquire)) return MISONET_OK;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!done[d].load(std::memory_order_acquire)) {
+      if (const int rc = init()) return rc;
+      done[d].store(true, std::memory_order_release);
+    }
+    return MISONET_OK;
+  }
+};
 template <class T>
 int dev_upload(const std::vector<T>& host, T** out) {
   HIPCHK(hipMalloc(reinterpret_cast<void**>(out), host.size() * sizeof(T)));
   HIPCHK(hipMemcpy(*out, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
   return MISONET_OK;
 }
+
+// ---- argument checks ----------------------------------------------------------------------------------------------------------
+// [a, a + na) and [b, b + nb) share a byte.  128 bits: the byte counts of a long stream do not fit 64, and an end must not wrap
+inline bool ranges_overlap(const void* a, unsigned __int128 na, const void* b, unsigned __int128 nb) {
+  const unsigned __int128 pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+// false for a NaN, each of them
+inline bool in_open_unit(double v) { return v > 0.0 && v < 1.0; }
+inline bool pos_finite(double v) { return v > 0.0 && std::isfinite(v); }
+inline bool nonneg_finite(double v) { return v >= 0.0 && std::isfinite(v); }
 
 // ---- what one domain's file needs of another's ---------------------------------------------------------------------------
 // api_frontend.hip: the STFT twiddles of the current device (builds both front-end tables at the first use there)

@@ -27,13 +27,13 @@
 //
 // Limits: 2 <= M <= 8 (2 M <= 16 rows: one tile), 2 <= K <= 5 (one wave per class).  38 KB of static LDS, nothing that grows with T.
 #include "kernels.hpp"
+#include "cplx.hpp"
 #include "stacked_gram.hpp"
 
 namespace mn {
 
 constexpr int CG_KMAX = 5;            // classes: four speakers and the noise
 constexpr int CG_ZP = 17;             // pitch of a frame's 16 rows of z, in doubles (odd)
-constexpr double CG_BIG = 1.7976931348623157e308;
 
 // workspace: fail int [B F] | ll double [B F] | pi double [B F][K] | B_k c128 [B F][K][M][M]
 struct CgWs { long long fail, ll, pi, bk, total; };
@@ -48,13 +48,6 @@ __host__ __device__ inline CgWs cg_ws(int B, int K, int F, int M) {
   return w;
 }
 long long cacgmm_ws_bytes(int B, int K, int F, int M) { return cg_ws(B, K, F, M).total; }
-
-// the sum of v over a wave by one butterfly, the same bits on every lane
-__device__ __forceinline__ double cg_wave_sum(double v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k, 64);
-  return v;
-}
 
 // grid (F, B), 512 threads
 __global__ __launch_bounds__(SG_THREADS) void cacgmm_bin_k(const CacgmmArgs a, int* fail_out, double* ll_out, double* pi_out,
@@ -183,18 +176,18 @@ __global__ __launch_bounds__(SG_THREADS) void cacgmm_bin_k(const CacgmmArgs a, i
 
     if (do_e) {                                                        // the log-likelihood of this E-step
       if (wave == 0) {
-        const double v = cg_wave_sum(ll_acc);
+        const double v = wave_sum(ll_acc);
         if (lane == 0) llsum = v;
       }
       __syncthreads();
       ll = llsum;
-      if (!(fabs(ll) <= CG_BIG)) { failed = ident = true; continue; }
+      if (!finite(ll)) { failed = ident = true; continue; }
     }
     if (!do_gram) break;
 
     // ---- the M-step: n_k, B_k, its factor, logdet_k, L_k^-1, pi
     if (k < K) {
-      const double v = cg_wave_sum(n_acc);
+      const double v = wave_sum(n_acc);
       if (lane == 0) nk[k] = v;
 #pragma unroll
       for (int r = 0; r < 4; ++r) gs[k * 256 + (lg + 4 * r) * 16 + lr] = acc[r];
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(SG_THREADS) void cacgmm_bin_k(const CacgmmArgs a, i
     double ntot = 0.0;
     for (int c = 0; c < K; ++c) {
       const double v = nk[c];
-      if (!(v > 0.0) || !(v <= CG_BIG)) bad = true;
+      if (!(v > 0.0) || !(v <= F64_MAX)) bad = true;
       ntot += v;
     }
     if (bad) { failed = ident = true; continue; }

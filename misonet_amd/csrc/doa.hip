@@ -26,6 +26,7 @@
 // flags are kept.  It also counts used and raises fail.
 // Every sum has one fixed order and every output has one writer: a recording's bits depend neither on B nor on its place.
 #include "kernels.hpp"
+#include "cplx.hpp"
 #include "jacobi.hpp"
 
 #include <cmath>
@@ -40,7 +41,6 @@ constexpr double DOA_RANK_TOL = 1e-12;
 int doa_tile() { return DOA_TILE; }
 int doa_bin_chunk() { return DOA_CHUNK; }
 
-__device__ __forceinline__ bool doa_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
 // grid B N F (bin fastest), DOA_FRAMES threads
 template <int M>
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(DOA_FRAMES) void doa_cov_k(const float2* __restrict
     for (int m = 0; m < M; ++m) {
       const float2 v = x[(long long)m * T + t];
       double re = (double)v.x, im = (double)v.y;
-      if (valid && (!doa_finite(v.x) || !doa_finite(v.y))) s_bad[0] = 1;
+      if (valid && (!finite(v.x) || !finite(v.y))) s_bad[0] = 1;
       if (kind == DOA_SRP_PHAT) {
         const double a = sqrt(re * re + im * im);
         if (a > 0.0) { re /= a; im /= a; }
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(DOA_FRAMES) void doa_cov_k(const float2* __restrict
     for (int k = 0; k < K; ++k) {
       float w = 1.0f;
       if (weight) w = weight[(((long long)b * K + k) * F + f) * T + t];
-      if (valid && !doa_finite(w)) s_bad[1 + k] = 1;
+      if (valid && !finite(w)) s_bad[1 + k] = 1;
       s_w[k][tid] = (double)w;
     }
     __syncthreads();

@@ -28,6 +28,7 @@
 // atomics and a workgroup never looks at another one's bin: the result is bit-reproducible and depends neither on B nor on the
 // position in the batch.  LDS is static and does not grow with T.
 #include "kernels.hpp"
+#include "cplx.hpp"
 #include "stacked_gram.hpp"
 #include "jacobi.hpp"
 
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(IVA_THREADS) void iva_pca_k(const float2* mix, int 
   int bad = 0;
   for (long long e = tid; e < (long long)M * T; e += IVA_THREADS) {
     const float2 v = x[e];
-    if (!(fabsf(v.x) <= 3.4028234663852886e38f) || !(fabsf(v.y) <= 3.4028234663852886e38f)) bad = 1;
+    if (!(fabsf(v.x) <= F32_MAX) || !(fabsf(v.y) <= F32_MAX)) bad = 1;
   }
   bad = __syncthreads_or(bad);
 
@@ -252,7 +253,7 @@ __device__ __forceinline__ void iva_step_sum(const double (&part)[3 * K], int s,
       const double d = den / (double)T;
       if (d != 0.0) vr = 1.0 - 1.0 / sqrt(d);
     }
-    if (!(fabs(vr) <= 1.7976931348623157e308) || !(fabs(vi) <= 1.7976931348623157e308)) {
+    if (!(fabs(vr) <= F64_MAX) || !(fabs(vi) <= F64_MAX)) {
       vr = vi = 0.0;
       *flag = 2;
     }

@@ -30,6 +30,7 @@
 // Limits: 2 <= M <= 8 (2 M <= 16 rows: one tile), 1 <= S <= 4 (one wave per class), S <= M.  63 KB of static LDS, nothing that
 // grows with T: the small matrices of the solve lie over the float64 rows, which are dead by then.
 #include "kernels.hpp"
+#include "cplx.hpp"
 #include "stacked_gram.hpp"
 #include "jacobi.hpp"
 
@@ -37,7 +38,6 @@ namespace mn {
 
 constexpr int JB_CMAX = 5;            // classes: four speakers and the noise
 constexpr int JB_ZP = 17;             // pitch of a frame's 16 rows, in doubles (odd)
-constexpr double JB_BIG = 1.7976931348623157e308;
 
 // workspace: fail int [B][S][F] | w c128 [B][S][F][M] | (lcmv) d c128 [B][S][F][M]
 struct JbWs { long long fail, w, d, total; };
@@ -97,7 +97,6 @@ __device__ __forceinline__ double2 jb_div(double2 a, double2 b) {
   const double d = b.x * b.x + b.y * b.y;
   return make_double2((a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d);
 }
-__device__ __forceinline__ bool jb_finite(double v) { return fabs(v) <= JB_BIG; }
 
 // L x = v and L^H x = v in place, L [n][n] lower (pitch n, a real diagonal), x with stride xs; one thread
 __device__ __forceinline__ void jb_fwd(const double2* L, int n, double2* x, int xs) {
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(SG_THREADS) void jbf_bin_k(const JbfArgs a, const C
     for (int s = 0; s < S && !failed; ++s) {                           // an exactly-zero estimate has no direction
       double tr = 0.0;
       for (int i = 0; i < M; ++i) tr += Phi[s * 64 + i * M + i].x;
-      if (tr == 0.0 || !jb_finite(tr)) failed = all;
+      if (tr == 0.0 || !finite(tr)) failed = all;
     }
     if (!failed) {
 #pragma unroll 1
@@ -293,7 +292,7 @@ __global__ __launch_bounds__(SG_THREADS) void jbf_bin_k(const JbfArgs a, const C
       double2 aref = make_double2(1.0, 0.0);
       for (int s = 0; s < S; ++s) {
         const double2 v = Dm[s * 8 + a.ref];
-        if ((v.x == 0.0 && v.y == 0.0) || !jb_finite(v.x) || !jb_finite(v.y)) failed = all;
+        if ((v.x == 0.0 && v.y == 0.0) || !finite(v.x) || !finite(v.y)) failed = all;
         if (tid / M == s) aref = v;
       }
       __syncthreads();
@@ -376,7 +375,7 @@ __global__ __launch_bounds__(SG_THREADS) void jbf_bin_k(const JbfArgs a, const C
       if (tid < S && !((failed >> tid) & 1u)) {                        // w_s = A_s e_ref / (mu + tr A_s)
         double2 den = make_double2(a.mu, 0.0);
         for (int i = 0; i < M; ++i) { den.x += Xs[tid * 64 + i * M + i].x; den.y += Xs[tid * 64 + i * M + i].y; }
-        if ((den.x == 0.0 && den.y == 0.0) || !jb_finite(den.x) || !jb_finite(den.y)) sbad[tid] = 1;
+        if ((den.x == 0.0 && den.y == 0.0) || !finite(den.x) || !finite(den.y)) sbad[tid] = 1;
         else
           for (int i = 0; i < M; ++i) Wm[tid * 8 + i] = jb_div(Xs[tid * 64 + i * M + a.ref], den);
       }

@@ -37,39 +37,29 @@
 // does not depend on how the stream is cut into calls.  One launch, no host synchronisation, no allocation; nothing in the
 // launch or the state depends on T.
 #include "kernels.hpp"
+#include "cplx.hpp"
 
 namespace mn {
 
-constexpr double OBF_DBL_MAX = 1.7976931348623157e308;
-
 template <int M> struct ObfGeom {
-  static constexpr int G = M <= 2 ? 2 : M <= 4 ? 4 : 8;                // lanes per cell
+  static constexpr int G = lanes_for(M);                               // lanes per cell
   static constexpr int THREADS = 64;                                   // one wave: the cells spread over as many CUs as there are
   static constexpr int CELLS = THREADS / G;                            // cells per workgroup: 32, 16, 16, 8, 8, 8, 8
 };
 
 int obf_cells_per_block(int M) {
-  switch (M) {
-    case 2: return ObfGeom<2>::CELLS;
-    case 3: return ObfGeom<3>::CELLS;
-    case 4: return ObfGeom<4>::CELLS;
-    case 5: return ObfGeom<5>::CELLS;
-    case 6: return ObfGeom<6>::CELLS;
-    case 7: return ObfGeom<7>::CELLS;
-    case 8: return ObfGeom<8>::CELLS;
-  }
-  return -1;
+  int cells = -1;
+  if (M >= 2 && M <= 8) with_m(M, [&](auto m) { cells = ObfGeom<decltype(m)::value>::CELLS; });
+  return cells;
 }
-
-__host__ __device__ inline long long obf_align(long long n) { return (n + 15) & ~15LL; }
 
 // state: fail int [cells] | n int [cells] | Phi_s c128 [cells][M][M] | Phi_n c128 [cells][M][M] | w c128 [cells][M]
 struct ObfWs { long long fail, n, ps, pn, w, total; };
 __host__ __device__ inline ObfWs obf_ws(long long cells, int M) {
   ObfWs w;
   w.fail = 0;
-  w.n = obf_align(cells * 4);
-  w.ps = obf_align(w.n + cells * 4);
+  w.n = align16(cells * 4);
+  w.ps = align16(w.n + cells * 4);
   w.pn = w.ps + cells * M * M * 16;
   w.w = w.pn + cells * M * M * 16;
   w.total = w.w + cells * M * 16;
@@ -86,32 +76,6 @@ struct ObfArgs {
   int S, T, F, noise, ref;
   double alpha, oma, mu, diag_load, epsi;                              // oma = 1 - alpha
 };
-
-__device__ __forceinline__ bool obf_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-__device__ __forceinline__ double2 obf_wide(float2 v) { return make_double2((double)v.x, (double)v.y); }
-__device__ __forceinline__ double2 obf_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-// acc - a b
-__device__ __forceinline__ double2 obf_fms(double2 acc, double2 a, double2 b) {
-  return make_double2(acc.x - (a.x * b.x - a.y * b.y), acc.y - (a.x * b.y + a.y * b.x));
-}
-// acc - a conj(b)
-__device__ __forceinline__ double2 obf_fmsc(double2 acc, double2 a, double2 b) {
-  return make_double2(acc.x - (a.x * b.x + a.y * b.y), acc.y - (a.y * b.x - a.x * b.y));
-}
-// 1 / p (Smith): no intermediate leaves the range of p
-__device__ __forceinline__ double2 obf_inv(double2 p) {
-  if (fabs(p.x) >= fabs(p.y)) {
-    const double r = p.y / p.x, d = p.x + p.y * r;
-    return make_double2(1.0 / d, -r / d);
-  }
-  const double r = p.x / p.y, d = p.x * r + p.y;
-  return make_double2(r / d, -1.0 / d);
-}
-// c ? a : b part by part: a conditional on the struct itself becomes a choice of addresses, and the struct scratch
-__device__ __forceinline__ double2 obf_sel(bool c, double2 a, double2 b) { return make_double2(c ? a.x : b.x, c ? a.y : b.y); }
-template <int G> __device__ __forceinline__ double2 obf_from(double2 v, int src) {
-  return make_double2(__shfl(v.x, src, G), __shfl(v.y, src, G));
-}
 
 // frame t of a cell: the M samples of the source image and of the mixture, as they lie (strided in m, contiguous in f)
 template <int M>
@@ -135,12 +99,12 @@ __device__ __forceinline__ void obf_update(double2 (&P)[M], const double2 (&u)[M
 #pragma unroll
   for (int c = 0; c < M; ++c) {
     const bool lower = jr >= c;
-    const double2 a = obf_sel(lower, uj, u[c]), b = obf_sel(lower, u[c], uj), o = P[c];
+    const double2 a = c_sel(lower, uj, u[c]), b = c_sel(lower, u[c], uj), o = P[c];
     const double oy = lower ? o.y : -o.y;
     const double re = alpha * o.x + oma * (a.x * b.x + a.y * b.y);
     double im = alpha * oy + oma * (a.y * b.x - a.x * b.y);
     im = jr == c ? 0.0 : lower ? im : -im;
-    P[c] = obf_sel(keep, o, make_double2(re, im));
+    P[c] = c_sel(keep, o, make_double2(re, im));
   }
 }
 
@@ -204,21 +168,21 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
     // ---- 0, 1. the frame's vectors; a bad frame runs on as zeros and changes nothing
     bool bad = false;
 #pragma unroll
-    for (int m = 0; m < M; ++m) bad |= !(obf_finite(x[m].x) && obf_finite(x[m].y) && obf_finite(y[m].x) && obf_finite(y[m].y));
+    for (int m = 0; m < M; ++m) bad |= !(finite(x[m].x) && finite(x[m].y) && finite(y[m].x) && finite(y[m].y));
     double2 xd[M], yd[M], vd[M];
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const double2 zero = make_double2(0.0, 0.0);
-      xd[m] = obf_sel(bad, zero, obf_wide(x[m]));
-      yd[m] = obf_sel(bad, zero, obf_wide(y[m]));
-      vd[m] = obf_sel(residual, make_double2(yd[m].x - xd[m].x, yd[m].y - xd[m].y), yd[m]);
+      xd[m] = c_sel(bad, zero, c_wide(x[m]));
+      yd[m] = c_sel(bad, zero, c_wide(y[m]));
+      vd[m] = c_sel(residual, make_double2(yd[m].x - xd[m].x, yd[m].y - xd[m].y), yd[m]);
     }
     double2 xj = xd[0], vj = vd[0];
 #pragma unroll
     for (int m = 1; m < M; ++m) {
       const bool mine = kbit >> m & 1u;
-      xj = obf_sel(mine, xd[m], xj);
-      vj = obf_sel(mine, vd[m], vj);
+      xj = c_sel(mine, xd[m], xj);
+      vj = c_sel(mine, vd[m], vj);
     }
 
     // ---- 2. the covariances
@@ -249,12 +213,12 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
       if (jk == c) s.x += load;
 #pragma unroll
       for (int k = 0; k < c; ++k) {
-        const double2 bc = obf_from<G>(Lr[k], c);                      // L[c][k]
-        s = obf_fmsc(s, Lr[k], bc);
-        Lc[c] = obf_sel(kbit >> k & 1u, bc, Lc[c]);
+        const double2 bc = c_from<G>(Lr[k], c);                      // L[c][k]
+        s = c_fmsc(s, Lr[k], bc);
+        Lc[c] = c_sel(kbit >> k & 1u, bc, Lc[c]);
       }
       const double p = __shfl(s.x, c, G);
-      pbad |= !(p > 0.0 && p <= OBF_DBL_MAX);
+      pbad |= !(p > 0.0 && p <= F64_MAX);
       const double inv = 1.0 / sqrt(p);
       invd[c] = inv;
       Lr[c] = make_double2(s.x * inv, s.y * inv);
@@ -270,9 +234,9 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
     for (int c = 0; c < M; ++c) {
 #pragma unroll
       for (int r = 0; r < M; ++r) {
-        const double2 zb = obf_from<G>(make_double2(rhs[r].x * invd[c], rhs[r].y * invd[c]), c);
-        const double2 below = obf_fms(rhs[r], Lr[c], zb);
-        rhs[r] = obf_sel(jk > c, below, obf_sel(jk == c, zb, rhs[r]));
+        const double2 zb = c_from<G>(make_double2(rhs[r].x * invd[c], rhs[r].y * invd[c]), c);
+        const double2 below = c_fms(rhs[r], Lr[c], zb);
+        rhs[r] = c_sel(jk > c, below, c_sel(jk == c, zb, rhs[r]));
       }
     }
     asm volatile("" : "+v"(jk));
@@ -281,7 +245,7 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
     double2 zr = rhs[0];
 #pragma unroll
     for (int r = 1; r < M; ++r)
-      zr = obf_sel(ref == r, rhs[r], zr);
+      zr = c_sel(ref == r, rhs[r], zr);
     double2 gd[M], gref[M];
 #pragma unroll
     for (int c = M - 1; c >= 0; --c) {
@@ -289,23 +253,23 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
       const double2 lc = make_double2(Lc[c].x, -Lc[c].y);              // conj(L[c][jk])
 #pragma unroll
       for (int r = 0; r <= c; ++r) {
-        const double2 gb = obf_from<G>(make_double2(rhs[r].x * invd[c], rhs[r].y * invd[c]), c);
+        const double2 gb = c_from<G>(make_double2(rhs[r].x * invd[c], rhs[r].y * invd[c]), c);
         if (r == c) gd[c] = gb;
-        const double2 up = obf_fms(rhs[r], lc, gb);
-        rhs[r] = obf_sel(above, up, rhs[r]);
+        const double2 up = c_fms(rhs[r], lc, gb);
+        rhs[r] = c_sel(above, up, rhs[r]);
       }
-      const double2 gb = obf_from<G>(make_double2(zr.x * invd[c], zr.y * invd[c]), c);
+      const double2 gb = c_from<G>(make_double2(zr.x * invd[c], zr.y * invd[c]), c);
       gref[c] = gb;
-      const double2 up = obf_fms(zr, lc, gb);
-      zr = obf_sel(above, up, zr);
+      const double2 up = c_fms(zr, lc, gb);
+      zr = c_sel(above, up, zr);
     }
     double2 acc = gd[0];
 #pragma unroll
     for (int m = 1; m < M; ++m) acc = make_double2(acc.x + gd[m].x, acc.y + gd[m].y);
     const double2 den = make_double2(a.mu + acc.x, acc.y);
-    const bool fin = fabs(den.x) <= OBF_DBL_MAX && fabs(den.y) <= OBF_DBL_MAX;
+    const bool fin = finite(den.x) && finite(den.y);
     const bool zero = den.x == 0.0 && den.y == 0.0;
-    const double2 iden = obf_inv(den);
+    const double2 iden = c_inv(den);
     const bool ok = !bad && !pbad && fin && !zero;
     if (bad) flags |= 1;
     else if (pbad) flags |= 2;
@@ -315,8 +279,8 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
     double2 o = make_double2(0.0, 0.0);
 #pragma unroll
     for (int m = 0; m < M; ++m) {
-      const double2 wn = obf_mul(gref[m], iden);
-      W[m] = obf_sel(bad, W[m], obf_sel(ok, wn, make_double2(0.0, 0.0)));
+      const double2 wn = c_mul(gref[m], iden);
+      W[m] = c_sel(bad, W[m], c_sel(ok, wn, make_double2(0.0, 0.0)));
       o.x += W[m].x * yd[m].x + W[m].y * yd[m].y;                      // conj(w) y
       o.y += W[m].x * yd[m].y - W[m].y * yd[m].x;
     }
@@ -330,7 +294,7 @@ __global__ __launch_bounds__(ObfGeom<M>::THREADS) void obf_k(const ObfArgs a) {
     double2 wj = W[0];
 #pragma unroll
     for (int m = 1; m < M; ++m)
-      wj = obf_sel(jbit >> m & 1u, W[m], wj);
+      wj = c_sel(jbit >> m & 1u, W[m], wj);
     wg[j] = wj;
   }
   if (act && j == 0) {
@@ -364,15 +328,7 @@ hipError_t launch_obf(const void* mix, const void* images, int B, int S, int M, 
   a.w = obf_ws(a.cells, M);
   a.S = S; a.T = T; a.F = F; a.noise = noise; a.ref = ref_ch;
   a.alpha = alpha; a.oma = 1.0 - alpha; a.mu = mu; a.diag_load = diag_load; a.epsi = epsi;
-  switch (M) {
-    case 2: obf_go<2>(a, s); break;
-    case 3: obf_go<3>(a, s); break;
-    case 4: obf_go<4>(a, s); break;
-    case 5: obf_go<5>(a, s); break;
-    case 6: obf_go<6>(a, s); break;
-    case 7: obf_go<7>(a, s); break;
-    default: obf_go<8>(a, s); break;
-  }
+  with_m(M, [&](auto m) { obf_go<decltype(m)::value>(a, s); });
   return hipGetLastError();
 }
 
@@ -380,14 +336,8 @@ hipError_t launch_obf_debug(const void* state, int B, int S, int M, int F, void*
                             hipStream_t s) {
   const long long cells = (long long)B * S * F;
   const ObfWs ws = obf_ws(cells, M);
-  const char* base = reinterpret_cast<const char*>(state);
-  hipError_t e = hipSuccess;
-  if (phi_s && (e = hipMemcpyAsync(phi_s, base + ws.ps, cells * M * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (phi_n && (e = hipMemcpyAsync(phi_n, base + ws.pn, cells * M * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (w && (e = hipMemcpyAsync(w, base + ws.w, cells * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (fail && (e = hipMemcpyAsync(fail, base + ws.fail, cells * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (n && (e = hipMemcpyAsync(n, base + ws.n, cells * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  return e;
+  return copy_parts(state, {{phi_s, ws.ps, cells * M * M * 16}, {phi_n, ws.pn, cells * M * M * 16}, {w, ws.w, cells * M * 16},
+                            {fail, ws.fail, cells * 4}, {n, ws.n, cells * 4}}, s);
 }
 
 }  // namespace mn

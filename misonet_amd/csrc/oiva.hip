@@ -36,41 +36,32 @@
 // the next -- does not depend on how the stream is cut into calls.  One launch, no host synchronisation, no allocation; nothing
 // in the launch or the state depends on T.
 #include "kernels.hpp"
+#include "cplx.hpp"
 
 namespace mn {
 
 constexpr int OIVA_FMAX = 1025;
-constexpr double OIVA_DBL_MAX = 1.7976931348623157e308;
 
 template <int M> struct OivaGeom {
-  static constexpr int G = M <= 2 ? 2 : M <= 4 ? 4 : 8;                // lanes per bin
+  static constexpr int G = lanes_for(M);                               // lanes per bin
   // 4, 3, 2 or 1 waves per SIMD: 128, 168, 256 or 512 registers each, what the rows of W, W V_k, V_k and u of that M take
   static constexpr int THREADS = M <= 2 ? 1024 : M <= 3 ? 768 : M <= 5 ? 512 : 256;
   static constexpr int BINS = THREADS / G;                             // bins per pass: 512, 192, 128, 64, 32, 32, 32
 };
 
 int oiva_bins_per_pass(int M) {
-  switch (M) {
-    case 2: return OivaGeom<2>::BINS;
-    case 3: return OivaGeom<3>::BINS;
-    case 4: return OivaGeom<4>::BINS;
-    case 5: return OivaGeom<5>::BINS;
-    case 6: return OivaGeom<6>::BINS;
-    case 7: return OivaGeom<7>::BINS;
-    case 8: return OivaGeom<8>::BINS;
-  }
-  return -1;
+  int bins = -1;
+  if (M >= 2 && M <= 8) with_m(M, [&](auto m) { bins = OivaGeom<decltype(m)::value>::BINS; });
+  return bins;
 }
-
-__host__ __device__ inline long long oiva_align(long long n) { return (n + 15) & ~15LL; }
 
 // state: fail int [bins] | n int [bins] | W c128 [bins][M][M] | V c128 [bins][M][M][M]
 struct OivaWs { long long fail, n, W, V, total; };
 __host__ __device__ inline OivaWs oiva_ws(long long bins, int M) {
   OivaWs w;
   w.fail = 0;
-  w.n = oiva_align(bins * 4);
-  w.W = oiva_align(w.n + bins * 4);
+  w.n = align16(bins * 4);
+  w.W = align16(w.n + bins * 4);
   w.V = w.W + bins * M * M * 16;
   w.total = w.V + bins * M * M * M * 16;
   return w;
@@ -86,37 +77,13 @@ struct OivaArgs {
   double alpha, oma, floor;                                            // oma = 1 - alpha
 };
 
-__device__ __forceinline__ bool oiva_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-__device__ __forceinline__ double2 oiva_wide(float2 v) { return make_double2((double)v.x, (double)v.y); }
-__device__ __forceinline__ double2 oiva_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-// acc + a b
-__device__ __forceinline__ double2 oiva_fma(double2 acc, double2 a, double2 b) {
-  return make_double2(acc.x + (a.x * b.x - a.y * b.y), acc.y + (a.x * b.y + a.y * b.x));
-}
-// acc - a b
-__device__ __forceinline__ double2 oiva_fms(double2 acc, double2 a, double2 b) {
-  return make_double2(acc.x - (a.x * b.x - a.y * b.y), acc.y - (a.x * b.y + a.y * b.x));
-}
-// 1 / p (Smith): no intermediate leaves the range of p
-__device__ __forceinline__ double2 oiva_inv(double2 p) {
-  if (fabs(p.x) >= fabs(p.y)) {
-    const double r = p.y / p.x, d = p.x + p.y * r;
-    return make_double2(1.0 / d, -r / d);
-  }
-  const double r = p.x / p.y, d = p.x * r + p.y;
-  return make_double2(r / d, -1.0 / d);
-}
-template <int G> __device__ __forceinline__ double2 oiva_from(double2 v, int src) {
-  return make_double2(__shfl(v.x, src, G), __shfl(v.y, src, G));
-}
-
 // the frame's M samples of one bin (widened where they are used); true when one of them is not finite (they then count as 0)
 template <int M> __device__ __forceinline__ bool oiva_load(const float2* p, long long stride, float2 (&x)[M]) {
   bool bad = false;
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const float2 v = p[m * stride];
-    bad |= !(oiva_finite(v.x) && oiva_finite(v.y));
+    bad |= !(finite(v.x) && finite(v.y));
     x[m] = v;
   }
   if (bad) {
@@ -137,7 +104,7 @@ __device__ __forceinline__ bool oiva_solve(double2 (&A)[M], double2 (&rhs)[R], i
 #pragma unroll
   for (int c = 0; c < M; ++c) {
     double bm = fabs(A[c].x) + fabs(A[c].y);
-    if (!(bm <= OIVA_DBL_MAX)) bm = __builtin_inf();                   // a non-finite one counts as the largest: it is flagged
+    if (!(bm <= F64_MAX)) bm = __builtin_inf();                        // a non-finite one counts as the largest: it is flagged
     if (j >= M || pos < c) bm = -1.0;
     int bp = pos, bl = j;
 #pragma unroll
@@ -146,22 +113,22 @@ __device__ __forceinline__ bool oiva_solve(double2 (&A)[M], double2 (&rhs)[R], i
       const int op = __shfl_xor(bp, s, G), ol = __shfl_xor(bl, s, G);
       if (om > bm || (om == bm && op < bp)) { bm = om; bp = op; bl = ol; }
     }
-    bad |= !(bm > 0.0 && bm <= OIVA_DBL_MAX);
+    bad |= !(bm > 0.0 && bm <= F64_MAX);
     if (j == bl) pos = c;                                              // the rows at c and at bp change places
     else if (pos == c) pos = bp;
     pl[c] = bl;
-    const double2 ip = oiva_inv(oiva_from<G>(A[c], bl));
+    const double2 ip = c_inv(c_from<G>(A[c], bl));
     const bool below = j < M && pos > c;
-    const double2 l = oiva_mul(A[c], ip);
+    const double2 l = c_mul(A[c], ip);
 #pragma unroll
     for (int cc = c + 1; cc < M; ++cc) {
-      const double2 pr = oiva_from<G>(A[cc], bl);
-      if (below) A[cc] = oiva_fms(A[cc], l, pr);
+      const double2 pr = c_from<G>(A[cc], bl);
+      if (below) A[cc] = c_fms(A[cc], l, pr);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const double2 pr = oiva_from<G>(rhs[r], bl);
-      if (below) rhs[r] = oiva_fms(rhs[r], l, pr);
+      const double2 pr = c_from<G>(rhs[r], bl);
+      if (below) rhs[r] = c_fms(rhs[r], l, pr);
     }
     __builtin_amdgcn_sched_barrier(0);                                 // one column at a time, for the registers' sake
   }
@@ -169,11 +136,11 @@ __device__ __forceinline__ bool oiva_solve(double2 (&A)[M], double2 (&rhs)[R], i
   for (int c = M - 1; c >= 0; --c) {
     double2 xc[R];
     const bool above = j < M && pos < c;
-    const double2 ip = oiva_inv(A[c]);                                 // the pivot on the lane that holds row c; unused elsewhere
+    const double2 ip = c_inv(A[c]);                                 // the pivot on the lane that holds row c; unused elsewhere
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      xc[r] = oiva_from<G>(oiva_mul(rhs[r], ip), pl[c]);
-      if (above) rhs[r] = oiva_fms(rhs[r], A[c], xc[r]);
+      xc[r] = c_from<G>(c_mul(rhs[r], ip), pl[c]);
+      if (above) rhs[r] = c_fms(rhs[r], A[c], xc[r]);
       take(c, r, xc[r]);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -238,7 +205,7 @@ __global__ __launch_bounds__(OivaGeom<M>::THREADS) void oiva_k(const OivaArgs a)
       const double2* wr = Wg + ((long long)fc * M + jr) * M;
       double2 y = make_double2(0.0, 0.0);
 #pragma unroll
-      for (int m = 0; m < M; ++m) y = oiva_fma(y, wr[m], oiva_wide(x[m]));
+      for (int m = 0; m < M; ++m) y = c_fma(y, wr[m], c_wide(x[m]));
       if (act && row) part[j * OIVA_FMAX + f] = y.x * y.x + y.y * y.y;
     }
     __syncthreads();
@@ -284,15 +251,15 @@ __global__ __launch_bounds__(OivaGeom<M>::THREADS) void oiva_k(const OivaArgs a)
         for (int m = 0; m < M; ++m) {
 #pragma unroll
           for (int c = 0; c <= m; ++c) {                               // the lower triangle; the upper is its conjugate
-            const double2 o = vk[m * M + c], xm = oiva_wide(x[m]), xc = oiva_wide(x[c]);
+            const double2 o = vk[m * M + c], xm = c_wide(x[m]), xc = c_wide(x[c]);
             double2 v;
             v.x = alpha * o.x + g * (xm.x * xc.x + xm.y * xc.y);
             v.y = c == m ? 0.0 : alpha * o.y + g * (xm.y * xc.x - xm.x * xc.y);
-            Tr[c] = oiva_fma(Tr[c], Wr[m], v);
+            Tr[c] = c_fma(Tr[c], Wr[m], v);
             if (jk == m) Vr[c] = v;
             if (c < m) {
               const double2 vc = make_double2(v.x, -v.y);
-              Tr[m] = oiva_fma(Tr[m], Wr[c], vc);
+              Tr[m] = c_fma(Tr[m], Wr[c], vc);
               if (jk == c) Vr[m] = vc;
             }
           }
@@ -309,13 +276,13 @@ __global__ __launch_bounds__(OivaGeom<M>::THREADS) void oiva_k(const OivaArgs a)
         double2 q = make_double2(0.0, 0.0), uj = u[0];
 #pragma unroll
         for (int c = 0; c < M; ++c) {
-          q = oiva_fma(q, Vr[c], u[c]);
+          q = c_fma(q, Vr[c], u[c]);
           if (jbit >> c & 1u) uj = u[c];
         }
         double d = jk < M ? uj.x * q.x + uj.y * q.y : 0.0;
 #pragma unroll
         for (int s = 1; s < G; s <<= 1) d += __shfl_xor(d, s, G);      // the same bits on every lane of the group
-        const bool ok = !sbad && d > 0.0 && d <= OIVA_DBL_MAX;
+        const bool ok = !sbad && d > 0.0 && d <= F64_MAX;
         if (!ok && !bad) flags |= 2;
         if (ok && jk == k) {
           const double inv = 1.0 / sqrt(d);
@@ -331,7 +298,7 @@ __global__ __launch_bounds__(OivaGeom<M>::THREADS) void oiva_k(const OivaArgs a)
       // ---- 4. y = W x, A = W^-1: lane k takes column k of A as the rows of the solution come by
       double2 y = make_double2(0.0, 0.0);
 #pragma unroll
-      for (int m = 0; m < M; ++m) y = oiva_fma(y, Wr[m], oiva_wide(x[m]));
+      for (int m = 0; m < M; ++m) y = c_fma(y, Wr[m], c_wide(x[m]));
       double2 eye[M], acol[M];
       int ja = j;
       asm volatile("" : "+v"(ja));
@@ -348,13 +315,13 @@ __global__ __launch_bounds__(OivaGeom<M>::THREADS) void oiva_k(const OivaArgs a)
 #pragma unroll
         for (int c = 1; c < M; ++c)
           if (rbit >> c & 1u) ar = acol[c];
-        const double2 e = oiva_mul(ar, y);
+        const double2 e = c_mul(ar, y);
         const long long o = (long long)t * F + f;
         eb[j * TF + o] = zero ? make_float2(0.f, 0.f) : make_float2((float)e.x, (float)e.y);
         if (ib) {
 #pragma unroll
           for (int m = 0; m < M; ++m) {
-            const double2 v = oiva_mul(acol[m], y);
+            const double2 v = c_mul(acol[m], y);
             ib[((long long)j * M + m) * TF + o] = zero ? make_float2(0.f, 0.f) : make_float2((float)v.x, (float)v.y);
           }
         }
@@ -392,28 +359,15 @@ hipError_t launch_oiva(const void* mix, int B, int M, int T, int F, int model, i
   a.w = oiva_ws((long long)B * F, M);
   a.T = T; a.F = F; a.model = model; a.ref = ref_ch;
   a.alpha = alpha; a.oma = 1.0 - alpha; a.floor = floor;
-  switch (M) {
-    case 2: oiva_go<2>(a, B, s); break;
-    case 3: oiva_go<3>(a, B, s); break;
-    case 4: oiva_go<4>(a, B, s); break;
-    case 5: oiva_go<5>(a, B, s); break;
-    case 6: oiva_go<6>(a, B, s); break;
-    case 7: oiva_go<7>(a, B, s); break;
-    default: oiva_go<8>(a, B, s); break;
-  }
+  with_m(M, [&](auto m) { oiva_go<decltype(m)::value>(a, B, s); });
   return hipGetLastError();
 }
 
 hipError_t launch_oiva_debug(const void* state, int B, int M, int F, void* w, void* v, int* fail, int* n, hipStream_t s) {
   const long long bins = (long long)B * F;
   const OivaWs ws = oiva_ws(bins, M);
-  const char* base = reinterpret_cast<const char*>(state);
-  hipError_t e = hipSuccess;
-  if (w && (e = hipMemcpyAsync(w, base + ws.W, bins * M * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (v && (e = hipMemcpyAsync(v, base + ws.V, bins * M * M * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (fail && (e = hipMemcpyAsync(fail, base + ws.fail, bins * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (n && (e = hipMemcpyAsync(n, base + ws.n, bins * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  return e;
+  return copy_parts(state, {{w, ws.W, bins * M * M * 16}, {v, ws.V, bins * M * M * M * 16}, {fail, ws.fail, bins * 4},
+                            {n, ws.n, bins * 4}}, s);
 }
 
 }  // namespace mn

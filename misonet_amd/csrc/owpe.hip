@@ -30,12 +30,11 @@
 // A failing frame (a non-finite sample, or d not finite or not > 0) is passed through: x = y, P and G stay, zeros enter both
 // rings, fail |= 1, n advances.
 #include "kernels.hpp"
+#include "cplx.hpp"
 
 namespace mn {
 
 constexpr int OWPE_THREADS = 512, OWPE_WAVES = OWPE_THREADS / 64;
-
-__host__ __device__ inline long long owpe_align(long long n) { return (n + 15) & ~15LL; }
 
 // state: fail int [bins] | n int [bins] | pos int [bins] | pw f64 [bins][CTX] | ring c64 [bins][R][M] | G c128 [bins][N][M] |
 //        P c128 [bins][N][N]
@@ -44,13 +43,13 @@ __host__ __device__ inline OwpeWs owpe_ws(long long bins, int M, int taps, int d
   const long long N = (long long)M * taps, R = (long long)delay + taps - 1;
   OwpeWs w;
   w.fail = 0;
-  w.n = owpe_align(bins * 4);
-  w.pos = owpe_align(w.n + bins * 4);
-  w.pw = owpe_align(w.pos + bins * 4);
-  w.ring = owpe_align(w.pw + bins * OWPE_CTX * 8);
-  w.g = owpe_align(w.ring + bins * R * M * 8);
-  w.p = owpe_align(w.g + bins * N * M * 16);
-  w.total = owpe_align(w.p + bins * N * N * 16);
+  w.n = align16(bins * 4);
+  w.pos = align16(w.n + bins * 4);
+  w.pw = align16(w.pos + bins * 4);
+  w.ring = align16(w.pw + bins * OWPE_CTX * 8);
+  w.g = align16(w.ring + bins * R * M * 8);
+  w.p = align16(w.g + bins * N * M * 16);
+  w.total = align16(w.p + bins * N * N * 16);
   return w;
 }
 long long owpe_state_bytes(long long bins, int M, int taps, int delay) { return owpe_ws(bins, M, taps, delay).total; }
@@ -131,15 +130,6 @@ __device__ __forceinline__ void owpe_store(const OwpeState& s, int N, int M, int
   if (tid < OWPE_CTX) s.pw[tid] = pw[tid];
 }
 
-// the sum of v over the 64 lanes of a wave, the same bits on every lane
-__device__ __forceinline__ double owpe_wave_sum(double v) {
-#pragma unroll
-  for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k, 64);
-  return v;
-}
-
-__device__ __forceinline__ bool owpe_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
-
 // grid (bins), 64 threads: P = init I behind the memset
 __global__ __launch_bounds__(64) void owpe_reset_k(char* state, long long bins, int M, int taps, int delay, double init) {
   const OwpeWs w = owpe_ws(bins, M, taps, delay);
@@ -189,7 +179,7 @@ __global__ __launch_bounds__(OWPE_THREADS) void owpe_k(const OwpeArgs a) {
     const float2 yraw = ynext;
     if (tid < M) {
       yl[tid] = make_double2((double)yraw.x, (double)yraw.y);
-      badl[tid] = !(owpe_finite(yraw.x) && owpe_finite(yraw.y));
+      badl[tid] = !(finite(yraw.x) && finite(yraw.y));
       src += F;
       if (t + 1 < T) ynext = *src;
     }
@@ -220,8 +210,8 @@ __global__ __launch_bounds__(OWPE_THREADS) void owpe_k(const OwpeArgs a) {
           sr += p.x * z1.x - p.y * z1.y;
           si += p.x * z1.y + p.y * z1.x;
         }
-        sr = owpe_wave_sum(sr);
-        si = owpe_wave_sum(si);
+        sr = wave_sum(sr);
+        si = wave_sum(si);
         if (lane == 0) ul[i] = make_double2(sr, si);
       }
       if (wave < M) {                                                  // conj(G[j][m]) z[j]
@@ -236,8 +226,8 @@ __global__ __launch_bounds__(OWPE_THREADS) void owpe_k(const OwpeArgs a) {
           sr += g.x * z1.x + g.y * z1.y;
           si += g.x * z1.y - g.y * z1.x;
         }
-        sr = owpe_wave_sum(sr);
-        si = owpe_wave_sum(si);
+        sr = wave_sum(sr);
+        si = wave_sum(si);
         if (lane == 0) {
           const double2 y = yl[wave];
           xl[wave] = make_double2(y.x - sr, y.y - si);
@@ -249,7 +239,7 @@ __global__ __launch_bounds__(OWPE_THREADS) void owpe_k(const OwpeArgs a) {
       double zu = 0.0;
       if (j0 < N) { const double2 u = ul[j0]; zu = z0.x * u.x + z0.y * u.y; }
       if (j1 < N) { const double2 u = ul[j1]; zu += z1.x * u.x + z1.y * u.y; }
-      zu = owpe_wave_sum(zu);
+      zu = wave_sum(zu);
       int bad = 0;
       double p = 0.0;
 #pragma unroll 1
@@ -267,7 +257,7 @@ __global__ __launch_bounds__(OWPE_THREADS) void owpe_k(const OwpeArgs a) {
       const double alpha = fr.par[0], inv_alpha = fr.par[1];
       lam = fmax(lam / (double)(cnt + 1), fr.par[2]);
       const double d = alpha * lam + zu;
-      const bool failed = bad || !(d > 0.0 && d <= 1.7976931348623157e308);
+      const bool failed = bad || !(d > 0.0 && d <= F64_MAX);
 
       if (!failed) {
         const double invd = 1.0 / d;
@@ -349,13 +339,8 @@ hipError_t launch_owpe_debug(const void* state, int B, int M, int F, int taps, i
                              hipStream_t s) {
   const long long bins = (long long)B * F, N = (long long)M * taps;
   const OwpeWs w = owpe_ws(bins, M, taps, delay);
-  const char* base = reinterpret_cast<const char*>(state);
-  hipError_t e = hipSuccess;
-  if (g && (e = hipMemcpyAsync(g, base + w.g, bins * N * M * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (p && (e = hipMemcpyAsync(p, base + w.p, bins * N * N * 16, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (fail && (e = hipMemcpyAsync(fail, base + w.fail, bins * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  if (n && (e = hipMemcpyAsync(n, base + w.n, bins * 4, hipMemcpyDeviceToDevice, s)) != hipSuccess) return e;
-  return e;
+  return copy_parts(state, {{g, w.g, bins * N * M * 16}, {p, w.p, bins * N * N * 16}, {fail, w.fail, bins * 4}, {n, w.n, bins * 4}},
+                    s);
 }
 
 }  // namespace mn

@@ -14,14 +14,13 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import math
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .beamform import _dev_c64
+from ._online import OnlineStream, _dev_c64, check_real, default_device, make_callable, spec_of
 
 HOP = 64
 
@@ -45,16 +44,7 @@ class Dereverb:
     @classmethod
     def of(cls, spec) -> "Dereverb":
         """None or True (the defaults), a Dereverb, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown dereverb field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("dereverb must be None, True, a Dereverb or a dict of its fields")
+        return spec_of(cls, spec, "dereverb", "dereverb must be None, True, a Dereverb or a dict of its fields")
 
     def validate(self, num_mic: Optional[int] = None) -> "Dereverb":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
@@ -72,9 +62,7 @@ class Dereverb:
         if not 1 <= self.iterations <= 10:
             raise ValueError(f"dereverb iterations must be in [1, 10], got {self.iterations}")
         for name in ("diag_load", "power_floor"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or v < 0:
-                raise ValueError(f"dereverb {name} must be finite and >= 0, got {v!r}")
+            check_real("dereverb", name, getattr(self, name), positive=False)
         return self
 
     def c_opts(self) -> "_lib.WpeOpts":
@@ -103,16 +91,8 @@ class OnlineDereverb:
     @classmethod
     def of(cls, spec) -> "OnlineDereverb":
         """None or True (the defaults), an OnlineDereverb, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown online dereverb field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("online dereverb must be None, True, an OnlineDereverb or a dict of its fields")
+        return spec_of(cls, spec, "online dereverb",
+                       "online dereverb must be None, True, an OnlineDereverb or a dict of its fields")
 
     def validate(self, num_mic: Optional[int] = None) -> "OnlineDereverb":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
@@ -130,9 +110,7 @@ class OnlineDereverb:
         if not 0 <= self.context <= 16:
             raise ValueError(f"online dereverb context must be in [0, 16], got {self.context}")
         for name in ("alpha", "power_floor", "init"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not math.isfinite(v) or not v > 0:
-                raise ValueError(f"online dereverb {name} must be finite and > 0, got {v!r}")
+            check_real("online dereverb", name, getattr(self, name), positive=True)
         if self.alpha > 1:
             raise ValueError(f"online dereverb alpha must be in (0, 1], got {self.alpha!r}")
         return self
@@ -142,7 +120,7 @@ class OnlineDereverb:
                              float(self.init))
 
 
-class DereverbStream:
+class DereverbStream(OnlineStream):
     """The state of one stream of online WPE, on the device: ``batch`` recordings of ``num_mic`` microphones and ``num_bins``
     bins.  ``opts``: the fields of :class:`OnlineDereverb`.  The state is allocated once; a call allocates only its output."""
 
@@ -152,26 +130,18 @@ class DereverbStream:
         if self.num_bins < 1 or self.batch < 1:
             raise ValueError(f"num_bins and batch must be positive, got {num_bins}, {batch}")
         self._c = self.opts.c_opts()
-        n = _lib.lib().misonet_owpe_state_bytes(self.batch, self.num_mic, self.num_bins, C.byref(self._c))
-        if n < 0:
-            _lib.check(_lib.EINVAL)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
-        self.reset()
+        self._alloc(_lib.lib().misonet_owpe_state_bytes(self.batch, self.num_mic, self.num_bins, C.byref(self._c)), device)
 
-    def reset(self):
+    def _reset_call(self):
         """P = init I, G = 0, the rings empty, no frame seen, no flag"""
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_owpe_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins,
-                                                     C.byref(self._c), _lib.stream_ptr(self.device)))
-        return self
+        return _lib.lib().misonet_owpe_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, C.byref(self._c),
+                                             _lib.stream_ptr(self.device))
 
     def process_into(self, block: torch.Tensor, out: torch.Tensor):
         """block, out: complex64 [B, M, T, F] contiguous on the stream's device, not the same buffer.  One launch, nothing
         allocated: the call a HIP graph captures."""
         B, M, T, F = block.shape
-        if (B, M, F) != (self.batch, self.num_mic, self.num_bins):
-            raise ValueError(f"block {tuple(block.shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        self._same_geometry(block.shape)
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().misonet_owpe(block.data_ptr(), B, M, T, F, C.byref(self._c), out.data_ptr(),
                                                self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
@@ -180,26 +150,19 @@ class DereverbStream:
     def process(self, block):
         """The next T >= 1 frames of the stream: complex [B, M, T, F] -> complex64 of the same shape, on the device for device
         input and on the CPU for an ndarray.  The bits do not depend on how the stream is cut into calls."""
-        shape = np.shape(block)
-        if len(shape) != 4 or shape[2] < 1:
-            raise ValueError(f"block {tuple(shape)} must be [B, M, T, F] with T >= 1")
-        if (shape[0], shape[1], shape[3]) != (self.batch, self.num_mic, self.num_bins):
-            raise ValueError(f"block {tuple(shape)} must be [{self.batch}, {self.num_mic}, T, {self.num_bins}]")
+        self._check_block(np.shape(block))
         x, np_in = _dev_c64(block, self.device)
         out = self.process_into(x, torch.empty_like(x))
         return out.cpu() if np_in else out
 
-    def _debug(self, want=("G", "P", "fail", "n")):
-        """copies of the named parts of the state, on the device"""
+    def _parts(self):
         B, M, F, N = self.batch, self.num_mic, self.num_bins, self.num_mic * self.opts.taps
-        shapes = dict(G=((B, F, N, M), torch.complex128), P=((B, F, N, N), torch.complex128), fail=((B, F), torch.int32),
-                      n=((B, F), torch.int32))
-        d = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=self.device) for k in want}
-        ptr = lambda k: d[k].data_ptr() if k in d else None
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_owpe_debug(self.state.data_ptr(), B, M, F, C.byref(self._c), ptr("G"), ptr("P"),
-                                                     ptr("fail"), ptr("n"), _lib.stream_ptr(self.device)))
-        return d
+        return dict(G=((B, F, N, M), torch.complex128), P=((B, F, N, N), torch.complex128), fail=((B, F), torch.int32),
+                    n=((B, F), torch.int32))
+
+    def _debug_call(self, ptr):
+        return _lib.lib().misonet_owpe_debug(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, C.byref(self._c),
+                                             ptr("G"), ptr("P"), ptr("fail"), ptr("n"), _lib.stream_ptr(self.device))
 
     def filters(self):
         """the prediction filter G complex128 [B, F, M taps, M] as it stands, on the device"""
@@ -209,14 +172,7 @@ class DereverbStream:
         """the inverse correlation matrix P complex128 [B, F, M taps, M taps] as it stands, on the device"""
         return self._debug(("P",))["P"]
 
-    @property
-    def frames_seen(self) -> int:
-        return int(self._debug(("n",))["n"].max().item())
-
-    @property
-    def fail(self) -> torch.Tensor:
-        """int32 [B, F] on the device: bit 0 set once a frame of that bin was passed through"""
-        return self._debug(("fail",))["fail"]
+    fail = property(OnlineStream.fail.fget, doc="int32 [B, F] on the device: bit 0 set once a frame of that bin was passed through")
 
 
 def dereverb_online(mix, *, return_debug=False, device=None, **opts):
@@ -228,9 +184,7 @@ def dereverb_online(mix, *, return_debug=False, device=None, **opts):
     o = OnlineDereverb(**opts).validate(shape[1] if len(shape) == 4 else None)
     if len(shape) != 4 or min(shape) < 1:
         raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F], all positive")
-    if device is None:
-        device = mix.device if isinstance(mix, torch.Tensor) and mix.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    st = DereverbStream(shape[1], shape[3], shape[0], device=device, **dataclasses.asdict(o))
+    st = DereverbStream(shape[1], shape[3], shape[0], device=default_device(mix, device), **dataclasses.asdict(o))
     out = st.process(mix)
     return (out, st._debug()) if return_debug else out
 
@@ -373,12 +327,5 @@ def dereverb_wav(wav, fs=16000, *, device=None, srmr=False, ref_ch=0, fs_in=None
     return y.cpu().numpy() if np_in else y
 
 
-# ``misonet_amd.dereverb`` names both this module and the function above: once the module is imported the package attribute is
-# the module, so the module itself is made callable -- ``misonet_amd.dereverb(mix)`` works either way.
-class _CallableModule(type(np)):
-    def __call__(self, *args, **kwargs):
-        return dereverb(*args, **kwargs)
-
-
-import sys as _sys
-_sys.modules[__name__].__class__ = _CallableModule
+# ``misonet_amd.dereverb`` names both this module and the function above: ``misonet_amd.dereverb(mix)`` works either way
+make_callable(__name__)

@@ -23,6 +23,7 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._online import make_callable, spec_of
 
 KINDS = ("srp", "srp_phat", "music")         # the kinds of misonet_doa_opts, in its numbering
 MAX_SRC, MAX_CLASSES, MAX_CANDIDATES = 4, 8, 65536
@@ -94,18 +95,8 @@ class Localizer:
     @classmethod
     def of(cls, spec) -> "Localizer":
         """None or True (the defaults), a Localizer, a kind name, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(kind=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown localizer field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("localizer must be None, True, a Localizer, a kind name or a dict of its fields")
+        return spec_of(cls, spec, "localizer", "localizer must be None, True, a Localizer, a kind name or a dict of its fields",
+                       "kind")
 
     def validate(self, num_mic=None, num_cand=None, num_frames=None) -> "Localizer":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""
@@ -206,7 +197,7 @@ def localize(spec, tau, pts, fs, kind="srp_phat", num_src=1, block=0, hop=0, ban
     :class:`DoaResult` -- on the CPU (NumPy) when ``spec`` was an ndarray, device tensors otherwise; with ``return_debug`` also C
     complex128 [B, K, N, F, M, M], the per-bin matrices that were steered."""
     import torch
-    from .beamform import _dev_c64
+    from ._online import _dev_c64
     opt = (Localizer(kind=kind, num_src=num_src, block=block, hop=hop, band=band, bins=bins, min_sep=min_sep)
            if localizer is None else Localizer.of(localizer))
     shape = tuple(np.shape(spec))
@@ -329,13 +320,6 @@ def angular_error(dirs, peak, truth):
     return out
 
 
-# ``misonet_amd.localize`` names both this module and the function above: once the module is imported the package attribute is
-# the module, so the module itself is made callable -- ``misonet_amd.localize(spec, tau, pts, fs)`` works either way (as
-# ``misonet_amd.resample`` and ``misonet_amd.dereverb`` do).
-class _CallableModule(type(np)):
-    def __call__(self, *args, **kwargs):
-        return localize(*args, **kwargs)
-
-
-import sys as _sys
-_sys.modules[__name__].__class__ = _CallableModule
+# ``misonet_amd.localize`` names both this module and the function above: ``misonet_amd.localize(spec, tau, pts, fs)`` works
+# either way
+make_callable(__name__)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .beamform import _dev_c64
+from ._online import _dev_c64, spec_of
 
 PRIORS = ("bin", "guided")                   # the priors of misonet_cacgmm_opts, in its numbering
 MAX_ITERATIONS = 1000
@@ -45,18 +45,7 @@ class Refine:
     @classmethod
     def of(cls, spec) -> "Refine":
         """None or True (the defaults), a Refine, a prior name, or a dict of the fields above"""
-        if spec is None or spec is True:
-            return cls()
-        if isinstance(spec, cls):
-            return spec
-        if isinstance(spec, str):
-            return cls(prior=spec)
-        if isinstance(spec, dict):
-            unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
-            if unknown:
-                raise ValueError(f"unknown refine field(s) {sorted(unknown)}")
-            return cls(**spec)
-        raise TypeError("refine must be None, True, a Refine, a prior name or a dict of its fields")
+        return spec_of(cls, spec, "refine", "refine must be None, True, a Refine, a prior name or a dict of its fields", "prior")
 
     def validate(self, num_mic=None, num_spks=None) -> "Refine":
         """ValueError for a bad field -- before anything is launched (the library checks again: MISONET_EINVAL)"""

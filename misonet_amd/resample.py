@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._online import make_callable
 
 MAX_RATE = 1024            # max(p, q)
 MAX_N = 1 << 28            # samples per channel
@@ -356,13 +357,6 @@ class ResampleStream:
         return self.process(block, flush=True)
 
 
-# ``misonet_amd.resample`` names both this module and the function above: once the module is imported the package attribute is
-# the module, so the module itself is made callable -- ``misonet_amd.resample(x, 48000, 16000)`` works either way (as
-# ``misonet_amd.dereverb`` does).
-class _CallableModule(type(np)):
-    def __call__(self, *args, **kwargs):
-        return resample(*args, **kwargs)
-
-
-import sys as _sys
-_sys.modules[__name__].__class__ = _CallableModule
+# ``misonet_amd.resample`` names both this module and the function above: ``misonet_amd.resample(x, 48000, 16000)`` works either
+# way
+make_callable(__name__)

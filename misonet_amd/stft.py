@@ -18,6 +18,8 @@ from typing import List, Tuple
 import numpy as np
 import torch
 
+from ._online import default_device
+
 NPERSEG, HOP = 256, 64
 N_FREQ = NPERSEG // 2 + 1
 MAX_INT16 = 32767
@@ -95,10 +97,6 @@ def istft_int16(spec: torch.Tensor) -> torch.Tensor:
     return (istft(spec) * MAX_INT16).to(torch.int16)
 
 
-def _stream_device(device):
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-
-
 class StftStream:
     """The analysis half of the streaming front end, on the device (csrc/stft.hip ``stft_stream_k``, C ABI
     ``misonet_stft_stream``): ``batch`` recordings of ``num_mic`` microphones, fed in blocks of any length.
@@ -112,7 +110,7 @@ class StftStream:
         n = _lib.lib().misonet_stft_stream_state_bytes(self.batch, self.num_mic)
         if n < 0:
             raise ValueError(f"num_mic must be in [1, 64] and batch in [1, 65535], got {num_mic}, {batch}")
-        self.device = _stream_device(device)
+        self.device = default_device(None, device)
         self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
         self.reset()
 
@@ -198,7 +196,7 @@ class IstftStream:
         n = _lib.lib().misonet_istft_stream_state_bytes(self.rows)
         if n < 0:
             raise ValueError(f"rows must be in [1, 65535], got {rows}")
-        self.device = _stream_device(device)
+        self.device = default_device(None, device)
         self.state = torch.empty(int(n), dtype=torch.uint8, device=self.device)
         self.reset()
 
