@@ -1,5 +1,7 @@
-// The float64 complex helpers and the complex Jacobi eigen-solver of the beamformers: mvdr.hip (bf_solve, mvdr_scm_eig) and
-// jbf.hip (jbf_bin_k) include it.  The arithmetic and its order are guarded bit for bit by the beamformer tests and goldens.
+// The float64 complex helpers and the one complex Jacobi eigen-solver of the library.  Five kernels call it: mvdr_scm_eig (the
+// steering vector) and bf_solve (gev) of mvdr.hip, jbf_bin_k (lcmv) of jbf.hip, iva_pca_k (the PCA) of iva.hip and doa_cov_k
+// (MUSIC) of doa.hip.  The arithmetic and its order are guarded bit for bit by the beamformer tests and goldens; tests/jacobi_ref.py
+// restates it and tests/test_gpu_eig_edges.py faces every call site with degenerate spectra.
 #pragma once
 #include <hip/hip_runtime.h>
 

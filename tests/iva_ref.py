@@ -18,9 +18,11 @@ mix complex64 [B, F, M, T]; float64 after the loads; every recording on its own:
     4. A[f, m, k] = sum_t x_m conj(y_k) / sum_t |y_k|^2 (0 when the denominator is 0),  power_k = sum_{f, t} |A[f, ref_ch, k] y_k|^2,
        order = the S rows of largest power, descending (ties: the lower index),  images[s, f, m, t] = A[f, m, order_s] y_{order_s}
 
-The eigenvectors come from np.linalg.eigh here and from a cyclic Jacobi on the device: they agree where the K leading
-eigenvalues are distinct and apart from the rest, which the generators below provide and tests/test_iva.py asserts.  The device
-tests compare against this file; it also holds their input generators and the planted faults their bars have to reject
+The eigenvectors come from np.linalg.eigh here and from a cyclic Jacobi on the device; the generators below keep the K leading
+eigenvalues distinct and apart from the rest (tests/test_iva.py asserts it), so that the two agree vector by vector.  Repeated
+and near-repeated eigenvalues, ranks 1 .. M - 1, dead and identical microphones and graded spectra are the business of
+tests/jacobi_ref.py and tests/test_gpu_eig_edges.py, which judge the PCA by figures that do not depend on the basis chosen
+inside a degenerate subspace.  The device tests compare against this file; it also holds their input generators and the planted faults their bars have to reject
 (``fault=``).  Nothing here was compared against pyroomacoustics or torchiva.
 """
 import os
