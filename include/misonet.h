@@ -76,9 +76,9 @@ int misonet_net_commit(misonet_net* net);
  *   5 "f32w"    (ABI 430) mode 0 with the DenseBlock convs (model.py:437-482: 94 % of the MACs) in Winograd F(2x2, 3x3) form:
  *               float32 products and sums on the same matrix cores, 2.25 x fewer of them (conv_wino.hip); measured 2.0e-6
  *               per forward against the reference (mode 0: 2.6e-6), 1.47 x mode 0's speed.  Same planar float32 layout.
- * Modes 1, 2 ("bf16x3": 16-bit operands), 4 ("f16x3": 22-bit operands) and 6 ("bf16x6w", ABI 440: the Winograd form in mode 3's
- * arithmetic -- correct, 0.8 x mode 3's speed) are measured alternatives that are NOT product modes (ABI 450): only the experiment
- * build of the library (csrc: `make exp`) contains them, the product library answers MISONET_EINVAL.
+ * The numbers 1, 2 ("bf16x3": 16-bit operands), 4 ("f16x3": 22-bit operands) and 6 ("bf16x6w", ABI 440: the Winograd form in mode
+ * 3's arithmetic -- correct, 0.8 x mode 3's speed) belonged to alternatives that were measured and dropped (ABI 450; LAB.md): the
+ * library answers MISONET_EINVAL to them.
  * The choice is internal to the workspace (whose size depends on it: misonet_net_workspace_bytes must be asked again
  * after a change): inputs, outputs and taps are the same float32 / complex64 tensors in every mode. */
 int misonet_net_set_precision(misonet_net* net, int mode);
@@ -111,8 +111,8 @@ int misonet_net_buffer_plan(const misonet_net* net, int n_frames, int max_buffer
  * the encoder stack, then the decoder stack, in launch order (64 layers).  The choice is made once, when the net is created,
  * from the layer shapes alone; a forward launches exactly these kernels or fails (there is no fall-back).  kind[i]:
  * 0 DIRECT (conv3x3_mfma, exact f32), 1 W1D (the same kernel in 1-D Winograd form along T), 2 FEW (conv3x3_few), 3 WINO
- * (conv3x3_wino_f32), 4 X6_FIRST (conv3x3_x6_first), 5 X6 (conv3x3_bf16x6); experiment build only: 6 BF16, 7 BF16_DMA, 8 WINO6.
- * Returns the number of layers written (<= max_layers), or MISONET_EINVAL for a mode this build of the library does not have. */
+ * (conv3x3_wino_f32), 4 X6_FIRST (conv3x3_x6_first), 5 X6 (conv3x3_bf16x6).
+ * Returns the number of layers written (<= max_layers), or MISONET_EINVAL for a mode the library does not have. */
 int misonet_net_conv_plan(const misonet_net* net, int mode, int max_layers, int* kind);
 /* test/diagnostic taps: copy an intermediate activation of the LAST forward (still in ws_dev) out as float32
  * [B, C, T, F] in the reference's layout and normalisation.  Names: enc0_conv, enc0..enc6, tcn_out, dec0..dec6.

@@ -31,7 +31,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 int conv_cop(int Cout) { return Cout <= 32 ? 32 : 64; }
-int conv_rows(int sf, int tr2) { return tr2 ? 3 : sf * (FT - 1) + 3; }   // (the staged rows of the row-per-wave geometry: conv_bf16*.hip)
 // staged input rows of conv3x3_mfma: MODE 2 (stride-2 transposed) runs a PAIR of output rows per wave = 8 output rows per
 // workgroup, which need input rows m0 - 1 .. m0 + 3; MODE 3 (stride-1 transposed on ONE input row) stages that row only
 static int f32_rows(const ConvArgs& a) { return a.tr2 ? 5 : a.sf * (FT - 1) + 3; }
@@ -276,8 +275,8 @@ __device__ __forceinline__ void w1d_epilogue(const ConvArgs& a, f32x16 (&acc)[4]
 // of chunk k and are normalised and written to LDS after it, so HBM/L2 latency hides under the matrix work.
 // Staging roles are division-free: thread (q = tid & 31, ci = tid >> 5) owns frames t0+4q..t0+4q+3 of channel ci
 // for every staged row; threads < 16*NR own the two halo frames t0-1 / t0+128 of one (row, channel).
-// OCTP = 3 / 4: the instantiations that write the bf16x6 (hi | mid | lo bf16 parts) / f16x3 (hi | lo fp16 parts) oct layout:
-// the planar-input layers in front of a dense block when the network runs in one of those modes.
+// OCTP = 3: the instantiations that write the bf16x6 oct3 layout (hi | mid | lo bf16 parts): the planar-input layers in front of
+// a dense block when the network runs in that mode.
 // HALFK: the instantiation for a layer whose LAST K-chunk holds <= CK/2 channels (the 12-channel network input, model.py:44):
 // that chunk runs half the channel pairs.  It is a separate instantiation because a second fully unrolled chunk_mfma body
 // inside the common kernel costs every MODE 0 instantiation its register allocation (round 3: 74-241 spilled VGPRs, f32
@@ -603,14 +602,7 @@ hipError_t conv_init() {
   if ((e = set_lds_attr<1, 3>()) != hipSuccess) return e;
   if ((e = set_lds_attr<2, 3>()) != hipSuccess) return e;
   if ((e = set_lds_attr<1, 0, 3>()) != hipSuccess) return e;
-  if ((e = set_lds_attr<1, 2, 3>()) != hipSuccess) return e;
   if ((e = set_lds_attr<2, 0, 3>()) != hipSuccess) return e;
-#ifdef MISONET_EXPERIMENTS                         // (fp16-piece outputs: the f16x3 mode of the experiment build)
-  if ((e = set_lds_attr<1, 0, 4>()) != hipSuccess) return e;
-  if ((e = set_lds_attr<1, 2, 4>()) != hipSuccess) return e;
-  if ((e = set_lds_attr<2, 0, 4>()) != hipSuccess) return e;
-  if ((e = set_lds_attr<1, 0, 4, true>()) != hipSuccess) return e;
-#endif
   if ((e = set_lds_attr<1, 0, 0, true>()) != hipSuccess) return e;
   return set_lds_attr<1, 0, 3, true>();
 }
@@ -625,12 +617,6 @@ int device_cus() {
     cus[dev].store(c, std::memory_order_relaxed);
   }
   return c;
-}
-
-int conv_xcd_env() {
-  static int v = -1;
-  if (v < 0) v = exp_env("MISONET_XCD", 1);
-  return v;
 }
 
 // the kernel's MODE of a layer: 0 stride 1, 1 frequency stride 2, 2 stride-2 transposed, 3 the stride-1 transposed conv on the single
@@ -650,7 +636,7 @@ bool conv_w1d_ok(const ConvShape& s) {
 // XCD-aware order deals whole SAMPLES to the 8 XCDs (n % 8 == xcd): with a sample count that is not a multiple of 8 some
 // XCDs get nothing (B = 1: MISO3 runs 2 samples -> 6 of 8 XCDs idle, the first layer took 114 us instead of ~30); the
 // natural (t, f, n) grid is used then
-static int conv_xcd(int n_samples) { return (n_samples % 8 == 0) ? conv_xcd_env() : 0; }
+static int conv_xcd(int n_samples) { return n_samples % 8 == 0; }
 
 // f32w: the frequency-strided layers (and the first layer) in 1-D Winograd form along T (32-channel groups, 4-row tiles)
 hipError_t launch_conv_w1d(const ConvArgs& a_in, int n_samples, hipStream_t s) {
@@ -691,25 +677,15 @@ hipError_t launch_conv(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   const size_t lds = conv_lds_bytes(a.NR, a.cop, a.Cin);
 #define MN_LAUNCH(NCO, MODE) hipLaunchKernelGGL((conv3x3_mfma<NCO, MODE>), grid, dim3(256), lds, s, a)
 #define MN_LAUNCH3(NCO, MODE) hipLaunchKernelGGL((conv3x3_mfma<NCO, MODE, 3>), grid, dim3(256), lds, s, a)
-#define MN_LAUNCH4(NCO, MODE) hipLaunchKernelGGL((conv3x3_mfma<NCO, MODE, 4>), grid, dim3(256), lds, s, a)
   // last K-chunk at most half full (the network's first layer): the HALFK instantiations, 32-channel groups only
   const bool halfk = mode == 0 && a.cop == 32 && ((a.Cin - 1) % CK) < CK / 2;
 #define MN_LAUNCH_H(OCTP) hipLaunchKernelGGL((conv3x3_mfma<1, 0, OCTP, true>), grid, dim3(256), lds, s, a)
   if (a.out_oct) {
-    // planar float32 in, oct layout out (bf16x6: three bf16 pieces; f16x3: two fp16 pieces): only the layer shapes that
-    // occur in front of a dense block
-    if ((a.out_oct != 3 && a.out_oct != 4) || mode == 1 || (a.Cout & 7) || (a.out_c0 & 7) || (a.out_sstride & 7)) return hipErrorInvalidValue;
-    if (a.out_oct == 3) {
-      if (a.cop == 32) { if (halfk) MN_LAUNCH_H(3); else if (mode == 0) MN_LAUNCH3(1, 0); else MN_LAUNCH3(1, 2); }
-      else { if (mode == 0) MN_LAUNCH3(2, 0); else return hipErrorInvalidValue; }
-    } else {
-#ifdef MISONET_EXPERIMENTS
-      if (a.cop == 32) { if (halfk) MN_LAUNCH_H(4); else if (mode == 0) MN_LAUNCH4(1, 0); else MN_LAUNCH4(1, 2); }
-      else { if (mode == 0) MN_LAUNCH4(2, 0); else return hipErrorInvalidValue; }
-#else
-      return hipErrorInvalidValue;
-#endif
-    }
+    // planar float32 in, oct3 layout out (bf16x6: three bf16 pieces): a first layer that conv3x3_x6_first does not take -- every
+    // other buffer of that mode is oct3, so no strided or transposed layer reads a planar one
+    if (a.out_oct != 3 || mode != 0 || (a.Cout & 7) || (a.out_c0 & 7) || (a.out_sstride & 7)) return hipErrorInvalidValue;
+    if (a.cop == 32) { if (halfk) MN_LAUNCH_H(3); else MN_LAUNCH3(1, 0); }
+    else MN_LAUNCH3(2, 0);
   } else if (a.cop == 32) {
     if (halfk) MN_LAUNCH_H(0); else if (mode == 0) MN_LAUNCH(1, 0); else if (mode == 1) MN_LAUNCH(1, 1); else if (mode == 2) MN_LAUNCH(1, 2); else MN_LAUNCH(1, 3);
   } else {
@@ -717,7 +693,6 @@ hipError_t launch_conv(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   }
 #undef MN_LAUNCH
 #undef MN_LAUNCH3
-#undef MN_LAUNCH4
 #undef MN_LAUNCH_H
   return hipGetLastError();
 }

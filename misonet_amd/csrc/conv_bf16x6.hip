@@ -11,7 +11,7 @@
 //     rounding of the product, of which the fp32 FMA chain of the reference makes one per accumulation step;
 //   * 6 x 32 cycles per 32x32x16 block against 8 x 64 on v_mfma_f32_32x32x2_f32.
 //
-// Data flow = the DMA dataflow of conv_bf16_dma.hip with three parts instead of two:
+// Data flow:
 //   * activations travel in the "oct3" layout: per sample [hi | mid | lo] parts, each [c/8][f][Tp][8] bf16 (8 channels
 //     of one frame = one 16-byte unit = one lane's MFMA operand), values RAW (bias + ELU, no instance norm), written
 //     pre-split by the PRODUCER's epilogue;
@@ -19,14 +19,14 @@
 //     exactly into three bf16 pieces by conv_wprep6_k) plus the border-aware shift table of conv_epilogue.hpp;
 //   * staging is `buffer_load_dwordx4 ... lds` (LDS-DMA) issued by four producer waves of a persistent 8-wave workgroup
 //     (one per CU, XCD-local tile walk), two complete stages in LDS, one workgroup barrier per K-chunk.
-// What is different from the bf16x3 kernel besides the third part:
+// Against a kernel with 16-channel K-chunks and two-piece operands (the dropped bf16x3 mode, LAB.md):
 //   * a K-chunk is 8 input channels (one octet), so NO layer pads K (Cin = 24 / 72 / 120 cost 25 / 10 / 6 % there);
 //   * the 16-deep K of an MFMA is filled by PAIRING TIME TAPS: lanes 0-31 (k = 0..7) read the 8 channels at time tap
 //     kt = 0 and lanes 32-63 (k = 8..15) the same 8 channels at kt = 1 -- for the B operand that is just a per-lane LDS
 //     address (frame + half), for the A operand a [kt0 | kt1] weight image.  The odd tap kt = 2 is paired ACROSS PARTS:
 //     B = [x_h | x_m] with A = [w_h | w_h] gives hh + hm, A = [w_m | w_m] gives mh + mm, and B = [x_l | x_h] with
 //     A = [w_h | w_l] gives hl + lh.  27 MFMAs per (output row, chunk) = 9 taps x 6 terms x 8 channels / 16: no padding;
-//   * row reuse as in the bf16x3 kernel: an input fragment of staged row R serves the output rows f' with f' + kf = R,
+//   * row reuse: an input fragment of staged row R serves the output rows f' with f' + kf = R,
 //     and the 18 weight fragments of a phase stay in registers: 48 LDS fragment reads per 108 MFMAs;
 //   * tiles are 128 frames x 8 output rows for the stride-1 and transposed layers (10 resp. 5 staged rows; 152 KB for two
 //     stride-1 stages, 249 VGPRs with 128 accumulator registers) and x 4 rows for the stride-2 layers (9 staged rows)
@@ -36,7 +36,6 @@
 #include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 #include "conv_bf16_core.hpp"
-#include <stdio.h>
 #include <stdlib.h>
 
 namespace mn {
@@ -331,11 +330,11 @@ __device__ __forceinline__ void conv_epilogue_rm(const ConvArgs& a, const f32x16
 // arrive at it when chunk b has landed, consumers when they are done reading chunk b - 1; behind it the producers put
 // chunk b + 1 into the stage that chunk b - 1 occupied (the first chunk of the next tile is in flight during an epilogue).
 //
-// Where a chunk period goes (MISONET_TIMELINE=96 with MISONET_WS_DEBUG ablations, tools/gpu_x6_ablate.sh; Cin = 96,
-// F = 63, all 256 CUs busy).  4-ROW tiles (MISONET_X6_ROWS8=0): 4.6k cycles = 3.9k of MFMA phase (108 MFMAs at 36 instead
+// Where a chunk period goes (the timeline stamps with the a.dbg ablations, measured with the former experiment build: LAB.md; Cin = 96,
+// F = 63, all 256 CUs busy).  4-ROW tiles: 4.6k cycles = 3.9k of MFMA phase (108 MFMAs at 36 instead
 // of 32 cycles: operand fill behind the barrier + LDS waits) + 0.7k at the barrier waiting for the stage.  With the DMA
 // off the period is 4.1k, with the MFMAs off 4.1-4.4k: the LDS-DMA stream of a CU (51 KB per chunk) runs at 17 B/clk when
-// 8 CUs are active and at ~12 B/clk when all 256 are (tools/gpu_x6_slots.sh), i.e. that tile is CO-LIMITED by the matrix
+// 8 CUs are active and at ~12 B/clk when all 256 are, i.e. that tile is CO-LIMITED by the matrix
 // pipe and by bytes through the texture path.  8-ROW tiles: 76 KB per 216 MFMAs = 10 B/clk at the MFMA rate, the
 // producers have slack, the barrier wait is 0.17k and a chunk takes 7.6k cycles = 35 per MFMA (tile incl. epilogue:
 // 35.5 instead of 43.4).  (What the stamps showed as a 5.6-8.9k wait at the LAST barrier of a tile was the producers'
@@ -366,9 +365,8 @@ __device__ __forceinline__ void x6_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// OUT16: the output goes to a buffer of the f16x3 mode (two fp16 pieces per value): the f16x3 networks run the layers that
-// read UN-NORMALISED data -- the first dense block, whose input is the raw first-layer output (model.py:44, 401-406) -- in
-// this exact arithmetic (net.hip, buf_oct); its last conv hands over to the fp16 dataflow.
+// OUT16: always false.  It selected the hand-over to the fp16 layout of a dropped mode; the parameter stays because it is part of
+// the kernels' symbols, which tests/test_build_resources.py names.
 // NQ = 3: an instantiation for layers of <= 24 output channels (the F = 127 dense blocks: 29 % of the conv time): the tile
 // epilogue skips the fourth register quad of every row (channels 24-31 of the 32-row MFMA tile are padding).
 // G16: the instantiation for layers whose last output-channel group has 16 channels (Cout % 32 == 16): the tiles of that group
@@ -387,6 +385,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_bf16x6(const ConvArgs a, int n
   constexpr int SF = MODE == 1 ? 2 : 1;
   constexpr bool TR2 = MODE == 2;
   constexpr bool RM = MODE == 3;                               // rows in M (chunk_mfma6_rm): Cout <= 4, act = 0, planar output
+  static_assert(!OUT16, "no instantiation writes anything but oct3 or planar float32");
   static_assert(FTR == 4 || (FTR == 8 && MODE != 1), "8-row tiles: not for the stride-2 layers (17 staged rows)");
   static_assert(!RM || FTR == 8, "rows-in-M tiles are 8 output rows x 4 channels");
   static_assert(!G16 || (MODE == 0 && FTR == 8 && !OUT16 && NQ == 4), "two-rows-in-M groups: stride-1 8-row tiles, oct3 output");
@@ -419,11 +418,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_bf16x6(const ConvArgs a, int n
   const int T = a.T, Tp = a.Tp, Fin = a.Fin, Cin = a.Cin;
   const int nchunk = Cin >> 3;
 
-  // MISONET_TIMELINE=<Cin>: clock64() stamps of the third tile of workgroup 8 (consumer wave 0 -> slots 0.., producer
-  // wave 4 -> slots 32..); experiments only
+  // clock64() stamps of one tile of workgroup 8 (consumer wave 0 -> slots 0.., producer wave 4 -> slots 32..) for the timeline
+  // experiments: a.dbg_buf is nullptr in every launch now (kernels.hpp ConvArgs; LAB.md "Leftovers of the experiment build")
   unsigned long long* const tl = (a.dbg_buf && blockIdx.x == 8 && lane == 0 && (wave == 0 || wave == 4)) ? a.dbg_buf + (wave ? 32 : 0) : nullptr;
   int tl_i = 0;
-  const unsigned tl_tile = (a.dbg >> 16) ? (unsigned)(a.dbg >> 16) : 2u;   // MISONET_WS_DEBUG bits 16+: the tile to stamp
+  const unsigned tl_tile = (a.dbg >> 16) ? (unsigned)(a.dbg >> 16) : 2u;   // a.dbg bits 16+: the tile to stamp
   unsigned long long tl_base = 0;
 #define STAMP(TI) do { if (tl && ((TI) == tl_tile || ((TI) == tl_tile + 1 && tl_i == 2 * nchunk)) && tl_i < 28) { const unsigned long long c_ = clock64(); if (!tl_i) { tl_base = c_; tl[28] = wall_clock64(); } tl[tl_i++] = c_ - tl_base; tl[31] = tl_i; tl[29] = wall_clock64(); } } while (0)
 
@@ -736,15 +735,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_bf16x6(const ConvArgs a, int n
       } else if (!(a.dbg & 4)) {
         float* sr = s_red + (ti & 1) * (NU * 4 * COP * 2) + wave * (COP * 2);
         const float* sc = a.act ? s_ctr + (ti & 3) * COP : nullptr;
-        if constexpr (OUT16)
-          conv_epilogue_rows_nb<2, true>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
-        else if constexpr (G16) {
-          if (g16) conv_epilogue_rows_nb<3, false, 2, true>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
-          else conv_epilogue_rows_nb<3, false, NQ>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
+        if constexpr (G16) {
+          if (g16) conv_epilogue_rows_nb<2, true>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
+          else conv_epilogue_rows_nb<NQ>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
         } else if constexpr (U2)
-          conv_epilogue_rows_nb<3, false, NQ, false, true>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc, 4 * COP * 2);
+          conv_epilogue_rows_nb<NQ, false, true>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc, 4 * COP * 2);
         else
-          conv_epilogue_rows_nb<3, false, NQ, false, false, (BN ? VR : 0)>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
+          conv_epilogue_rows_nb<NQ, false, false, (BN ? VR : 0)>(a, acc, n, cg, f0, t0 + 32 * wave, lane, sr, FTR, sc);
       }
       ++ti;
       k += (unsigned)nslots;
@@ -857,7 +854,7 @@ __global__ __launch_bounds__(256, 3) void conv3x3_x6_first(const ConvArgs a, con
     if (wave_live) chunk_mfma6<NR, 1, false, FTR>(acc, s_x, s_w, wave, half, l31);
   }
   if (wave_live && !(a.dbg & 4))
-    conv_epilogue_rows_nb<3, false, NQ>(a, acc, n, 0, f0, t0 + 32 * wave, lane, s_z /*unused: act = 0*/, FTR, nullptr);
+    conv_epilogue_rows_nb<NQ>(a, acc, n, 0, f0, t0 + 32 * wave, lane, s_z /*unused: act = 0*/, FTR, nullptr);
 #endif
 }
 
@@ -870,8 +867,7 @@ bool conv_x6_first_ok(const ConvShape& s) {
 hipError_t launch_conv_x6_first(const ConvArgs& a_in, const void* wimg, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
   if (!conv_x6_first_ok(conv_shape(a, true)) || !wimg) return hipErrorInvalidValue;   // (the caller vouches for the network input)
-  static const int dbg = exp_env("MISONET_WS_DEBUG", 0);
-  a.dbg = dbg;
+  a.dbg = 0;
   const dim3 grid((a.T + TT - 1) / TT, (a.Fout + 3) / 4, n_samples);
   const size_t lds = (size_t)(3 * 6 * X6_TW + X6_WU) * 16 + (size_t)(2 * 4 * 32) * sizeof(float);
   if (a.Cout <= 24 && a.out_oct == 3) hipLaunchKernelGGL((conv3x3_x6_first<3>), grid, dim3(256), lds, s, a, reinterpret_cast<const u32x4_t*>(wimg));
@@ -994,13 +990,11 @@ hipError_t conv_bf16x6_init() {
   if ((e = x6_set_attr<1, 4>()) != hipSuccess) return e;
   if ((e = x6_set_attr<2, 8>()) != hipSuccess) return e;
   if ((e = x6_set_attr<3, 8>()) != hipSuccess) return e;
-  if ((e = x6_set_attr<0, 8, true>()) != hipSuccess) return e;
   if ((e = x6_set_attr<0, 8, false, 3>()) != hipSuccess) return e;
   if ((e = x6_set_attr<0, 8, false, 4, true>()) != hipSuccess) return e;
   if ((e = x6_set_attr<0, 8, false, 4, false, true>()) != hipSuccess) return e;
   if ((e = x6_set_attr<0, 4, false, 4, false, false, 1>()) != hipSuccess) return e;
   if ((e = x6_set_attr<0, 4, false, 4, false, false, 2>()) != hipSuccess) return e;
-  if ((e = x6_set_attr<0, 4, true>()) != hipSuccess) return e;
   return x6_set_attr<2, 4>();
 }
 
@@ -1026,36 +1020,19 @@ hipError_t launch_conv_wprep6(const ConvArgs& a, const float* wf, int n_samples,
 hipError_t launch_conv_bf16x6(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
   if (a.in_oct != 3 || !a.wps || a.cop != 32 || (a.Cin & 7) || (a.in_c0 & 7) || (a.in_sstride & 7)) return hipErrorInvalidValue;
-  if (a.out_oct && ((a.out_oct != 3 && a.out_oct != 4) || (a.Cout & 7) || (a.out_c0 & 7) || (a.out_sstride & 7))) return hipErrorInvalidValue;
-  if (a.out_oct == 4 && (a.tr2 || a.sf != 1 || a.descale != 1.f)) return hipErrorInvalidValue;   // stride-1 layers only (see OUT16)
-  // measurement hooks: read once per process (thread-safe function-local statics)
-  static const int dbg = exp_env("MISONET_WS_DEBUG", 0);
-  a.dbg = dbg;
+  if (a.out_oct && (a.out_oct != 3 || (a.Cout & 7) || (a.out_c0 & 7) || (a.out_sstride & 7))) return hipErrorInvalidValue;
+  a.dbg = 0;
   a.dbg_buf = nullptr;
-  static const int tl_env = exp_env("MISONET_TIMELINE", 0);
-  // MISONET_TIMELINE_F / _MODE: which layer (defaults: F = 63, stride 1); the timeline itself is a single-threaded experiment
-  static const int tl_f = exp_env("MISONET_TIMELINE_F", 63);
-  static const int tl_mode = exp_env("MISONET_TIMELINE_MODE", 0);
-  static int tl_done = 0;
-  static unsigned long long* tl_buf = nullptr;
-  const bool do_tl = tl_env && tl_done < 2 && (a.tr2 ? 2 : (a.sf == 2 ? 1 : 0)) == tl_mode && a.Cin == tl_env && a.Fout == tl_f && n_samples >= 8;
-  if (do_tl) {
-    if (!tl_buf && hipMalloc(reinterpret_cast<void**>(&tl_buf), 64 * 8) != hipSuccess) tl_buf = nullptr;
-    if (tl_buf) { (void)hipMemsetAsync(tl_buf, 0, 64 * 8, s); a.dbg_buf = tl_buf; }
-  }
   const int mode = a.tr2 ? 2 : (a.sf == 2 ? 1 : 0);
-  // tile geometry: 128 frames x 8 rows for the stride-1 layers with more than 4 rows (10 staged rows per 8 instead of
-  // 6 per 4 and one weight image per 216 instead of 108 MFMAs: 25 % fewer staged bytes per MFMA), else x 4 rows
-  static const int ft8 = exp_env("MISONET_X6_ROWS8", 3);   // bit 0: stride-1, bit 1: transposed
-  // rows-in-M tiles (MODE 3) for the raw 4-channel output layer (MISONET_X6_RM=0: the 32-channel tiles, for A/B runs)
-  static const int rm_env = exp_env("MISONET_X6_RM", 1);
-  const bool rows_in_m = rm_env && mode == 0 && a.padf == 2 && !a.act && !a.out_oct && a.Cout <= 4 && a.ncg == 1 && a.Fout > 4;
-  int ftr = rows_in_m ? 8 : ((mode != 1 && a.Fout > 4 && (ft8 & (mode == 0 ? 1 : 2))) ? 8 : 4);
+  // rows-in-M tiles (MODE 3) for the raw 4-channel output layer
+  const bool rows_in_m = mode == 0 && a.padf == 2 && !a.act && !a.out_oct && a.Cout <= 4 && a.ncg == 1 && a.Fout > 4;
+  // tile geometry: 128 frames x 8 rows for the stride-1 and transposed layers with more than 4 rows (10 staged rows per 8 instead
+  // of 6 per 4 and one weight image per 216 instead of 108 MFMAs: 25 % fewer staged bytes per MFMA), else x 4 rows
+  int ftr = rows_in_m ? 8 : ((mode != 1 && a.Fout > 4) ? 8 : 4);
   // "flexible" layers: stride-1, oct3 in and out, 4 < F <= 31.  Their 8-row kernel forms the statistics per half tile (U2), so
   // 4-row tiles give the same bits: the launch takes 4-row tiles when 8-row tiles would leave CUs without work (one utterance:
-  // 48 frame-tile columns x ceil(F / 8) row tiles).  MISONET_X6_FLEX=0: always 8-row tiles with one statistic unit (A/B runs).
-  static const int flex_env = exp_env("MISONET_X6_FLEX", 1);
-  const bool flex = flex_env && mode == 0 && ftr == 8 && !rows_in_m && a.out_oct == 3 && a.Fout <= 31 && (a.Cout & 31) == 0;
+  // 48 frame-tile columns x ceil(F / 8) row tiles).
+  const bool flex = mode == 0 && ftr == 8 && !rows_in_m && a.out_oct == 3 && a.Fout <= 31 && (a.Cout & 31) == 0;
   if (flex) {
     const int g_cus_ = device_cus();
     const long long ntx_ = (a.T + TT - 1) / TT;
@@ -1079,26 +1056,16 @@ hipError_t launch_conv_bf16x6(const ConvArgs& a_in, int n_samples, hipStream_t s
   int nslots = g_cus / 8;
   if (nslots < 1) nslots = 1;
   if (nslots > nk_max) nslots = (int)nk_max;
-  {
-    static const int cap = exp_env("MISONET_X6_SLOTS", 0);   // workgroups per XCD (experiments)
-    if (cap > 0 && nslots > cap) nslots = cap;
-  }
   const dim3 pgrid((unsigned)(8 * nslots), 1, 1);
-  // <= 24 output channels in one group: the epilogue variant that skips the padded register quad (MISONET_X6_Q3=0: A/B runs)
-  static const int q3_env = exp_env("MISONET_X6_Q3", 1);
-  const bool q3 = q3_env && a.ncg == 1 && a.Cout <= 24 && a.out_oct == 3;
-  // the F = 1 bottleneck pair on their reduced 4-row tiles (MISONET_X6_BN=0: the full tiles, for A/B runs)
-  static const int bn_env = exp_env("MISONET_X6_BN", 1);
-  const int bn = (!bn_env || mode != 0 || ftr != 4 || a.out_oct != 3 || a.nty != 1) ? 0
+  // <= 24 output channels in one group: the epilogue variant that skips the padded register quad
+  const bool q3 = a.ncg == 1 && a.Cout <= 24 && a.out_oct == 3;
+  // the F = 1 bottleneck pair on their reduced 4-row tiles
+  const int bn = (mode != 0 || ftr != 4 || a.out_oct != 3 || a.nty != 1) ? 0
                  : ((a.Fin == 3 && a.Fout == 1 && a.padf == 0) ? 1 : ((a.Fin == 1 && a.Fout == 3 && a.padf == 2) ? 2 : 0));
   // Cout % 32 == 16 (the 48-channel conv of the last decoder's dense block): its 16-channel group as two rows in M
-  // (MISONET_X6_G16=0: the padded 32-channel tiles, for A/B runs)
-  static const int g16_env = exp_env("MISONET_X6_G16", 1);
-  const bool g16 = g16_env && mode == 0 && ftr == 8 && a.out_oct == 3 && a.ncg >= 2 && (a.Cout & 31) == 16;
+  const bool g16 = mode == 0 && ftr == 8 && a.out_oct == 3 && a.ncg >= 2 && (a.Cout & 31) == 16;
   if (g16) hipLaunchKernelGGL((conv3x3_bf16x6<0, 8, false, 4, true>), pgrid, dim3(512), x6_lds_bytes(10, 8), s, a, nslots);
   else if (flex && ftr == 8) hipLaunchKernelGGL((conv3x3_bf16x6<0, 8, false, 4, false, true>), pgrid, dim3(512), x6_lds_bytes(10, 8, 2), s, a, nslots);
-  else if (a.out_oct == 4 && ftr == 8) hipLaunchKernelGGL((conv3x3_bf16x6<0, 8, true>), pgrid, dim3(512), x6_lds_bytes(10, 8), s, a, nslots);
-  else if (a.out_oct == 4) hipLaunchKernelGGL((conv3x3_bf16x6<0, 4, true>), pgrid, dim3(512), x6_lds_bytes(6, 4), s, a, nslots);
   else if (rows_in_m) hipLaunchKernelGGL((conv3x3_bf16x6<3, 8>), pgrid, dim3(512), x6_lds_bytes(10, 8), s, a, nslots);
   else if (mode == 0 && ftr == 8 && q3) hipLaunchKernelGGL((conv3x3_bf16x6<0, 8, false, 3>), pgrid, dim3(512), x6_lds_bytes(10, 8), s, a, nslots);
   else if (mode == 0 && ftr == 8) hipLaunchKernelGGL((conv3x3_bf16x6<0, 8>), pgrid, dim3(512), x6_lds_bytes(10, 8), s, a, nslots);
@@ -1108,19 +1075,6 @@ hipError_t launch_conv_bf16x6(const ConvArgs& a_in, int n_samples, hipStream_t s
   else if (mode == 1) hipLaunchKernelGGL((conv3x3_bf16x6<1, 4>), pgrid, dim3(512), x6_lds_bytes(9, 4), s, a, nslots);
   else if (ftr == 8) hipLaunchKernelGGL((conv3x3_bf16x6<2, 8>), pgrid, dim3(512), x6_lds_bytes(5, 8), s, a, nslots);
   else hipLaunchKernelGGL((conv3x3_bf16x6<2, 4>), pgrid, dim3(512), x6_lds_bytes(3, 4), s, a, nslots);
-  if (do_tl && tl_buf) {
-    unsigned long long h[64];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(h, tl_buf, sizeof(h), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[timeline-x6] Cin=%d Fout=%d n=%d consumer(%llu):", a.Cin, a.Fout, n_samples, h[31]);
-    for (unsigned long long i = 0; i < h[31] && i < 28; ++i) fprintf(stderr, " %llu", h[i]);
-    if (h[31] > 1 && h[29] > h[28])                                // shader cycles per 100 MHz wall-clock tick
-      fprintf(stderr, "\n[timeline-x6] shader clock over the stamped tile: %.3f GHz", 0.1 * (double)h[h[31] - 1] / (double)(h[29] - h[28]));
-    fprintf(stderr, "\n[timeline-x6] producer(%llu):", h[63]);
-    for (unsigned long long i = 0; i < h[63] && i < 28; ++i) fprintf(stderr, " %llu", h[32 + i]);
-    fprintf(stderr, "\n");
-    ++tl_done;
-  }
   return hipGetLastError();
 }
 

@@ -51,16 +51,6 @@ __device__ __forceinline__ f32x2_t elu_fast2(f32x2_t v) {
   return r;
 }
 
-// sum over the 32 lanes of each half-wave; the result is valid in lanes 16..31 (lower half) and 48..63 (upper half)
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));  // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false)); // row_bcast15 -> rows 1, 3
-  return v;
-}
-
 template <int CTRL>
 __device__ __forceinline__ float dpp_get(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
@@ -98,57 +88,8 @@ __device__ __forceinline__ float reduce16_halfwave(const float (&v)[16], int lan
   return r;
 }
 
-// In-register 4x4 transpose inside every lane quad (two xor butterflies over DPP quad_perm): on entry lane i of a quad
-// holds x[k] = value of channel k at frame 4q+i; on exit x[j] = value of channel i at frame 4q+j, i.e. 4 consecutive
-// frames of ONE channel -> one 16-byte store per lane instead of four 4-byte stores (the epilogue was store-issue bound).
-__device__ __forceinline__ void quad_transpose4(float (&x)[4], int lane) {
-  const bool o1 = (lane & 1) != 0, o2 = (lane & 2) != 0;
-  {  // xor 1: 2x2 blocks (x0,x1) and (x2,x3)
-    const float g0 = dpp_get<0xB1>(o1 ? x[0] : x[1]);
-    const float g1 = dpp_get<0xB1>(o1 ? x[2] : x[3]);
-    if (o1) { x[0] = g0; x[2] = g1; } else { x[1] = g0; x[3] = g1; }
-  }
-  {  // xor 2: 2x2 blocks (x0,x2) and (x1,x3)
-    const float g0 = dpp_get<0x4E>(o2 ? x[0] : x[2]);
-    const float g1 = dpp_get<0x4E>(o2 ? x[1] : x[3]);
-    if (o2) { x[0] = g0; x[1] = g1; } else { x[2] = g0; x[3] = g1; }
-  }
-}
-
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-// two values -> packed (hi, hi) and (lo, lo) bf16 pairs (x = hi + lo + O(2^-17 |x|)); element 0 in the low half
-__device__ __forceinline__ void split_pair_t(float x0, float x1, unsigned& hi, unsigned& lo) {
-  f32x2_t x = {x0, x1};
-  const bf16x2_t h = __builtin_convertvector(x, bf16x2_t);
-  const unsigned hu = __builtin_bit_cast(unsigned, h);
-  f32x2_t r;
-  r.x = x0 - __builtin_bit_cast(float, hu << 16);
-  r.y = x1 - __builtin_bit_cast(float, hu & 0xffff0000u);
-  const bf16x2_t l = __builtin_convertvector(r, bf16x2_t);
-  hi = hu;
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
-// fp16 flavour (f16x3 mode): x = hi + lo + O(2^-22 |x|) for |x| in fp16's normal range (11-bit pieces; the MFMA keeps
-// fp16 subnormals, tools/micro/mfma_f16_denorm.hip, so smaller values degrade gracefully to an absolute 2^-25)
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split_pair_h(float x0, float x1, unsigned& hi, unsigned& lo) {
-  f32x2_t x = {x0, x1};
-  const f16x2_t h = __builtin_convertvector(x, f16x2_t);
-  f32x2_t r;
-  r.x = x0 - (float)h.x;
-  r.y = x1 - (float)h.y;
-  const f16x2_t l = __builtin_convertvector(r, f16x2_t);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-template <bool F16>
-__device__ __forceinline__ void split_pair_x(float x0, float x1, unsigned& hi, unsigned& lo) {
-  if (F16) split_pair_h(x0, x1, hi, lo);
-  else split_pair_t(x0, x1, hi, lo);
-}
-
 // two values -> three packed bf16 pairs with x = hi + mid + lo EXACTLY (bf16x6 mode): hi = rne(x), mid = rne(x - hi),
 // lo = x - hi - mid.  x - hi is exact in float32 and has at most 16 significant bits, x - hi - mid at most 8, so the
 // last conversion does not round (float32 has 24 significant bits = 3 x 8); bf16 has the exponent range of float32.
@@ -194,12 +135,12 @@ __device__ __forceinline__ void split3_quad_t(float x0, float x1, float x2, floa
 }
 
 // One accumulator row (16 values of one lane: channel (i&3) + 8*(i>>2) + 4*half of a 32-channel group at one frame)
-// -> NP bf16 parts in the oct layout: part p of octet pair k is one 16-byte store per lane (lanes 0-31 store octet 2k,
+// -> the three bf16 parts of the oct3 layout: part p of octet pair k is one 16-byte store per lane (lanes 0-31 store octet 2k,
 // lanes 32-63 octet 2k + 1, after a half-wave swap).  rs[p]: descriptor of part p; vo: byte offset of (row, frame) in
 // the plane of octet (group base + half); ok0 / ok1: this lane's octet of pair 0 / 1 exists and its frame is valid.
 // NQ: register quads (= octets of this half-wave pair) that can hold channels: 3 for a group of <= 24 output channels, whose
 // fourth octet is not split (it does not exist: its lanes' stores fall outside num_records).
-template <int NP, bool F16 = false, int NQ = 4>
+template <int NQ = 4>
 __device__ __forceinline__ void store_oct_row(const float (&v)[16], const __amdgpu_buffer_rsrc_t (&rs)[3], unsigned vo,
                                               unsigned P16, bool ok0, bool ok1) {
   unsigned P[3][4][2];
@@ -208,17 +149,14 @@ __device__ __forceinline__ void store_oct_row(const float (&v)[16], const __amdg
     if (o >= NQ) {
 #pragma unroll
       for (int p = 0; p < 3; ++p) { P[p][o][0] = 0u; P[p][o][1] = 0u; }
-    } else if (NP == 3) {
-      split3_quad_t(v[4 * o + 0], v[4 * o + 1], v[4 * o + 2], v[4 * o + 3], P[0][o], P[1][o], P[2][o]);
     } else {
-      split_pair_x<F16>(v[4 * o + 0], v[4 * o + 1], P[0][o][0], P[1][o][0]);
-      split_pair_x<F16>(v[4 * o + 2], v[4 * o + 3], P[0][o][1], P[1][o][1]);
+      split3_quad_t(v[4 * o + 0], v[4 * o + 1], v[4 * o + 2], v[4 * o + 3], P[0][o], P[1][o], P[2][o]);
     }
   }
 #pragma unroll
   for (int k = 0; k < (NQ <= 2 ? 1 : 2); ++k) {          // NQ <= 2 (a 16-channel group): octets 2, 3 do not exist
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
+    for (int p = 0; p < 3; ++p) {
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
         auto rr = __builtin_amdgcn_permlane32_swap(P[p][2 * k][d], P[p][2 * k + 1][d], false, false);
@@ -227,7 +165,7 @@ __device__ __forceinline__ void store_oct_row(const float (&v)[16], const __amdg
     }
     if (k == 0 ? ok0 : ok1) {
 #pragma unroll
-      for (int p = 0; p < NP; ++p) {
+      for (int p = 0; p < 3; ++p) {
         const u32x4_t u = {P[p][2 * k][0], P[p][2 * k][1], P[p][2 * k + 1][0], P[p][2 * k + 1][1]};
         // non-temporal: a layer's output (2-10 GB) is read back by the NEXT launch, long after it left the L2; streaming
         // stores measured +0.3 % on the whole step (A/B on one box: 144.6 -> 145.1 utt/s; sc0 / sc0+sc1: +-0)
@@ -250,8 +188,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_e(unsigned long long
 // s_b4:   optional LDS table [COP][4] = (bL, bC, bR, bL + bC + bR) of THIS wave's row: the bias plus the folded
 //         instance-norm shift of the DMA dataflow, split by time tap so that the first / last frame of the utterance
 //         (whose left / right taps fall into the zero padding) can drop their share.
-// OCTP:   0, or the number of bf16 parts of the oct-layout output path to compile: 2 (bf16x3: hi | lo) or 3 (bf16x6:
-//         hi | mid | lo) or 4 (f16x3: fp16 hi | lo); a.out_oct selects it at run time.
+// OCTP:   3: the oct3 output path (bf16x6: hi | mid | lo bf16 parts) is compiled in and a.out_oct selects it at run time; 0: planar only.
 // CENTRE: the activation is STORED centred, y = ELU(conv + bias) - ELU(bias) (ELU(bias) is the activation at the exact
 //         mean of the pre-activation when the inputs are instance-normalised), and the statistics are those of y.  Every
 //         consumer of an activated conv output instance-normalises it, and the instance norm does not see a per-channel
@@ -276,9 +213,7 @@ __device__ __forceinline__ void conv_epilogue_impl(const ConvArgs& a, f32x16_t (
   const bool t_edge = s_b4 && (t0 == 0 || t0 + NSEG * 32 >= T);             // uniform: tile holds frame 0 or T - 1
 
   if (OCTP && a.out_oct) {
-    // ---- oct layout: per (octet, frame) one 16-byte unit in each of the OCTP parts ----
-    constexpr int NP = OCTP == 3 ? 3 : 2;                                   // OCTP 2: bf16 hi|lo, 3: bf16 hi|mid|lo, 4: fp16 hi|lo
-    constexpr bool F16 = OCTP == 4;
+    // ---- oct3 layout: per (octet, frame) one 16-byte unit in each of the three parts ----
     const unsigned P16 = (unsigned)a.Fout * (unsigned)Tp * 16u;             // bytes per octet plane
     const unsigned long long pa = reinterpret_cast<unsigned long long>(a.out) + (unsigned long long)n * a.out_bstride * 4ull +
                                   (unsigned long long)(a.out_c0 >> 3) * P16;
@@ -287,7 +222,7 @@ __device__ __forceinline__ void conv_epilogue_impl(const ConvArgs& a, f32x16_t (
     __amdgpu_buffer_rsrc_t rs[3];
     rs[0] = make_rsrc_e(pa, nrec);
     rs[1] = make_rsrc_e(pa + part_b, nrec);
-    rs[2] = NP == 3 ? make_rsrc_e(pa + 2 * part_b, nrec) : rs[1];
+    rs[2] = make_rsrc_e(pa + 2 * part_b, nrec);
     unsigned voff[NSEG];
 #pragma unroll
     for (int s = 0; s < NSEG; ++s)
@@ -330,7 +265,7 @@ __device__ __forceinline__ void conv_epilogue_impl(const ConvArgs& a, f32x16_t (
         // this lane's octet (2k + half of group j) exists and its frame is inside the utterance
         const bool ok0 = !(a.dbg & 8) && (unmasked || (tm[s] && (cbase + j * 32 + (0 + half) * 8 < a.Cout)));
         const bool ok1 = !(a.dbg & 8) && (unmasked || (tm[s] && (cbase + j * 32 + (2 + half) * 8 < a.Cout)));
-        store_oct_row<NP, F16>(v, rs, voff[s] + (unsigned)((cbase >> 3) + j * 4) * P16, P16, ok0, ok1);
+        store_oct_row(v, rs, voff[s] + (unsigned)((cbase >> 3) + j * 4) * P16, P16, ok0, ok1);
       }
       if (ACT && !(a.dbg & 16)) {
         const float x1 = reduce16_halfwave(s1, lane);
@@ -434,146 +369,17 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16_t (&acc)
   else conv_epilogue_impl<NCO, NSEG, OCTP, false, CENTRE>(a, acc, n, cg, f, t0, row_ok, lane, s_red, s_bias, s_b4);
 }
 
-// Tile epilogue of the row-reuse mapping (conv_bf16_dma.hip): one wave owns 32 frames [tw, tw + 32) of FOUR output rows
-// f0 .. f0 + 3 (acc[r] = 32 channels x 32 frames of row f0 + r).
-//   s_bs / s_bl / s_br: LDS tables [4 rows][2 half-waves][16] in ACCUMULATOR order (entry i of half h = channel
-//   (i&3) + 8*(i>>2) + 4*h): bias + folded instance-norm shift summed over all in-range taps (s_bs), and the shares of
-//   the left / right time tap (s_bl, s_br) that the first / last frame of the utterance must drop (their tap falls into
-//   the zero padding).  A lane reads its 16 values with four 16-byte broadcast reads.
-//   s_red: [32][2] floats of THIS wave (the caller adds the waves of a tile).  Output layout by a.out_oct.
-// Channels >= Cout need no masking in the statistics: their weights and bias are zero-padded, so the value is
-// ELU(0) = 0 exactly.  Everything that depends only on the wave (tile edges) selects between a branch-free fast path
-// and a masked path; nothing is decided per element.
-template <bool MASKED, bool ACT, bool F16 = false>
-__device__ __forceinline__ void conv_epilogue_rows_impl(const ConvArgs& a, f32x16_t (&acc)[4], int cg, int f0, int tw,
-                                                        int lane, const float* s_bs, const float* s_bl,
-                                                        const float* s_br, const __amdgpu_buffer_rsrc_t rs_h,
-                                                        const __amdgpu_buffer_rsrc_t rs_l, float (&s1)[16],
-                                                        float (&s2)[16]) {
-  constexpr int COP = 32;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int T = a.T, Tp = a.Tp;
-  const int cbase = cg * COP;
-  const int t = tw + l31;
-  const unsigned P16 = (unsigned)a.Fout * (unsigned)Tp * 16u;               // bytes per octet plane (oct)
-  const unsigned P4 = (unsigned)a.Fout * (unsigned)Tp * 4u;                 // bytes per channel plane (planar)
-  const bool oct_ok0 = cbase + (0 + half) * 8 < a.Cout;                      // this lane's octet of pair 0 / 1 exists
-  const bool oct_ok1 = cbase + (2 + half) * 8 < a.Cout;
-  const float e0 = (MASKED && t == 0) ? 1.f : 0.f;                          // drop the left / right tap share
-  const float e1 = (MASKED && t == T - 1) ? 1.f : 0.f;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int f = f0 + r;
-    const bool ok = !MASKED || ((f < a.Fout) && (t < T));                   // this lane's (row, frame) exists
-    const float m = ok ? 1.f : 0.f;
-    float bs[16];
-    {
-      const float4* pb = reinterpret_cast<const float4*>(s_bs + (r * 2 + half) * 16);
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 q = pb[q4];
-        bs[4 * q4 + 0] = q.x; bs[4 * q4 + 1] = q.y; bs[4 * q4 + 2] = q.z; bs[4 * q4 + 3] = q.w;
-      }
-      if (MASKED) {
-        const float4* pl = reinterpret_cast<const float4*>(s_bl + (r * 2 + half) * 16);
-        const float4* pr = reinterpret_cast<const float4*>(s_br + (r * 2 + half) * 16);
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const float4 ql = pl[q4], qr = pr[q4];
-          bs[4 * q4 + 0] -= e0 * ql.x + e1 * qr.x; bs[4 * q4 + 1] -= e0 * ql.y + e1 * qr.y;
-          bs[4 * q4 + 2] -= e0 * ql.z + e1 * qr.z; bs[4 * q4 + 3] -= e0 * ql.w + e1 * qr.w;
-        }
-      }
-    }
-    float v[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      float x = (F16 ? acc[r][i] * a.descale : acc[r][i]) + bs[i];       // f16x3: the weights carry a power-of-two scale
-      if (ACT) x = elu_fast(x) - elu_fast(a.bias[cbase + (i & 3) + 8 * (i >> 2) + 4 * half]);   // stored centred
-      v[i] = x;
-      const float vm = MASKED ? x * m : x;
-      s1[i] += vm;
-      s2[i] = fmaf(vm, vm, s2[i]);
-    }
-    if (a.dbg & 8) continue;
-    if (a.out_oct) {
-      const __amdgpu_buffer_rsrc_t rs2[3] = {rs_h, rs_l, rs_l};
-      const unsigned vo = (unsigned)(f * Tp + t) * 16u + (unsigned)half * P16 + (unsigned)(cbase >> 3) * P16;
-      store_oct_row<2, F16>(v, rs2, vo, P16, ok && oct_ok0, ok && oct_ok1);
-    } else {
-      // planar: channel (i&3) + 8*(i>>2) + 4*half of the group; out-of-range channels fall outside num_records,
-      // missing frames / rows get an out-of-range offset (4-byte stores: dropped by the hardware)
-      const unsigned vo = ok ? ((unsigned)(f * Tp + t) * 4u + (unsigned)(4 * half) * P4) : 0x80000000u;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int kr = (i & 3) + 8 * (i >> 2);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[i]), rs_h, vo + (unsigned)(cbase + kr) * P4, 0, 0);
-      }
-    }
-  }
-}
-
-template <bool F16 = false>
-__device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, f32x16_t (&acc)[4], int n, int cg, int f0, int tw,
-                                                   int lane, float* s_red, const float* s_bs, const float* s_bl,
-                                                   const float* s_br) {
-  const int half = lane >> 5;
-  const int T = a.T, Tp = a.Tp;
-  // uniform per wave: all 32 frames and 4 rows exist and none of the frames is the first / last of the utterance
-  const bool fast = (tw > 0) && (tw + 32 < T) && (f0 + 4 <= a.Fout);
-  float s1[16], s2[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
-
-  // descriptors
-  const unsigned P16 = (unsigned)a.Fout * (unsigned)Tp * 16u;
-  const unsigned P4 = (unsigned)a.Fout * (unsigned)Tp * 4u;
-  unsigned long long pa, pb;
-  unsigned nrec;
-  if (a.out_oct) {
-    pa = reinterpret_cast<unsigned long long>(a.out) + (unsigned long long)n * a.out_bstride * 4ull +
-         (unsigned long long)(a.out_c0 >> 3) * P16;
-    pb = pa + (unsigned long long)(a.out_sstride >> 3) * P16;
-    nrec = (unsigned)(a.Cout >> 3) * P16;
-  } else {
-    pa = reinterpret_cast<unsigned long long>(a.out + (long long)n * a.out_bstride + (long long)a.out_c0 * a.Fout * Tp);
-    pb = pa;
-    nrec = (unsigned)a.Cout * P4;
-  }
-  // NB: readfirstlane returns int -- unsigned temporaries, or the OR below sign-extends the low half into the high half
-  const unsigned pa_lo = __builtin_amdgcn_readfirstlane((unsigned)pa), pa_hi = __builtin_amdgcn_readfirstlane((unsigned)(pa >> 32));
-  const unsigned pb_lo = __builtin_amdgcn_readfirstlane((unsigned)pb), pb_hi = __builtin_amdgcn_readfirstlane((unsigned)(pb >> 32));
-  const int nrec_s = __builtin_amdgcn_readfirstlane((int)nrec);
-  const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(((unsigned long long)pa_hi << 32) | pa_lo), 0, nrec_s, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_l = __builtin_amdgcn_make_buffer_rsrc(
-      reinterpret_cast<void*>(((unsigned long long)pb_hi << 32) | pb_lo), 0, nrec_s, 0x00020000);
-
-  if (a.act) {
-    if (fast) conv_epilogue_rows_impl<false, true, F16>(a, acc, cg, f0, tw, lane, s_bs, s_bl, s_br, rs_h, rs_l, s1, s2);
-    else conv_epilogue_rows_impl<true, true, F16>(a, acc, cg, f0, tw, lane, s_bs, s_bl, s_br, rs_h, rs_l, s1, s2);
-  } else {
-    conv_epilogue_rows_impl<true, false, F16>(a, acc, cg, f0, tw, lane, s_bs, s_bl, s_br, rs_h, rs_l, s1, s2);
-  }
-
-  if (a.act && !(a.dbg & 16)) {
-    const float x1 = reduce16_halfwave(s1, lane);
-    const float x2 = reduce16_halfwave(s2, lane);
-    if ((lane & 16) == 0) {
-      const int q = lane & 15;
-      const int co_l = (q & 3) + 8 * (q >> 2) + 4 * half;
-      s_red[co_l * 2 + 0] = x1;
-      s_red[co_l * 2 + 1] = x2;
-    }
-  }
-}
-
 // ---- epilogue of the persistent DMA kernel: the accumulators were INITIALISED with the bias (conv_acc_init_rows), so
 // the element work is ELU + statistics only, written with 2-wide vector types so that the multiplies, adds and FMAs
 // become v_pk_*_f32 (two elements per instruction).
 typedef float f32x2_e __attribute__((ext_vector_type(2)));
 
-// acc[r][i] = bias + folded shift of (row f0 + r, channel of accumulator slot i); tables as in conv_epilogue_rows.
+// One wave owns 32 frames [tw, tw + 32) of NROW output rows f0 .. (acc[r] = 32 channels x 32 frames of row f0 + r).
+// acc[r][i] = bias + folded shift of (row f0 + r, channel of accumulator slot i).
+//   s_bs / s_bl / s_br: LDS tables [NROW rows][2 half-waves][16] in ACCUMULATOR order (entry i of half h = channel
+//   (i&3) + 8*(i>>2) + 4*h): bias + folded instance-norm shift summed over all in-range taps (s_bs), and the shares of
+//   the left / right time tap (s_bl, s_br) that the first / last frame of the utterance must drop (their tap falls into
+//   the zero padding).  A lane reads its 16 values with four 16-byte broadcast reads.
 template <int NROW>
 __device__ __forceinline__ void conv_acc_init_rows(f32x16_t (&acc)[NROW], int tw, int T, int lane, const float* s_bs,
                                                    const float* s_bl, const float* s_br) {
@@ -646,8 +452,7 @@ __device__ __forceinline__ void conv_acc_init_rows_rm2(f32x16_t (&acc)[NROW], in
 // RM2: the accumulators are those of a two-rows-in-M tile (row r = registers 8 (r & 1) .. + 7 of accumulator r >> 1: the first
 // NROW / 2 of the array are in use; NQ must be 2).
 // RBEG, REND: the rows of the tile this call handles (all of them by default; the two-unit statistics call it per half).
-template <bool MASKED, bool ACT, int NP, bool F16 = false, int NROW = 4, int NQ = 4, bool RM2 = false, int RBEG = 0,
-          int REND = NROW>
+template <bool MASKED, bool ACT, int NROW = 4, int NQ = 4, bool RM2 = false, int RBEG = 0, int REND = NROW>
 __device__ __forceinline__ void conv_epilogue_rows_nb_impl(const ConvArgs& a, f32x16_t (&acc)[NROW], int cg, int f0, int tw,
                                                            int lane, const __amdgpu_buffer_rsrc_t (&rs)[3],
                                                            f32x2_e (&s1)[8], f32x2_e (&s2)[8], int rows,
@@ -693,7 +498,6 @@ __device__ __forceinline__ void conv_epilogue_rows_nb_impl(const ConvArgs& a, f3
       const int ar = r >> AR_SHIFT, ab = RM2 ? 8 * (r & 1) : 0;            // compile-time after unrolling
       f32x2_e xa = {acc[ar][ab + 4 * i4], acc[ar][ab + 4 * i4 + 1]};
       f32x2_e xb = {acc[ar][ab + 4 * i4 + 2], acc[ar][ab + 4 * i4 + 3]};
-      if (F16) { xa = xa * f32x2_e{a.descale, a.descale}; xb = xb * f32x2_e{a.descale, a.descale}; }
       if (ACT) {                                   // compile-time: a run-time test here becomes a branch per pair and
                                                    // serialises the exp latency of the eight pairs
         f32x2_e ea = xa * kl2e;
@@ -724,8 +528,8 @@ __device__ __forceinline__ void conv_epilogue_rows_nb_impl(const ConvArgs& a, f3
       const unsigned vo = (unsigned)(f * Tp + t) * 16u + (unsigned)half * P16 + (unsigned)(cbase >> 3) * P16;
       // un-masked tiles: no predicates at all -- octets past Cout lie outside num_records of the part descriptors and
       // are dropped by the hardware (the masked path still needs the per-lane frame / row test)
-      if (MASKED) store_oct_row<NP, F16, NQ>(v, rs, vo, P16, ok && oct_ok0, ok && oct_ok1);
-      else store_oct_row<NP, F16, NQ>(v, rs, vo, P16, true, true);
+      if (MASKED) store_oct_row<NQ>(v, rs, vo, P16, ok && oct_ok0, ok && oct_ok1);
+      else store_oct_row<NQ>(v, rs, vo, P16, true, true);
     } else {
       const unsigned vo = ok ? ((unsigned)(f * Tp + t) * 4u + (unsigned)(4 * half) * P4) : 0x80000000u;
 #pragma unroll
@@ -737,7 +541,9 @@ __device__ __forceinline__ void conv_epilogue_rows_nb_impl(const ConvArgs& a, f3
   }
 }
 
-// rows: output rows of the tile (4, or 2 for the stride-2 layers of the bf16x3 kernel); NP: bf16 parts of an oct output
+// rows: output rows of the tile that this call handles (NROW by default).  s_red: [32][2] floats of THIS wave (the caller adds
+// the waves of a tile).  Output layout by a.out_oct (oct3 or planar).  Channels >= Cout need no masking in the statistics: their
+// weights and bias are zero-padded, so the value is ELU(0) = 0 exactly.
 // U2 ("two statistic units", NROW = 8): the float partial sums of the statistics are formed per HALF tile (rows 0-3, rows 4-7:
 // two reduce-scatters, two partial sets at s_red and s_red + u2_stride) and each half is added to the exact accumulator on
 // its own.  An 8-row tile then contributes EXACTLY what two 4-row tiles at the same rows contribute, so a layer may run on
@@ -746,7 +552,7 @@ __device__ __forceinline__ void conv_epilogue_rows_nb_impl(const ConvArgs& a, f3
 // second pair of reductions costs ~1.5 % of a tile.
 // VR: output rows of the tile that can exist at all (default: all): rows >= VR are not post-processed (the F = 1 bottleneck
 // layers run 4-row tiles of which 1 / 3 rows exist).
-template <int NP = 2, bool F16 = false, int NQ = 4, bool RM2 = false, bool U2 = false, int VR = 0, int NROW>
+template <int NQ = 4, bool RM2 = false, bool U2 = false, int VR = 0, int NROW>
 __device__ __forceinline__ void conv_epilogue_rows_nb(const ConvArgs& a, f32x16_t (&acc)[NROW], int n, int cg, int f0, int tw,
                                                       int lane, float* s_red, int rows = NROW, const float* s_ctr = nullptr,
                                                       int u2_stride = 0) {
@@ -768,7 +574,7 @@ __device__ __forceinline__ void conv_epilogue_rows_nb(const ConvArgs& a, f32x16_
     const unsigned nrec = (unsigned)(a.Cout >> 3) * P16;
     rs[0] = make_rsrc_e(pa, nrec);
     rs[1] = make_rsrc_e(pa + part_b, nrec);
-    rs[2] = NP == 3 ? make_rsrc_e(pa + 2 * part_b, nrec) : rs[1];
+    rs[2] = make_rsrc_e(pa + 2 * part_b, nrec);
   } else {
     rs[0] = make_rsrc_e(reinterpret_cast<unsigned long long>(a.out + (long long)n * a.out_bstride + (long long)a.out_c0 * a.Fout * Tp),
                         (unsigned)a.Cout * P4);
@@ -792,123 +598,23 @@ __device__ __forceinline__ void conv_epilogue_rows_nb(const ConvArgs& a, f32x16_
   static_assert(!(U2 && VR > 0), "either two statistic units or a reduced row count");
 
   if (a.act) {
-    if (fast) conv_epilogue_rows_nb_impl<false, true, NP, F16, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
-    else conv_epilogue_rows_nb_impl<true, true, NP, F16, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
+    if (fast) conv_epilogue_rows_nb_impl<false, true, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
+    else conv_epilogue_rows_nb_impl<true, true, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
   } else {
-    conv_epilogue_rows_nb_impl<true, false, NP, F16, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows);
+    conv_epilogue_rows_nb_impl<true, false, NROW, NQ, RM2, 0, RMID>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows);
   }
   if (a.act && !(a.dbg & 16)) reduce_to(s_red);
   if constexpr (U2) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) { s1[i] = f32x2_e{0.f, 0.f}; s2[i] = f32x2_e{0.f, 0.f}; }
     if (a.act) {
-      if (fast) conv_epilogue_rows_nb_impl<false, true, NP, F16, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
-      else conv_epilogue_rows_nb_impl<true, true, NP, F16, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
+      if (fast) conv_epilogue_rows_nb_impl<false, true, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
+      else conv_epilogue_rows_nb_impl<true, true, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows, s_ctr);
     } else {
-      conv_epilogue_rows_nb_impl<true, false, NP, F16, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows);
+      conv_epilogue_rows_nb_impl<true, false, NROW, NQ, RM2, RMID, NROW>(a, acc, cg, f0, tw, lane, rs, s1, s2, rows);
     }
     if (a.act && !(a.dbg & 16)) reduce_to(s_red + u2_stride);
   }
-}
-
-
-// ---- deferred tile epilogue of the persistent kernel: ELU + statistics + bf16 split + stores of the PREVIOUS tile, cut
-// into pieces that run between the MFMAs of the current tile (one call per MFMA step, st compile-time after unrolling).
-// Row ROW of the previous tile is handled during K-chunk ROW of the current one:
-//   pieces 0-7  : element pair q: ELU in place, statistics
-//   piece  8/10 : bf16 hi/lo split of elements 0-7 / 8-15      piece 9/11: half-wave swaps + the two 16-byte stores
-//   pieces 12-14 (row 3 only): the two reduce-scatters of the tile's statistics, partials to LDS
-// State lives in the caller: prev (accumulators of the previous tile, bias included), s1/s2, per-row mask pm and store
-// offset pvo, and the pack registers PH/PL.  Everything is branch-free except the store predicates.
-struct EpiState {
-  f32x2_e s1[8], s2[8];
-  float pmt;                // 1 if this lane's frame of the previous tile exists (t < T), else 0
-  unsigned pvo0;            // byte offset of (row 0, this lane's frame) in the octet plane of the lane's half-wave
-  int prows;                // rows of the previous tile that exist (uniform: min(4, Fout - f0), 0 = no previous tile)
-  unsigned prow_b;          // bytes per output row (Tp * 16)
-  unsigned PH[2][2], PL[2][2];
-  bool okk0, okk1;          // this lane's octet of pair 0 / 1 exists (Cout)
-  float dsc;                // f16x3: 2^-k of the layer's weight scale (1 otherwise)
-  const float* ctr;         // LDS: ELU(bias) per channel in accumulator order [2 half-waves][16]; rows are stored centred
-};
-
-template <int ROW, int NSTEP, bool F16 = false>
-__device__ __forceinline__ void conv_epi_step(int st, f32x16_t (&prev)[4], EpiState& e, const __amdgpu_buffer_rsrc_t rs_h,
-                                              const __amdgpu_buffer_rsrc_t rs_l, unsigned P16, int lane) {
-  constexpr int NPIECE = 12;
-  constexpr int PP = (NPIECE + NSTEP - 1) / NSTEP;
-  const f32x2_e kl2e = {1.4426950408889634f, 1.4426950408889634f};
-  const f32x2_e kone = {1.f, 1.f};
-#pragma unroll
-  for (int pi = 0; pi < PP; ++pi) {
-    const int q = st * PP + pi;
-    if (q < 8) {
-      f32x2_e x = {prev[ROW][2 * q], prev[ROW][2 * q + 1]};
-      if (F16) x = x * f32x2_e{e.dsc, e.dsc};
-      f32x2_e ex = x * kl2e;
-      ex.x = __builtin_amdgcn_exp2f(ex.x);
-      ex.y = __builtin_amdgcn_exp2f(ex.y);
-      ex = ex - kone;
-      x.x = x.x > 0.f ? x.x : ex.x;
-      x.y = x.y > 0.f ? x.y : ex.y;
-      {                                                  // stored centred (conv_epilogue_impl's CENTRE note)
-        const float2 c2 = reinterpret_cast<const float2*>(e.ctr + (lane >> 5) * 16)[q];
-        x.x -= c2.x; x.y -= c2.y;
-      }
-      prev[ROW][2 * q] = x.x; prev[ROW][2 * q + 1] = x.y;
-      const float mr = (ROW < e.prows) ? e.pmt : 0.f;
-      const f32x2_e m2 = {mr, mr};
-      const f32x2_e vm = x * m2;
-      e.s1[q] = e.s1[q] + vm;
-      // explicit FMAs: with contraction left to the compiler the interleaved and the flush instantiation of this piece
-      // rounded differently, which made a tile's sum of squares depend on whether it was the last tile of its workgroup
-      e.s2[q].x = fmaf(vm.x, vm.x, e.s2[q].x);
-      e.s2[q].y = fmaf(vm.y, vm.y, e.s2[q].y);
-    } else if (q == 8 || q == 10) {
-      const int b = (q == 8) ? 0 : 8;
-      split_pair_x<F16>(prev[ROW][b + 0], prev[ROW][b + 1], e.PH[0][0], e.PL[0][0]);
-      split_pair_x<F16>(prev[ROW][b + 2], prev[ROW][b + 3], e.PH[0][1], e.PL[0][1]);
-      split_pair_x<F16>(prev[ROW][b + 4], prev[ROW][b + 5], e.PH[1][0], e.PL[1][0]);
-      split_pair_x<F16>(prev[ROW][b + 6], prev[ROW][b + 7], e.PH[1][1], e.PL[1][1]);
-    } else if (q == 9 || q == 11) {
-      const int k = (q == 9) ? 0 : 1;
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        auto rh = __builtin_amdgcn_permlane32_swap(e.PH[0][d], e.PH[1][d], false, false);
-        e.PH[0][d] = rh[0]; e.PH[1][d] = rh[1];
-        auto rl = __builtin_amdgcn_permlane32_swap(e.PL[0][d], e.PL[1][d], false, false);
-        e.PL[0][d] = rl[0]; e.PL[1][d] = rl[1];
-      }
-      const u32x4_t uh = {e.PH[0][0], e.PH[0][1], e.PH[1][0], e.PH[1][1]};
-      const u32x4_t ul = {e.PL[0][0], e.PL[0][1], e.PL[1][0], e.PL[1][1]};
-      if (ROW < e.prows && e.pmt != 0.f && (k == 0 ? e.okk0 : e.okk1)) {
-        const unsigned off = e.pvo0 + (unsigned)ROW * e.prow_b + (unsigned)(2 * k) * P16;
-        __builtin_amdgcn_raw_buffer_store_b128(uh, rs_h, off, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(ul, rs_l, off, 0, 0);
-      }
-    }
-  }
-}
-
-// statistics of the previous tile: reduce-scatter over the half-waves, partials to LDS, accumulators reset.  Called once
-// per tile right after the MFMA loop of K-chunk 3 (not interleaved: its temporaries would not fit the register budget).
-__device__ __forceinline__ void conv_epi_reduce(EpiState& e, float* s_red_w, int lane) {
-  float f1[16], f2[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    f1[2 * i] = e.s1[i].x; f1[2 * i + 1] = e.s1[i].y;
-    f2[2 * i] = e.s2[i].x; f2[2 * i + 1] = e.s2[i].y;
-  }
-  const float x1 = reduce16_halfwave(f1, lane);
-  const float x2 = reduce16_halfwave(f2, lane);
-  if ((lane & 16) == 0) {
-    const int qq = lane & 15;
-    const int co_l = (qq & 3) + 8 * (qq >> 2) + 4 * (lane >> 5);
-    s_red_w[co_l * 2 + 0] = x1;
-    s_red_w[co_l * 2 + 1] = x2;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) { e.s1[i] = f32x2_e{0.f, 0.f}; e.s2[i] = f32x2_e{0.f, 0.f}; }
 }
 
 

@@ -226,7 +226,7 @@ hipError_t launch_conv_few(const ConvArgs& a_in, int n_samples, hipStream_t s) {
   ConvArgs a = a_in;
   if (!conv_few_ok(conv_shape(a)) || !a.wsm) return hipErrorInvalidValue;
   a.ncg = 1;
-  const dim3 grid = conv_grid(a, n_samples, TT, FW_RT, (n_samples % 8 == 0) ? conv_xcd_env() : 0);
+  const dim3 grid = conv_grid(a, n_samples, TT, FW_RT, n_samples % 8 == 0);
   const size_t lds = few_lds_bytes(a.Cin);
   if (a.Cout == 2) hipLaunchKernelGGL(conv3x3_few<2>, grid, dim3(256), lds, s, a);
   else hipLaunchKernelGGL(conv3x3_few<4>, grid, dim3(256), lds, s, a);

@@ -8,22 +8,13 @@
 #pragma once
 #include "kernels.hpp"
 
-// Product arithmetic modes: 0 "f32", 3 "bf16x6", 5 "f32w".  The measured alternatives that earn nothing (1 / 2 "bf16x3": 16-bit
-// operands, 4 "f16x3": 22-bit operands, 6 "bf16x6w": correct but slower than mode 3 -- DESIGN 3.4) exist only in the experiment
-// build (`make exp`): their kernels (conv_bf16.hip, conv_bf16_dma.hip, conv_wino6.hip), weight images and dispatch are compiled
-// out of the product library, which answers MISONET_EINVAL to them.
-#ifdef MISONET_EXPERIMENTS
-#define MN_ALT_MODES 1
-#else
-#define MN_ALT_MODES 0
-#endif
+// Arithmetic modes: 0 "f32", 3 "bf16x6", 5 "f32w".  The numbers 1, 2 (bf16x3), 4 (f16x3) and 6 (bf16x6w) belonged to alternatives that
+// were measured and dropped (LAB.md, "Leftovers of the experiment build"); the library answers MISONET_EINVAL to them.
 
 namespace mn {
 
-constexpr int CONV_NMODES = 7;                    // precision modes 0 ... 6 (ConvL::kind[] is indexed by the mode)
-inline bool conv_mode_built(int mode) {
-  return mode == 0 || mode == 3 || mode == 5 || (MN_ALT_MODES && mode >= 1 && mode < CONV_NMODES);
-}
+constexpr int CONV_NMODES = 6;                    // ConvL::kind[] is indexed by the mode number, 0 ... 5
+inline bool conv_mode_built(int mode) { return mode == 0 || mode == 3 || mode == 5; }
 
 // the values are ABI: misonet_net_conv_plan (include/misonet.h) reports them
 enum class ConvKind : int {
@@ -33,11 +24,8 @@ enum class ConvKind : int {
   WINO,          // conv3x3_wino_f32 (conv_wino.hip): Winograd F(2x2, 3x3), the DenseBlock convs in f32w
   X6_FIRST,      // conv3x3_x6_first (conv_bf16x6.hip): the network's first layer, planar float32 in, oct3 out
   X6,            // conv_wprep6_k + conv3x3_bf16x6 (conv_bf16x6.hip): oct3 in
-  BF16,          // conv3x3_bf16x3 (conv_bf16.hip): planar in, split-bf16 operands            (experiment build)
-  BF16_DMA,      // conv_wprep_k + conv3x3_bf16x3_dma* (conv_bf16_dma.hip): oct / fp16-oct in (experiment build)
-  WINO6,         // conv3x3_wino_x6 (conv_wino6.hip): Winograd in the bf16x6 arithmetic       (experiment build)
 };
-constexpr int CONV_NKIND = 9;
+constexpr int CONV_NKIND = 6;
 
 // What a kernel's eligibility depends on: static per layer and mode, nothing of T, N or a pointer.
 struct ConvShape {
@@ -58,20 +46,14 @@ bool conv_w1d_ok(const ConvShape& s);        // conv.hip
 bool conv_few_ok(const ConvShape& s);        // conv_few.hip
 bool conv_wino_ok(const ConvShape& s);       // conv_wino.hip
 bool conv_x6_first_ok(const ConvShape& s);   // conv_bf16x6.hip
-bool conv_wino6_ok(const ConvShape& s);      // conv_wino6.hip (experiment build)
 
 // The kernel of a layer in precision mode `mode`; s.in_oct / s.out_oct are that mode's layouts of the layer's buffers.  First match
-// wins.  The oct layouts leave no choice (only their own kernels read them); planar-input layers of the modes >= 3 that are not the
-// first layer run on the exact f32 kernel.
+// wins.  The oct3 layout leaves no choice (only its own kernel reads it); a first layer of bf16x6 that conv3x3_x6_first does not take
+// runs on the exact f32 kernel.
 inline ConvKind conv_select(const ConvShape& s, int mode) {
-  const bool planar = mode == 0 || mode == 5 || mode == 6;      // every buffer planar float32
+  const bool planar = mode == 0 || mode == 5;                   // every buffer planar float32
   if (s.out_oct == 3 && conv_x6_first_ok(s)) return ConvKind::X6_FIRST;
   if (s.in_oct == 3) return ConvKind::X6;
-#if MN_ALT_MODES
-  if (s.in_oct) return ConvKind::BF16_DMA;
-  if (mode == 1 || mode == 2) return ConvKind::BF16;
-  if (mode == 6 && conv_wino6_ok(s)) return ConvKind::WINO6;
-#endif
   if (planar && conv_few_ok(s)) return ConvKind::FEW;
   if (mode == 5 && conv_wino_ok(s)) return ConvKind::WINO;
   if (mode == 5 && conv_w1d_ok(s)) return ConvKind::W1D;
@@ -90,6 +72,5 @@ long long conv_image_floats(ConvKind k, const ConvWeights& c);
 void conv_image_pack(ConvKind k, const ConvWeights& c, float* img);
 // WINO: the image of the last 16 output channels of a layer with Cout % 32 == 16 (ConvArgs::ww16) lies behind the main image
 inline long long conv_wino_ww16_at(int Cin, int Cout) { return (long long)((Cout + 31) / 32) * (Cin / 8) * 16 * 8 * 32; }
-float conv_f16_wscale(const float* W, long long n);   // f16x3: power of two that brings max |W| of a layer to [32, 64)
 
 }  // namespace mn

@@ -51,43 +51,6 @@ static inline float bf16_to_f32(unsigned short h) {
   return f;
 }
 
-// f16x3: a static power of two per layer brings max |W| to [32, 64): with rstd in [2^-6, 2^9] the folded weights
-// W * rstd stay below fp16's 65504 and the lo pieces of all but negligible weights stay normal
-float conv_f16_wscale(const float* W, long long n) {
-  float m = 0.f;
-  for (long long i = 0; i < n; ++i) m = std::max(m, fabsf(W[i]));
-  return (m > 0.f && std::isfinite(m)) ? exp2f(floorf(log2f(64.f / m))) : 1.f;
-}
-
-// BF16, conv3x3_bf16x3: [cg of 32 co][chunk of 16 ci][hi|lo][tap][octet h][32][8] bf16 (PIECES);
-// BF16_DMA, conv_wprep_k's source: the same order in float32, one value where the pieces have two
-static void bf16_image(const ConvWeights& c, float* dst, bool pieces) {
-  const int nchunk = (c.Cin + 15) / 16;
-  const int COP = 32;                       // the bf16x3 kernels always work on 32-channel output groups
-  const int ncg16 = (c.Cout + 31) / 32;
-  unsigned short* w = reinterpret_cast<unsigned short*>(dst);
-  const long long img = 9LL * 2 * COP * 8;
-  for (int cg = 0; cg < ncg16; ++cg)
-    for (int kc = 0; kc < nchunk; ++kc)
-      for (int kt = 0; kt < 3; ++kt)
-        for (int kf = 0; kf < 3; ++kf)
-          for (int h = 0; h < 2; ++h)
-            for (int col = 0; col < COP; ++col)
-              for (int e = 0; e < 8; ++e) {
-                const int ci = kc * 16 + 8 * h + e, co = cg * COP + col;
-                const float v = (ci < c.Cin && co < c.Cout) ? tap(c, co, ci, kt, kf) : 0.f;
-                const long long idx = ((((long long)(kt * 3 + kf)) * 2 + h) * COP + col) * 8 + e;
-                if (pieces) {
-                  const unsigned short hi = f32_to_bf16_rne(v);
-                  const long long base = ((long long)cg * nchunk + kc) * 2 * img;
-                  w[base + idx] = hi;
-                  w[base + img + idx] = f32_to_bf16_rne(v - bf16_to_f32(hi));
-                } else {
-                  dst[((long long)cg * nchunk + kc) * img + idx] = v;
-                }
-              }
-}
-
 // X6, conv_wprep6_k's source: float32 weights [cg][chunk of 8 ci][tap = kt*3 + kf][32 co][8 ci], zero padded
 static void wf6_image(const ConvWeights& c, float* wf) {
   const int nchunk = (c.Cin + 7) / 8;
@@ -191,36 +154,9 @@ static void wino_image16(const ConvWeights& c, int co0, float* img) {
       }
 }
 
-// WINO6, conv3x3_wino_x6: the three-piece bf16 form of the bf16x6w mode: per (cg of 32 co, K-step of 16 ci) four QUARTERS
-// (position rows xi), each [nu][piece h | m | l][lane = co + 32 * (ci / 8 % 2)][8 bf16 = channels 8 * (ci / 8 % 2) .. + 7]: one
-// lane's MFMA A operand is 16 consecutive bytes.  U in double, rounded once to float32, then split exactly at fixed bit
-// positions (top 8 / next 8 / last 8 significant bits).  No sign flips (the kernel's transform is the plain B^T d B).
-static void wino6_image(const ConvWeights& c, float* dst) {
-  const int nk = (c.Cin + 15) / 16, ncg = (c.Cout + 31) / 32;
-  unsigned short* img = reinterpret_cast<unsigned short*>(dst);
-  auto top16 = [](float x) { unsigned u; memcpy(&u, &x, 4); return (unsigned short)(u >> 16); };
-  for (int cg = 0; cg < ncg; ++cg)
-    for (int kk = 0; kk < nk; ++kk)
-      for (int pos = 0; pos < 16; ++pos)
-        for (int col = 0; col < 32; ++col)
-          for (int cil = 0; cil < 16; ++cil) {
-            const int ci = kk * 16 + cil, co = cg * 32 + col, xi = pos >> 2, nu = pos & 3;
-            const float v = (float)((co < c.Cout && ci < c.Cin) ? wino_u(c, co, ci, xi, nu) : 0.0);
-            unsigned vb; memcpy(&vb, &v, 4);
-            unsigned hb = vb & 0xffff0000u, wb = vb & 0xffffff00u;
-            float h, w; memcpy(&h, &hb, 4); memcpy(&w, &wb, 4);
-            const float m = w - h, l = v - w;
-            const int lane = col + 32 * (cil >> 3), j = cil & 7;
-            const long long q = (((long long)cg * nk + kk) * 4 + xi) * (3 * 4 * 64 * 8);
-            img[q + ((long long)(nu * 3 + 0) * 64 + lane) * 8 + j] = top16(h);
-            img[q + ((long long)(nu * 3 + 1) * 64 + lane) * 8 + j] = top16(m);
-            img[q + ((long long)(nu * 3 + 2) * 64 + lane) * 8 + j] = top16(l);
-          }
-}
-
 // ---- kind -> image ------------------------------------------------------------------------------------------------------------------
 long long conv_image_floats(ConvKind k, const ConvWeights& c) {
-  const long long g32 = (c.Cout + 31) / 32, k8 = (c.Cin + 7) / 8, k16 = (c.Cin + 15) / 16;
+  const long long g32 = (c.Cout + 31) / 32, k8 = (c.Cin + 7) / 8;
   switch (k) {
     case ConvKind::DIRECT: return (long long)c.ncg * ((c.Cin + CK - 1) / CK) * 9 * CK * c.cop;
     case ConvKind::W1D: return g32 * ((c.Cin + CK - 1) / CK) * 12 * CK * 32;
@@ -228,9 +164,6 @@ long long conv_image_floats(ConvKind k, const ConvWeights& c) {
     case ConvKind::WINO: return conv_wino_ww16_at(c.Cin, c.Cout) + ((c.Cout & 31) == 16 ? (long long)(c.Cin / 8) * 2048 : 0);
     case ConvKind::X6_FIRST: return k8 * 864 * 4;                     // 864 units x 16 bytes = x 4 floats
     case ConvKind::X6: return g32 * k8 * 9 * 32 * 8;
-    case ConvKind::BF16: return g32 * k16 * 2 * 9 * 2 * 32 * 8 / 2;   // u16 -> floats
-    case ConvKind::BF16_DMA: return g32 * k16 * 9 * 2 * 32 * 8;
-    case ConvKind::WINO6: return g32 * k16 * (16 * 3 * 64 * 16 / 4);
   }
   return 0;
 }
@@ -246,13 +179,6 @@ void conv_image_pack(ConvKind k, const ConvWeights& c, float* img) {
       break;
     case ConvKind::X6_FIRST: w6s_image(c, img); break;
     case ConvKind::X6: wf6_image(c, img); break;
-#if MN_ALT_MODES
-    case ConvKind::BF16: bf16_image(c, img, true); break;
-    case ConvKind::BF16_DMA: bf16_image(c, img, false); break;
-    case ConvKind::WINO6: wino6_image(c, img); break;
-#else
-    default: break;
-#endif
   }
 }
 

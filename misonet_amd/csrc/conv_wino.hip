@@ -38,7 +38,6 @@
 #include "conv_select.hpp"
 #include "conv_epilogue.hpp"
 #include "wino_regs.hpp"
-#include <stdio.h>
 #include <stdlib.h>
 #include <utility>
 
@@ -125,9 +124,9 @@ constexpr unsigned WBIAS_B = WDUMMY_B + 64u * 4u;       // per output channel: b
 constexpr size_t WINO_LDS = WBIAS_B + WCO_MAX * 24;
 static_assert(WINO_LDS <= 160 * 1024, "one workgroup per CU: at most 160 KB of LDS");
 
-// DBG (timing experiments only, -DMISONET_EXPERIMENTS + MISONET_WINO_DBG): 1 = no staging side work in the chunk loop (wrong
-// results), 2 = no epilogue arithmetic / stores, 4 = no input transform, 8 / 16 / 32 = no weight DMA / input DMA / staging
-// arithmetic + LDS traffic (the three parts of 1), 64 / 128 / 256 = no epilogue stores / statistics / ELU.
+// DBG: ablation bits of the timing experiments (LAB.md round 6: 1 = no staging side work in the chunk loop, 2 = no epilogue
+// arithmetic / stores, 4 = no input transform, 8 / 16 / 32 = no weight DMA / input DMA / staging arithmetic + LDS traffic, 64 / 128 /
+// 256 = no epilogue stores / statistics / ELU).  Only DBG = 0 is instantiated; the parameter is part of the kernel's symbol.
 // G16: the instantiation for a 16-channel output group (the second group of the 48-channel layer dec6.db.c5, model.py:64-73: half of
 // a 32-row MFMA would be padding -- 5.9 ms per step).  Same stream, staging, DMA and bookkeeping; what differs is the operand path:
 //   v_mfma_f32_16x16x4_f32: lane (kk = lane >> 4, nn = lane & 15) <-> B operand V_p[ci = 4 s + kk][tile nn + 16 g], A operand
@@ -391,14 +390,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
   }
 
 #define W_SB __builtin_amdgcn_sched_barrier(0);
-#ifdef MISONET_EXPERIMENTS
-  // timeline of ONE wave (MISONET_WINO_TIMELINE=<Cin>): s_memtime stamps of the iterations around the first tile epilogues
-  unsigned long long* const tl_buf = (blockIdx.x == 8 && wave == 1) ? a.dbg_buf : nullptr;
-  int tl_n = 0;
-#define W_STAMP(ID) if (tl_buf && tl_n < 250) { if (lane == 0) { tl_buf[2 * tl_n] = (ID); tl_buf[2 * tl_n + 1] = __builtin_readcyclecounter(); } ++tl_n; }
-#else
-#define W_STAMP(ID)
-#endif
 #define W_MF(P, CS) wino_mfma<P, (POST == 2 && (CS) == 0)>(u[(P) >> 2][(P) & 3], vp[(P) >> 2][((P) & 3) >> 1][(P) & 1]);
 #define W_NONE
 #define W_X(...) if (!(DBG & (1 | 32))) { __VA_ARGS__ }      /* staging arithmetic, norm / raw reads, LDS writes */
@@ -481,7 +472,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
   rofs = rofs0 + rsl_; rhofs = rhofs0 + rsl_;
 #define W_CHUNK_                                                                                      \
   W_STEP(0, d1, uc, 1, W_NONE, W_NONE, W_NONE, W_NONE, W_NONE, W_NONE, W_NONE,                        \
-         W_X(W_STAMP(1) if (POST) { W_VMCNT(26) } else { W_VMCNT(10) } W_STAMP(2) W_RR(rwa, 0)), W_NONE, W_X(W_RR(rwb, 1)), W_X(W_NR(nra, 0)), W_X(W_NR(nrb, 1)), W_NONE, W_NONE, \
+         W_X(if (POST) { W_VMCNT(26) } else { W_VMCNT(10) } W_RR(rwa, 0)), W_NONE, W_X(W_RR(rwb, 1)), W_X(W_NR(nra, 0)), W_X(W_NR(nrb, 1)), W_NONE, W_NONE, \
          W_X(W_CC(cva, rwa, nra) W_CC(cvb, rwb, nrb)))                                                \
   W_STEP(1, d2, uc, 2, W_X(W_CW(cva, 0)), W_X(W_CW(cvb, 1)), W_NONE, W_NONE, W_NONE, W_NONE, W_NONE,  \
          W_X(W_RR(rwa, 2)), W_NONE, W_X(W_RR(rwb, 3)), W_X(W_NR(nra, 2)), W_X(W_NR(nrb, 3)), W_NONE, W_NONE,  \
@@ -490,7 +481,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
          W_X(W_RR(rwa, 4)), W_NONE, W_X(W_RRH), W_X(W_NR(nra, 4)), W_X(W_NR(nrb, 5)), W_NONE, W_NONE, \
          W_X(W_CC(cva, rwa, nra) W_CCH(nrb)))                                                         \
   W_STEP(3, d0n, un, 0, W_X(W_CW(cva, 4)), W_X(W_CWH), W_NONE,                                        \
-         W_STAMP(3) W_XW(if (POST == 2) { W_VMCNT(22) } else { W_VMCNT(6) }) W_STAMP(4) W_BARRIER W_STAMP(5), \
+         W_XW(if (POST == 2) { W_VMCNT(22) } else { W_VMCNT(6) }) W_BARRIER, \
          W_XW(W_ISSUE_W(0, stnn, Dwso)), W_XW(W_ISSUE_W(1, stnn, Dwso)), W_XW(W_ISSUE_W(2, stnn, Dwso)), W_XW(W_ISSUE_W(3, stnn, Dwso)), \
          W_XL(W_ISSUE_I(0)), W_XL(W_ISSUE_I(1)), W_XL(W_ISSUE_I(2)), W_XL(W_ISSUE_I(3)), W_XL(W_ISSUE_I(4)),  \
          W_XL(W_ISSUE_H) W_BK_S1 W_BK_S2 W_BK_S3, W_BK_V)
@@ -637,7 +628,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
     if (++kc == nchunk) {
       // ---- tile epilogue: Y = A^T M A per (channel, tile), + bias, ELU, centring, stores, statistics ----
       asm volatile("s_nop 15\n\ts_nop 7");             // the last MFMA's result (16 passes) before any accumulator read
-      W_STAMP(10)
       if (!(DBG & 2)) {
       int tt_, ft_, n, cg;
       W_DECODE(qc, tt_, ft_, n, cg)
@@ -723,7 +713,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
           });
         });
         wfor<8>([&](auto) __attribute__((always_inline)) { dummy_store(); });
-        W_STAMP(11)
         if (!(DBG & 128)) {
           // sums over the 16 tiles of a lane row (DPP: xor 1, xor 2, row_half_mirror, row_mirror) and the two tile groups
           wfor<4>([&](auto rc) __attribute__((always_inline)) {
@@ -780,7 +769,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
                    tab_a + kr * 24, vo_x + (unsigned)(cbase + kr) * P4, ev, mt, mb, s1[r], s2[r]);
         });
       });
-      W_STAMP(11)
       if (!(DBG & 128)) {
         const float x1 = reduce16_halfwave(s1, lane);
         const float x2 = reduce16_halfwave(s2, lane);
@@ -807,14 +795,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_f32(const ConvArgs a) {
         }
       }
       }
-      W_STAMP(12)
       // (no zeroing: the next tile's first K-step starts its accumulators with C = 0 -- the POST == 2 chunk bodies; the
       // ablation builds that skip the epilogue keep post = 0 and therefore the explicit pass)
       if (DBG & (2 | 64)) {
         wfor<256>([&](auto i) __attribute__((always_inline)) { agpr_zero<decltype(i)::value>(); });
         asm volatile("s_nop 4");
       }
-      W_STAMP(13)
       kc = 0;
       qc += qstep;
       post = (DBG & (2 | 64)) ? 0 : 2;               // (the body has already counted this iteration down)
@@ -834,23 +820,11 @@ bool conv_wino_ok(const ConvShape& s) {
          !s.out_oct;
 }
 
-#ifdef MISONET_EXPERIMENTS
-static int wino_dbg_env() {
-  static const int v = exp_env("MISONET_WINO_DBG", 0);
-  return v;
-}
-#endif
-
 hipError_t conv_wino_init() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_f32<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)WINO_LDS);
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_f32<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_LDS);
-#ifdef MISONET_EXPERIMENTS
-#define W_ATTR(D) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_f32<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_LDS);
-  W_ATTR(1) W_ATTR(2) W_ATTR(3) W_ATTR(4) W_ATTR(7) W_ATTR(10) W_ATTR(18) W_ATTR(34) W_ATTR(64) W_ATTR(128) W_ATTR(256) W_ATTR(448) W_ATTR(512)
-#undef W_ATTR
-#endif
   return e;
 }
 
@@ -885,7 +859,7 @@ static hipError_t launch_wino_groups(ConvArgs a, int n_samples, hipStream_t s, b
   a.ncg = g16 ? 1 : (a.Cout + 31) / 32;
   const int cus = device_cus();
   if (cus <= 0) return hipErrorInvalidDevice;
-  (void)conv_grid(a, n_samples, WTT, WFT, (n_samples % 8 == 0 && cus % 8 == 0) ? conv_xcd_env() : 0);   // ntx, nty, nsamp, xcd
+  (void)conv_grid(a, n_samples, WTT, WFT, n_samples % 8 == 0 && cus % 8 == 0);   // ntx, nty, nsamp, xcd
   const long long tiles = (long long)n_samples * a.ntx * a.nty * a.ncg;
   const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
   const dim3 g(a.xcd ? (unsigned)cus : grid);
@@ -893,34 +867,6 @@ static hipError_t launch_wino_groups(ConvArgs a, int n_samples, hipStream_t s, b
     hipLaunchKernelGGL((conv3x3_wino_f32<0, true>), g, dim3(256), WINO_LDS, s, a);
     return hipGetLastError();
   }
-#ifdef MISONET_EXPERIMENTS
-  {
-    static const int tl_cin = exp_env("MISONET_WINO_TIMELINE", 0);
-    static unsigned long long* tl_dev = nullptr;
-    static int tl_done = 0;
-    if (tl_cin && a.Cin == tl_cin && a.Fin == 63 && n_samples == 96 && tl_done < 2) {
-      if (!tl_dev) (void)hipMalloc(reinterpret_cast<void**>(&tl_dev), 512 * 8);
-      (void)hipMemsetAsync(tl_dev, 0, 512 * 8, s);
-      a.dbg_buf = tl_dev;
-      hipLaunchKernelGGL(conv3x3_wino_f32<0>, g, dim3(256), WINO_LDS, s, a);
-      (void)hipStreamSynchronize(s);
-      unsigned long long h[512];
-      (void)hipMemcpy(h, tl_dev, sizeof(h), hipMemcpyDeviceToHost);
-      if (++tl_done == 2) {
-        fprintf(stderr, "[wino timeline] Cin=%d nchunk=%d: id, cycles since previous stamp\n", a.Cin, a.Cin / 8);
-        for (int i = 0; i < 250 && h[2 * i]; ++i)
-          fprintf(stderr, "  %2llu %8lld\n", h[2 * i], i ? (long long)(h[2 * i + 1] - h[2 * i - 1]) : 0ll);
-      }
-      return hipGetLastError();
-    }
-  }
-  switch (wino_dbg_env()) {
-#define W_CASE(D) case D: hipLaunchKernelGGL(conv3x3_wino_f32<D>, g, dim3(256), WINO_LDS, s, a); return hipGetLastError();
-    W_CASE(1) W_CASE(2) W_CASE(3) W_CASE(4) W_CASE(7) W_CASE(10) W_CASE(18) W_CASE(34) W_CASE(64) W_CASE(128) W_CASE(256) W_CASE(448) W_CASE(512)
-#undef W_CASE
-    default: break;
-  }
-#endif
   hipLaunchKernelGGL(conv3x3_wino_f32<0>, g, dim3(256), WINO_LDS, s, a);
   return hipGetLastError();
 }

@@ -21,15 +21,6 @@ constexpr int FT = 4;       // output rows (frequency bins) per workgroup = wave
 constexpr float IN_EPS = 1e-5f;    // nn.InstanceNorm{1,2}d default eps (reference model.py:413,579)
 constexpr float GLN_EPS = 1e-8f;   // reference model.py:6
 
-// Experiment switches (kernel variants for A/B runs, timelines, parts switched off): they exist only in the experiment build
-// (`make exp` -> libmisonet_hip_exp.so, -DMISONET_EXPERIMENTS; tools/gpu_*.sh select it through MISONET_LIB_PATH).  In the
-// product library every switch is its default, a compile-time constant: no environment variable changes what it runs.
-#ifdef MISONET_EXPERIMENTS
-inline int exp_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#else
-constexpr int exp_env(const char*, int dflt) { return dflt; }
-#endif
-
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int frames_pitch(int T) { return round_up(T, 32); }
 
@@ -41,8 +32,11 @@ struct ConvArgs {
   dstat_t* out_stats;       // [n][out_sstride][2][DS_NL], accumulated with integer atomics (ds_add) when act != 0
   const float* w;           // packed [ncg][nchunk][9][CK][COP]
   const float* bias;        // [ncg*COP]
-  const unsigned short* w16; // bf16x3 path: packed [ncg][nchunk16][hi|lo][9][2][COP][8] bf16, or nullptr
-  const void* ww6;          // bf16x6w path (conv_wino6.hip): the same weights as three bf16 pieces, [cg32][K-step of 16][xi][nu][piece][lane][8], or nullptr
+  // Fields marked (constant) hold the same value in every launch since the measured alternative modes (bf16x3, f16x3, bf16x6w) and
+  // the timing switches left the library.  They remain because the struct's byte layout, and with it every kernel's argument
+  // offsets and code, stays what it was; the device-side tests of `dbg` are listed in LAB.md ("Leftovers of the experiment build").
+  const unsigned short* w16; // (constant) nullptr
+  const void* ww6;          // (constant) nullptr
   const float* wsm;         // conv_few.hip (<= 4 output channels): [Cin][9 = kt * 3 + kf][4 co] conv-form taps, or nullptr
   const float* ww16;        // f32w path: the LAST 16 output channels of a layer with Cout % 32 == 16 as their own Winograd image for the 16-row body
                             // (conv_wino.hip G16): [chunk of 8][K-step of 4 ci][pos / 4][ci % 4][16 co][pos % 4], or nullptr
@@ -62,21 +56,18 @@ struct ConvArgs {
   int NR;                   // staged input rows per workgroup (set by the launcher)
   int ncg;                  // output-channel groups (grid.z = n_samples * ncg)
   int cop;                  // 32 or 64 output channels per group
-  // "oct" activation layout of the bf16x3 DMA dataflow (conv_bf16_dma.hip): per sample [hi | lo] halves, each
-  // [c/8][f][Tp][8] bf16 (8 channels of one frame = one 16-byte unit), values RAW (bias + ELU, no instance norm).
-  int in_oct, out_oct;      // layout of the input / output buffer: 0 planar float32, 1 oct (bf16x3: hi | lo halves),
-                            // 3 oct3 (bf16x6, conv_bf16x6.hip: hi | mid | lo parts, 6 bytes per element),
-                            // 4 oct with fp16 pieces (f16x3)
-  float wscale, descale;    // f16x3: power-of-two scale 2^k carried by the folded weights and its inverse (1, 1 otherwise)
+  int in_oct, out_oct;      // layout of the input / output buffer: 0 planar float32, 3 oct3 (bf16x6, conv_bf16x6.hip: per sample
+                            // [hi | mid | lo] parts, each [c/8][f][Tp][8] bf16, 6 bytes per element; values RAW: bias + ELU, no norm)
+  float wscale, descale;    // (constant) 1, 1
   const void* wps;          // per-sample weights with the instance norm of the input folded in (conv_wprep), LDS image order
   long long wps_nstride;    // bytes between samples (0: one image shared by all samples)
   const float* btab;        // [n][ncg*32][9] border-aware shift table: sum_ci W[co][ci][tap] * shift[ci], or nullptr
   long long btab_nstride;   // floats between samples
   int xcd;                  // 1: 1-D grid with the XCD-aware tile order of conv_tile() (ntx, nty, nsamp valid)
   int ntx, nty, nsamp;      // frame tiles, row tiles, samples of this launch
-  unsigned long long* dbg_buf;   // timeline stamps of one workgroup (MISONET_TIMELINE=1, experiments only)
-  int dbg;                  // timing experiments only (MISONET_WS_DEBUG bits): 1 skip MFMAs, 4 skip epilogue, 8 skip stores,
-                            // 16 skip statistics reductions, 32 no deferred epilogue
+  unsigned long long* dbg_buf;   // (constant) nullptr: where the timeline experiments had one workgroup write its clock stamps
+  int dbg;                  // (constant) 0: ablation bits of the timing experiments (1 skip MFMAs, 4 skip epilogue, 8 skip stores,
+                            // 16 skip statistics reductions, 32 no deferred epilogue)
 };
 // Workgroup -> tile.  Hardware hands consecutive workgroup ids to the 8 XCDs round-robin and every XCD has its own
 // L2, so with the natural (t, f, n) order the 8 frame tiles of a row sit on 8 different XCDs and every halo line is
@@ -111,10 +102,8 @@ inline dim3 conv_grid(ConvArgs& a, int n_samples, int tt, int ft, int xcd) {
   if (xcd) return dim3((unsigned)(8 * ((n_samples + 7) / 8) * a.ntx * a.nty * a.ncg), 1, 1);
   return dim3(a.ntx, a.nty, n_samples * a.ncg);
 }
-int conv_xcd_env();                          // MISONET_XCD (default 1)
 int device_cus();                            // compute units of the CURRENT device (cached per device, thread-safe); <= 0 on error
 int conv_cop(int Cout);                      // 32 (Cout <= 32) or 64
-int conv_rows(int sf, int tr2);              // staged rows of the row-per-wave geometry (conv_bf16*.hip)
 // Which of these launchers runs a layer: conv_select.hpp (one ConvKind per layer and arithmetic mode, with the launchers' own guards).
 // Every launcher answers hipErrorInvalidValue to a layer its kernel does not take, and sets ConvArgs::NR itself.
 hipError_t launch_conv(const ConvArgs& a, int n_samples, hipStream_t s);       // any shape (needs a.w)
@@ -127,13 +116,6 @@ hipError_t conv_wino_init();
 // <= 4 output channels, stride 1, no activation (the network's last layer) on the vector ALU (conv_few.hip; needs a.wsm)
 hipError_t launch_conv_few(const ConvArgs& a, int n_samples, hipStream_t s);
 hipError_t conv_few_init();
-hipError_t launch_conv_wino6(const ConvArgs& a, int n_samples, hipStream_t s);   // conv_wino6.hip (needs a.ww6)
-hipError_t conv_wino6_init();
-hipError_t launch_conv_bf16(const ConvArgs& a, int n_samples, hipStream_t s);   // conv_bf16.hip (needs a.w16)
-hipError_t conv_bf16_init();
-hipError_t launch_conv_bf16_dma(const ConvArgs& a, int n_samples, hipStream_t s);   // conv_bf16_dma.hip (oct input)
-hipError_t launch_conv_wprep(const ConvArgs& a, const float* wf, int n_samples, hipStream_t s);   // a.in_oct == 4: fp16 pieces
-hipError_t conv_bf16_dma_init();
 // bf16x6 (fp32-faithful) DMA dataflow, conv_bf16x6.hip: oct3 input, oct3 or planar output
 hipError_t launch_conv_bf16x6(const ConvArgs& a, int n_samples, hipStream_t s);
 hipError_t launch_conv_wprep6(const ConvArgs& a, const float* wf6, int n_samples, hipStream_t s);
@@ -180,8 +162,8 @@ hipError_t launch_unpack(const float* src, long long src_bstride, int Tp, int S,
 // planar view (+ optional instance norm) -> float32 [n][C][T][F]  (diagnostic taps)
 hipError_t launch_export(const float* src, long long src_bstride, int c0, int C, int Fq, int T, int Tp,
                          const dstat_t* stats, int sstride, int ident_c, float* dst, int n_samples, hipStream_t s,
-                         int oct = 0);   // oct: bf16 parts of a source in the oct layout (0 planar, 2, 3; sstride = channels
-                                         // of the whole buffer)
+                         int oct = 0);   // oct: 0 planar, 3 a source in the oct3 layout (sstride = channels of the
+                                         // whole buffer)
 // what the fused pipeline adds: launch_unpack's general form (layout.hip: real / imaginary planes from channel c_re0 / c_im0 on,
 // sources picked through sel); the shift and clean alignments composed into one sel, and the MISO3 input [mixture | beamformer
 // planes, written by launch_mvdr | MISO1 estimate at ref_ch] (both mvdr.hip)

@@ -86,8 +86,8 @@ __global__ __launch_bounds__(256) void unpack_k(const float* src, long long bstr
   if (nan_flag && bad) atomicOr(nan_flag, 1);
 }
 
-// oct = 2 / 3 / 4: the source buffer is in the oct layout of the bf16x3 / bf16x6 / f16x3 DMA dataflow (kernels.hpp), value =
-// the sum of its pieces (exact for three bf16 parts)
+// oct = 3: the source buffer is in the oct3 layout of the bf16x6 DMA dataflow (kernels.hpp), value = the sum of its three bf16
+// parts (exact).  No caller passes 2 or 4 any more (two bf16 / fp16 pieces, the dropped modes): LAB.md lists those branches.
 __global__ __launch_bounds__(256) void export_k(const float* src, long long src_bstride, int c0, int C, int Fq, int T,
                                                 int Tp, const dstat_t* stats, int sstride, int ident_c, float* dst,
                                                 int oct) {

@@ -77,21 +77,13 @@ static void add_dense(misonet_net* n, std::vector<ConvL>& v, const std::string& 
   }
 }
 
-// precision 2 ("bf16x3") and 3 ("bf16x6"), the DMA dataflows: the dense-block buffers and everything between them travel
-// in the oct layout (2 bf16 parts = the bytes of float32, or 3 parts = 6 bytes per element); the network input/output
-// and the TCN stay planar float32, and so do the F <= 3 bottleneck buffers except in bf16x6.  Returns the ConvArgs::in_oct /
-// out_oct code.
+// precision 3 ("bf16x6"), the DMA dataflow: every buffer between the network input and its output travels in the oct3 layout (3
+// bf16 parts = 6 bytes per element) -- the dense-block buffers and what lies between them, and the F <= 3 bottleneck buffers D0 / D1
+// (the TCN reads / writes the layout at its two ends), so that encoder 6 and decoders 0-1 run on the persistent kernel too.  The
+// network input / output and the TCN stay planar float32.  Returns the ConvArgs::in_oct / out_oct code.
 static inline int buf_oct(int precision, int b) {
-  if (precision < 2 || precision >= 5) return 0;
-  const bool o = (b >= B_E0 && b <= B_E4) || (b >= B_D2 && b <= B_D6) || (b >= B_X2 && b <= B_X6);
-  // bf16x6 also keeps the F <= 3 bottleneck buffers D0 / D1 in its layout (the TCN reads / writes it at its two ends), so
-  // that encoder 6 and decoders 0-1 run on the persistent kernel instead of the one-row-per-wave f32 kernel
-  if (precision == 3 && (b == B_D0 || b == B_D1)) return 3;
-  // f16x3: the first dense-block buffer holds the RAW first-layer output (un-normalised, its scale follows the input), which
-  // two fp16 pieces cannot carry for every input scale nor to 24 bits: it stays in the exact three-bf16 layout and the
-  // layers that read it run on the bf16x6 kernel (its last conv writes the fp16 layout of the next buffer)
-  if (precision == 4 && b == B_E0) return 3;
-  return o ? (precision == 3 ? 3 : (precision == 4 ? 4 : 1)) : 0;
+  if (precision != 3) return 0;
+  return ((b >= B_E0 && b <= B_E4) || (b >= B_D0 && b <= B_D6) || (b >= B_X2 && b <= B_X6)) ? 3 : 0;
 }
 static inline int buf_oct(const misonet_net* n, int b) { return buf_oct(n->precision, b); }
 
@@ -211,16 +203,13 @@ static int build_plan(misonet_net* n) {
     n->taps.push_back({nm, B_D0 + i + 1, 0, de[i + 1], true});
   }
   n->taps.push_back({"dec6", B_OUT, 0, c.out_ch, false});
-  // ---- the kernel of every conv layer in every arithmetic mode of the build ----
-  // (MISONET_X6_FIRST=0, experiment build: the first layer of the bf16x6 / f16x3 networks on the exact-f32 kernel of rounds 1-3)
-  static const int x6first_env = exp_env("MISONET_X6_FIRST", 1);
+  // ---- the kernel of every conv layer in every arithmetic mode ----
   for (std::vector<ConvL>* v : {&n->enc, &n->dec})
     for (ConvL& l : *v)
       for (int mode = 0; mode < CONV_NMODES; ++mode) {
         const ConvShape sh = {l.Cin, l.Cout, n->bufs[l.in_buf].F, n->bufs[l.out_buf].F, l.sf, l.padf, l.tr2, l.act, l.transposed,
                               l.ident_c, l.in_buf == B_IN, buf_oct(mode, l.in_buf), buf_oct(mode, l.out_buf)};
         l.kind[mode] = conv_mode_built(mode) ? conv_select(sh, mode) : ConvKind::DIRECT;
-        if (l.kind[mode] == ConvKind::X6_FIRST && !x6first_env) l.kind[mode] = ConvKind::DIRECT;
       }
   return MISONET_OK;
 }
@@ -307,10 +296,8 @@ Layout mn::make_layout(const misonet_net* n, int N, int T, bool ext_in) {
   long long wmax = 0, cmax = 0;
   auto scan = [&](const std::vector<ConvL>& v) {
     for (const ConvL& c : v) {
-      const long long g = (c.Cout + 31) / 32, k = (c.Cin + 15) / 16;
-      wmax = std::max(wmax, g * k * (2LL * 9 * 2 * 32 * 16));
       wmax = std::max(wmax, conv_bf16x6_wps_bytes((c.Cin + 7) / 8 * 8, c.Cout));
-      cmax = std::max(cmax, g * 32);
+      cmax = std::max(cmax, (c.Cout + 31) / 32 * 32LL);
     }
   };
   scan(n->enc); scan(n->dec);
@@ -326,19 +313,19 @@ Layout mn::make_layout(const misonet_net* n, int N, int T, bool ext_in) {
 static inline dstat_t* stats_base(void* ws) { return reinterpret_cast<dstat_t*>(reinterpret_cast<char*>(ws) + 256); }
 static inline dstat_t* stats_ptr(const Layout& L, void* ws, int b) { return stats_base(ws) + L.stats_off[b]; }
 
-// launch layer c on samples [n0, n0 + nb) with the kernel the plan chose for the current mode (ConvL::kind)
-static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL& c, hipStream_t s, int n0 = 0, int nb = -1) {
+// launch layer c on all samples with the kernel the plan chose for the current mode (ConvL::kind)
+static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL& c, hipStream_t s) {
   const ConvKind kind = c.kind[n->precision];
-  if (nb < 0) nb = L.N;
+  const int nb = L.N;
   ConvArgs a = {};
   a.in_bstride = bstride(n, L, c.in_buf);
   a.out_bstride = bstride(n, L, c.out_buf);
   a.in_sstride = n->bufs[c.in_buf].C;
   a.out_sstride = n->bufs[c.out_buf].C;
-  a.in = buf_ptr(L, ws, c.in_buf) + (long long)n0 * a.in_bstride;
-  a.out = buf_ptr(L, ws, c.out_buf) + (long long)n0 * a.out_bstride;
-  a.in_stats = stats_ptr(L, ws, c.in_buf) + (long long)n0 * a.in_sstride * 2 * DS_NL;
-  a.out_stats = stats_ptr(L, ws, c.out_buf) + (long long)n0 * a.out_sstride * 2 * DS_NL;
+  a.in = buf_ptr(L, ws, c.in_buf);
+  a.out = buf_ptr(L, ws, c.out_buf);
+  a.in_stats = stats_ptr(L, ws, c.in_buf);
+  a.out_stats = stats_ptr(L, ws, c.out_buf);
   a.bias = n->w_dev + c.b_off;
   a.in_c0 = c.in_c0; a.Cin = c.Cin; a.Fin = n->bufs[c.in_buf].F; a.ident_c = c.ident_c;
   a.out_c0 = c.out_c0; a.Cout = c.Cout; a.Fout = n->bufs[c.out_buf].F;
@@ -350,26 +337,14 @@ static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL
   a.cop = kind == ConvKind::DIRECT ? c.cop : 32;
   a.ncg = (c.Cout + a.cop - 1) / a.cop;
   a.wscale = a.descale = 1.f;
-  // MISONET_SYNC_DEBUG=1: name every conv launch and wait for it (fault hunting)
-  static const int sync_dbg = exp_env("MISONET_SYNC_DEBUG", 0);
-  struct SyncDbg {
-    hipStream_t s; const ConvArgs& a; int on;
-    ~SyncDbg() {
-      if (!on) return;
-      fprintf(stderr, "[conv] Cin=%d Cout=%d Fin=%d Fout=%d T=%d in_oct=%d out_oct=%d mode=%d ... ", a.Cin, a.Cout, a.Fin, a.Fout,
-              a.T, a.in_oct, a.out_oct, a.tr2 ? 2 : (a.sf == 2 ? 1 : 0));
-      const hipError_t e = hipStreamSynchronize(s);
-      fprintf(stderr, "%s\n", hipGetErrorString(e));
-    }
-  } sync_guard{s, a, sync_dbg};
-  // the oct-input kernels read per-sample weights with the input's instance norm folded in: their prep kernel runs first
-  auto prep = [&](hipError_t (*launch_wprep)(const ConvArgs&, const float*, int, hipStream_t)) {
-    a.wps = reinterpret_cast<char*>(ws) + L.wps_base + (long long)n0 * L.wps_nstride;
+  // the oct3-input kernel reads per-sample weights with the input's instance norm folded in: its prep kernel runs first
+  auto prep = [&]() {
+    a.wps = reinterpret_cast<char*>(ws) + L.wps_base;
     a.wps_nstride = L.wps_nstride;
-    a.btab = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.btab_base) + (long long)n0 * L.btab_nstride;
+    a.btab = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + L.btab_base);
     a.btab_nstride = L.btab_nstride;
     ProfScope pw(s, PK_OTHER);                                     // its own kind: part of the step, not of the conv kernel
-    return launch_wprep(a, c.img(n->w_dev, kind), nb, s);
+    return launch_conv_wprep6(a, c.img(n->w_dev, kind), nb, s);
   };
   hipError_t e = hipSuccess;
   switch (kind) {
@@ -384,22 +359,9 @@ static int run_conv(const misonet_net* n, const Layout& L, void* ws, const ConvL
     } break;
     case ConvKind::X6_FIRST: { ProfScope ps(s, PK_CONV); e = launch_conv_x6_first(a, c.img(n->w_dev, kind), nb, s); } break;
     case ConvKind::X6:
-      e = prep(launch_conv_wprep6);
+      e = prep();
       if (e == hipSuccess) { ProfScope ps(s, PK_CONV); e = launch_conv_bf16x6(a, nb, s); }
       break;
-#if MN_ALT_MODES
-    case ConvKind::BF16: {
-      a.w16 = reinterpret_cast<const unsigned short*>(c.img(n->w_dev, kind));
-      ProfScope ps(s, PK_CONV);
-      e = launch_conv_bf16(a, nb, s);
-    } break;
-    case ConvKind::BF16_DMA:
-      if (a.in_oct == 4) { a.wscale = c.wscale; a.descale = 1.f / c.wscale; }
-      e = prep(launch_conv_wprep);
-      if (e == hipSuccess) { ProfScope ps(s, PK_CONV); e = launch_conv_bf16_dma(a, nb, s); }
-      break;
-    case ConvKind::WINO6: { a.ww6 = c.img(n->w_dev, kind); ProfScope ps(s, PK_CONV); e = launch_conv_wino6(a, nb, s); } break;
-#endif
     default: e = hipErrorInvalidValue; break;
   }
   // a launcher that refuses the layer its kind was chosen for: the selector and the kernel disagree -- never a silent fall-back
@@ -425,28 +387,8 @@ int mn::forward_planar(misonet_net* n, const Layout& L, void* ws, hipStream_t s)
   // the nan flag + the conv statistics (integer limbs are ACCUMULATED); the TCN partial arrays behind them are plainly written
   HIPCHK(hipMemsetAsync(ws, 0, (size_t)(256 + L.tcn_xs * 8), s));
   HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<char*>(ws) + 8), (int)layout_stamp(n, L), 1, s));
-  // Optional sample sub-batching of the conv stacks (MISONET_SUBBATCH = samples per pass at F = 127; deeper levels take
-  // proportionally more): keeps a level's producer->consumer traffic inside the 256 MiB Infinity Cache.
-  static const int sub_env = exp_env("MISONET_SUBBATCH", 0);
   auto run_stack = [&](const std::vector<ConvL>& v) -> int {
-    if (sub_env <= 0) {
-      for (const ConvL& c : v) { int r = run_conv(n, L, ws, c, s); if (r) return r; }
-      return MISONET_OK;
-    }
-    // group consecutive layers by output frequency size; sub-batch each group
-    size_t i = 0;
-    while (i < v.size()) {
-      const int Fg = n->bufs[v[i].out_buf].F;
-      size_t j = i;
-      while (j < v.size() && n->bufs[v[j].out_buf].F == Fg) ++j;
-      int sb = sub_env * (127 / (Fg > 0 ? Fg : 1));
-      if (sb < 1) sb = 1;
-      for (int n0 = 0; n0 < L.N; n0 += sb) {
-        const int nb = (L.N - n0) < sb ? (L.N - n0) : sb;
-        for (size_t k = i; k < j; ++k) { int r = run_conv(n, L, ws, v[k], s, n0, nb); if (r) return r; }
-      }
-      i = j;
-    }
+    for (const ConvL& c : v) { int r = run_conv(n, L, ws, c, s); if (r) return r; }
     return MISONET_OK;
   };
   { int r = run_stack(n->enc); if (r) return r; }
@@ -469,9 +411,7 @@ int mn::forward_planar(misonet_net* n, const Layout& L, void* ws, hipStream_t s)
                               n->bufs[B_D0].C, xa, xs, 128, T, Tp, N, s, buf_oct(n, B_D0) == 3));
     float* cur = xa;
     float* nxt = xb;
-    // bf16x6 mode: the point-wise convs in the same arithmetic as the 3x3 convs (MISONET_TCN_X6=0: fp32 MFMA, A/B runs)
-    static const int tcn_x6_env = exp_env("MISONET_TCN_X6", 1);
-    const int tcn_x6 = (n->precision == 3 && tcn_x6_env) ? 1 : 0;
+    const int tcn_x6 = n->precision == 3;     // bf16x6 mode: the point-wise convs in the same arithmetic as the 3x3 convs
     for (int k = 0; k < 14; ++k) {
       const TcnBlock& tb = n->tcn[k];
       const float* W = n->w_dev;
@@ -512,7 +452,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 660; }   // 660: misonet_resample_stream_carry, misonet_resample_stream_state_bytes, misonet_resample_stream_outputs, misonet_resample_stream_tile, misonet_resample_stream_reset, misonet_resample_stream (streaming polyphase resampler: blocks in, blocks out, bits of misonet_resample); 650: misonet_stft_stream_state_bytes, misonet_stft_stream_reset, misonet_stft_stream_frames, misonet_stft_stream, misonet_istft_stream_state_bytes, misonet_istft_stream_reset, misonet_istft_stream_hops, misonet_istft_stream (streaming STFT / iSTFT: blocks in, blocks out, bits of the offline kernels); 640: misonet_obf_opts, misonet_obf_opts_default, misonet_obf_state_bytes, misonet_obf_cells_per_block, misonet_obf_reset, misonet_obf, misonet_obf_debug (online beamformer: frame-recursive MVDR / MWF, state carried); 630: misonet_oiva_opts, misonet_oiva_opts_default, misonet_oiva_state_bytes, misonet_oiva_bins_per_pass, misonet_oiva_reset, misonet_oiva, misonet_oiva_debug (online AuxIVA: frame-recursive separation, state carried); 620: misonet_owpe_opts, misonet_owpe_opts_default, misonet_owpe_state_bytes, misonet_owpe_lds_bytes, misonet_owpe_reset, misonet_owpe, misonet_owpe_debug (online WPE: frame-recursive, state carried); 610: misonet_doa_opts, misonet_doa_opts_default, misonet_doa_tile, misonet_doa_bin_chunk, misonet_doa_blocks, misonet_doa_workspace_bytes, misonet_doa, misonet_doa_debug (source localisation: SRP, SRP-PHAT and MUSIC maps); 600: misonet_room_tile, misonet_room_rir_len, misonet_room_mix_len, misonet_room_rir, misonet_room_mix (room simulator: image-source RIRs and scene mixing); 590: misonet_resample, misonet_resample_ratio, misonet_resampled_len, misonet_resample_taps, misonet_resample_tile (polyphase resampler for any rational rate); 580: misonet_iva_opts, misonet_auxiva, misonet_auxiva_debug, misonet_auxiva_workspace_bytes, misonet_auxiva_resident_frames (blind separation, AuxIVA-ISS); 570: misonet_jbf_opts, misonet_beamform_joint, misonet_beamform_joint_debug, misonet_pipeline_set_joint (joint multi-speaker beamformers); 560: misonet_cacgmm_opts, misonet_cacgmm, misonet_cacgmm_debug, misonet_masks_from_estimates, misonet_pipeline_set_refine (guided spatial clustering, cACGMM); 550: misonet_srmr_frames / misonet_srmr_scratch_bytes / misonet_srmr_chunk / misonet_srmr_measure (SRMR, the figure without a clean reference); 540: misonet_reverb_frames / misonet_reverb_scratch_bytes / misonet_reverb_measure (cepstral distance, LLR, fwSegSNR); 530: misonet_wpd_opts, misonet_wpd, misonet_wpd_debug, misonet_pipeline_set_wpd (WPD convolutional beamformer); 520: misonet_wpe_opts, misonet_wpe, misonet_wpe_debug (WPE dereverberation); 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6: experiment build); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 660; }   // 660: misonet_resample_stream_carry, misonet_resample_stream_state_bytes, misonet_resample_stream_outputs, misonet_resample_stream_tile, misonet_resample_stream_reset, misonet_resample_stream (streaming polyphase resampler: blocks in, blocks out, bits of misonet_resample); 650: misonet_stft_stream_state_bytes, misonet_stft_stream_reset, misonet_stft_stream_frames, misonet_stft_stream, misonet_istft_stream_state_bytes, misonet_istft_stream_reset, misonet_istft_stream_hops, misonet_istft_stream (streaming STFT / iSTFT: blocks in, blocks out, bits of the offline kernels); 640: misonet_obf_opts, misonet_obf_opts_default, misonet_obf_state_bytes, misonet_obf_cells_per_block, misonet_obf_reset, misonet_obf, misonet_obf_debug (online beamformer: frame-recursive MVDR / MWF, state carried); 630: misonet_oiva_opts, misonet_oiva_opts_default, misonet_oiva_state_bytes, misonet_oiva_bins_per_pass, misonet_oiva_reset, misonet_oiva, misonet_oiva_debug (online AuxIVA: frame-recursive separation, state carried); 620: misonet_owpe_opts, misonet_owpe_opts_default, misonet_owpe_state_bytes, misonet_owpe_lds_bytes, misonet_owpe_reset, misonet_owpe, misonet_owpe_debug (online WPE: frame-recursive, state carried); 610: misonet_doa_opts, misonet_doa_opts_default, misonet_doa_tile, misonet_doa_bin_chunk, misonet_doa_blocks, misonet_doa_workspace_bytes, misonet_doa, misonet_doa_debug (source localisation: SRP, SRP-PHAT and MUSIC maps); 600: misonet_room_tile, misonet_room_rir_len, misonet_room_mix_len, misonet_room_rir, misonet_room_mix (room simulator: image-source RIRs and scene mixing); 590: misonet_resample, misonet_resample_ratio, misonet_resampled_len, misonet_resample_taps, misonet_resample_tile (polyphase resampler for any rational rate); 580: misonet_iva_opts, misonet_auxiva, misonet_auxiva_debug, misonet_auxiva_workspace_bytes, misonet_auxiva_resident_frames (blind separation, AuxIVA-ISS); 570: misonet_jbf_opts, misonet_beamform_joint, misonet_beamform_joint_debug, misonet_pipeline_set_joint (joint multi-speaker beamformers); 560: misonet_cacgmm_opts, misonet_cacgmm, misonet_cacgmm_debug, misonet_masks_from_estimates, misonet_pipeline_set_refine (guided spatial clustering, cACGMM); 550: misonet_srmr_frames / misonet_srmr_scratch_bytes / misonet_srmr_chunk / misonet_srmr_measure (SRMR, the figure without a clean reference); 540: misonet_reverb_frames / misonet_reverb_scratch_bytes / misonet_reverb_measure (cepstral distance, LLR, fwSegSNR); 530: misonet_wpd_opts, misonet_wpd, misonet_wpd_debug, misonet_pipeline_set_wpd (WPD convolutional beamformer); 520: misonet_wpe_opts, misonet_wpe, misonet_wpe_debug (WPE dereverberation); 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6 answer MISONET_EINVAL); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");
@@ -645,7 +585,7 @@ int misonet_net_commit(misonet_net* n) {
   long long off = 0;
   auto take = [&off](long long nfl) { long long o = off; off += (nfl + 63) / 64 * 64; return o; };
   // per conv layer: the bias, the direct image (always: the exact-f32 mode, the self-check's reference) and the image of every
-  // other kind the plan holds for the layer over the modes of this build
+  // other kind the plan holds for the layer over the three modes
   auto conv_weights = [n](const ConvL& c) { return ConvWeights{n->tensors[c.wt].host.data(), c.Cin, c.Cout, c.transposed, c.cop, c.ncg}; };
   for (std::vector<ConvL>* v : {&n->enc, &n->dec})
     for (ConvL& c : *v) {
@@ -674,7 +614,6 @@ int misonet_net_commit(misonet_net* n) {
         if (c.img_off[k] >= 0) conv_image_pack((ConvKind)k, conv_weights(c), arena.data() + c.img_off[k]);
       const std::vector<float>& Bv = n->tensors[c.bt].host;
       for (int co = 0; co < c.ncg * c.cop; ++co) arena[c.b_off + co] = co < c.Cout ? Bv[co] : 0.f;
-      if (MN_ALT_MODES) c.wscale = conv_f16_wscale(n->tensors[c.wt].host.data(), n->tensors[c.wt].numel);
     }
   for (const TcnBlock& tb : n->tcn)
     for (int h = 0; h < 2; ++h) {
@@ -705,16 +644,8 @@ int misonet_net_commit(misonet_net* n) {
   HIPCHK(conv_init());
   HIPCHK(conv_wino_init());
   HIPCHK(conv_few_init());
-#ifdef MISONET_EXPERIMENTS                  // (timing ablations compute garbage by design: MISONET_WINO_DBG skips the self-check)
-  if (!exp_env("MISONET_WINO_DBG", 0))
-#endif
   if (wino_selftest() != 1 && n->precision == 5)
     return fail(MISONET_ESTATE, "the f32w kernel failed its self-check on this device (see stderr): use mode 0 (f32) or 3 (bf16x6)");
-#if MN_ALT_MODES
-  HIPCHK(conv_wino6_init());
-  HIPCHK(conv_bf16_init());
-  HIPCHK(conv_bf16_dma_init());
-#endif
   HIPCHK(conv_bf16x6_init());
   { int rf = misonet_frontend_init(); if (rf) return rf; }     // STFT / iSTFT tables: never allocated inside an asynchronous call
   n->committed = true;
@@ -724,9 +655,7 @@ int misonet_net_commit(misonet_net* n) {
 int misonet_net_set_precision(misonet_net* n, int mode) {
   if (!n) return fail(MISONET_EINVAL, "null argument");
   if (mode < 0 || mode >= CONV_NMODES || !conv_mode_built(mode))
-    return fail(MISONET_EINVAL, "precision mode must be 0 (f32), 3 (bf16x6) or 5 (f32w: f32 with the dense-block convs in Winograd form)%s",
-                MN_ALT_MODES ? "; experiment build: also 1 / 2 (bf16x3), 4 (f16x3), 6 (bf16x6w)"
-                             : "; modes 1, 2, 4, 6 exist only in the experiment build (make exp)");
+    return fail(MISONET_EINVAL, "precision mode must be 0 (f32), 3 (bf16x6) or 5 (f32w: f32 with the dense-block convs in Winograd form)");
   if (mode == 5 && g_wino_state[cur_dev()].load(std::memory_order_acquire) == 2)
     return fail(MISONET_ESTATE, "the f32w kernel failed its self-check on this device: mode 5 is disabled (use 0 or 3)");
   n->precision = mode;
@@ -750,7 +679,7 @@ int misonet_net_buffer_plan(const misonet_net* n, int n_frames, int max_buffers,
 
 int misonet_net_conv_plan(const misonet_net* n, int mode, int max_layers, int* kind) {
   if (!n || !kind) return fail(MISONET_EINVAL, "null argument");
-  if (mode < 0 || mode >= CONV_NMODES || !conv_mode_built(mode)) return fail(MISONET_EINVAL, "precision mode %d is not in this build", mode);
+  if (mode < 0 || mode >= CONV_NMODES || !conv_mode_built(mode)) return fail(MISONET_EINVAL, "precision mode %d does not exist (0, 3, 5)", mode);
   int k = 0;
   for (const std::vector<ConvL>* v : {&n->enc, &n->dec})
     for (const ConvL& c : *v)

@@ -27,11 +27,10 @@ struct ConvL {
   bool transposed;
   int wt, bt;                   // tensor indices
   int cop, ncg;
-  ConvKind kind[CONV_NMODES];       // the layer's kernel per precision mode of the build (conv_select.hpp), filled by build_plan
+  ConvKind kind[CONV_NMODES];       // the layer's kernel per precision mode (conv_select.hpp), filled by build_plan
   long long img_off[CONV_NKIND];    // commit: offset (floats) into the device weight arena of the image of each kind that occurs in
                                     // kind[] (and of DIRECT, always); -1: not packed
   long long b_off = 0;              // ... and of the bias [ncg * cop]
-  float wscale = 1.f;               // f16x3: power of two that brings max |W| of the layer to [32, 64)
   const float* img(const float* w_dev, ConvKind k) const { return w_dev + img_off[(int)k]; }
 };
 
@@ -76,11 +75,10 @@ struct misonet_net {
   float* w_dev = nullptr;
   bool committed = false;
   bool keep_taps = false;        // true: no buffer shares memory with another (every tap stays readable after a forward)
-  int precision = 3;             // 0: exact f32 MFMA, 1: bf16x3 planar, 2: bf16x3 DMA dataflow, 3: bf16x6 DMA dataflow (the
-                                 // default: fp32-faithful, what bench.py reports), 4: f16x3 DMA dataflow, 5: f32 MFMA with the
-                                 // dense-block convs in Winograd F(2x2, 3x3) form ("f32w": planar float32 layout like mode 0)
+  int precision = 3;             // 0: exact f32 MFMA, 3: bf16x6 DMA dataflow (the default: fp32-faithful, what bench.py reports),
+                                 // 5: f32 MFMA with the dense-block convs in Winograd F(2x2, 3x3) form ("f32w": planar float32
+                                 // layout like mode 0); conv_select.hpp conv_mode_built
 };
-// (the modes of this build, product 0 / 3 / 5 or all seven: conv_select.hpp conv_mode_built)
 
 namespace mn {
 

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void tcn_dw_k(const float* x, const double2* x
 constexpr int PW_TT = 128;
 constexpr int PW_KC = 16;
 // Y_OCT3: y is an oct3 buffer of the bf16x6 mode (the TCN output feeds decoder 0 there): the accumulator layout is the
-// conv kernels', so the row goes out through store_oct_row<3>; y_bstride in floats, y_cbuf = channels of that buffer.
+// conv kernels', so the row goes out through store_oct_row; y_bstride in floats, y_cbuf = channels of that buffer.
 // X6: the 128x128 product in the bf16x6 arithmetic of conv_bf16x6.hip (both operands split exactly into three bf16
 // pieces, six leading partial products on v_mfma_f32_32x32x16_bf16, float32 accumulation) instead of the fp32 MFMA: the
 // kernel is bound by the matrix pipe otherwise (3.2 GFLOP per launch at 52 TF/s).  The split of the normalised input
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256) void tcn_pw_k(const float* d, const double2* g
       s2[r] = fmaf(vm, vm, s2[r]);
     }
     if (Y_OCT3)     // octets 4 * wave + {0, 2} + half of this kernel's 16 octets, frame t
-      store_oct_row<3>(vrow, rs_o, (unsigned)t * 16u + (unsigned)(4 * wave + half) * OP16, OP16, ok, ok);
+      store_oct_row(vrow, rs_o, (unsigned)t * 16u + (unsigned)(4 * wave + half) * OP16, OP16, ok, ok);
   }
   if (y_part) {              // this 128-frame tile's partial of every output channel (tcn_dw_k adds a row's tiles in order)
     const float x1 = reduce16_halfwave(s1, lane);

@@ -1,5 +1,4 @@
-// Shared by the Winograd kernels (conv_wino.hip: f32, conv_wino6.hip: bf16x6): the fixed accumulator registers and the
-// compile-time loops.
+// The fixed accumulator registers and the compile-time loops of the Winograd kernel (conv_wino.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <utility>

@@ -59,7 +59,7 @@ class _Trunk:
         # (BatchNorm1d's int64 counter num_batches_tracked lives in the state_dict only: eval mode does not read it)
         if names != [k for k in self.spec.keys() if not k.endswith(".num_batches_tracked")]:
             raise RuntimeError("library tensor list differs from weights.tensor_spec")
-        default_prec = os.environ.get("MISONET_PRECISION")      # e.g. MISONET_PRECISION=bf16x3 for an unmodified harness
+        default_prec = os.environ.get("MISONET_PRECISION")      # e.g. MISONET_PRECISION=f32w for an unmodified harness
         if default_prec:
             self.set_precision(default_prec)
 
@@ -95,8 +95,7 @@ class _Trunk:
         self.training = False
         return self
 
-    PRECISIONS = {"f32": 0, "bf16x3p": 1, "bf16x3": 2, "bf16x6": 3, "f16x3": 4, "f32w": 5, "bf16x6w": 6}
-    PRODUCT_PRECISIONS = ("f32", "f32w", "bf16x6")     # the others exist only in the experiment build (csrc: make exp)
+    PRECISIONS = {"f32": 0, "bf16x6": 3, "f32w": 5}    # the library's mode numbers (1, 2, 4, 6: measured and dropped, LAB.md)
 
     def set_precision(self, mode: str):
         """Arithmetic of the 3x3 convolutions (99.4 % of the FLOPs; the reference computes them in float32, model.py:77-80):
@@ -104,16 +103,10 @@ class _Trunk:
         products and sums throughout, 2.25x fewer matrix instructions (conv_wino.hip); "f32" -- the same matrix cores in the
         direct form (bitwise an fmaf chain, conv.hip); "bf16x6" (the default of a new handle) -- fp32-faithful on the bf16 matrix
         cores: both operands split EXACTLY into three bf16 pieces, the six leading partial products accumulated in float32
-        (conv_bf16x6.hip).  The measured alternatives "bf16x3" / "bf16x3p" (16-bit operands), "f16x3" (22-bit operands) and
-        "bf16x6w" (Winograd in the bf16x6 arithmetic: correct, slower than "bf16x6") are not product modes: they are compiled
-        only into the experiment library (`make exp`, loaded through MISONET_LIB_PATH)."""
+        (conv_bf16x6.hip)."""
         if mode not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)}")
-        rc = _lib.lib().misonet_net_set_precision(self._net, self.PRECISIONS[mode])
-        if rc != 0 and mode not in self.PRODUCT_PRECISIONS:
-            raise ValueError(f"precision {mode!r} exists only in the experiment build of the library (csrc: `make exp`, "
-                             f"MISONET_LIB_PATH=.../libmisonet_hip_exp.so); product modes: {self.PRODUCT_PRECISIONS}")
-        _lib.check(rc)
+        _lib.check(_lib.lib().misonet_net_set_precision(self._net, self.PRECISIONS[mode]))
         if mode != self.precision:
             self._ws.clear()           # the workspace layout (and size) depends on the arithmetic mode
         self.precision = mode

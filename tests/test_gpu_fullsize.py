@@ -17,11 +17,11 @@ B_BENCH, T_FULL = 16, 1001
 CHECK_UTTS = (3, 12)               # positions inside the batch of 16 (different XCD / tile-walk positions)
 # measured per-mode bound on the end-to-end magnitude rel-L2 (tolerance of the path: 1e-3); fp32-faithful modes must be
 # indistinguishable from each other
-MODE_TOL = {"f32": 4e-5, "f32w": 4e-5, "bf16x6": 4e-5, "bf16x6w": 4e-5, "f16x3": 4e-5, "bf16x3": 3e-4, "bf16x3p": 3e-4}   # measured: <= 1.9e-5 / 6.7e-5
+MODE_TOL = {"f32": 4e-5, "f32w": 4e-5, "bf16x6": 4e-5}   # measured: <= 1.9e-5
 
 
 def _modes():
-    return modes("f32", "f32w", "bf16x6", "bf16x6w", "f16x3", "bf16x3")
+    return modes("f32", "f32w", "bf16x6")
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +36,7 @@ def bench_batch(sd1, sd3):
     return mix, clean, refs
 
 
-@pytest.mark.parametrize("mode", modes("f32", "f32w", "bf16x6", "bf16x6w", "f16x3", "bf16x3"))
+@pytest.mark.parametrize("mode", modes("f32", "f32w", "bf16x6"))
 def test_full_size_batch16_pipeline_vs_oracle(bench_batch, sd1, sd3, mode):
     import misonet_amd as mz
     from misonet_amd import weights as W
@@ -141,8 +141,7 @@ def test_folded_norm_ill_conditioned_statistics(sd1, dc, bias_sigma):
     products W' * x cancel against the shift when |mean| >> std.  Inputs with a DC offset per channel and weights with
     large biases (post-ELU means far from zero) make the whole forward ill-conditioned for ANY float32 implementation,
     so the ground truth here is the oracle run in float64 and the yardstick is the exact-f32 mode's distance from it.
-    bf16x6 (exact operands, fp32-faithful) must stay at that yardstick; bf16x3 (16-bit operands) is only reported --
-    this loss of |mean| / std is why it is not the headline arithmetic."""
+    bf16x6 (exact operands, fp32-faithful) must stay at that yardstick."""
     _need_gpu()
     import misonet_amd as mz
     from misonet_amd import weights as W

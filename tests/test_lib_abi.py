@@ -34,9 +34,9 @@ def test_header_symbols_exported():
 
 
 def test_product_library_has_no_experiment_switches():
-    """the kernel-variant / ablation / timeline switches (MISONET_X6_*, MISONET_DMA*, MISONET_SUBBATCH, ...)
-    exist only in the experiment build (`make exp`, -DMISONET_EXPERIMENTS).  The product library reads NO environment
-    variable: not one MISONET_* name (nor a getenv import) is in the binary, and its ABI version says at least 450 (product modes 0 / 3 / 5 only)."""
+    """the library reads NO environment variable: not one MISONET_* name (nor a getenv import) is in the binary,
+    and its ABI version says at least 450 (modes 0 / 3 / 5 only).  The kernel-variant / ablation / timeline switches (MISONET_X6_*,
+    MISONET_DMA*, MISONET_SUBBATCH, ...) and the second build that read them are gone from the sources and the Makefile too."""
     L = _lib()
     assert os.path.realpath(L.LIB_PATH).endswith("libmisonet_hip.so")
     blob = open(L.LIB_PATH, "rb").read()
@@ -45,7 +45,13 @@ def test_product_library_has_no_experiment_switches():
     assert b"getenv" not in blob
     assert L.lib().misonet_version() >= 450
     src = "".join(open(f).read() for f in __import__("glob").glob(os.path.join(ROOT, "misonet_amd", "csrc", "*.hip")))
-    assert "getenv" not in src                                   # every switch goes through kernels.hpp exp_env()
+    assert "getenv" not in src
+    csrc = os.path.join(ROOT, "misonet_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)):
+        if os.path.isfile(os.path.join(csrc, fn)):
+            text = open(os.path.join(csrc, fn), errors="replace").read()
+            assert "MISONET_EXPERIMENTS" not in text and "exp_env" not in text, fn
+    assert not re.search(r"^exp\s*:", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
 
 
 def _make(in_ch=12, out_ch=4, en=(24, 32, 32, 32, 32, 64, 128), de=(128, 64, 32, 32, 32, 32, 24), nf=129, tcn_norm=0):
@@ -157,7 +163,7 @@ def test_precision_switch_host_side():
     assert lib.misonet_net_get_precision(h) == 3                 # bf16x6 (fp32-faithful, the bench's mode) by default
     assert lib.misonet_net_set_precision(h, 0) == 0 and lib.misonet_net_get_precision(h) == 0   # f32
     assert lib.misonet_net_set_precision(h, 5) == 0 and lib.misonet_net_get_precision(h) == 5   # f32w
-    # the product library has exactly three arithmetic modes; bf16x3 (1, 2), f16x3 (4), bf16x6w (6) are experiment-build modes
+    # the library has exactly three arithmetic modes; the numbers 1, 2, 4 and 6 belonged to measured and dropped alternatives
     for alt in (1, 2, 4, 6):
         assert lib.misonet_net_set_precision(h, alt) == L.EINVAL and lib.misonet_net_get_precision(h) == 5, alt
     assert lib.misonet_net_set_precision(h, 7) == L.EINVAL and lib.misonet_net_set_precision(h, -1) == L.EINVAL
@@ -168,7 +174,7 @@ def test_precision_switch_host_side():
     assert m.precision == "bf16x6"
     m.set_precision("f32w")
     assert m.precision == "f32w"
-    with pytest.raises(ValueError, match="experiment build"):
+    with pytest.raises(ValueError, match="precision must be one of"):
         m.set_precision("bf16x3")
     assert m.precision == "f32w"
     with pytest.raises(ValueError):
@@ -393,7 +399,7 @@ def test_conv_plan_rejects_modes_not_in_build():
     L, rc, h = _make()
     lib = L.lib()
     kind = (C.c_int * 64)()
-    for mode in (1, 2, 4, 6, 7, -1):                                     # experiment-build modes and nonsense
+    for mode in (1, 2, 4, 6, 7, -1):                                     # numbers of dropped modes and nonsense
         assert lib.misonet_net_conv_plan(h, mode, 64, kind) == L.EINVAL, mode
     assert lib.misonet_net_conv_plan(h, 5, 64, None) == L.EINVAL
     assert lib.misonet_version() >= 470

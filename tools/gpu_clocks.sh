@@ -1,6 +1,6 @@
 #!/bin/bash
 # sample sclk / power while bench.py runs a long timed region: gpu_clocks.sh PREC [steps]
-PREC=${1:-bf16x3}; STEPS=${2:-150}
+PREC=${1:-bf16x6}; STEPS=${2:-150}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 python bench.py --steps $STEPS --warmup 2 --no-cpu-baseline --no-alt --no-profile --precision $PREC > /tmp/clk_bench.json 2>/dev/null &

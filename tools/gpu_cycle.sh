@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box cycle: parity tests, bench line, rocprofv3 kernel trace summarised to text.
-# usage: gpu_cycle.sh TAG [notest|test] [f32|bf16x3]
+# usage: gpu_cycle.sh TAG [notest|test] [f32|f32w|bf16x6]
 TAG=${1:-x}
 PREC=${3:-f32}
 R=${GRAFT_REPO_ROOT:-/root/repo}

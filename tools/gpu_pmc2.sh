@@ -1,7 +1,7 @@
 #!/bin/bash
-# L2 (TCC) counters for the conv kernels.  usage: gpu_pmc2.sh TAG [f32|bf16x3]
+# L2 (TCC) counters for the conv kernels.  usage: gpu_pmc2.sh TAG [f32|f32w|bf16x6]
 TAG=${1:-x}
-PREC=${2:-bf16x3}
+PREC=${2:-bf16x6}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp

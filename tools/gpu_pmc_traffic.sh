@@ -1,6 +1,6 @@
 #!/bin/bash
 # HBM traffic passes only (FETCH_SIZE, WRITE_SIZE; separate runs, --kernel-trace only).  usage: gpu_pmc_traffic.sh TAG PREC
-TAG=${1:-x}; PREC=${2:-bf16x3}
+TAG=${1:-x}; PREC=${2:-bf16x6}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp

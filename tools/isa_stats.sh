@@ -4,7 +4,7 @@
 R=/root/repo/misonet_amd/csrc
 F=$1; K=$2; OUT=${3:-/tmp/isa_$F.s}
 EXTRA=""
-case $F in conv_bf16|conv_bf16_dma|conv_bf16x6) EXTRA="-fno-slp-vectorize";; esac
+case $F in conv_bf16x6|conv_wino) EXTRA="-fno-slp-vectorize";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 $EXTRA --cuda-device-only -S $R/$F.hip -o $OUT 2>&1 | grep -v "warning\|^$"
 awk -v k="$K" '$0 ~ "^_Z[A-Za-z0-9_]*"k"[A-Za-z0-9_]*:" {p=1} p {print} p && /\.end_amdhsa_kernel/ {exit}' $OUT > ${OUT%.s}_k.s
 echo "kernel lines: $(wc -l < ${OUT%.s}_k.s)"
