@@ -792,6 +792,61 @@ int misonet_oiva(const void* mix_dev, int B, int M, int T, int F, const misonet_
 int misonet_oiva_debug(const void* state_dev, int B, int M, int F, void* w_c128_dev, void* v_c128_dev, int* fail_dev, int* n_dev,
                        misonet_stream stream);
 
+/* ---- online AuxIVA for fewer sources than microphones: K rows out, its state carried from call to call (ABI 670) --------- */
+/* The project's own definition in the OverIVA family (Scheibler & Ono, "Independent vector analysis with more microphones than
+ * sources", WASPAA 2019) in the frame-recursive form of misonet_oiva (INTEGRATION.md 4w in full, tests/overiva_ref.py restates it
+ * in NumPy float64).  pyroomacoustics and torchiva were not available: nothing here was compared against them.  Audio is fed as
+ * it arrives: a call takes any T >= 1 new frames and advances the state; the memory does not grow.  Each item b runs on its own.
+ * K sources at M microphones, 2 <= M <= 8 and 1 <= K <= M - 1; K = 1 is blind extraction of one source; K = M is refused with a
+ * message that names misonet_oiva.  The options are misonet_oiva_opts: K is a dimension, not an option.
+ * State per (b, f), all complex128: Ws [K, M] (row k is w_k^H, y = Ws x), J [M - K, K], V [K, M, M] (one Hermitian matrix per
+ * source), C [M, M] (Hermitian, the recursive mixture covariance); n int32 (the frames seen; it stops at 2^31 - 1) and fail
+ * int32.  The full demixing matrix is W = [Ws ; J, -I_{M-K}].  misonet_overiva_reset: Ws = [I_K 0], J = 0, V_k = init I,
+ * C = init I, n = 0, fail = 0; it writes every byte of the state.  Per new frame, x the frame's M samples of bin f, float64
+ * after the load:
+ *   0. a bin whose frame holds a non-finite sample: fail |= 1; its x counts as 0 in steps 1-2, step 3 is skipped for it (Ws, J, V
+ *      and C stay) and its outputs for this frame are 0
+ *   1. yt_k[f] = sum_m Ws_f[k, m] x_f[m], m ascending, for k < K, with Ws as it stood before this frame
+ *   2. r_k = sum_f |yt_k[f]|^2, in one fixed order that depends on M, K and F alone;
+ *      model 0 "gauss": phi_k = 1 / max(r_k / F, floor);  model 1 "laplace": phi_k = 1 / max(2 sqrt(r_k), floor)
+ *   3. per bin:  C <- alpha C + (1 - alpha) x x^H     the lower triangle is computed, the upper is its mirror, the diagonal's
+ *                                                     imaginary part is exactly 0
+ *      then, for k = 0 .. K - 1 in order:
+ *        V_k <- alpha V_k + (1 - alpha) phi_k x x^H   by the same rule: C and every V_k stay exactly Hermitian
+ *        (W V_k) u = e_k                              the full M x M W as it stands, with the rows replaced and the J re-solved
+ *                                                     earlier in this frame; the elimination of misonet_oiva: partial pivoting
+ *                                                     on |re| + |im|, a non-finite entry counts as the largest, ties go to the
+ *                                                     lower row, then back substitution
+ *        d = Re(u^H V_k u)
+ *        a pivot 0 or non-finite, or d not finite or not > 0: row k stays and fail |= 2; otherwise row k of Ws <- conj(u) / sqrt(d)
+ *        J is re-solved after every k, not once per frame: P = C Ws^H [M, K], summed over m ascending, P1 its first K rows and
+ *        P2 its last M - K; J P1 = P2 is solved as P1^T J^T = P2^T by the same elimination (K x K, M - K right-hand sides);
+ *        a pivot 0 or non-finite: J stays and fail |= 8
+ *   4. y_k = sum_m Ws[k, m] x[m] with the new Ws;  S = Ws[:, :K] + Ws[:, K:] J (K x K);  A_top = S^-1 by the same elimination with
+ *      right-hand side I_K;  A_bot = J A_top;  A = [A_top; A_bot] is the first K columns of W^-1;  est[k] = A[ref_ch, k] y_k,
+ *      images[k, m] = A[m, k] y_k, each rounded once to complex64;  S singular: fail |= 4 and the outputs of this (f, t) are 0
+ *   5. n <- n + 1
+ * Nothing is clamped.  By construction [J, -I] C Ws^H = 0 after step 3, Re(w_k^H V_k w_k) = 1 and W A = [I_K; 0].  sum_k images = x
+ * does NOT hold as it does for misonet_oiva: the background is what is left.  Every sum runs in one fixed order, without
+ * atomics: the bits of an item depend neither on B, nor on its position in the batch, nor on how the stream is cut into calls.
+ * misonet_overiva is one launch for any T >= 1, with no host synchronisation and no allocation: it can be captured in a HIP
+ * graph (after one misonet_overiva_reset outside the capture).  Every element of every output is written.
+ * mix_dev complex64 [B, M, T, F]; est_out_dev complex64 [B, K, T, F]; images_out_dev (may be NULL) complex64 [B, K, M, T, F]; no
+ * two of them may overlap.  state_dev: misonet_overiva_state_bytes bytes, 16-byte aligned, written by misonet_overiva_reset
+ * before the first call; its size does not depend on T.  2 <= M <= 8, 1 <= K <= M - 1, B >= 1, T >= 1, 1 <= F <= 1025, the
+ * fields of opts as misonet_oiva takes them (0 <= ref_ch < M), B F < 2^31: anything else is refused on the host with
+ * MISONET_EINVAL and a message (the size functions: -1), before any launch and before any pointer is looked at; a short state
+ * is MISONET_ENOMEM.  misonet_overiva_bins_per_pass: the bins of an item that one workgroup covers at once. */
+long long misonet_overiva_state_bytes(int B, int M, int K, int F);
+int misonet_overiva_bins_per_pass(int M, int K);
+int misonet_overiva_reset(void* state_dev, int B, int M, int K, int F, const misonet_oiva_opts* opts, misonet_stream stream);
+int misonet_overiva(const void* mix_dev, int B, int M, int K, int T, int F, const misonet_oiva_opts* opts, void* est_out_dev,
+                    void* images_out_dev_or_null, void* state_dev, long long state_bytes, misonet_stream stream);
+/* diagnostic: copy Ws complex128 [B, F, K, M], J complex128 [B, F, M - K, K], V complex128 [B, F, K, M, M], C complex128
+ * [B, F, M, M], fail int32 [B, F] and n int32 [B, F] out of the state to device buffers (any may be NULL) */
+int misonet_overiva_debug(const void* state_dev, int B, int M, int K, int F, void* ws_c128_dev, void* j_c128_dev, void* v_c128_dev,
+                          void* c_c128_dev, int* fail_dev, int* n_dev, misonet_stream stream);
+
 /* ---- online beamformer: frame-recursive MVDR / MWF, its state carried from call to call (ABI 640) ------------------------ */
 /* The project's own definition in the family of mask- or estimate-driven beamformers with exponentially forgotten spatial
  * covariance matrices, re-solved every frame (Souden, Benesty & Affes 2010 for the filter; Higuchi et al. 2017 and Boeddeker et

@@ -11,7 +11,8 @@ Host-side mirror of the reference call surface:
                              to call; OnlineDereverb: its options)
   cacgmm, masks_from_estimates  (guided spatial clustering between MISO1 and the beamformer; Refine: its options)
   auxiva, BlindSeparator    (blind separation, AuxIVA-ISS: a front end that needs no weights; AuxIVA: its options)
-  SeparateStream, auxiva_online   (online AuxIVA: frame-recursive separation, state carried; OnlineAuxIVA: its options)
+  SeparateStream, auxiva_online   (online AuxIVA: frame-recursive separation, state carried; OnlineAuxIVA: its options; with
+                             num_src = K below the number of microphones the overdetermined form: K rows out)
   BeamformStream, beamform_online  (online beamformer: frame-recursive Souden MVDR / rank-1 MWF behind the online separation,
                              state carried; OnlineBeamformer: its options)
   StftStream, IstftStream   (streaming STFT / iSTFT: waveform blocks in, frames out; frames in, waveform blocks out; the bits

@@ -171,6 +171,13 @@ SIGNATURES = {
                                C.c_void_p, C.c_longlong, C.c_void_p]),
     "misonet_oiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "misonet_overiva_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "misonet_overiva_bins_per_pass": (C.c_int, [C.c_int, C.c_int]),
+    "misonet_overiva_reset": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OivaOpts), C.c_void_p]),
+    "misonet_overiva": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OivaOpts), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "misonet_overiva_debug": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "misonet_obf_opts_default": (C.c_int, [C.POINTER(ObfOpts)]),
     "misonet_obf_state_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "misonet_obf_cells_per_block": (C.c_int, [C.c_int]),

@@ -11,7 +11,6 @@ Importing this module does not import torch: :mod:`misonet_amd.localize` imports
 """
 from __future__ import annotations
 
-import dataclasses
 import math
 import sys
 import types
@@ -32,7 +31,7 @@ def spec_of(cls, spec, label, type_error, shorthand=None, true_ok=True):
     if shorthand is not None and isinstance(spec, str):
         return cls(**{shorthand: spec})
     if isinstance(spec, dict):
-        unknown = set(spec) - {f.name for f in dataclasses.fields(cls)}
+        unknown = set(spec) - set(cls.__dataclass_fields__)                   # the fields and the init-only arguments
         if unknown:
             raise ValueError(f"unknown {label} field(s) {sorted(unknown)}")
         return cls(**spec)

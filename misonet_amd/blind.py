@@ -18,6 +18,10 @@ Online AuxIVA (csrc/oiva.hip, C ABI ``misonet_oiva``): the fr
 ``SeparateStream``               -- the state of one stream; ``process(block)`` takes any T >= 1 new frames
 ``auxiva_online(mix, ...)``      -- the one-shot call: reset, then process
 ``OnlineAuxIVA``                 -- its options as plain data
+
+With ``num_src`` = K below the number of microphones the same three run the overdetermined form (csrc/overiva.hip, C ABI
+``misonet_overiva``; OverIVA, Scheibler & Ono 2019, frame-recursive): K rows out, the other M - K rows of the
+demixing matrix fixed as [J, -I].  The project's own definition; nothing was compared against other packages.
 """
 from __future__ import annotations
 
@@ -103,12 +107,38 @@ class OnlineAuxIVA:
     floor    the floor under the weights' denominators (> 0)
     init     V_k = init I at reset (> 0)
     ref_ch   the microphone ``est`` is projected to
+    num_src  K, the sources the stream returns: None or the number of microphones -- the determined case, ``misonet_oiva``;
+             1 <= K < M -- the overdetermined one, ``misonet_overiva``, K rows out
+
+    ``num_src`` is a dimension and not a member of ``misonet_oiva_opts``: it is the last argument of the constructor, it is
+    kept by ``dataclasses.replace`` and compared by ``==``, and ``dataclasses.astuple`` / ``asdict`` stay the five members of the
+    C structure, as they were.  :meth:`as_kwargs` has all six.
     """
     alpha: float = 0.98
     model: str = "gauss"
     floor: float = 1e-10
     init: float = 1.0
     ref_ch: int = 0
+    num_src: dataclasses.InitVar[Optional[int]] = None
+
+    def __post_init__(self, num_src):
+        object.__setattr__(self, "num_src", num_src)
+
+    def __eq__(self, other):
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return self.as_kwargs() == other.as_kwargs()
+
+    def __repr__(self):
+        return f"OnlineAuxIVA({', '.join(f'{k}={v!r}' for k, v in self.as_kwargs().items())})"
+
+    def as_kwargs(self) -> dict:
+        """every argument of the constructor, ``num_src`` included"""
+        return dict(dataclasses.asdict(self), num_src=self.num_src)
+
+    def sources(self, num_mic: int) -> int:
+        """K: the rows the stream returns at ``num_mic`` microphones"""
+        return int(num_mic if self.num_src is None else self.num_src)
 
     @classmethod
     def of(cls, spec) -> "OnlineAuxIVA":
@@ -131,79 +161,138 @@ class OnlineAuxIVA:
                 raise ValueError(f"online blind separation needs 2 <= M <= 8 microphones, got {num_mic}")
             if r >= num_mic:
                 raise ValueError(f"online blind ref_ch {r} outside [0, {num_mic})")
+        k = self.num_src
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+                raise ValueError(f"online blind num_src must be None or a positive integer, got {k!r}")
+            if num_mic is not None and k > num_mic:
+                raise ValueError(f"online blind num_src {k} outside [1, {num_mic}]: no more sources than microphones")
         return self
 
     def c_opts(self) -> "_lib.OivaOpts":
         return _lib.OivaOpts(MODELS.index(self.model), int(self.ref_ch), float(self.alpha), float(self.floor), float(self.init))
 
 
-def bins_per_pass(num_mic: int) -> int:
-    """the bins of an item that one workgroup of the online kernel covers at once (``misonet_oiva_bins_per_pass``)"""
-    return int(_lib.lib().misonet_oiva_bins_per_pass(int(num_mic)))
+def bins_per_pass(num_mic: int, num_src: Optional[int] = None) -> int:
+    """the bins of an item that one workgroup of the online kernel covers at once (``misonet_oiva_bins_per_pass``; with
+    ``num_src`` < ``num_mic``, ``misonet_overiva_bins_per_pass``)"""
+    if num_src is None or int(num_src) == int(num_mic):
+        return int(_lib.lib().misonet_oiva_bins_per_pass(int(num_mic)))
+    return int(_lib.lib().misonet_overiva_bins_per_pass(int(num_mic), int(num_src)))
 
 
 class SeparateStream(OnlineStream):
-    """The state of one stream of online AuxIVA, on the device: ``batch`` recordings of ``num_mic`` microphones (= sources) and
+    """The state of one stream of online AuxIVA, on the device: ``batch`` recordings of ``num_mic`` microphones and
     ``num_bins`` bins.  ``opts``: the fields of :class:`OnlineAuxIVA`.  The state is allocated once; a call allocates only its
-    outputs.  The stream returns all M rows, in no particular order of the sources."""
+    outputs.
+
+    ``num_src`` None or equal to ``num_mic``: the determined case (``misonet_oiva``); the stream returns all M rows, in no
+    particular order of the sources.  ``num_src`` = K < M: the overdetermined case (``misonet_overiva``); the
+    stream returns exactly K rows, est [B, K, T, F] and images [B, K, M, T, F], and the images no longer add up to the input: the
+    background is what is left.  The project's own definition in the OverIVA family; nothing was compared against other
+    packages."""
 
     def __init__(self, num_mic, num_bins=129, batch=1, *, device=None, **opts):
         self.opts = OnlineAuxIVA(**opts).validate(int(num_mic))
         self.num_mic, self.num_bins, self.batch = int(num_mic), int(num_bins), int(batch)
+        self.num_src = self.opts.sources(self.num_mic)
+        self._over = self.num_src < self.num_mic
         if not 1 <= self.num_bins <= 1025 or self.batch < 1:
             raise ValueError(f"num_bins must be in [1, 1025] and batch positive, got {num_bins}, {batch}")
         self._c = self.opts.c_opts()
-        self._alloc(_lib.lib().misonet_oiva_state_bytes(self.batch, self.num_mic, self.num_bins), device)
+        if self._over:
+            nbytes = _lib.lib().misonet_overiva_state_bytes(self.batch, self.num_mic, self.num_src, self.num_bins)
+        else:
+            nbytes = _lib.lib().misonet_oiva_state_bytes(self.batch, self.num_mic, self.num_bins)
+        self._alloc(nbytes, device)
 
     def _reset_call(self):
-        """W = I, V_k = init I, no frame seen, no flag"""
+        """W = I (Ws = [I 0], J = 0), V_k = init I (and C = init I), no frame seen, no flag"""
+        if self._over:
+            return _lib.lib().misonet_overiva_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_src, self.num_bins,
+                                                    C.byref(self._c), _lib.stream_ptr(self.device))
         return _lib.lib().misonet_oiva_reset(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, C.byref(self._c),
                                              _lib.stream_ptr(self.device))
 
     def process_into(self, block: torch.Tensor, est: torch.Tensor, images: Optional[torch.Tensor] = None):
-        """block, est: complex64 [B, M, T, F], images: complex64 [B, M, M, T, F] or None, contiguous on the stream's device and
-        not overlapping.  One launch, nothing allocated: the call a HIP graph captures."""
+        """block: complex64 [B, M, T, F], est: complex64 [B, K, T, F], images: complex64 [B, K, M, T, F] or None (K = M in the
+        determined case), contiguous on the stream's device and not overlapping.  One launch, nothing allocated: the call a HIP
+        graph captures."""
         B, M, T, F = block.shape
         self._same_geometry(block.shape)
+        img_ptr = images.data_ptr() if images is not None else None
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().misonet_oiva(block.data_ptr(), B, M, T, F, C.byref(self._c), est.data_ptr(),
-                                               images.data_ptr() if images is not None else None, self.state.data_ptr(),
-                                               self.state.numel(), _lib.stream_ptr(self.device)))
+            if self._over:
+                K = self.num_src
+                if tuple(est.shape) != (B, K, T, F) or (images is not None and tuple(images.shape) != (B, K, M, T, F)):
+                    raise ValueError(f"est must be [{B}, {K}, {T}, {F}] and images [{B}, {K}, {M}, {T}, {F}]")
+                _lib.check(_lib.lib().misonet_overiva(block.data_ptr(), B, M, K, T, F, C.byref(self._c), est.data_ptr(), img_ptr,
+                                                      self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
+            else:
+                _lib.check(_lib.lib().misonet_oiva(block.data_ptr(), B, M, T, F, C.byref(self._c), est.data_ptr(), img_ptr,
+                                                   self.state.data_ptr(), self.state.numel(), _lib.stream_ptr(self.device)))
         return est if images is None else (est, images)
 
     def process(self, block, images=False):
-        """The next T >= 1 frames of the stream: complex [B, M, T, F] -> est complex64 [B, M, T, F] (row k at ``ref_ch``), with
-        ``images=True`` also the images complex64 [B, M(k), M, T, F]; on the device for device input and on the CPU for an
-        ndarray.  The bits do not depend on how the stream is cut into calls."""
+        """The next T >= 1 frames of the stream: complex [B, M, T, F] -> est complex64 [B, K, T, F] (row k at ``ref_ch``), with
+        ``images=True`` also the images complex64 [B, K, M, T, F] (K = M in the determined case); on the device for device input
+        and on the CPU for an ndarray.  The bits do not depend on how the stream is cut into calls."""
         shape = np.shape(block)
         self._check_block(shape)
         x, np_in = _dev_c64(block, self.device)
-        est = torch.empty_like(x)
-        img = torch.empty((shape[0], shape[1]) + tuple(x.shape[1:]), dtype=torch.complex64, device=x.device) if images else None
+        K = self.num_src
+        est = torch.empty((shape[0], K) + tuple(x.shape[2:]), dtype=torch.complex64, device=x.device) if self._over \
+            else torch.empty_like(x)
+        img = torch.empty((shape[0], K) + tuple(x.shape[1:]), dtype=torch.complex64, device=x.device) if images else None
         self.process_into(x, est, img)
         if np_in:
             est, img = est.cpu(), (img.cpu() if images else None)
         return (est, img) if images else est
 
     def _parts(self):
-        B, M, F = self.batch, self.num_mic, self.num_bins
+        B, M, K, F = self.batch, self.num_mic, self.num_src, self.num_bins
+        if self._over:
+            return dict(Ws=((B, F, K, M), torch.complex128), J=((B, F, M - K, K), torch.complex128),
+                        V=((B, F, K, M, M), torch.complex128), C=((B, F, M, M), torch.complex128), fail=((B, F), torch.int32),
+                        n=((B, F), torch.int32))
         return dict(W=((B, F, M, M), torch.complex128), V=((B, F, M, M, M), torch.complex128), fail=((B, F), torch.int32),
                     n=((B, F), torch.int32))
 
     def _debug_call(self, ptr):
+        if self._over:
+            return _lib.lib().misonet_overiva_debug(self.state.data_ptr(), self.batch, self.num_mic, self.num_src, self.num_bins,
+                                                    ptr("Ws"), ptr("J"), ptr("V"), ptr("C"), ptr("fail"), ptr("n"),
+                                                    _lib.stream_ptr(self.device))
         return _lib.lib().misonet_oiva_debug(self.state.data_ptr(), self.batch, self.num_mic, self.num_bins, ptr("W"), ptr("V"),
                                              ptr("fail"), ptr("n"), _lib.stream_ptr(self.device))
 
     def demixing(self):
-        """the demixing matrices W complex128 [B, F, M, M] as they stand (row k = w_k^H), on the device"""
-        return self._debug(("W",))["W"]
+        """the demixing matrices as they stand (row k = w_k^H), on the device: W complex128 [B, F, M, M], or with K < M sources
+        Ws complex128 [B, F, K, M]"""
+        return self._debug(("Ws",))["Ws"] if self._over else self._debug(("W",))["W"]
 
     def covariance(self):
-        """the weighted covariances V complex128 [B, F, M(k), M, M] as they stand, on the device"""
+        """the weighted covariances V complex128 [B, F, K, M, M] as they stand (K = M in the determined case), on the device"""
         return self._debug(("V",))["V"]
 
+    def _only_over(self, what):
+        if not self._over:
+            raise ValueError(f"{what} belongs to the overdetermined stream: set num_src below the number of microphones")
+
+    def background(self):
+        """J complex128 [B, F, M - K, K] as it stands, on the device: the rows [J, -I] of the full demixing matrix, which keep
+        the background uncorrelated with the sources under the mixture covariance (K < M only)"""
+        self._only_over("background()")
+        return self._debug(("J",))["J"]
+
+    def mixture_covariance(self):
+        """the recursive mixture covariance C complex128 [B, F, M, M] as it stands, on the device (K < M only)"""
+        self._only_over("mixture_covariance()")
+        return self._debug(("C",))["C"]
+
     fail = property(OnlineStream.fail.fget, doc="int32 [B, F] on the device: bit 0 a non-finite sample, bit 1 a row update that "
-                                                "was dropped, bit 2 a singular W")
+                                                "was dropped, bit 2 a singular W (with K < M: a singular Ws[:, :K] + Ws[:, K:] "
+                                                "J), bit 3 (K < M only) a re-solve of J that was dropped")
 
 
 def auxiva_online(mix, *, return_debug=False, images=False, device=None, **opts):
@@ -211,12 +300,13 @@ def auxiva_online(mix, *, return_debug=False, images=False, device=None, **opts)
     complex64 of the same shape (with ``images=True``: ``(est, images [B, M, M, T, F])``), on the device for device input and on
     the CPU for an ndarray.  ``opts``: the fields of :class:`OnlineAuxIVA`.  ``return_debug`` adds, on the device, ``W``, ``V``,
     ``fail`` and ``n`` of the final state.  Causal: frame t of the output depends on no later frame.  It does not separate better
-    than :func:`auxiva`."""
+    than :func:`auxiva`.  With ``num_src=K`` below M: est [B, K, T, F], images [B, K, M, T, F], and the debug parts ``Ws``,
+    ``J``, ``V``, ``C``, ``fail`` and ``n`` (:class:`SeparateStream`)."""
     shape = np.shape(mix)
     o = OnlineAuxIVA(**opts).validate(shape[1] if len(shape) == 4 else None)
     if len(shape) != 4 or min(shape) < 1:
         raise ValueError(f"mix {tuple(shape)} must be [B, M, T, F], all positive")
-    st = SeparateStream(shape[1], shape[3], shape[0], device=default_device(mix, device), **dataclasses.asdict(o))
+    st = SeparateStream(shape[1], shape[3], shape[0], device=default_device(mix, device), **o.as_kwargs())
     out = st.process(mix, images=images)
     if not return_debug:
         return out
@@ -350,21 +440,25 @@ class BlindSeparator:
         ``beamform`` (an OnlineBeamformer) the rows of the online beamformer at the same indices"""
         M = spec.shape[1]
         online.validate(M)
+        K = online.sources(M)                                                # the rows the stream returns
         if beamform is not None:
-            beamform.validate(M, M)
-        if self.num_spks > M:
-            raise ValueError(f"online separation returns M = {M} rows; {self.num_spks} speakers were asked for")
+            beamform.validate(M, K)
+        if self.num_spks > K:
+            raise ValueError(f"online separation returns {K} rows; {self.num_spks} speakers were asked for"
+                             + ("" if online.num_src is None else f" (num_src must be >= num_spks)"))
+        # num_src == num_spks: every row is a speaker and nothing is chosen; without num_src the rows are ordered as they always were
+        pick = online.num_src is None or K > self.num_spks
         if dereverb is not None:
             from .dereverb import DereverbStream
             spec = DereverbStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(dereverb.validate(M))).process(spec)
-        sep = SeparateStream(M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(online))
+        sep = SeparateStream(M, spec.shape[3], 1, device=self.device, **online.as_kwargs())
         if beamform is None:
             est = sep.process(spec)[0]
-            return est[self._online_pick(est)].contiguous()
+            return est[self._online_pick(est)].contiguous() if pick else est
         from .beamform import BeamformStream
         est, images = sep.process(spec, images=True)
-        out = BeamformStream(M, M, spec.shape[3], 1, device=self.device, **dataclasses.asdict(beamform)).process(images, spec)
-        return out[0][self._online_pick(est[0])].contiguous()
+        out = BeamformStream(M, K, spec.shape[3], 1, device=self.device, **dataclasses.asdict(beamform)).process(images, spec)
+        return out[0][self._online_pick(est[0])].contiguous() if pick else out[0]
 
     def separate_recording(self, wav, num_ch_utilize: Optional[int] = None, save_path: Optional[str] = None, fs: int = 16000,
                            beamform: Optional[bool] = None, srmr: bool = False, fs_in=None, fs_out=None, online=None,
@@ -392,7 +486,13 @@ class BlindSeparator:
         :class:`misonet_amd.beamform.BeamformStream` with M sources runs on those images and on the spectrum AuxIVA saw (behind
         ``dereverb``: the dereverberated one), the rows are chosen as above, by the power of ``est``, and the beamformed rows of
         those indices go to the iSTFT.  An ``OnlineBeamformer`` without ``online`` is refused; so is ``dereverb`` without
-        ``online``."""
+        ``online``.
+
+        ``online`` with ``num_src`` = K set: K < M runs the overdetermined stream, which returns exactly K
+        rows (the online beamformer behind it is a ``BeamformStream(M, K)``); K >= ``num_spks`` is required.  With K > ``num_spks``
+        the strongest ``num_spks`` rows are chosen as above, after the fact.  With K == ``num_spks`` every row of the stream is a
+        speaker and the path makes no choice after the whole recording has been seen: that is what makes it causal -- frame t of
+        every wave depends on no later frame."""
         from .beamform import OnlineBeamformer
         online_bf = None
         if isinstance(beamform, OnlineBeamformer):

@@ -368,6 +368,62 @@ int misonet_oiva_debug(const void* state, int B, int M, int F, void* w, void* v,
   return MISONET_OK;
 }
 
+// ---- online AuxIVA for fewer sources than microphones: K rows, state carried (ABI 670) ------------------------------------
+static int overiva_geom_check(int B, int M, int K, int F) {
+  { int r = oiva_geom_check(B, M, F); if (r) return r; }
+  if (K == M) return fail(MISONET_EINVAL, "K = M = %d is the determined case: that is misonet_oiva", M);
+  if (K < 1 || K > M) return fail(MISONET_EINVAL, "K must be in [1, M - 1] = [1, %d] (got %d)", M - 1, K);
+  return MISONET_OK;
+}
+
+static int overiva_check(int B, int M, int K, int F, const misonet_oiva_opts* o) {
+  if (!o) return fail(MISONET_EINVAL, "null online separation options");
+  { int r = overiva_geom_check(B, M, K, F); if (r) return r; }
+  return oiva_check(B, M, F, o);
+}
+
+long long misonet_overiva_state_bytes(int B, int M, int K, int F) {
+  if (overiva_geom_check(B, M, K, F)) return -1;
+  return overiva_state_bytes((long long)B * F, M, K);
+}
+
+int misonet_overiva_bins_per_pass(int M, int K) {
+  if (M < 2 || M > 8) { fail(MISONET_EINVAL, "M must be in [2, 8] (got %d)", M); return -1; }
+  if (K == M) { fail(MISONET_EINVAL, "K = M = %d is the determined case: that is misonet_oiva_bins_per_pass", M); return -1; }
+  if (K < 1 || K > M) { fail(MISONET_EINVAL, "K must be in [1, M - 1] = [1, %d] (got %d)", M - 1, K); return -1; }
+  return overiva_bins_per_pass(M, K);
+}
+
+int misonet_overiva_reset(void* state, int B, int M, int K, int F, const misonet_oiva_opts* opts, misonet_stream stream) {
+  { int r = overiva_check(B, M, K, F, opts); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_overiva_reset(state, B, M, K, F, opts->init, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_overiva(const void* mix, int B, int M, int K, int T, int F, const misonet_oiva_opts* opts, void* est, void* images,
+                    void* state, long long state_bytes, misonet_stream stream) {
+  { int r = overiva_check(B, M, K, F, opts); if (r) return r; }
+  if (T < 1) return fail(MISONET_EINVAL, "T must be >= 1 (got %d)", T);
+  if (!mix || !est || !state) return fail(MISONET_EINVAL, "null argument");
+  const unsigned __int128 n = (unsigned __int128)B * T * F * 8;             // one microphone or one source of the block
+  if (ranges_overlap(mix, n * M, est, n * K) ||
+      (images && (ranges_overlap(mix, n * M, images, n * K * M) || ranges_overlap(est, n * K, images, n * K * M))))
+    return fail(MISONET_EINVAL, "mix_dev, est_out_dev and images_out_dev must not overlap");
+  if (state_bytes < overiva_state_bytes((long long)B * F, M, K)) return fail(MISONET_ENOMEM, "state too small");
+  HIPCHK(launch_overiva(mix, B, M, K, T, F, opts->model, opts->ref_ch, opts->alpha, opts->floor, est, images, state,
+                        reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
+int misonet_overiva_debug(const void* state, int B, int M, int K, int F, void* ws, void* j, void* v, void* c, int* fail_dev,
+                          int* n_dev, misonet_stream stream) {
+  { int r = overiva_geom_check(B, M, K, F); if (r) return r; }
+  if (!state) return fail(MISONET_EINVAL, "null argument");
+  HIPCHK(launch_overiva_debug(state, B, M, K, F, ws, j, v, c, fail_dev, n_dev, reinterpret_cast<hipStream_t>(stream)));
+  return MISONET_OK;
+}
+
 // ---- online beamformer: frame-recursive MVDR / MWF, state carried (ABI 640) ---------------------------------------------
 int misonet_obf_opts_default(misonet_obf_opts* o) {
   if (!o) return fail(MISONET_EINVAL, "null argument");

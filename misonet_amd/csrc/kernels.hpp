@@ -380,6 +380,20 @@ hipError_t launch_oiva(const void* mix, int B, int M, int T, int F, int model, i
                        void* images, void* state, hipStream_t s);
 hipError_t launch_oiva_debug(const void* state, int B, int M, int F, void* w, void* v, int* fail, int* n, hipStream_t s);
 
+// Online AuxIVA for K < M sources (overiva.hip): the frame-recursive overdetermined separation, its state
+// carried from call to call.  mix complex64 [B][M][T][F], est complex64 [B][K][T][F], images complex64 [B][K][M][T][F] or nullptr,
+// any T >= 1; the state holds fail int [B F], n int [B F], Ws complex128 [B F][K][M], J complex128 [B F][M - K][K], V complex128
+// [B F][K][M][M] and C complex128 [B F][M][M], which launch_overiva_debug copies out.  2 <= M <= 8, 1 <= K <= M - 1, 1 <= F <=
+// 1025, B F < 2^31, 0 < alpha < 1: the caller checks them.  overiva_bins_per_pass(M, K): the bins one workgroup covers at once
+// (-1 outside those ranges).
+long long overiva_state_bytes(long long bins, int M, int K);
+int overiva_bins_per_pass(int M, int K);
+hipError_t launch_overiva_reset(void* state, int B, int M, int K, int F, double init, hipStream_t s);
+hipError_t launch_overiva(const void* mix, int B, int M, int K, int T, int F, int model, int ref_ch, double alpha, double floor,
+                          void* est, void* images, void* state, hipStream_t s);
+hipError_t launch_overiva_debug(const void* state, int B, int M, int K, int F, void* ws, void* jm, void* v, void* c, int* fail,
+                                int* n, hipStream_t s);
+
 // Online beamformer (obf.hip): the frame-recursive Souden MVDR / rank-1 MWF, its state carried from call to
 // call.  mix complex64 [B][M][T][F], images complex64 [B][S][M][T][F], out complex64 [B][S][T][F], any T >= 1; the state holds fail
 // int [B S F], n int [B S F], Phi_s and Phi_n complex128 [B S F][M][M] and w complex128 [B S F][M], which launch_obf_debug copies

@@ -452,7 +452,7 @@ const char* misonet_strerror(int code) {
   }
 }
 const char* misonet_last_error(void) { return g_err; }
-int misonet_version(void) { return 660; }   // 660: misonet_resample_stream_carry, misonet_resample_stream_state_bytes, misonet_resample_stream_outputs, misonet_resample_stream_tile, misonet_resample_stream_reset, misonet_resample_stream (streaming polyphase resampler: blocks in, blocks out, bits of misonet_resample); 650: misonet_stft_stream_state_bytes, misonet_stft_stream_reset, misonet_stft_stream_frames, misonet_stft_stream, misonet_istft_stream_state_bytes, misonet_istft_stream_reset, misonet_istft_stream_hops, misonet_istft_stream (streaming STFT / iSTFT: blocks in, blocks out, bits of the offline kernels); 640: misonet_obf_opts, misonet_obf_opts_default, misonet_obf_state_bytes, misonet_obf_cells_per_block, misonet_obf_reset, misonet_obf, misonet_obf_debug (online beamformer: frame-recursive MVDR / MWF, state carried); 630: misonet_oiva_opts, misonet_oiva_opts_default, misonet_oiva_state_bytes, misonet_oiva_bins_per_pass, misonet_oiva_reset, misonet_oiva, misonet_oiva_debug (online AuxIVA: frame-recursive separation, state carried); 620: misonet_owpe_opts, misonet_owpe_opts_default, misonet_owpe_state_bytes, misonet_owpe_lds_bytes, misonet_owpe_reset, misonet_owpe, misonet_owpe_debug (online WPE: frame-recursive, state carried); 610: misonet_doa_opts, misonet_doa_opts_default, misonet_doa_tile, misonet_doa_bin_chunk, misonet_doa_blocks, misonet_doa_workspace_bytes, misonet_doa, misonet_doa_debug (source localisation: SRP, SRP-PHAT and MUSIC maps); 600: misonet_room_tile, misonet_room_rir_len, misonet_room_mix_len, misonet_room_rir, misonet_room_mix (room simulator: image-source RIRs and scene mixing); 590: misonet_resample, misonet_resample_ratio, misonet_resampled_len, misonet_resample_taps, misonet_resample_tile (polyphase resampler for any rational rate); 580: misonet_iva_opts, misonet_auxiva, misonet_auxiva_debug, misonet_auxiva_workspace_bytes, misonet_auxiva_resident_frames (blind separation, AuxIVA-ISS); 570: misonet_jbf_opts, misonet_beamform_joint, misonet_beamform_joint_debug, misonet_pipeline_set_joint (joint multi-speaker beamformers); 560: misonet_cacgmm_opts, misonet_cacgmm, misonet_cacgmm_debug, misonet_masks_from_estimates, misonet_pipeline_set_refine (guided spatial clustering, cACGMM); 550: misonet_srmr_frames / misonet_srmr_scratch_bytes / misonet_srmr_chunk / misonet_srmr_measure (SRMR, the figure without a clean reference); 540: misonet_reverb_frames / misonet_reverb_scratch_bytes / misonet_reverb_measure (cepstral distance, LLR, fwSegSNR); 530: misonet_wpd_opts, misonet_wpd, misonet_wpd_debug, misonet_pipeline_set_wpd (WPD convolutional beamformer); 520: misonet_wpe_opts, misonet_wpe, misonet_wpe_debug (WPE dereverberation); 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6 answer MISONET_EINVAL); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
+int misonet_version(void) { return 670; }   // 670: misonet_overiva_state_bytes, misonet_overiva_bins_per_pass, misonet_overiva_reset, misonet_overiva, misonet_overiva_debug (online AuxIVA for K < M sources; overiva.hip). 660: misonet_resample_stream_carry, misonet_resample_stream_state_bytes, misonet_resample_stream_outputs, misonet_resample_stream_tile, misonet_resample_stream_reset, misonet_resample_stream (streaming polyphase resampler: blocks in, blocks out, bits of misonet_resample); 650: misonet_stft_stream_state_bytes, misonet_stft_stream_reset, misonet_stft_stream_frames, misonet_stft_stream, misonet_istft_stream_state_bytes, misonet_istft_stream_reset, misonet_istft_stream_hops, misonet_istft_stream (streaming STFT / iSTFT: blocks in, blocks out, bits of the offline kernels); 640: misonet_obf_opts, misonet_obf_opts_default, misonet_obf_state_bytes, misonet_obf_cells_per_block, misonet_obf_reset, misonet_obf, misonet_obf_debug (online beamformer: frame-recursive MVDR / MWF, state carried); 630: misonet_oiva_opts, misonet_oiva_opts_default, misonet_oiva_state_bytes, misonet_oiva_bins_per_pass, misonet_oiva_reset, misonet_oiva, misonet_oiva_debug (online AuxIVA: frame-recursive separation, state carried); 620: misonet_owpe_opts, misonet_owpe_opts_default, misonet_owpe_state_bytes, misonet_owpe_lds_bytes, misonet_owpe_reset, misonet_owpe, misonet_owpe_debug (online WPE: frame-recursive, state carried); 610: misonet_doa_opts, misonet_doa_opts_default, misonet_doa_tile, misonet_doa_bin_chunk, misonet_doa_blocks, misonet_doa_workspace_bytes, misonet_doa, misonet_doa_debug (source localisation: SRP, SRP-PHAT and MUSIC maps); 600: misonet_room_tile, misonet_room_rir_len, misonet_room_mix_len, misonet_room_rir, misonet_room_mix (room simulator: image-source RIRs and scene mixing); 590: misonet_resample, misonet_resample_ratio, misonet_resampled_len, misonet_resample_taps, misonet_resample_tile (polyphase resampler for any rational rate); 580: misonet_iva_opts, misonet_auxiva, misonet_auxiva_debug, misonet_auxiva_workspace_bytes, misonet_auxiva_resident_frames (blind separation, AuxIVA-ISS); 570: misonet_jbf_opts, misonet_beamform_joint, misonet_beamform_joint_debug, misonet_pipeline_set_joint (joint multi-speaker beamformers); 560: misonet_cacgmm_opts, misonet_cacgmm, misonet_cacgmm_debug, misonet_masks_from_estimates, misonet_pipeline_set_refine (guided spatial clustering, cACGMM); 550: misonet_srmr_frames / misonet_srmr_scratch_bytes / misonet_srmr_chunk / misonet_srmr_measure (SRMR, the figure without a clean reference); 540: misonet_reverb_frames / misonet_reverb_scratch_bytes / misonet_reverb_measure (cepstral distance, LLR, fwSegSNR); 530: misonet_wpd_opts, misonet_wpd, misonet_wpd_debug, misonet_pipeline_set_wpd (WPD convolutional beamformer); 520: misonet_wpe_opts, misonet_wpe, misonet_wpe_debug (WPE dereverberation); 510: misonet_bf_opts, misonet_beamform, misonet_pipeline_set_beamformer (selectable beamformers: MPDR, Souden MVDR, GEV, BAN); 500: misonet_stoi_resample / misonet_stoi_measure (STOI and ESTOI); 490: misonet_bss_corr / misonet_bss_solve (BSS-eval SDR, SIR, SAR); 480: misonet_score_wave / misonet_score_spec (scores against clean references); 470: misonet_net_conv_plan (the kernel of every conv layer, decided at plan time); 460: misonet_css_align / misonet_css_stitch (continuous separation); 450:product modes 0 / 3 / 5 only (1, 2, 4, 6 answer MISONET_EINVAL); 410: misonet_pipeline_create accepts miso3 == NULL (separation-only pipeline); 420: misonet_istft; 430: misonet_frontend_init, precision mode 5 (f32w); 440: precision mode 6 (bf16x6w)
 
 int misonet_net_create(const misonet_cfg* cfg, misonet_net** out) {
   if (!cfg || !out) return fail(MISONET_EINVAL, "null argument");

@@ -33,13 +33,15 @@ class StreamSeparator:
                WPE in front of the separation
     separate   True, an :class:`misonet_amd.blind.OnlineAuxIVA`, a model name or a dict of its fields (its ``ref_ch`` is replaced
                by this object's): online AuxIVA with all microphones as sources; None leaves it out, and the rows are the
-               (dereverberated) microphones
+               (dereverberated) microphones.  With ``num_src`` = K below ``num_mic`` (``OnlineAuxIVA(num_src=K)`` or
+               ``dict(num_src=K)``) it is the overdetermined stream: it has exactly K rows, and the online
+               beamformer behind it is a ``BeamformStream(num_mic, K)`` on its K images and on the spectrum it saw
     beamform   None, or an :class:`misonet_amd.beamform.OnlineBeamformer` (True or a dict of its fields are taken as well; its
                ``ref_ch`` is replaced by this object's): the online beamformer on AuxIVA's images and on the spectrum AuxIVA saw;
                needs ``separate``
-    rows       the rows that go to the iSTFT, a sequence of indices in [0, num_mic); default: all of them, in order.  The choice
-               stays with the caller: the strongest-rows pick of ``BlindSeparator.separate_recording`` needs the whole recording,
-               is not causal and is NOT offered here
+    rows       the rows that go to the iSTFT, a sequence of indices in [0, num_mic) -- in [0, K) with ``num_src`` = K; default:
+               all of them, in order.  The choice stays with the caller: the strongest-rows pick of
+               ``BlindSeparator.separate_recording`` needs the whole recording, is not causal and is NOT offered here
     int16      True: int16 waves, ``(short)(int)(y * 32767)`` as ``istft_int16``; False: float32
     fs, fs_in, fs_out   the model's rate, the rate of the blocks that come in and the rate of the waves that go out
                (:func:`misonet_amd.resample.plan_rates`; ``fs_out="in"``: the input's rate).  ``fs`` is required with either of
@@ -56,9 +58,15 @@ class StreamSeparator:
         self.num_mic, self.batch, self.ref_ch = M, B, int(ref_ch)
         if not 0 <= self.ref_ch < max(M, 1):
             raise ValueError(f"ref_ch {ref_ch} outside [0, {M})")
-        self.rows = list(range(M)) if rows is None else [int(r) for r in rows]
-        if not self.rows or any(not 0 <= r < M for r in self.rows):
-            raise ValueError(f"rows must be a non-empty sequence of indices in [0, {M}), got {rows!r}")
+        sep_opts = None
+        if separate is not None and separate is not False:
+            from .blind import OnlineAuxIVA
+            sep_opts = dataclasses.replace(OnlineAuxIVA.of(separate), ref_ch=self.ref_ch).validate(M)
+        K = M if sep_opts is None else sep_opts.sources(M)       # the rows of the stream: num_src of them where that is set
+        self.num_src = K
+        self.rows = list(range(K)) if rows is None else [int(r) for r in rows]
+        if not self.rows or any(not 0 <= r < K for r in self.rows):
+            raise ValueError(f"rows must be a non-empty sequence of indices in [0, {K}), got {rows!r}")
         if beamform is not None and beamform is not False and (separate is None or separate is False):
             raise ValueError("beamform= runs on the images of the online separation: it needs separate=")
         if fs is None and (fs_in is not None or fs_out is not None):
@@ -85,15 +93,14 @@ class StreamSeparator:
             o = OnlineDereverb.of(dereverb).validate(M)
             self.dereverb = DereverbStream(M, S.N_FREQ, B, device=self.device, **dataclasses.asdict(o))
         if separate is not None and separate is not False:
-            from .blind import OnlineAuxIVA, SeparateStream
-            o = dataclasses.replace(OnlineAuxIVA.of(separate), ref_ch=self.ref_ch).validate(M)
-            self.separate = SeparateStream(M, S.N_FREQ, B, device=self.device, **dataclasses.asdict(o))
+            from .blind import SeparateStream
+            self.separate = SeparateStream(M, S.N_FREQ, B, device=self.device, **sep_opts.as_kwargs())
         if beamform is not None and beamform is not False:
             from .beamform import BeamformStream, OnlineBeamformer
-            o = dataclasses.replace(OnlineBeamformer.of(beamform), ref_ch=self.ref_ch).validate(M, M)
-            self.beamform = BeamformStream(M, M, S.N_FREQ, B, device=self.device, **dataclasses.asdict(o))
+            o = dataclasses.replace(OnlineBeamformer.of(beamform), ref_ch=self.ref_ch).validate(M, K)
+            self.beamform = BeamformStream(M, K, S.N_FREQ, B, device=self.device, **dataclasses.asdict(o))
         self.istft = S.IstftStream(B * len(self.rows), int16=int16, device=self.device)
-        self._pick = None if self.rows == list(range(M)) else torch.tensor(self.rows, dtype=torch.long, device=self.device)
+        self._pick = None if self.rows == list(range(K)) else torch.tensor(self.rows, dtype=torch.long, device=self.device)
 
     def reset(self):
         """every link back to its first state"""

@@ -16,7 +16,10 @@ online WPE (``dereverb_wav(online=True)``: causal, frame-recursive) in front of 
 online AuxIVA (``separate_recording(online=True)``: causal, frame-recursive, M sources at M microphones) on 2 of the 6 microphones
 (``[0:6:3]``) and on all 6 with the two strongest rows kept, alone (``oiva``, ``oiva6``) and behind the online WPE stream
 (``owpe+oiva``, ``owpe+oiva6``), and with the online beamformer on the images of the online AuxIVA
-(``separate_recording(online=True, beamform=OnlineBeamformer())``, its defaults: ``oiva+obf``, ``oiva6+obf``, ``owpe+oiva6+obf``).  Every output is scored against the EARLY images at
+(``separate_recording(online=True, beamform=OnlineBeamformer())``, its defaults: ``oiva+obf``, ``oiva6+obf``, ``owpe+oiva6+obf``);
+the online AuxIVA for K = 2 sources at all 6 microphones (``online=dict(num_src=2)``: two rows out, no choice after the fact), alone
+(``overiva``), behind the online WPE stream (``owpe+overiva``) and with the online beamformer behind it (``owpe+overiva+obf``).
+Every output is scored against the EARLY images at
 ``ref_ch`` (the direct path and the first 50 ms) on the device: SI-SDR of the best assignment and its improvement over the
 mixture, BSS-eval SDR, STOI, cepstral distance, LLR, fwSegSNR and SRMR, averaged over the speakers and the scenes.  No figure is
 required to come out any particular way: the table is what was measured, a front end that makes things worse included.
@@ -77,6 +80,10 @@ def arms(which):
     out["oiva+obf"] = (False, False, dict(mics=2, obf=True))
     out["oiva6+obf"] = (False, False, dict(mics=6, obf=True))
     out["owpe+oiva6+obf"] = (False, False, dict(mics=6, owpe=True, obf=True))
+    # the same chain with K = 2 sources at the 6 microphones ("src"): two rows out, nothing chosen after the fact
+    out["overiva"] = (False, False, dict(mics=6, src=2))
+    out["owpe+overiva"] = (False, False, dict(mics=6, src=2, owpe=True))
+    out["owpe+overiva+obf"] = (False, False, dict(mics=6, src=2, owpe=True, obf=True))
     return out
 
 
@@ -142,7 +149,8 @@ def main(argv=None):
             try:
                 if "mics" in kw:
                     sep = mz.BlindSeparator(2, kw["mics"], ref_ch=a.ref_ch)
-                    pcm = sep.separate_recording(wav, fs=FS, online=True, dereverb=True if kw.get("owpe") else None,
+                    online = dict(num_src=kw["src"]) if "src" in kw else True
+                    pcm = sep.separate_recording(wav, fs=FS, online=online, dereverb=True if kw.get("owpe") else None,
                                                  beamform=mz.OnlineBeamformer() if kw.get("obf") else None)
                 else:
                     sep = mz.BlindSeparator(2, 6, ref_ch=a.ref_ch, **kw)
